@@ -22,6 +22,8 @@ Prints ONE JSON line (rank 0) with the driver's contract plus
                  60..80 atoms, other batch sizes.
   --config C5 / C4 / C1 / C2L select another workload as the headline; --backend gloo runs --gpus N as N ranks
   on ONE GPU (functional check of the sharded branch on a single-GPU box).
+  --dump-outputs DIR writes the chain the last timed step returned as DIR/chain.npy (float32), so that two builds run with the
+  same arguments (same inputs, weights and noise) can be compared output for output.
 """
 import argparse
 import json
@@ -68,7 +70,35 @@ def parse():
     ap.add_argument('--precision', default=None, choices=['f16x3', 'fp32', 'f16x2'], help='arithmetic mode (default: f16x3)')
     ap.add_argument('--traffic-child', action='store_true', help=argparse.SUPPRESS)     # the profiled child of measure_traffic()
     ap.add_argument('--no-traffic', action='store_true', help='skip the two rocprofv3 --pmc passes behind roofline.traffic')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one returned (the chain) as DIR/<name>.npy, float32, at most '
+                         '64 MB (a fixed, seeded sample of molecules beyond that); the same arguments give the same inputs')
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    return a
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each ``[frames, B, ...]`` tensor of `arrays` as ``out_dir/<name>.npy`` in float32.  Should they hold more than
+    DUMP_LIMIT_BYTES together, the same fixed, seeded sample of molecules (the batch axis, dim 1) is kept in every one of them;
+    ``molecule_index.npy`` then names the molecules kept."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    B = next(iter(arrays.values())).shape[1]
+    if total > DUMP_LIMIT_BYTES:
+        keep = max(1, B * DUMP_LIMIT_BYTES // total)
+        idx = np.sort(np.random.default_rng(0).choice(B, size=keep, replace=False))
+        arrays = {k: v[:, idx] for k, v in arrays.items()}
+        arrays['molecule_index'] = idx.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, f'{k}.npy'), np.ascontiguousarray(v))
+    return sorted(arrays)
 
 
 def build_model(cfg, device):
@@ -102,53 +132,19 @@ def pocket_edge_count(inp, cutoff_cross=10.0):
     return int(adj.sum()), int(into_linker.sum())
 
 
-REFERENCE_ROOT = '/root/reference'     # the unmodified reference: present in the build container, absent on the GPU box
-
-
-def reference_forward(edm, cfg):
-    """``Dynamics.forward`` of the UNMODIFIED reference (src/egnn.py:374-447 / :471-552) with this model's weights, or None
-    where the reference tree does not exist (the GPU box: the oracle port - the same numbers to the bit, 4 % apart in time,
-    profiles/r04/cpu_reference_vs_port.log - is timed instead)."""
-    if not os.path.isfile(os.path.join(REFERENCE_ROOT, 'src', 'egnn.py')):
-        return None
-    try:
-        sys.dont_write_bytecode = True                         # the reference tree is read-only
-        sys.path.insert(0, REFERENCE_ROOT)
-        from src import egnn as ref_egnn
-        pockets = cfg['graph_type'] != 'FC'
-        cls = ref_egnn.DynamicsWithPockets if pockets else ref_egnn.Dynamics
-        ref = cls(n_dims=3, in_node_nf=cfg['nf'], context_node_nf=cfg['ctx'], hidden_nf=128, device='cpu', n_layers=cfg['n_layers'],
-                  attention=False, tanh=False, norm_constant=1e-6, inv_sublayers=2, sin_embedding=False, normalization_factor=100,
-                  aggregation_method='sum', model='egnn_dynamics', normalization='batch_norm', centering=False,
-                  graph_type=cfg['graph_type'])
-        ref.load_state_dict({k: v.detach().cpu().clone() for k, v in edm.dynamics.state_dict().items()}, strict=True)
-        ref.eval()
-        return lambda sd, ocfg, t, z, nm, lm, em, ctx: ref.forward(t=t, xh=z, node_mask=nm, linker_mask=lm, edge_mask=em, context=ctx)
-    except Exception as e:                                     # a reference tree that does not import here: the port
-        print(f'note: the reference modules under {REFERENCE_ROOT} could not be used ({type(e).__name__}: {e}); timing the port',
-              file=sys.stderr)
-        return None
-    finally:
-        if sys.path and sys.path[0] == REFERENCE_ROOT:
-            sys.path.pop(0)
-
-
 def cpu_baseline(edm, cfg, inp, n_forwards, sample_batch=32):
     """The reference path on the host cores, bounded sample: the first `sample_batch` molecules of the same batch, best of a
     few thread counts (PyTorch CPU ops stop scaling well before a many-core host is full), scaled linearly to the whole
-    batch and to T+1 forwards (per-edge cost is constant; every step costs the same).  What is timed: the unmodified
-    reference modules where /root/reference exists (``kind: "reference"``), else the oracle = the PyTorch-CPU port of the
-    same op sequence (``kind: "port"``)."""
+    batch and to T+1 forwards (per-edge cost is constant; every step costs the same).  What is timed: the oracle = the
+    PyTorch-CPU port of the reference's op sequence (``kind: "port"``)."""
     from oracle import egnn_oracle
     cores = os.cpu_count() or 1
     sd = {k: v.detach().cpu().clone() for k, v in edm.dynamics.state_dict().items()}
     pockets = cfg['graph_type'] != 'FC'
     ocfg = egnn_oracle.EGNNConfig(in_node_nf=cfg['nf'], context_node_nf=cfg['ctx'], n_layers=cfg['n_layers'],
                                   graph_type=cfg['graph_type'])
-    forward = reference_forward(edm, cfg)
-    kind = 'reference' if forward is not None else 'port'
-    if forward is None:
-        forward = egnn_oracle.dynamics_forward_pockets if pockets else egnn_oracle.dynamics_forward
+    kind = 'port'
+    forward = egnn_oracle.dynamics_forward_pockets if pockets else egnn_oracle.dynamics_forward
     B, N = inp['x'].shape[:2]
     b = min(8 if pockets else sample_batch, B)
     g = torch.Generator().manual_seed(1)
@@ -171,8 +167,7 @@ def cpu_baseline(edm, cfg, inp, n_forwards, sample_batch=32):
     dt, threads = best
     fwd_full = dt * B / b
     chain_s = fwd_full * (cfg['T'] + 1)
-    what = 'Dynamics.forward calls of the unmodified reference (src/egnn.py)' if kind == 'reference' else \
-        'Dynamics.forward calls of the oracle port (the reference\'s op sequence on PyTorch-CPU; /root/reference is absent here)'
+    what = 'Dynamics.forward calls of the oracle port (the reference\'s op sequence on PyTorch-CPU)'
     return {'value': B / chain_s, 'unit': 'molecules/s', 'cores': threads, 'kind': kind,
             'sample': f'{n_forwards} {what} on the first {b} of the {B} molecules (N={N}, '
                       f'L={cfg["n_layers"]}) after 1 warm-up, best of 8/16/32/64 threads ({threads}): {dt:.2f} s each; '
@@ -284,8 +279,8 @@ def secondary_measurements(device, a):
         B = inp['x'].shape[0]
         fused = (not pockets) and kms is not None
         if tag == 'c4_pockets' and not a.no_cpu_baseline:
-            # C4's own CPU baseline: DynamicsWithPockets.forward (src/egnn.py:471-552) of the reference
-            # where it exists, else of the port, on 8 of the 64 molecules
+            # C4's own CPU baseline: DynamicsWithPockets.forward (src/egnn.py:471-552) of the port,
+            # on 8 of the 64 molecules
             try:
                 kept['c4_cpu_baseline'] = cpu_baseline(edm, cfg, inp_cpu, 1)
             except Exception as e:
@@ -470,7 +465,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        one_chain()
+        chain = one_chain()
         kernel_ms.append(getattr(edm, 'last_kernel_events', None))
         split_events = getattr(edm, 'last_split_event', None)
     torch.cuda.synchronize()
@@ -481,6 +476,9 @@ def main():
         tt = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt)
+    if a.dump_outputs and rank == 0 and not a.traffic_child:   # outside the timed region: what the last timed step returned
+        written = dump_outputs(a.dump_outputs, {'chain': chain})
+        print(f'outputs of the last timed step: {", ".join(written)} (.npy) in {a.dump_outputs}', file=sys.stderr, flush=True)
     if kernel_ms[0] is not None:
         k_ms = [s.elapsed_time(e) for s, e in kernel_ms]
         k_avg_ms = sum(k_ms) / len(k_ms)

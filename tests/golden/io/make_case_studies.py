@@ -1,6 +1,7 @@
 """Copy the reference's real case-study inputs into small fixtures (build container only; reads /root/reference):
 the fragment SDF files as they are, the protein PDB files trimmed to the residues that have an atom within 12 A of a
-fragment atom (the 6 A pocket selection of generate_with_protein.py:85-148 then still has residues to reject).
+fragment atom (the 6 A pocket selection of generate_with_protein.py:85-148 then still has residues to reject); and the
+few case-study files test_io.py reads whole, under their own names (case_studies/<case>/<file>).
     python tests/golden/io/make_case_studies.py"""
 import os
 import shutil
@@ -9,6 +10,8 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REF = '/root/reference/case_studies'
+WHOLE = ('hsp90/3hz1_original_fragments.sdf', 'hsp90/3hz1_protein.pdb', 'impdh/5ou2_fragments_input.sdf', 'jnk/3fi3_fragments.sdf',
+         'jnk/3fi3_linker.sdf')
 CASES = {'hsp90': ('3hz1_modified_fragments_obabel.sdf', '3hz1_protein.pdb'),
          'jnk': ('3fi3_fragments.sdf', '3fi3_protein.pdb')}
 
@@ -34,3 +37,10 @@ for case, (sdf, pdb) in CASES.items():
     with open(os.path.join(out, f'{case}_protein_12A.pdb'), 'w') as f:
         f.write('\n'.join(kept) + '\nEND\n')
     print(case, len(frag), 'fragment atoms;', len(kept), 'of', len(atoms), 'protein atoms kept')
+
+for rel in WHOLE:
+    dst = os.path.join(HERE, 'case_studies', rel)
+    os.makedirs(os.path.dirname(dst), exist_ok=True)
+    shutil.copy(os.path.join(REF, rel), dst)
+    os.chmod(dst, 0o644)
+    print('copied', rel)

@@ -494,6 +494,20 @@ def xyz_writer():
     save('xyz_writer', **out)
 
 
+def reference_init():
+    """``Dynamics`` as the reference initialises it after ``torch.manual_seed(7)`` (test_host_logic.py::
+    test_same_seed_same_init_as_reference): per tensor, in registration order, its shape and the SHA-256 of its float32 bytes."""
+    import hashlib
+    import json
+    torch.manual_seed(7)
+    ref = Dynamics(n_dims=3, in_node_nf=8, context_node_nf=1, hidden_nf=128, n_layers=2, norm_constant=1e-6)
+    out = [[k, list(v.shape), hashlib.sha256(v.detach().float().contiguous().numpy().tobytes()).hexdigest()]
+           for k, v in ref.state_dict().items()]
+    with open(os.path.join(HERE, 'reference_init_seed7.json'), 'w') as f:
+        f.write('[\n' + ',\n'.join(json.dumps(row) for row in out) + '\n]\n')
+    print('wrote reference_init_seed7', len(out), 'tensors')
+
+
 if __name__ == '__main__':
     torch.set_num_threads(8)
     if len(sys.argv) > 1:                                  # regenerate selected fixtures only
@@ -502,6 +516,7 @@ if __name__ == '__main__':
         sys.exit(0)
     c1_chain()
     ddpm_glue()
+    reference_init()
     fc_forward_flags()
     xyz_writer()
     gamma_tables()

@@ -1,5 +1,5 @@
-"""CPU tests of the RDKit-free molecule I/O (difflinker_amd/io.py) on hand-made fixtures (tests/golden/io/) and,
-in the build container only, on the reference's case-study files."""
+"""CPU tests of the RDKit-free molecule I/O (difflinker_amd/io.py) on hand-made fixtures (tests/golden/io/) and on the
+reference's case-study files (copies under tests/golden/io/case_studies/, made by make_case_studies.py)."""
 import os
 
 import numpy as np
@@ -10,7 +10,7 @@ from difflinker_amd import const, io
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 IO_DIR = os.path.join(HERE, 'golden', 'io')
-CASES = '/root/reference/case_studies'
+CASES = os.path.join(IO_DIR, 'case_studies')          # the reference's case_studies/ layout, the files the tests read
 
 
 def test_sdf_first_record_without_hydrogens():
@@ -76,7 +76,6 @@ def test_xyz_roundtrip_and_format(tmp_path):
     assert back.symbols == ['C', 'Cl', 'P']
 
 
-@pytest.mark.skipif(not os.path.isdir(CASES), reason='reference tree only exists in the build container')
 def test_reference_case_study_files_parse():
     frag = io.read_molecule(os.path.join(CASES, 'hsp90', '3hz1_original_fragments.sdf'))
     assert len(frag) == 27 and set(frag.symbols) <= set(const.GEOM_ATOM2IDX)
