@@ -19,6 +19,7 @@ Out of scope (training only): ``EDM.forward`` and the likelihood/KL terms (edm.p
 ``GammaNetwork`` schedule.
 """
 import ctypes
+import functools
 import os
 import threading
 import warnings
@@ -34,14 +35,26 @@ from .noise import PredefinedNoiseSchedule
 
 # measured +2.8 .. 3.2 % on the C2 headline, same box (profiles/r05/ab_split_chain.log); DIFFLINKER_SPLIT_CHAIN=0 turns it off
 SPLIT_CHAIN_DEFAULT = os.environ.get('DIFFLINKER_SPLIT_CHAIN', '1') == '1'
-SPLIT_STAGES_DEFAULT = int(os.environ.get('DIFFLINKER_SPLIT_STAGES', '2'))
-XCD_ORDER_MODE = int(os.environ.get('DIFFLINKER_XCD_ORDER', '2'))
-XCD_AWARE_ORDER = XCD_ORDER_MODE != 0
 
 
 def compute_units(dev):
     """compute units of the device (256 on an MI355X): what one-molecule-per-compute-unit launches fill"""
     return torch.cuda.get_device_properties(dev).multi_processor_count
+
+
+@functools.lru_cache(maxsize=None)
+def xcd_layout(bs):
+    """Launch positions of a size-sorted batch of `bs` molecules that fits the chip in one wave: ``order[xcd_layout(bs)]``.
+    Workgroup k runs on XCD k % 8 (observed dispatch pattern; only speed depends on it), and the compute units of an XCD share
+    one 4 MB L2 through which each of them streams the same 5.8 MB of weights per forward.  Molecules of SIMILAR SIZE on one XCD
+    stay in phase, and a weight chunk one of them pulled in is still there when the others ask: the sorted batch is cut into
+    16 runs of ceil(bs / 16) and every XCD gets two, one from the big end and one from the small end, dealt in a zig-zag (run
+    xcd and run 15 - xcd): the same load on every XCD.  A CPU int64 tensor, a permutation of range(bs)."""
+    ln = -(-bs // 16)
+    k = np.arange(16 * ln)
+    xcd, j = k % 8, k // 8
+    idx = np.where(j < ln, xcd, 15 - xcd) * ln + j % ln
+    return torch.from_numpy(idx[idx < bs])
 
 
 def _pass_steps(receivers, senders):
@@ -62,28 +75,28 @@ def forward_cost(n, n_linker, n_layers, sublayers, team=1):
     return n_layers * (sublayers * (_pass_steps(own, n) + a_gcl) + _pass_steps(own_l, n) + a_eq)
 
 
+# The plan cache, and per device the side stream and the workspace of the launch on it, are shared by every EDM of the process;
+# _CACHE_LOCK guards the three dicts (lookup and insertion), not the tensors or streams in them.  One side workspace per device
+# is safe for any number of EDMs and caller streams because only the team launch beside the main one (_sample_chain_fused)
+# uses it, and that launch always runs on the device's one side stream, which serializes every use of the workspace.
+_CACHE_LOCK = threading.Lock()
 _PLAN_CACHE = {}
-_CACHE_LOCK = threading.Lock()           # the plan cache, the side streams and their workspaces are shared by every EDM of the process
-_SPLIT_QSCALE = os.environ.get('DIFFLINKER_SPLIT_QSCALE', '1.0')          # (calibration experiments: scripts/r5/ab_split_qscale.sh)
+_SIDE_STREAMS = {}
+_SIDE_WORKSPACE = {}
 
 
-def split_plan(sizes, linkers, n_calls, compute_units, n_layers, sublayers, min_gain=0.02, grid=48, allow_singles=None):
+def split_plan(sizes, linkers, n_calls, compute_units, n_layers, sublayers, min_gain=0.02, grid=48):
     """The static hand-over inside a ragged batch that holds one compute unit per molecule.  FIRST launch: every molecule on its
     compute unit for about the same time tau - the small molecules complete their chain, every other molecule b stops after
-    s_b = floor(tau / cost_b) denoiser calls and leaves its state in HBM.  SECOND phase: the unfinished molecules finish on TEAMS
+    s_b = floor(tau / cost_b) denoiser calls and leaves its state in HBM.  SECOND launch: the unfinished molecules finish on TEAMS
     OF TWO, which take the compute units the small ones left (2 x teams <= compute units).  tau runs over a grid between the
     cheapest and the dearest molecule's chain; the plan with the smallest predicted makespan wins, provided it beats the single
     launch by `min_gain`.  A function of the sizes alone (cached by them).
-    ``allow_singles`` (measured, not adopted: profiles/r05/ab_split_chain.log): when the compute units do not suffice for teams
-    everywhere, the molecules with the least work left resume on ONE compute unit each in a launch beside the teams' - a better
-    makespan on paper (0.90 instead of 0.94 of the single launch at C2), a worse one on the chip, whose power cap taxes a first
-    launch that keeps every compute unit busy to its end.
-    Returns (q_end of the first launch [B], molecules for teams, molecules for single compute units) or None."""
+    Returns (q_end of the first launch [B], molecules for teams) or None."""
     B = len(sizes)
     if B > compute_units or B == 0:
         return None
-    allow_singles = bool(allow_singles)
-    key = (tuple(sizes), tuple(linkers), n_calls, compute_units, n_layers, sublayers, min_gain, grid, bool(allow_singles), _SPLIT_QSCALE)
+    key = (tuple(sizes), tuple(linkers), n_calls, compute_units, n_layers, sublayers, min_gain, grid)
     with _CACHE_LOCK:
         if key in _PLAN_CACHE:
             return _PLAN_CACHE[key]
@@ -99,101 +112,19 @@ def split_plan(sizes, linkers, n_calls, compute_units, n_layers, sublayers, min_
         tau = lo + (single - lo) * i / grid
         q_end = np.clip((tau / c1).astype(np.int64), 1, n_calls)
         rest = np.nonzero(q_end < n_calls)[0]
-        if rest.size == 0:
+        if rest.size == 0 or 2 * rest.size > compute_units:        # every unfinished molecule on a team of two
             continue
         left1 = (n_calls - q_end[rest]) * c1[rest]
-        rest = rest[np.lexsort((rest, -left1))]                     # most work left first; ties by index: deterministic
-        m = min(rest.size, compute_units - rest.size)               # teams of two: 2 m + (unfinished - m) <= compute units
-        if m < 0 or (m < rest.size and not allow_singles):
-            continue
-        teams, singles = rest[:m], rest[m:]
-        second = max(float(((n_calls - q_end[teams]) * c2[teams]).max()) if m else 0.0,
-                     float(((n_calls - q_end[singles]) * c1[singles]).max()) if singles.size else 0.0)
-        total = float((q_end * c1).max()) + second
+        teams = rest[np.lexsort((rest, -left1))]                    # most work left first; ties by index: deterministic
+        total = float((q_end * c1).max()) + float(((n_calls - q_end[teams]) * c2[teams]).max())
         if best is None or total < best[0]:
-            best = (total, q_end.tolist(), teams.tolist(), singles.tolist())
-    plan = None if best is None or best[0] > (1.0 - min_gain) * single else (best[1], best[2], best[3])
-    qscale = float(_SPLIT_QSCALE)
-    if plan is not None and qscale != 1.0:
-        stop = set(plan[1]) | set(plan[2])
-        plan = ([max(1, min(n_calls - 1, int(round(q * qscale)))) if b in stop else q for b, q in enumerate(plan[0])], plan[1], plan[2])
+            best = (total, q_end.tolist(), teams.tolist())
+    plan = None if best is None or best[0] > (1.0 - min_gain) * single else (best[1], best[2])
     with _CACHE_LOCK:
         if len(_PLAN_CACHE) > 64:
             _PLAN_CACHE.clear()
         _PLAN_CACHE[key] = plan
     return plan
-
-
-def split_plan_stages(sizes, linkers, n_calls, compute_units, n_layers, sublayers, max_stages=6, min_gain=0.02):
-    """The hand-over of split_plan in MORE than two stages (round 6).  split_plan waits until the
-    43..45-atom molecules are done before any compute unit changes hands: the compute units of the 35..40-atom molecules idle for
-    up to a third of the first launch.  Here a stage ends when a number of molecules have completed their chain; the compute
-    units they leave go, at once, to the unfinished molecules with the most work left, which run as TEAMS OF TWO from then on.
-    Every stage is one launch of the molecules still on one compute unit (the current stream) beside one launch of the teams
-    (the side stream); a molecule's state crosses a stage boundary through dl_chain_args.z_state.  Within a stage every workgroup
-    is busy for about the stage's length: molecule b runs floor(length / cost_b) denoiser calls.
-    The number of completions that ends a stage is searched over a small grid; the plan with the smallest predicted makespan and
-    at most `max_stages` stages wins, provided it beats the single launch by `min_gain` (cost model: forward_cost).
-    A function of the sizes alone (cached).  Returns a list of stages ``(q_end [B] - calls completed when the stage ends,
-    teams - molecules it runs on teams of two, singles - on one compute unit)``, or None."""
-    B = len(sizes)
-    if B > compute_units or B == 0:
-        return None
-    key = ('stages', tuple(sizes), tuple(linkers), n_calls, compute_units, n_layers, sublayers, max_stages, min_gain)
-    with _CACHE_LOCK:
-        if key in _PLAN_CACHE:
-            return _PLAN_CACHE[key]
-    table = {}
-    for n, l in set(zip(sizes, linkers)):
-        table[(n, l)] = (forward_cost(n, l, n_layers, sublayers, 1), forward_cost(n, l, n_layers, sublayers, 2))
-    c1 = np.array([table[k][0] for k in zip(sizes, linkers)])
-    c2 = np.array([table[k][1] for k in zip(sizes, linkers)])
-    single = float(c1.max()) * n_calls
-
-    def simulate(events):
-        left = np.full(B, n_calls, dtype=np.int64)
-        mode = np.ones(B, dtype=np.int64)
-        done = np.zeros(B, dtype=np.int64)
-        total, stages = 0.0, []
-        while (left > 0).any():
-            act = np.nonzero(left > 0)[0]
-            free = compute_units - int(mode[act].sum())
-            if stages:                                                  # (the first stage: everybody on one compute unit)
-                cand = [b for b in act if mode[b] == 1]
-                cand.sort(key=lambda b: (-left[b] * c1[b], b))          # most work left first; ties by index: deterministic
-                # teams of two sit in groups of eight molecules (dl_team_max): at most compute_units / 2 of them, rounded down to 8
-                room = (compute_units // 2) // 8 * 8 - int((mode[act] == 2).sum())
-                for b in cand[:max(0, min(free, room))]:
-                    mode[b] = 2
-            cost = np.where(mode == 2, c2, c1)
-            fin = np.sort(left[act] * cost[act])
-            tau = float(fin[min(len(fin) - 1, events - 1)])
-            calls = np.minimum(left[act], np.maximum(1, np.floor(tau / cost[act]).astype(np.int64)))
-            total += float((calls * cost[act]).max())
-            left[act] -= calls
-            done[act] += calls
-            stages.append((done.tolist(), [int(b) for b in act if mode[b] == 2], [int(b) for b in act if mode[b] == 1]))
-            if len(stages) > max_stages:
-                return None
-        return total, stages
-
-    best = None
-    for events in (12, 16, 24, 32, 48, 64, 96, 128):
-        got = simulate(events)
-        if got is not None and len(got[1]) >= 2 and (best is None or got[0] < best[0]):
-            best = got
-    plan = None if best is None or best[0] > (1.0 - min_gain) * single else best[1]
-    with _CACHE_LOCK:
-        if len(_PLAN_CACHE) > 64:
-            _PLAN_CACHE.clear()
-        _PLAN_CACHE[key] = plan
-    return plan
-
-
-# second stream (and its workspace) of the launch that samples the molecules beyond one per compute unit on teams
-# (EDM._sample_chain_fused); per device, shared by every EDM of the process - launches on one stream are ordered
-_SIDE_STREAMS = {}
-_SIDE_WORKSPACE = {}
 
 
 class EDM(torch.nn.Module):
@@ -244,9 +175,6 @@ class EDM(torch.nn.Module):
         # rounding); the plan is a function of the batch's sizes alone, so a batch is sampled bit for bit the same every time.
         # False: one launch, every molecule on one compute unit for the whole chain.
         self.split_chain = SPLIT_CHAIN_DEFAULT
-        # how many launches deep the hand-over may go (split_plan_stages; 2 = the two launches of round 5: split_plan)
-        self.split_stages = SPLIT_STAGES_DEFAULT
-        self.split_singles = os.environ.get('DIFFLINKER_SPLIT_SINGLES', '0') == '1'     # (measured, not adopted: see split_plan)
 
     @staticmethod
     def _side_stream(dev):
@@ -258,7 +186,8 @@ class EDM(torch.nn.Module):
 
     @staticmethod
     def _side_workspace(key, need, dev):
-        """scratch of a launch beside the main one, one buffer per (device, role): grown, never shrunk, reused by every chain"""
+        """scratch of the team launch beside the main one, one buffer per key (device, 'teams'): grown, never shrunk, reused by
+        every chain (see _CACHE_LOCK)"""
         with _CACHE_LOCK:
             ws = _SIDE_WORKSPACE.get(key)
             if ws is None or ws.numel() < need:
@@ -576,8 +505,10 @@ class EDM(torch.nn.Module):
 
     def _sample_chain_fused(self, x, h, node_mask, fragment_mask, linker_mask, edge_mask, context, keep_frames, noise_bank,
                             seed, mol_offset, mol_index, team=None):
-        """The whole chain as ONE launch (``dl_sample_chain_fc``).  ``noise_bank`` = device tensors, or None: draws generated
-        in the kernel from ``seed`` and the molecules' global indices ``mol_offset + mol_index[b]`` (``mol_index`` None: b)."""
+        """The whole chain as ONE launch (``dl_sample_chain_fc``) on the current stream, plus at most one launch of teams beside
+        it on the side stream: the molecules beyond one per compute unit (overflow teams), or those that resume after the first
+        launch's q_end (split_plan).  ``noise_bank`` = device tensors, or None: draws generated in the kernel from ``seed`` and
+        the molecules' global indices ``mol_offset + mol_index[b]`` (``mol_index`` None: b)."""
         dev = x.device
         lib = _lib.load()
         bs, n = x.size(0), x.size(1)
@@ -597,26 +528,9 @@ class EDM(torch.nn.Module):
         # with n_b^2, so the big ones are launched first (matters once the batch exceeds the number of compute units)
         n_real = nm.ne(0).sum(1)
         order = torch.argsort(n_real, descending=True, stable=True).to(torch.int32).contiguous()
-        if XCD_AWARE_ORDER and bs <= compute_units(dev) and bs >= 16:
-            # a batch that fits the chip in one wave of workgroups: workgroup k runs on XCD k % 8 (observed dispatch pattern; only
-            # speed depends on it), and the compute units of an XCD share one 4 MB L2 through which each of them streams the same
-            # 5.8 MB of weights per forward.  Molecules of SIMILAR SIZE on one XCD stay in phase, and a weight chunk one of them
-            # pulled in is still there when the others ask: deal the size-sorted molecules to the XCDs in contiguous runs
-            if XCD_ORDER_MODE >= 2:
-                # ... R runs per XCD (2: one from the big end and one from the small end of the sorted batch), dealt in a zig-zag:
-                # the same load on every XCD
-                R = XCD_ORDER_MODE
-                ln = -(-bs // (8 * R))
-                k = torch.arange(8 * R * ln, device=dev)
-                x, j = k % 8, k // 8
-                r = j // ln                                   # which of the XCD's runs
-                run = torch.where(r % 2 == 0, 8 * r + x, 8 * r + 7 - x)
-                idx = run * ln + j % ln
-            else:
-                per = -(-bs // 8)
-                k = torch.arange(8 * per, device=dev)
-                idx = (k % 8) * per + k // 8
-            order = order[idx[idx < bs]].contiguous()
+        cus = compute_units(dev)
+        if 16 <= bs <= cus:                 # a batch that fits the chip in one wave of workgroups: two size runs per XCD
+            order = order[xcd_layout(bs).to(dev)].contiguous()
         chain = torch.zeros((keep_frames, bs, n, self.n_dims + nf), device=dev)
         flags = torch.zeros(bs, dtype=torch.int32, device=dev)
         steps = torch.full((bs,), -1, dtype=torch.int32, device=dev)
@@ -631,7 +545,6 @@ class EDM(torch.nn.Module):
         # launch leave after ~0.6 of the chain, and a team of four samples a 35-atom molecule in a quarter of the chain.
         over = 0
         if team == 1 and self.overflow_teams and self.team_batch is None and not self.dynamics._no_teams:
-            cus = torch.cuda.get_device_properties(dev).multi_processor_count
             if cus < bs <= cus + cus // 4:
                 over = bs - cus
                 team2 = 4 if over <= cus // 16 else 2
@@ -654,27 +567,20 @@ class EDM(torch.nn.Module):
         # molecules at hand, and a molecule's sample must not depend on how its batch was split - SURVEY 8e)
         plan = None
         if team == 1 and over == 0 and self.split_chain and self.team_batch is None and not self.dynamics._no_teams \
-                and bs <= compute_units(dev) and T >= 20:
+                and bs <= cus and T >= 20:
             counts = torch.stack([n_real, lm.ne(0).sum(1)]).cpu()             # ONE device-to-host copy: sizes and linker sizes
             sizes_h, linkers_h = counts[0].tolist(), counts[1].tolist()
             if max(sizes_h) <= int(lib.dl_max_atoms()) and min(sizes_h) > 0:
-                sub_ = int(getattr(self.dynamics, 'inv_sublayers', 2))
-                if int(self.split_stages) > 2:
-                    plan = split_plan_stages(sizes_h, linkers_h, T + 1, compute_units(dev), self.dynamics.n_layers, sub_,
-                                             max_stages=int(self.split_stages))
-                else:
-                    two = split_plan(sizes_h, linkers_h, T + 1, compute_units(dev), self.dynamics.n_layers, sub_,
-                                     allow_singles=bool(self.split_singles))
-                    # (as a list of stages: everybody on one compute unit up to q_end, then the teams and the single ones to the end)
-                    plan = None if two is None else [(two[0], [], list(range(bs))), ([T + 1] * bs, two[1], two[2])]
-                if plan is not None and any(t_ and int(lib.dl_team_max(len(t_))) < 2 for _, t_, _ in plan):
-                    plan = None                                               # the teams of a stage would not fit at once
+                plan = split_plan(sizes_h, linkers_h, T + 1, cus, self.dynamics.n_layers,
+                                  int(getattr(self.dynamics, 'inv_sublayers', 2)))
+                if plan is not None and int(lib.dl_team_max(len(plan[1]))) < 2:
+                    plan = None                                               # the teams would not fit at once
         q_end_t = z_state = None
         if plan is not None:
-            q_end_t = torch.tensor(plan[0][0], dtype=torch.int32, device=dev)
+            q_end_t = torch.tensor(plan[0], dtype=torch.int32, device=dev)
             z_state = torch.empty((bs, n, self.n_dims + nf), device=dev)
 
-        def chain_args(flags_, steps_, team_, ws_, ws_bytes_, first, count, q_begin=None, q_end=None, skip=None, order_=None):
+        def chain_args(flags_, steps_, team_, ws_, ws_bytes_, order_, first, count, q_begin=None, q_end=None, skip=None):
             return _lib.DLChainArgs(
                 q_begin=q_begin.data_ptr() if q_begin is not None else None, q_end=q_end.data_ptr() if q_end is not None else None,
                 z_state=z_state.data_ptr() if z_state is not None else None, skip_flags=skip.data_ptr() if skip is not None else None,
@@ -686,91 +592,56 @@ class EDM(torch.nn.Module):
                 noise_seed=seed, mol_offset=int(mol_offset), team=team_, coefs=coefs.data_ptr(),
                 inv_alpha0=inv_alpha0, sigma0=sigma0, sigma_x=sigma_x,
                 norm_x=float(self.norm_values[0]), norm_h=float(self.norm_values[1]), bias_h=float(self.norm_biases[1]),
-                chain=chain.data_ptr(), nan_flags=flags_.data_ptr(), nan_step=steps_.data_ptr(),
-                order=(order if order_ is None else order_).data_ptr(),
+                chain=chain.data_ptr(), nan_flags=flags_.data_ptr(), nan_step=steps_.data_ptr(), order=order_.data_ptr(),
                 workspace=ws_.data_ptr(), workspace_bytes=ws_bytes_,
                 mol_index=mol_index.data_ptr() if mol_index is not None else None, order_first=first, order_count=count)
-        args = chain_args(flags, steps, team, ws, ws_bytes, 0, bs - over if over else 0, q_end=q_end_t)
+
+        def side_launch(after, team_, order_, first, count, q_begin=None):
+            """The launch of teams beside the main one: on the device's side stream behind the event `after`, the current stream
+            behind it.  `q_begin`: the molecules resume from z_state, skipping those the first launch flagged.  Its own flag
+            arrays (the team entry point clears them on its stream); returns flags and steps merged with the main launch's."""
+            side = self._side_stream(dev)
+            flags2 = torch.empty(bs, dtype=torch.int32, device=dev)
+            steps2 = torch.empty(bs, dtype=torch.int32, device=dev)
+            need = int(lib.dl_workspace_bytes(count, team_))
+            ws2 = self._side_workspace((dev.index, 'teams'), need, dev)
+            skip = flags if q_begin is not None else None
+            args2 = chain_args(flags2, steps2, team_, ws2, need, order_, first, count, q_begin=q_begin, skip=skip)
+            side.wait_event(after)
+            _lib.check(lib.dl_sample_chain_fc(handle, ctypes.byref(args2), ctypes.c_void_p(side.cuda_stream)),
+                       'dl_sample_chain_fc (teams, beside the main launch)')
+            done = torch.cuda.Event()
+            done.record(side)
+            cur.wait_event(done)
+            for t_ in (xs, hs, nm, fm, lm, em, ctx, coefs, order_, chain, noise_x, noise_h, mol_index, q_begin, z_state, skip):
+                if t_ is not None:
+                    t_.record_stream(side)                 # the caching allocator must not hand these out while the side launch runs
+            return flags | flags2, torch.where(steps2 >= 0, steps2, steps)
+
+        args = chain_args(flags, steps, team, ws, ws_bytes, order, 0, bs - over if over else 0, q_end=q_end_t)
+        profile = bool(getattr(self, 'profile_events', False))      # bench.py: HIP events right around the launches
         with torch.cuda.device(dev):
             cur = torch.cuda.current_stream(dev)
-            if getattr(self, 'profile_events', False):     # bench.py: HIP events right around the launch
+            if profile:
                 ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 ev0.record(cur)
             if over:
-                # (its own flag arrays: the team entry point clears them on its stream; its own workspace: the launches overlap)
-                side = self._side_stream(dev)
-                flags2 = torch.zeros(bs, dtype=torch.int32, device=dev)
-                steps2 = torch.full((bs,), -1, dtype=torch.int32, device=dev)
-                need2 = int(lib.dl_workspace_bytes(over, team2))
-                ws2 = self._side_workspace((dev.index, 'teams'), need2, dev)
-                args2 = chain_args(flags2, steps2, team2, ws2, need2, bs - over, over)
                 ready = torch.cuda.Event()
                 ready.record(cur)                          # inputs, coefficients, noise bank: enqueued on the current stream
             _lib.check(lib.dl_sample_chain_fc(handle, ctypes.byref(args), ctypes.c_void_p(cur.cuda_stream)),
                        'dl_sample_chain_fc')
             if over:
-                side.wait_event(ready)
-                _lib.check(lib.dl_sample_chain_fc(handle, ctypes.byref(args2), ctypes.c_void_p(side.cuda_stream)),
-                           'dl_sample_chain_fc (molecules beyond one per compute unit, on teams)')
-                done = torch.cuda.Event()
-                done.record(side)
-                cur.wait_event(done)
-                for t_ in (xs, hs, nm, fm, lm, em, ctx, coefs, order, chain, noise_x, noise_h, mol_index):
-                    if t_ is not None:
-                        t_.record_stream(side)             # the caching allocator must not hand these out while the side launch runs
-                flags = flags | flags2
-                steps = torch.where(steps2 >= 0, steps2, steps)
+                # the molecules beyond one per compute unit, on teams beside the first launch
+                flags, steps = side_launch(ready, team2, order, bs - over, over)
             if plan is not None:
-                # later stages: the molecules with the most work left resume from z_state on teams of two (a launch on the side stream),
-                # the others on one compute unit each (a launch on this stream) - side by side, both behind the stage before; a
-                # molecule that ended in an earlier launch (NaN) is skipped
-                by_size = lambda idx: torch.tensor(sorted(idx, key=lambda b_: (-sizes_h[b_], b_)), dtype=torch.int32, device=dev)  # noqa: E731
-                after_first = torch.cuda.Event(enable_timing=bool(getattr(self, 'profile_events', False)))
+                # the molecules with the most work left resume from z_state on teams of two, behind the first launch, biggest first
+                after_first = torch.cuda.Event(enable_timing=profile)
                 after_first.record(cur)
                 self.last_split_event = after_first
-                side = self._side_stream(dev)
-                q_begin_t = q_end_t
-                for si in range(1, len(plan)):
-                    q_end_list, teams_, singles_ = plan[si]
-                    last = si == len(plan) - 1
-                    q_end_s = None if last else torch.tensor(q_end_list, dtype=torch.int32, device=dev)
-                    boundary = torch.cuda.Event()
-                    boundary.record(cur)               # everything of the stages before is behind this point of the current stream
-                    parts = []
-                    if teams_:
-                        rest, m2 = by_size(teams_), len(teams_)
-                        flags2 = torch.zeros(bs, dtype=torch.int32, device=dev)
-                        steps2 = torch.full((bs,), -1, dtype=torch.int32, device=dev)
-                        need2 = int(lib.dl_workspace_bytes(m2, 2))
-                        ws2 = self._side_workspace((dev.index, 'teams'), need2, dev)
-                        args2 = chain_args(flags2, steps2, 2, ws2, need2, 0, m2, q_begin=q_begin_t, q_end=q_end_s, skip=flags, order_=rest)
-                        side.wait_event(boundary)
-                        _lib.check(lib.dl_sample_chain_fc(handle, ctypes.byref(args2), ctypes.c_void_p(side.cuda_stream)),
-                                   'dl_sample_chain_fc (a later stage of a split chain: teams of two)')
-                        done2 = torch.cuda.Event()
-                        done2.record(side)
-                        parts.append((flags2, steps2, done2, rest))
-                    if singles_:
-                        rest1, m1 = by_size(singles_), len(singles_)
-                        flags3 = torch.zeros(bs, dtype=torch.int32, device=dev)
-                        steps3 = torch.full((bs,), -1, dtype=torch.int32, device=dev)
-                        need3 = int(lib.dl_workspace_bytes(m1, 1))
-                        ws3 = self._side_workspace((dev.index, 'singles'), need3, dev)
-                        args3 = chain_args(flags3, steps3, 1, ws3, need3, 0, m1, q_begin=q_begin_t, q_end=q_end_s, skip=flags, order_=rest1)
-                        _lib.check(lib.dl_sample_chain_fc(handle, ctypes.byref(args3), ctypes.c_void_p(cur.cuda_stream)),
-                                   'dl_sample_chain_fc (a later stage of a split chain: one compute unit each)')
-                        parts.append((flags3, steps3, None, rest1))
-                    for f_, s_, done_, rest_ in parts:
-                        if done_ is not None:
-                            cur.wait_event(done_)
-                            for t_ in (xs, hs, nm, fm, lm, em, ctx, coefs, rest_, chain, noise_x, noise_h, mol_index, q_begin_t, q_end_s, z_state, flags):
-                                if t_ is not None:
-                                    t_.record_stream(side)
-                        # (the single-compute-unit kernel initialises its molecules' words itself: 0 / -1; merge only what the phase set)
-                        flags = flags | f_
-                        steps = torch.where(s_ >= 0, s_, steps)
-                    q_begin_t = q_end_s
-            if getattr(self, 'profile_events', False):
+                teams = sorted(plan[1], key=lambda b_: (-sizes_h[b_], b_))
+                flags, steps = side_launch(after_first, 2, torch.tensor(teams, dtype=torch.int32, device=dev), 0, len(teams),
+                                           q_begin=q_end_t)
+            if profile:
                 ev1.record(cur)
                 self.last_kernel_events = (ev0, ev1)
         self._raise_on_chain_flags(flags, steps)

@@ -478,34 +478,26 @@ def test_non_finite_weights_reach_the_kernels_and_raise(bad):
 
 
 # ---- a chain in two phases: the static hand-over --------------------------------------------------------------------------
-@pytest.mark.parametrize('case', ['teams only', 'teams and single compute units'])
-def test_split_chain_hands_compute_units_over_and_samples_the_oracles_chain(case):
+def test_split_chain_hands_compute_units_over_and_samples_the_oracles_chain():
     """``EDM.split_chain``: the small molecules of a ragged batch complete in the first launch, the others stop at the call where
-    the small ones end (dl_chain_args.q_end), leave their state in HBM and finish in a second phase (q_begin, z_state) - the ones
-    with the most work left on teams of two, and, when the compute units do not suffice for teams everywhere (the second case:
-    more unfinished molecules than half the compute units - the shape of the C2 plan: 124 teams + 8 singles), the rest on one compute
-    unit each, side by side (here 136 unfinished: 120 teams + 16 singles).  The chain must be the oracle's - every kept frame - and agree with the one-launch chain to fp32
-    rounding (the steps on teams sum messages in the team's order); molecules that never run on a team are bit-identical;
-    repeatable bit for bit; the plan comes from the sizes alone."""
+    the small ones end (dl_chain_args.q_end), leave their state in HBM and finish in a second launch (q_begin, z_state) on teams
+    of two.  The chain must be the oracle's - every kept frame - and agree with the one-launch chain to fp32 rounding (the steps
+    on teams sum messages in the team's order); molecules that never run on a team are bit-identical; repeatable bit for bit;
+    the plan comes from the sizes alone."""
     from difflinker_amd import edm as edm_mod
-    nf, L, T = 8, (2 if case == 'teams only' else 1), 24
-    if case == 'teams only':
-        sizes, linkers = [50, 48, 50, 47, 20, 22, 18, 25, 21, 19, 23, 20], [8, 7, 9, 6, 4, 5, 3, 6, 4, 4, 5, 4]
-    else:
-        sizes, linkers = [30] * 100 + [26] * 36 + [10] * 60, [6] * 100 + [5] * 36 + [3] * 60          # 136 unfinished: 120 teams + 16 singles
+    nf, L, T = 8, 2, 24
+    sizes, linkers = [50, 48, 50, 47, 20, 22, 18, 25, 21, 19, 23, 20], [8, 7, 9, 6, 4, 5, 3, 6, 4, 4, 5, 4]
     cus = torch.cuda.get_device_properties(P.dev()).multi_processor_count
-    plan = edm_mod.split_plan(sizes, linkers, T + 1, cus, L, 2, allow_singles=(case != 'teams only'))
+    plan = edm_mod.split_plan(sizes, linkers, T + 1, cus, L, 2)
     assert plan is not None
-    q_end, teams, singles = plan
-    assert teams and all(0 < q_end[b] < T + 1 for b in teams + singles) and 2 * len(teams) + len(singles) <= cus
-    assert (len(singles) > 0) == (case != 'teams only')
-    untouched = sorted(set(range(len(sizes))) - set(teams))              # complete in the first launch, or resume on ONE compute unit
+    q_end, teams = plan
+    assert teams and all(0 < q_end[b] < T + 1 for b in teams) and 2 * len(teams) <= cus
+    untouched = sorted(set(range(len(sizes))) - set(teams))              # complete in the first launch
     dyn, sd, cfg = P.make_dynamics(nf, 1, L, seed=171)
     dyn.team = 1
     inp, _, _ = P.ragged_inputs(sizes, linkers, nf, seed=172)
     B, N = inp['x'].shape[:2]
     edm = _edm(dyn, nf, T)
-    edm.split_singles = case != 'teams only'        # (the variant with single compute units beside the teams is opt-in: split_plan)
     bank = edm_oracle.NoiseBank.generate(T, B, N, 3, nf, seed=173)
     orc = edm_oracle.EDMOracle(edm_oracle.make_dynamics_oracle(sd, cfg), in_node_nf=nf, timesteps=500)
     orc.T = T
@@ -526,7 +518,7 @@ def test_split_chain_hands_compute_units_over_and_samples_the_oracles_chain(case
         torch.cuda.synchronize()
         return out.cpu()
     got = run(True)
-    P.check_chain(f'split chain ({case}: {len(teams)} teams, {len(singles)} singles), T=24, 6 frames', got, want, inp)
+    P.check_chain(f'split chain ({len(teams)} teams), T=24, 6 frames', got, want, inp)
     assert torch.equal(got, run(True)), 'bitwise repeatable'
     one = run(False)
     assert torch.equal(got[:, untouched], one[:, untouched]), 'molecules that never run on a team: the bits of the one-launch chain'
@@ -548,7 +540,7 @@ def test_split_chain_reports_nans_of_either_launch_like_one_launch():
     from difflinker_amd.utils import FoundNaNException
     nf, L, T = 8, 1, 24
     sizes, linkers = [50, 48, 50, 47, 20, 22, 18, 25, 21, 19, 23, 20], [8, 7, 9, 6, 4, 5, 3, 6, 4, 4, 5, 4]
-    q_end, teams, _ = edm_mod.split_plan(sizes, linkers, T + 1, 256, L, 2)
+    q_end, teams = edm_mod.split_plan(sizes, linkers, T + 1, 256, L, 2)
     assert 0 in teams and 2 in teams and 3 < q_end[0] < T - 3
     dyn, sd, cfg = P.make_dynamics(nf, 1, L, seed=181)
     dyn.team = 1

@@ -449,7 +449,7 @@ def test_found_nan_exception_from_index_sets_and_split_terms():
 
 def test_split_plan_is_a_deterministic_feasible_function_of_the_sizes():
     """``edm.split_plan`` (the static hand-over of a chain in two launches): deterministic, a function of the sizes alone; every
-    unfinished molecule stops strictly inside the chain; the second phase fits the chip (2 x teams + singles <= compute units);
+    unfinished molecule stops strictly inside the chain; the second launch fits the chip (2 x teams <= compute units);
     the predicted makespan beats the single launch; a uniform batch, a batch that leaves the chip room for teams anyway and a
     batch larger than the chip get no plan.  The C2 batch: the plan the benchmark runs (115 molecules of 43..50 atoms stop at
     call 427 of 501)."""
@@ -460,16 +460,13 @@ def test_split_plan_is_a_deterministic_feasible_function_of_the_sizes():
     linkers = data['linker_mask'].squeeze(-1).sum(1).long().tolist()
     plan = split_plan(sizes, linkers, 501, 256, 6, 2)
     assert plan == split_plan(list(sizes), list(linkers), 501, 256, 6, 2)
-    q_end, teams, singles = plan
-    assert singles == [] and len(teams) == 115 and min(q_end) == 427 and min(sizes[b] for b in teams) == 43
+    q_end, teams = plan
+    assert len(teams) == 115 and min(q_end) == 427 and min(sizes[b] for b in teams) == 43
     assert all(q_end[b] == 501 for b in range(256) if b not in teams) and all(0 < q_end[b] < 501 for b in teams)
     c1 = [forward_cost(n, l, 6, 2, 1) for n, l in zip(sizes, linkers)]
     c2 = [forward_cost(n, l, 6, 2, 2) for n, l in zip(sizes, linkers)]
     total = max(q_end[b] * c1[b] for b in range(256)) + max((501 - q_end[b]) * c2[b] for b in teams)
     assert total < 0.96 * max(c1) * 501
-    # with single compute units beside the teams (opt-in): more molecules stop, the chip is exactly full in the second phase
-    q2, t2, s2 = split_plan(sizes, linkers, 501, 256, 6, 2, allow_singles=True)
-    assert 2 * len(t2) + len(s2) <= 256 and len(s2) > 0 and set(t2).isdisjoint(s2) and all(0 < q2[b] < 501 for b in t2 + s2)
     # no plan: nothing to hand over / no room / more molecules than compute units
     assert split_plan([50] * 256, [8] * 256, 501, 256, 6, 2) is None
     assert split_plan([50] * 200 + [49] * 56, [8] * 256, 501, 256, 6, 2) is None
@@ -478,6 +475,24 @@ def test_split_plan_is_a_deterministic_feasible_function_of_the_sizes():
     assert forward_cost(35, 6, 6, 2) < forward_cost(43, 6, 6, 2) < forward_cost(50, 6, 6, 2)
     assert 1.3 < forward_cost(50, 8, 6, 2, 1) / forward_cost(50, 8, 6, 2, 2) < 2.0
 
+
+
+def test_xcd_layout_deals_the_size_sorted_batch_to_the_xcds_in_two_zig_zag_runs_each():
+    """``edm.xcd_layout`` (launch positions of a size-sorted batch that fits the chip in one wave; workgroup k runs on XCD
+    k % 8): a permutation of range(bs) - no molecule dropped or sampled twice - for every size up to beyond the chip.  The sorted
+    batch is cut into 16 runs of ceil(bs / 16): the first 8 x ceil(bs / 16) workgroups deal runs 0..7 round-robin (XCD x: run x,
+    from the big end), the rest runs 15..8 (XCD x: run 15 - x, from the small end) - a zig-zag.  With bs a multiple of 16 every
+    XCD holds exactly its two runs."""
+    from difflinker_amd.edm import xcd_layout
+    for bs in range(16, 321):
+        got = xcd_layout(bs).tolist()
+        assert sorted(got) == list(range(bs)), f'bs = {bs}: not a permutation'
+        ln = -(-bs // 16)
+        assert got[:8 * ln] == [x * ln + j for j in range(ln) for x in range(8)], f'bs = {bs}: the runs from the big end'
+        assert got[8 * ln:] == sorted(range(8 * ln, bs), key=lambda p: (p % ln, 15 - p // ln)), f'bs = {bs}: the runs from the small end'
+        if bs % 16 == 0:
+            for x in range(8):
+                assert got[x::8] == list(range(x * ln, (x + 1) * ln)) + list(range((15 - x) * ln, (16 - x) * ln)), (bs, x)
 
 def test_nan_flag_word_decodes_into_the_references_index_sets_and_the_f16_range_set():
     """include/difflinker_hip.h: bit0 NaN in the velocity, bit1 in the node features (utils.py:274-289: x&h / x only / h only),
