@@ -66,12 +66,29 @@ class DLChainArgs(ctypes.Structure):
     ]
 
 
+LOSS_ROW = 8          # DL_LOSS_ROW: error_t, |eps_hat|, kl_prior, log p(x|z0), log p(h|z0), log constant, SNR weight, atoms
+
+
+class DLLossArgs(ctypes.Structure):
+    _fields_ = [
+        ('B', ctypes.c_int32), ('N', ctypes.c_int32), ('nf', ctypes.c_int32), ('T', ctypes.c_int32),
+        ('timesteps', ctypes.c_int32), ('inpainting', ctypes.c_int32),
+        ('xh', ctypes.c_void_p), ('node_mask', ctypes.c_void_p), ('fragment_mask', ctypes.c_void_p),
+        ('linker_mask', ctypes.c_void_p), ('gamma_table', ctypes.c_void_p), ('noise_x', ctypes.c_void_p),
+        ('noise_h', ctypes.c_void_p), ('noise_seed', ctypes.c_uint64), ('mol_offset', ctypes.c_int32),
+        ('t_given', ctypes.c_int32), ('t_int', ctypes.c_void_p), ('t', ctypes.c_void_p), ('gamma', ctypes.c_void_p),
+        ('z_t', ctypes.c_void_p), ('eps_hat', ctypes.c_void_p), ('norm_h', ctypes.c_float), ('bias_h', ctypes.c_float),
+        ('prior', ctypes.c_void_p), ('rows', ctypes.c_void_p),
+    ]
+
+
 EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_string', 'dl_model_num_tensors',
            'dl_model_create', 'dl_model_destroy', 'dl_egnn_forward_fc', 'dl_sampler_step', 'dl_sample_chain_fc',
            'dl_set_profile_buffer', 'dl_profile_max_events', 'dl_pocket_workspace_bytes', 'dl_egnn_forward_pocket',
            'dl_size_model_num_tensors', 'dl_size_model_create', 'dl_size_model_destroy', 'dl_size_max_fragment_atoms',
            'dl_size_gnn_forward', 'dl_philox_fill', 'dl_egnn_forward_fc_large', 'dl_inpaint_step', 'dl_workspace_bytes',
-           'dl_team_max', 'dl_egnn_forward_fc_team', 'dl_team_max_atoms')
+           'dl_team_max', 'dl_egnn_forward_fc_team', 'dl_team_max_atoms',
+           'dl_edm_loss_prologue', 'dl_edm_loss_epilogue')
 TEST_HOOK_EXPORTS = ('dl_debug_team_fault',)       # declared under #ifdef DL_TEST_HOOKS: the test-hooks build only
 
 _lib = None
@@ -158,6 +175,9 @@ def _open(path):
     lib.dl_inpaint_step.argtypes = [i32, i32, i32] + [vp] * 10 + [DLInpaintCoef, vp, vp]
     lib.dl_philox_fill.restype = i32
     lib.dl_philox_fill.argtypes = [ctypes.c_uint64, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp]
+    for name in ('dl_edm_loss_prologue', 'dl_edm_loss_epilogue'):
+        getattr(lib, name).restype = i32
+        getattr(lib, name).argtypes = [ctypes.POINTER(DLLossArgs), vp]
     lib.dl_size_model_num_tensors.restype = i32
     lib.dl_size_model_num_tensors.argtypes = [ctypes.POINTER(DLSizeConfig)]
     lib.dl_size_model_create.restype = i32

@@ -15,8 +15,10 @@ of the reference's ``[B,1]`` shape (``step_coefficients``).  The reference evalu
 cancellation in sigma^2_{t|s} amplifies a 1-ulp difference of a device's transcendental to ~2e-5, so "same seed, same
 samples" is claimed — and tested (golden fixtures) — against the reference run on the CPU.
 
-Out of scope (training only): ``EDM.forward`` and the likelihood/KL terms (edm.py:41-124, 244-326), the learned
-``GammaNetwork`` schedule.
+``EDM.forward`` / ``InpaintingEDM.forward`` (edm.py:41-124, :467-548) evaluate the diffusion loss and the VLB terms of held-out
+data (:244-326): a HIP noising prologue, the unchanged denoiser, a HIP per-molecule epilogue; no backward.
+
+Out of scope (training only): the backward pass of the loss, the learned ``GammaNetwork`` schedule.
 """
 import ctypes
 import functools
@@ -194,9 +196,154 @@ class EDM(torch.nn.Module):
                 ws = _SIDE_WORKSPACE[key] = torch.empty(need, dtype=torch.uint8, device=dev)
             return ws
 
-    def forward(self, *args, **kwargs):
-        raise NotImplementedError('EDM.forward is the training loss (edm.py:41-124): out of scope of the '
-                                  'sampling hot path')
+    # ---- loss / VLB of held-out data (edm.py:41-124) -------------------------------------------------------
+    def forward(self, x, h, node_mask, fragment_mask, linker_mask, edge_mask, context=None, *, t_int=None, noise=None,
+                mol_offset=0):
+        """``EDM.forward`` (edm.py:41-124) for EVALUATION: one ``t`` per molecule, ``z_t`` from ``q(z_t | x, h)``, one denoiser
+        call, the diffusion L2 loss and the VLB terms.  Returns the reference's 7-tuple ``(delta_log_px, kl_prior, loss_term_t,
+        loss_term_0, l2_loss, noise_t, noise_0)`` with its batch reductions: ``loss_term_t`` / ``noise_t`` are NaN when no
+        molecule has ``t > 0`` (the reference's 0/0), ``loss_term_0`` / ``noise_0`` the float ``0.`` when none has ``t = 0``.
+
+        Three HIP launches: the noising prologue (``dl_edm_loss_prologue``), ``self.dynamics.forward`` (every kernel family,
+        pockets, teams and FoundNaNException as in sampling), the per-molecule epilogue (``dl_edm_loss_epilogue``).
+        Draws: ``noise_source='torch'`` - the reference's ``torch.randint`` then x- and h-``torch.randn`` on the tensors'
+        device; ``'philox'`` - drawn in the kernels from (``noise_seed``, ``mol_offset`` + row, atom), ``noise_seed`` advances
+        by one per call.  ``t_int`` (``[B]`` or ``[B,1]`` integers in ``0..T``) and ``noise = (noise_x [B,N,3], noise_h
+        [B,N,nf])`` (unmasked) override the draws; neither is in the reference signature.
+
+        Inference only: there is no backward (training is out of scope), so a call under grad mode with trainable dynamics
+        parameters raises instead of returning losses that silently carry no gradient."""
+        self._check_no_grad()
+        rows, t_int_d = self._loss_rows(x, h, node_mask, fragment_mask, linker_mask, edge_mask, context, t_int, noise,
+                                        mol_offset)
+        return self._reduce_loss_rows(rows, t_int_d)
+
+    _inpainting = False
+
+    def _check_no_grad(self):
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.dynamics.parameters()):
+            raise NotImplementedError('EDM.forward evaluates the loss without a backward pass (training is out of scope): '
+                                      'wrap the call in torch.no_grad()')
+
+    def _loss_rows(self, x, h, node_mask, fragment_mask, linker_mask, edge_mask, context, t_int, noise, mol_offset):
+        """Prologue, denoiser, epilogue.  Returns (rows [B, _lib.LOSS_ROW] fp32, t_int [B] int32), both on the device."""
+        dev = x.device
+        if dev.type != 'cuda':
+            raise _lib.HipLibraryError(f'{type(self).__name__}.forward runs on the HIP device only (no CPU fallback): '
+                                       f'got tensors on {dev}')
+        lib = _lib.load()
+        bs, n = x.size(0), x.size(1)
+        nf, T = self.in_node_nf, int(self.T)
+        f32 = lambda t_, shape: t_.reshape(shape).to(dev, torch.float32).contiguous()      # noqa: E731
+        xn, hn = self.normalize(x, h)
+        xh = torch.cat([xn, hn], dim=2).to(torch.float32).contiguous()
+        nm = f32(node_mask, (bs, n))
+        fm = f32(fragment_mask, (bs, n)) if fragment_mask is not None else None
+        lm = f32(linker_mask, (bs, n)) if linker_mask is not None else None
+        philox = self.noise_source == 'philox'
+        if mol_offset and not philox and (t_int is None or noise is None):
+            raise NotImplementedError("a shard of a batch (mol_offset) needs noise_source='philox' or explicit t_int and noise: "
+                                      'the torch.randn stream is a property of the whole batch')
+        if t_int is None and not philox:            # the reference's call order: randint, then the x- and h-randn
+            t_int = torch.randint(0, T + 1, size=(bs, 1), device=dev)
+        if noise is None and not philox:
+            noise = (torch.randn((bs, n, self.n_dims), device=dev), torch.randn((bs, n, nf), device=dev))
+        seed = 0
+        if philox and (t_int is None or noise is None):
+            seed = int(self.noise_seed) & 0xFFFFFFFFFFFFFFFF
+            self.noise_seed = int(self.noise_seed) + 1
+        t_given = t_int is not None
+        t_int_d = (t_int.reshape(bs).to(dev, torch.int32).contiguous() if t_given
+                   else torch.empty(bs, dtype=torch.int32, device=dev))
+        nx = nh = None
+        if noise is not None:
+            nx, nh = f32(noise[0], (bs, n, self.n_dims)), f32(noise[1], (bs, n, nf))
+        table = self.gamma.gamma.detach().to(dev, torch.float32).contiguous()
+        prior = self._prior_constants(bs, dev)
+        t_f = torch.empty(bs, dtype=torch.float32, device=dev)
+        gam = torch.empty((bs, 2), dtype=torch.float32, device=dev)
+        z_t = torch.empty_like(xh)
+        rows = torch.empty((bs, _lib.LOSS_ROW), dtype=torch.float32, device=dev)
+        if bs == 0:
+            return rows, t_int_d
+        args = _lib.DLLossArgs(
+            B=bs, N=n, nf=nf, T=T, timesteps=int(self.gamma.timesteps), inpainting=int(self._inpainting),
+            xh=xh.data_ptr(), node_mask=nm.data_ptr(), fragment_mask=fm.data_ptr() if fm is not None else None,
+            linker_mask=lm.data_ptr() if lm is not None else None, gamma_table=table.data_ptr(),
+            noise_x=nx.data_ptr() if nx is not None else None, noise_h=nh.data_ptr() if nh is not None else None,
+            noise_seed=seed, mol_offset=int(mol_offset), t_given=int(t_given), t_int=t_int_d.data_ptr(), t=t_f.data_ptr(),
+            gamma=gam.data_ptr(), z_t=z_t.data_ptr(), eps_hat=None, norm_h=float(self.norm_values[1]),
+            bias_h=float(self.norm_biases[1]), prior=prior.data_ptr(), rows=rows.data_ptr())
+        with torch.cuda.device(dev):
+            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(lib.dl_edm_loss_prologue(ctypes.byref(args), stream), 'dl_edm_loss_prologue')
+        # (InpaintingEDM denoises every atom: linker_mask=None, edm.py:499-506)
+        eps_hat = self._loss_denoise(z_t, t_f.reshape(bs, 1), node_mask, None if self._inpainting else linker_mask, edge_mask,
+                                     context)
+        eps_hat = eps_hat.to(torch.float32).contiguous()
+        args.eps_hat = eps_hat.data_ptr()
+        with torch.cuda.device(dev):
+            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(lib.dl_edm_loss_epilogue(ctypes.byref(args), stream), 'dl_edm_loss_epilogue')
+        return rows, t_int_d
+
+    def _prior_constants(self, batch_size, dev):
+        """``(alpha_T, sigma_T, log(1 / sigma_T))`` per molecule, device fp32 ``[B,3]``: ``kl_prior``'s constants
+        (edm.py:244-272) evaluated as the reference evaluates them, on ``[B,1]`` CPU fp32 tensors (its vectorised and scalar
+        paths may round differently, see ``step_coefficients``).  Each term of the KL cancels to a few ulp of these values,
+        so the epilogue takes them as inputs.  Cached per batch size and table version."""
+        key = (int(batch_size), self.gamma.gamma._version, str(dev))
+        cached = getattr(self, '_prior_cache', None)
+        if cached is not None and cached[0] == key:
+            return cached[1]
+        gamma = self.gamma.gamma.detach().to('cpu', torch.float32)
+        gamma_T = gamma[torch.round(torch.ones((batch_size, 1)) * self.gamma.timesteps).long()]
+        alpha_T = torch.sqrt(torch.sigmoid(-gamma_T))
+        sigma_T = torch.sqrt(torch.sigmoid(gamma_T))
+        log_inv = torch.log(torch.ones_like(sigma_T) / sigma_T)
+        prior = torch.cat([alpha_T, sigma_T, log_inv], 1).to(dev).contiguous()
+        self._prior_cache = (key, prior)
+        return prior
+
+    def _loss_denoise(self, z_t, t, node_mask, linker_mask, edge_mask, context):
+        """The denoiser call of the loss (edm.py:77-84): ``Dynamics.forward`` unchanged; team sizes follow ``EDM.team_batch``
+        when a shard of a batch pins it, and a team that cannot assemble means one more run on one compute unit per
+        molecule from the same ``z_t``."""
+        dyn = self.dynamics
+        bs = z_t.size(0)
+
+        def call():
+            return dyn.forward(xh=z_t, t=t, node_mask=node_mask, linker_mask=linker_mask, context=context,
+                               edge_mask=edge_mask)
+        if not hasattr(dyn, 'without_teams'):
+            return call()
+        saved = dyn.team_batch
+        dyn.team_batch = bs if self.team_batch is None else max(bs, int(self.team_batch))
+        try:
+            return dyn.without_teams(call)
+        finally:
+            dyn.team_batch = saved
+
+    def _reduce_loss_rows(self, rows, t_int):
+        """The reference's batch reductions (edm.py:64-66, 89-121) of the per-molecule rows of ``dl_edm_loss_epilogue``."""
+        error_t, noise, kl, log_px, log_ph, log_const, snr_weight, n_mask = rows.unbind(1)
+        d = (n_mask - 1) * self.n_dims if self._inpainting else n_mask * self.n_dims
+        delta_log_px = (-d * np.log(self.norm_values[0])).mean()
+        t_is_zero = (t_int == 0).float()
+        t_is_not_zero = 1 - t_is_zero
+        l2_loss = (error_t / ((self.n_dims + self.in_node_nf) * n_mask)).mean()
+        kl_prior = kl.mean()
+        loss_term_t = self.T * 0.5 * snr_weight * error_t
+        loss_term_t = (loss_term_t * t_is_not_zero).sum() / t_is_not_zero.sum()
+        noise_t = (noise * t_is_not_zero).sum() / t_is_not_zero.sum()
+        if t_is_zero.sum() > 0:                     # one host sync: the branch of edm.py:105
+            loss_term_0 = -(log_px + log_ph) + (-log_const)
+            loss_term_0 = (loss_term_0 * t_is_zero).sum() / t_is_zero.sum()
+            noise_0 = (noise * t_is_zero).sum() / t_is_zero.sum()
+        else:
+            loss_term_0 = 0.
+            noise_0 = 0.
+        return delta_log_px, kl_prior, loss_term_t, loss_term_0, l2_loss, noise_t, noise_0
 
     # ---- gamma algebra (host scalars; edm.py:369-403) -----------------------------------------------
     def sigma(self, gamma, target_tensor):
@@ -774,6 +921,16 @@ class InpaintingEDM(EDM):
     the linker atoms keep the ``p(z_s | z_t)`` sample, the fragment atoms are re-drawn from ``q(z_s | z_t, x)``, and the
     centre of gravity is projected out after every step.  One HIP denoiser call + one fused HIP tail
     (``dl_inpaint_step``) per step; no released configuration uses it."""
+
+    _inpainting = True
+
+    def forward(self, x, h, node_mask, fragment_mask, linker_mask, edge_mask, context=None, *, t_int=None, noise=None,
+                mol_offset=0):
+        """``InpaintingEDM.forward`` (edm.py:467-548): ``EDM.forward`` with noise on every atom of ``node_mask`` (the x-part
+        centre-of-gravity free, edm.py:715-727), ``z_t = alpha_t xh + sigma_t eps`` for every atom, the denoiser output
+        unmasked and ``dimensionality = (n - 1) * 3``.  Same draws, overrides and return value as ``EDM.forward``."""
+        return EDM.forward(self, x, h, node_mask, fragment_mask, linker_mask, edge_mask, context, t_int=t_int, noise=noise,
+                           mol_offset=mol_offset)
 
     def inpaint_coefficients(self, batch_size=1):
         """Per-step scalars in execution order: ``(t, alpha_ts, c_eps, sigma, a_q, b_q)`` (edm.py:616-672), evaluated on

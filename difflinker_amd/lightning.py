@@ -1,8 +1,10 @@
 """``DDPM`` — the wrapper the reference's CLI scripts talk to (``src/lightning.py::DDPM``).
 
-Sampling boundary only: hyper-parameter wiring (lightning.py:39-112), ``load_from_checkpoint`` for
-Lightning-format checkpoints (``{'hyper_parameters', 'state_dict'}``), and ``sample_chain``
-(:405-463).  Training / validation / metrics (RDKit, WandB, PL Trainer hooks) are out of scope.
+Hyper-parameter wiring (lightning.py:39-112), ``load_from_checkpoint`` for Lightning-format checkpoints
+(``{'hyper_parameters', 'state_dict'}``), ``sample_chain`` (:405-463), and the evaluation of held-out data: ``forward``
+(:148-199) with ``training=False``, ``validation_step`` / ``test_step`` (:228-268) and ``aggregate_metric`` (:478-480).
+Training (backward, optimiser, data augmentation, ``training_step``), RDKit metrics, WandB and PL Trainer hooks are out
+of scope.
 Subclasses ``pytorch_lightning.LightningModule`` when that package is importable (it is not in the
 build image), else ``torch.nn.Module`` with the same surface the callers use
 (generate.py:101-175, sample.py:84-164).
@@ -138,8 +140,92 @@ class DDPM(_Base):
         from .datasets import collate, get_dataloader
         return get_dataloader(self.test_dataset, self.batch_size, collate_fn=collate_fn or collate)
 
-    def forward(self, data, training):
-        raise NotImplementedError('DDPM.forward is the training step (lightning.py:148-199): out of scope')
+    # ---- evaluation of held-out data -------------------------------------------------------------------------
+    def _context_and_com_mask(self, data, node_mask, fragment_mask, anchors):
+        """Context and centre-of-mass mask (lightning.py:157-183).  Pocket data is recognised by ``self.pockets`` (a MOAD
+        prefix), not by ``isinstance(self.train_dataset, MOADDataset)``: after ``setup('val')`` the train dataset is None,
+        and the reference would then build the context of a pocket model without its pocket channels."""
+        if self.anchors_context:
+            context = torch.cat([anchors, fragment_mask], dim=-1)
+        else:
+            context = fragment_mask
+        if self.pockets:
+            fragment_only_mask = data['fragment_only_mask']
+            pocket_only_mask = fragment_mask - fragment_only_mask
+            if self.anchors_context:
+                context = torch.cat([anchors, fragment_only_mask, pocket_only_mask], dim=-1)
+            else:
+                context = torch.cat([fragment_only_mask, pocket_only_mask], dim=-1)
+        if self.inpainting:
+            center_of_mass_mask = node_mask
+        elif self.pockets and self.center_of_mass == 'fragments':
+            center_of_mass_mask = data['fragment_only_mask']
+        elif self.center_of_mass == 'fragments':
+            center_of_mass_mask = fragment_mask
+        elif self.center_of_mass == 'anchors':
+            center_of_mass_mask = anchors
+        else:
+            raise NotImplementedError(self.center_of_mass)
+        return context, center_of_mass_mask
+
+    def forward(self, data, training=False, mol_offset=0):
+        """``DDPM.forward`` (lightning.py:148-199) for evaluation: context, fragment centre of mass removed (and asserted
+        zero), then ``self.edm.forward`` - the reference's 7-tuple.  ``training=True`` (data augmentation, a loss to
+        back-propagate) is out of scope and raises; call it under ``torch.no_grad()`` (``validation_step`` does).
+        Deviation: pocket context keyed on ``self.pockets`` (see ``_context_and_com_mask``), as in ``sample_chain``.
+        ``mol_offset`` (not in the reference signature): global index of the batch's first molecule, for
+        ``noise_source='philox'`` (``EDM.forward``)."""
+        if training:
+            raise NotImplementedError('DDPM.forward(training=True) is the training step: out of scope (no backward); '
+                                      'evaluate with training=False, validation_step or test_step')
+        x = data['positions']
+        h = data['one_hot']
+        node_mask = data['atom_mask']
+        edge_mask = data['edge_mask']
+        anchors = data['anchors']
+        fragment_mask = data['fragment_mask']
+        linker_mask = data['linker_mask']
+        context, center_of_mass_mask = self._context_and_com_mask(data, node_mask, fragment_mask, anchors)
+        x = utils.remove_partial_mean_with_mask(x, node_mask, center_of_mass_mask)
+        utils.assert_partial_mean_zero_with_mask(x, node_mask, center_of_mass_mask)
+        return self.edm.forward(x=x, h=h, node_mask=node_mask, fragment_mask=fragment_mask, linker_mask=linker_mask,
+                                edge_mask=edge_mask, context=context, mol_offset=mol_offset)
+
+    def _metrics(self, data, mol_offset=0):
+        with torch.no_grad():
+            delta_log_px, kl_prior, loss_term_t, loss_term_0, l2_loss, noise_t, noise_0 = self.forward(data, training=False,
+                                                                                                      mol_offset=mol_offset)
+        vlb_loss = kl_prior + loss_term_t + loss_term_0 - delta_log_px
+        if self.loss_type == 'l2':
+            loss = l2_loss
+        elif self.loss_type == 'vlb':
+            loss = vlb_loss
+        else:
+            raise NotImplementedError(self.loss_type)
+        return {
+            'loss': loss,
+            'delta_log_px': delta_log_px,
+            'kl_prior': kl_prior,
+            'loss_term_t': loss_term_t,
+            'loss_term_0': loss_term_0,
+            'l2_loss': l2_loss,
+            'vlb_loss': vlb_loss,
+            'noise_t': noise_t,
+            'noise_0': noise_0,
+        }
+
+    def validation_step(self, data, *args):
+        """lightning.py:228-247: the 9 metrics of one batch (``loss`` = ``l2_loss`` or ``vlb_loss`` by ``loss_type``)."""
+        return self._metrics(data)
+
+    def test_step(self, data, *args):
+        """lightning.py:249-268 (the same metrics as ``validation_step``)."""
+        return self._metrics(data)
+
+    @staticmethod
+    def aggregate_metric(step_outputs, metric):
+        """lightning.py:478-480: the mean of one metric over the step outputs."""
+        return torch.tensor([float(out[metric]) for out in step_outputs]).mean()
 
     # ---- sampling -------------------------------------------------------------------------------------
     def sample_chain(self, data, sample_fn=None, keep_frames=None):

@@ -24,6 +24,10 @@
  *                                        <- the same Dynamics.forward / EDM.sample_chain with several compute
  *                                           units per molecule (batches smaller than the chip; no reference
  *                                           counterpart: a launch-geometry knob, results agree to fp32 rounding)
+ *   dl_edm_loss_prologue / dl_edm_loss_epilogue
+ *                                        <- EDM.forward / InpaintingEDM.forward around the denoiser call
+ *                                           (src/edm.py:41-124, :467-548; the terms of :244-326): the noising of
+ *                                           the data at a drawn t and the per-molecule loss / VLB terms
  *   dl_size_model_create / dl_size_gnn_forward
  *                                        <- SizeGNN (src/linker_size.py:45-91) as driven by
  *                                           SizeClassifier.forward at inference
@@ -316,6 +320,47 @@ int32_t dl_inpaint_step(int32_t B, int32_t N, int32_t nf, const float* z_t, cons
  * Independent of the batch split. */
 int32_t dl_philox_fill(uint64_t seed, int32_t mol_offset, const int32_t* mol_index, int32_t B, int32_t N, int32_t nf, int32_t draw0,
                        int32_t n_draws, float* noise_x, float* noise_h, void* stream);
+
+/* ---- loss / VLB of held-out data (EDM.forward; edm_loss.hip) ------------------------------------------
+ * Two launches around the unchanged denoiser forward (one workgroup per molecule each):
+ *   dl_edm_loss_prologue  t_int (read, or drawn), t = t_int / T, (gamma_t, gamma_s) from the schedule's table, eps (read, or
+ *                         drawn) and z_t;
+ *   dl_edm_loss_epilogue  one row of DL_LOSS_ROW floats per molecule from xh, z_t, eps (read, or drawn again) and eps_hat.
+ * In-kernel draws (noise_x = noise_h = NULL, t_given = 0): Philox4x32-10, key = noise_seed, counter = (mol_offset + b, atom,
+ * draw word, component / 4) with draw word 0x80000000 for eps (components as in dl_philox_fill) and 0x80000001 for t_int
+ * (atom 0, component 0: t_int = mulhi(r[0], T + 1), uniform on 0 .. T) - disjoint from every draw of a sampling chain.
+ * Deterministic: fixed reduction order, no atomics. */
+#define DL_LOSS_ROW 8               /* error_t, |eps_hat|_F, kl_prior, log p(x|z0) w/o constants, log p(h|z0), log constant
+                                       of p(x|z0), SNR(gamma_s - gamma_t) - 1, atoms under the noise mask */
+typedef struct dl_loss_args {
+    int32_t B, N, nf;
+    int32_t T;                      /* EDM.T: t = t_int / T */
+    int32_t timesteps;              /* the table has timesteps + 1 entries: gamma(t) = table[round(t * timesteps)] */
+    int32_t inpainting;             /* 0: EDM (noise on linker_mask, fragments kept); 1: InpaintingEDM (noise on node_mask,
+                                       centre of gravity of the x-noise removed, eps_hat unmasked) */
+    const float* xh;                /* device f32 [B,N,3+nf]: normalised x, h */
+    const float* node_mask;         /* device f32 [B,N] */
+    const float* fragment_mask;     /* device f32 [B,N] (may be NULL for inpainting) */
+    const float* linker_mask;       /* device f32 [B,N] (may be NULL for inpainting) */
+    const float* gamma_table;       /* device f32 [timesteps + 1] */
+    const float* noise_x;           /* device f32 [B,N,3], unmasked, or NULL (drawn) */
+    const float* noise_h;           /* device f32 [B,N,nf], unmasked, or NULL (drawn); NULL exactly when noise_x is */
+    uint64_t noise_seed;
+    int32_t mol_offset;             /* global index of molecule 0 (a shard of a batch) */
+    int32_t t_given;                /* 1: t_int is read; 0: it is drawn and written */
+    int32_t* t_int;                 /* device int32 [B] */
+    float* t;                       /* device f32 [B] out (prologue): the denoiser's t */
+    float* gamma;                   /* device f32 [B,2] out (prologue), in (epilogue): gamma_t, gamma_s */
+    float* z_t;                     /* device f32 [B,N,3+nf] out (prologue), in (epilogue) */
+    const float* eps_hat;           /* device f32 [B,N,3+nf] (epilogue): the raw denoiser output */
+    float norm_h, bias_h;           /* norm_values[1], norm_biases[1] */
+    const float* prior;             /* device f32 [B,3] (epilogue): alpha_T, sigma_T, log(1 / sigma_T) of gamma(1) per molecule,
+                                       evaluated by the caller as the reference evaluates them (the KL prior cancels to a few
+                                       ulp of these per entry, so they are inputs rather than kernel-side transcendentals) */
+    float* rows;                    /* device f32 [B,DL_LOSS_ROW] out (epilogue) */
+} dl_loss_args;
+int32_t dl_edm_loss_prologue(const dl_loss_args* args, void* stream);
+int32_t dl_edm_loss_epilogue(const dl_loss_args* args, void* stream);
 
 /* Diagnostics (libraries built with -DDL_PROFILE only; dl_profile_max_events() returns 0 otherwise): when set
  * (device uint64 [8 waves][dl_profile_max_events()][2], or NULL to disable), the first workgroup of the next
