@@ -12,12 +12,16 @@ final frame (RCCL over xGMI) inside the timed region.  Inputs are resident in HB
 region; the noise is drawn inside the kernel (counter-based Philox keyed by the global molecule index, the
 same source at every --gpus; --noise torch = the reference's ``torch.randn`` call sequence, a secondary line).
 
-Prints ONE JSON line (rank 0) with the driver's contract plus
+Prints ONE JSON line (rank 0) with the driver's contract (metric, value, unit, higher_is_better, dtype, ms_per_step) plus
   roofline     — MFMA roofline of the dominant kernel (``sample_chain_fc_kernel``): the FLOPs the kernel
-                 executes x 501 forwards / live HIP-event duration of the launch (the reference algorithm's
+                 executes x 501 forwards / live HIP-event duration of the timed launches (the reference algorithm's
                  count, SURVEY 8d F_min, is the `algorithmic` side entry)
+A plain run does only what that line needs: it sets up, warms up, times the steps, writes --dump-outputs and prints.
+--full adds, after the timed steps, what takes runs of its own:
+  roofline.traffic — fabric-side bytes per launch from two rocprofv3 --pmc passes over a child process.
   cpu_baseline — the oracle (PyTorch-CPU port of the reference path) timed on this box's host cores
-                 on a bounded sample (2 forwards of the same batch, extrapolated x501).
+                 on a bounded sample (2 forwards of the same batch, extrapolated x501); eager_rocm_baseline, the same
+                 port as plain PyTorch on the GPU.
   secondary    — driver-timed companions: exact-fp32 mode, torch noise, C4, C5 (one GPU's shard), molecules of
                  60..80 atoms, other batch sizes.
   --config C5 / C4 / C1 / C2L select another workload as the headline; --backend gloo runs --gpus N as N ranks
@@ -63,13 +67,16 @@ def parse():
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                     help="torch.distributed backend of --gpus > 1: 'nccl' = RCCL over xGMI (default); 'gloo' lets several ranks "
                          "share ONE GPU (functional check of the sharded path on a single-GPU box; RCCL refuses that)")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure what takes runs of its own: the secondary lines, the CPU and '
+                         'eager-ROCm baselines and roofline.traffic (off by default: a plain run measures the headline only)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU and eager-ROCm baselines')
     ap.add_argument('--cpu-forwards', type=int, default=2)
     ap.add_argument('--no-secondary', action='store_true',
-                    help='skip the secondary measurements (exact-fp32 mode, C4 pockets, other batch sizes) of the N=1 line')
+                    help='--full without the secondary measurements (exact-fp32 mode, C4 pockets, other batch sizes) of the N=1 line')
     ap.add_argument('--precision', default=None, choices=['f16x3', 'fp32', 'f16x2'], help='arithmetic mode (default: f16x3)')
     ap.add_argument('--traffic-child', action='store_true', help=argparse.SUPPRESS)     # the profiled child of measure_traffic()
-    ap.add_argument('--no-traffic', action='store_true', help='skip the two rocprofv3 --pmc passes behind roofline.traffic')
+    ap.add_argument('--no-traffic', action='store_true', help='--full without the two rocprofv3 --pmc passes behind roofline.traffic')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last one returned (the chain) as DIR/<name>.npy, float32, at most '
                          '64 MB (a fixed, seeded sample of molecules beyond that); the same arguments give the same inputs')
@@ -192,8 +199,8 @@ def measure_traffic(a, cfg, child_T=50):
     for counter in ('FETCH_SIZE', 'WRITE_SIZE'):
         out_dir = tempfile.mkdtemp(prefix=f'dl_pmc_{counter}_', dir='/tmp')
         cmd = ['rocprofv3', '--pmc', counter, '-d', out_dir, '--output-format', 'csv', '--', sys.executable, os.path.abspath(__file__),
-               '--traffic-child', '--config', a.config, '--T', str(child_T), '--noise', a.noise, '--steps', '1', '--warmup', '1',
-               '--no-secondary', '--no-cpu-baseline'] + (['--batch', str(a.batch)] if a.batch is not None else []) + \
+               '--traffic-child', '--config', a.config, '--T', str(child_T), '--noise', a.noise, '--steps', '1', '--warmup', '1'] + \
+              (['--batch', str(a.batch)] if a.batch is not None else []) + \
               (['--precision', a.precision] if a.precision else []) + (['--uniform-size'] if a.uniform_size else [])
         # (counter collection of ROCm 7.2 crashes on cooperative launches - the second launch of a split chain is one: the child
         # issues the same kernel, grid and arguments through the plain launch API)
@@ -377,6 +384,15 @@ def eager_rocm_baseline(edm, cfg, inp_cpu, device, n_forwards=3):
                       f'algebra of a step is not counted)', 'ms_per_forward': 1e3 * dt}
 
 
+def extras(a, world, pockets):
+    """Which measurements beyond the headline this run makes, each after the timed steps and in runs of its own: none without
+    --full, and only on one rank (never in the profiled child of measure_traffic())."""
+    full = a.full and world == 1 and not a.traffic_child
+    return {'secondary': full and not a.no_secondary and a.config == 'C2' and not a.uniform_size and a.batch is None and a.T is None,
+            'traffic': full and not a.no_traffic and not pockets,
+            'baselines': full and not a.no_cpu_baseline}
+
+
 def self_spawn(a):
     """``python bench.py --gpus N`` started WITHOUT a launcher (the driver's command shape for N = 1): start the
     N ranks ourselves through ``torch.distributed.run`` (one process per GPU, rendezvous on 127.0.0.1, a free port) and hand
@@ -508,10 +524,11 @@ def main():
                 'atom-stationary GEMM chain with LDS-streamed weights, profiles/r06) by chains of latencies, see DESIGN.md'
         else:
             peak, peak_note = FP32_MFMA_PEAK_TFLOPS, 'v_mfma_f32_32x32x2_f32 = fp32 vector peak'
-        # fabric-side bytes per launch of the dominant kernel: two rocprofv3 --pmc passes of a T = 50 child, outside the timed
-        # region (measure_traffic); null with the reason when they could not run
-        traffic, traffic_note = None, 'not measured (pocket path: many kernels per chain; multi-rank runs; --no-traffic)'
-        if not pockets and world == 1 and not a.no_traffic and not a.traffic_child:
+        # fabric-side bytes per launch of the dominant kernel (--full): two rocprofv3 --pmc passes of a T = 50 child, outside the
+        # timed region (measure_traffic); null with the reason when they could not run
+        todo = extras(a, world, pockets)
+        traffic, traffic_note = None, 'not measured (--full measures it on one rank; not on the pocket path: many kernels per chain; --no-traffic)'
+        if todo['traffic']:
             traffic, traffic_note = measure_traffic(a, cfg)
         DTYPES = {'f16x3': 'f32 (f16x3 split MFMA, fp32 accumulate)', 'fp32': 'f32',
                   'f16x2': 'f32 (f16x2 / f16x3 split MFMA, fp32 accumulate)'}
@@ -565,7 +582,7 @@ def main():
             return
         # the optional companions must not cost the line: an error in one of them is recorded, not raised
         c4_cpu = None
-        if world == 1 and not a.no_secondary and a.config == 'C2' and not a.uniform_size and a.batch is None and a.T is None:
+        if todo['secondary']:
             out['secondary'], kept = secondary_measurements(device, a)
             # the companions the driver's record must not lose (its `parsed` keeps the contract keys,
             # `roofline` and `cpu_baseline` and drops everything else): small top-level keys AND a copy inside `roofline`
@@ -596,7 +613,7 @@ def main():
             if tn:
                 out['value_by_noise_source'] = {'philox (in-kernel, this line)': out['value'],
                                                 'torch (reference randn stream, library default)': tn[0]['molecules_per_s']}
-        if world == 1 and not a.no_cpu_baseline:
+        if todo['baselines']:
             for key, fn in (('cpu_baseline', lambda: cpu_baseline(edm, cfg, inp_cpu, a.cpu_forwards)),
                             ('eager_rocm_baseline', lambda: eager_rocm_baseline(edm, cfg, inp_cpu, device))):
                 try:

@@ -1,11 +1,11 @@
 #!/bin/bash
-# End-of-round validation on the GPU box: build check, GPU suite, smoke, the default bench line (with secondaries and CPU baseline)
+# End-of-round validation on an MI355X: build check, GPU suite, smoke, the full bench line (--full: secondaries, CPU baseline)
 mkdir -p gpurun_out
 O=gpurun_out
 python -c "import __graft_entry__ as g; g.build()" > $O/build_final.log 2>&1; echo "build exit $?"
 timeout 1200 python -m pytest tests -m gpu -q > $O/pytest_final.log 2>&1; echo "pytest exit $?"; tail -2 $O/pytest_final.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke_final.log 2>&1; echo "smoke exit $?"; tail -2 $O/smoke_final.log
-timeout 1500 python bench.py > $O/bench_final.log 2>&1; echo "bench exit $?"
+timeout 1500 python bench.py --full > $O/bench_final.log 2>&1; echo "bench exit $?"
 python - <<'PY'
 import json
 l=[x for x in open('gpurun_out/bench_final.log') if x.startswith('{')][-1]

@@ -1,12 +1,12 @@
 #!/bin/bash
-# End-of-round validation on the GPU box: build check, GPU suite, smoke, the default bench line (secondaries, CPU + eager baselines),
+# End-of-round validation on an MI355X: build check, GPU suite, smoke, the --full bench line (secondaries, CPU + eager baselines),
 # and `python bench.py --gpus 2 --backend gloo` started WITHOUT a launcher (two ranks on the one GPU of the box)
 O=gpurun_out/r4/final
 mkdir -p $O
 python -c "import __graft_entry__ as g; g.build()" > $O/build.log 2>&1; echo "build exit $?"
 timeout 1500 python -m pytest tests -m gpu -q -s > $O/pytest_gpu_verbose.log 2>&1; echo "pytest exit $?"; tail -n 2 $O/pytest_gpu_verbose.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke exit $?"; tail -n 1 $O/smoke.log
-timeout 1800 python bench.py > $O/bench.log 2> $O/bench.err; echo "bench exit $?"
+timeout 1800 python bench.py --full > $O/bench.log 2> $O/bench.err; echo "bench exit $?"
 timeout 600 python bench.py --gpus 2 --backend gloo --steps 2 --warmup 1 > $O/bench_2ranks_selfspawn.log 2>&1; echo "bench --gpus 2 (self-spawned, gloo) exit $?"; tail -n 1 $O/bench_2ranks_selfspawn.log | cut -c1-300
 python - <<'PY'
 import json

@@ -428,6 +428,27 @@ def test_bench_gpus_8_rendezvous_on_cpu():
     assert err.count('bench.py needs an MI355X') >= 8, err[-3000:]
 
 
+def test_bench_plain_run_measures_the_headline_only(monkeypatch):
+    """``python bench.py --gpus 1 --steps N --warmup W`` times its steps and prints its line, nothing more: the secondary lines,
+    the CPU / eager-ROCm baselines and the rocprofv3 traffic passes - runs of their own - happen under --full only, which the
+    --no-* options thin out; never on several ranks, nor in the profiled child of the traffic passes."""
+    import bench
+
+    def todo(*args, world=1, pockets=False):
+        monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', str(world), '--steps', '2', '--warmup', '1', *args])
+        return bench.extras(bench.parse(), world, pockets)
+
+    assert not any(todo().values())
+    assert not any(todo('--no-secondary', '--no-traffic').values())
+    assert all(todo('--full').values())
+    assert todo('--full', '--no-traffic') == {'secondary': True, 'traffic': False, 'baselines': True}
+    assert todo('--full', '--no-secondary', '--no-cpu-baseline') == {'secondary': False, 'traffic': True, 'baselines': False}
+    assert todo('--full', '--config', 'C4', pockets=True) == {'secondary': False, 'traffic': False, 'baselines': True}
+    assert todo('--full', '--batch', '64') == {'secondary': False, 'traffic': True, 'baselines': True}
+    assert not any(todo('--full', world=8).values())
+    assert not any(todo('--full', '--traffic-child').values())
+
+
 def test_found_nan_exception_from_index_sets_and_split_terms():
     """Round-4 host helpers: the exception rebuilt from whole-batch index sets keeps the reference's three-way partition
     (utils.py:274-289); the average number of fp16 MFMA terms per multiply-accumulate prices the f16x2 ceiling between 2 and 3."""
