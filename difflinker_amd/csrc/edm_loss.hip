@@ -209,6 +209,30 @@ __global__ void __launch_bounds__(LT) loss_epilogue_kernel(dl_loss_args a) {
     }
 }
 
+// d eps_hat of the loss terms (include/difflinker_hip.h, dl_edm_loss_grad): weights[b] = (w_err, w_noise, w_logpx)
+__global__ void __launch_bounds__(LT) loss_grad_kernel(dl_loss_args a, const float* __restrict__ weights, float* __restrict__ g) {
+    __shared__ float lds[4 * 4];
+    const int b = blockIdx.x;
+    const int D = 3 + a.nf;
+    const float w_err = weights[3 * b], w_noise = weights[3 * b + 1], w_logpx = weights[3 * b + 2];
+    const float norm = a.rows[size_t(b) * DL_LOSS_ROW + 1];
+    float mean[3];
+    eps_mean(a, b, lds, mean);
+    for (int i = threadIdx.x; i < a.N; i += LT) {
+        const size_t bi = size_t(b) * a.N + i;
+        const float m = noise_mask(a, bi);
+        const float lm = a.inpainting ? 1.0f : a.linker_mask[bi];
+        for (int c = 0; c < D; ++c) {
+            const float eh = a.eps_hat[bi * D + c] * lm;
+            const float d = eps_of(a, b, i, c, m, mean) - eh;
+            float v = -2.0f * d * w_err;
+            if (w_noise != 0.0f) v += eh * (w_noise / norm);
+            if (c < 3) v += d * w_logpx;
+            g[bi * D + c] = v * lm;
+        }
+    }
+}
+
 int32_t check_loss_args(const dl_loss_args* a, bool epilogue) {
     if (!a || a->B < 0 || a->N < 1 || a->nf < 1 || 3 + a->nf > DMAX || a->T < 1 || a->timesteps < 1 || a->mol_offset < 0)
         return DL_ERR_BAD_ARG;
@@ -236,6 +260,15 @@ int32_t dl_edm_loss_epilogue(const dl_loss_args* args, void* stream) {
     if (st != DL_OK) return st;
     if (args->B == 0) return DL_OK;
     hipLaunchKernelGGL(loss_epilogue_kernel, dim3(args->B), dim3(LT), 0, static_cast<hipStream_t>(stream), *args);
+    return hipGetLastError() == hipSuccess ? DL_OK : DL_ERR_HIP;
+}
+
+int32_t dl_edm_loss_grad(const dl_loss_args* args, const float* weights, float* d_eps_hat, void* stream) {
+    const int32_t st = check_loss_args(args, true);
+    if (st != DL_OK) return st;
+    if (!weights || !d_eps_hat) return DL_ERR_BAD_ARG;
+    if (args->B == 0) return DL_OK;
+    hipLaunchKernelGGL(loss_grad_kernel, dim3(args->B), dim3(LT), 0, static_cast<hipStream_t>(stream), *args, weights, d_eps_hat);
     return hipGetLastError() == hipSuccess ? DL_OK : DL_ERR_HIP;
 }
 

@@ -225,8 +225,11 @@ class EDM(torch.nn.Module):
             raise NotImplementedError('EDM.forward evaluates the loss without a backward pass (training is out of scope): '
                                       'wrap the call in torch.no_grad()')
 
-    def _loss_rows(self, x, h, node_mask, fragment_mask, linker_mask, edge_mask, context, t_int, noise, mol_offset):
-        """Prologue, denoiser, epilogue.  Returns (rows [B, _lib.LOSS_ROW] fp32, t_int [B] int32), both on the device."""
+    def _loss_rows(self, x, h, node_mask, fragment_mask, linker_mask, edge_mask, context, t_int, noise, mol_offset,
+                   train_state=None):
+        """Prologue, denoiser, epilogue.  Returns (rows [B, _lib.LOSS_ROW] fp32, t_int [B] int32), both on the device.
+        ``train_state`` (a dict, training only): the denoiser output carries a gradient to the parameters, and the dict
+        receives the kernel arguments and the tensors they point to (for ``dl_edm_loss_grad`` in the backward)."""
         dev = x.device
         if dev.type != 'cuda':
             raise _lib.HipLibraryError(f'{type(self).__name__}.forward runs on the HIP device only (no CPU fallback): '
@@ -279,13 +282,42 @@ class EDM(torch.nn.Module):
             _lib.check(lib.dl_edm_loss_prologue(ctypes.byref(args), stream), 'dl_edm_loss_prologue')
         # (InpaintingEDM denoises every atom: linker_mask=None, edm.py:499-506)
         eps_hat = self._loss_denoise(z_t, t_f.reshape(bs, 1), node_mask, None if self._inpainting else linker_mask, edge_mask,
-                                     context)
+                                     context, train=train_state is not None)
         eps_hat = eps_hat.to(torch.float32).contiguous()
         args.eps_hat = eps_hat.data_ptr()
         with torch.cuda.device(dev):
             stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             _lib.check(lib.dl_edm_loss_epilogue(ctypes.byref(args), stream), 'dl_edm_loss_epilogue')
+        if train_state is not None:
+            train_state.update(args=args, eps_hat=eps_hat, keep=(xh, nm, fm, lm, table, nx, nh, t_int_d, t_f, gam, z_t, prior,
+                                                                 rows))
         return rows, t_int_d
+
+    # ---- training (edm.py:41-124 with loss.backward()) ------------------------------------------------------------
+    def training_forward(self, x, h, node_mask, fragment_mask, linker_mask, edge_mask, context=None, *, t_int=None,
+                         noise=None, mol_offset=0):
+        """``forward`` for TRAINING: the same draws and the same 7-tuple, bit for bit, and ``l2_loss``, ``loss_term_t``,
+        ``loss_term_0``, ``noise_t`` and ``noise_0`` carry a gradient to the parameters of ``self.dynamics`` (the others do
+        not depend on them).  The backward is HIP: ``dl_edm_loss_grad`` forms d eps_hat from the per-molecule weights of the
+        batch means, ``dl_egnn_backward_fc`` the parameter gradients (``Dynamics.training_forward``).  Fully-connected
+        ``Dynamics`` with the released hyper-parameters only (``egnn.check_trainable``; anything else raises
+        ``NotImplementedError``)."""
+        from .egnn import check_trainable
+        check_trainable(self.dynamics)
+        if x.device.type != 'cuda':
+            raise _lib.HipLibraryError(f'{type(self).__name__}.training_forward runs on the HIP device only (no CPU fallback): '
+                                       f'got tensors on {x.device}')
+        state = {}
+        rows, t_int_d = self._loss_rows(x, h, node_mask, fragment_mask, linker_mask, edge_mask, context, t_int, noise,
+                                        mol_offset, train_state=state)
+        if rows.size(0) == 0:
+            return self._reduce_loss_rows(rows, t_int_d)
+        vals = {}
+        loss_term_t, loss_term_0, l2_loss, noise_t, noise_0 = _LossTerms.apply(state['eps_hat'], self, rows, t_int_d, state,
+                                                                               vals)
+        if vals['no_t0']:
+            loss_term_0, noise_0 = 0., 0.
+        return vals['delta_log_px'], vals['kl_prior'], loss_term_t, loss_term_0, l2_loss, noise_t, noise_0
 
     def _prior_constants(self, batch_size, dev):
         """``(alpha_T, sigma_T, log(1 / sigma_T))`` per molecule, device fp32 ``[B,3]``: ``kl_prior``'s constants
@@ -305,7 +337,7 @@ class EDM(torch.nn.Module):
         self._prior_cache = (key, prior)
         return prior
 
-    def _loss_denoise(self, z_t, t, node_mask, linker_mask, edge_mask, context):
+    def _loss_denoise(self, z_t, t, node_mask, linker_mask, edge_mask, context, train=False):
         """The denoiser call of the loss (edm.py:77-84): ``Dynamics.forward`` unchanged; team sizes follow ``EDM.team_batch``
         when a shard of a batch pins it, and a team that cannot assemble means one more run on one compute unit per
         molecule from the same ``z_t``."""
@@ -313,8 +345,8 @@ class EDM(torch.nn.Module):
         bs = z_t.size(0)
 
         def call():
-            return dyn.forward(xh=z_t, t=t, node_mask=node_mask, linker_mask=linker_mask, context=context,
-                               edge_mask=edge_mask)
+            fn = dyn.training_forward if train else dyn.forward
+            return fn(xh=z_t, t=t, node_mask=node_mask, linker_mask=linker_mask, context=context, edge_mask=edge_mask)
         if not hasattr(dyn, 'without_teams'):
             return call()
         saved = dyn.team_batch
@@ -916,6 +948,55 @@ class EDM(torch.nn.Module):
         return chain
 
 
+class _LossTerms(torch.autograd.Function):
+    """The eps_hat-dependent batch terms of ``EDM.forward`` (values from ``_reduce_loss_rows``, unchanged) with their
+    gradient: per molecule the weights of error_t, |eps_hat| and log p(x | z_0) in the batch means, then
+    ``dl_edm_loss_grad``."""
+
+    @staticmethod
+    def forward(ctx, eps_hat, edm, rows, t_int, state, vals):
+        ctx.set_materialize_grads(False)
+        delta_log_px, kl_prior, loss_term_t, loss_term_0, l2_loss, noise_t, noise_0 = edm._reduce_loss_rows(rows, t_int)
+        vals.update(delta_log_px=delta_log_px, kl_prior=kl_prior, no_t0=not torch.is_tensor(loss_term_0))
+        ctx.edm, ctx.state = edm, state
+        ctx.save_for_backward(rows, t_int)
+        zero = torch.zeros((), dtype=torch.float32, device=rows.device)
+        return (loss_term_t, loss_term_0 if torch.is_tensor(loss_term_0) else zero, l2_loss, noise_t,
+                noise_0 if torch.is_tensor(noise_0) else zero.clone())
+
+    @staticmethod
+    def backward(ctx, g_lt, g_l0, g_l2, g_nt, g_n0):
+        edm, state = ctx.edm, ctx.state
+        rows, t_int = ctx.saved_tensors
+        bs = rows.size(0)
+        error_t, noise, kl, log_px, log_ph, log_const, snr_weight, n_mask = rows.unbind(1)
+        tz = (t_int == 0).float()
+        tnz = 1 - tz
+        w_err = torch.zeros_like(error_t)
+        w_noise = torch.zeros_like(error_t)
+        w_logpx = torch.zeros_like(error_t)
+        if g_l2 is not None:                                # l2_loss = mean(error_t / ((3 + nf) n))
+            w_err = w_err + g_l2 / (bs * (edm.n_dims + edm.in_node_nf) * n_mask)
+        if g_lt is not None:                                # loss_term_t = sum(T / 2 SNR_w error_t [t > 0]) / count(t > 0)
+            w_err = w_err + g_lt * (edm.T * 0.5) * snr_weight * tnz / tnz.sum()
+        if g_nt is not None:
+            w_noise = w_noise + g_nt * tnz / tnz.sum()
+        if g_l0 is not None:                                # loss_term_0 = -(log p(x) + log p(h)) - const over t = 0
+            w_logpx = w_logpx - g_l0 * tz / tz.sum()
+        if g_n0 is not None:
+            w_noise = w_noise + g_n0 * tz / tz.sum()
+        weights = torch.stack([w_err, w_noise, w_logpx], 1).to(torch.float32).contiguous()
+        eps_hat = state['eps_hat']
+        grad = torch.empty_like(eps_hat)
+        dev = eps_hat.device
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(lib.dl_edm_loss_grad(ctypes.byref(state['args']), _lib.ptr(weights), _lib.ptr(grad), stream),
+                       'dl_edm_loss_grad')
+        return grad, None, None, None, None, None
+
+
 class InpaintingEDM(EDM):
     """``InpaintingEDM`` (edm.py:466-727), sampling side: every atom is denoised (``linker_mask=None``, centred dynamics),
     the linker atoms keep the ``p(z_s | z_t)`` sample, the fragment atoms are re-drawn from ``q(z_s | z_t, x)``, and the
@@ -931,6 +1012,13 @@ class InpaintingEDM(EDM):
         unmasked and ``dimensionality = (n - 1) * 3``.  Same draws, overrides and return value as ``EDM.forward``."""
         return EDM.forward(self, x, h, node_mask, fragment_mask, linker_mask, edge_mask, context, t_int=t_int, noise=noise,
                            mol_offset=mol_offset)
+
+    def training_forward(self, x, h, node_mask, fragment_mask, linker_mask, edge_mask, context=None, *, t_int=None,
+                         noise=None, mol_offset=0):
+        """``InpaintingEDM.forward`` for training: ``EDM.training_forward`` with the inpainting draws (the denoiser must be
+        ``centering=True``, as ``DDPM(inpainting=True)`` builds it)."""
+        return EDM.training_forward(self, x, h, node_mask, fragment_mask, linker_mask, edge_mask, context, t_int=t_int,
+                                    noise=noise, mol_offset=mol_offset)
 
     def inpaint_coefficients(self, batch_size=1):
         """Per-step scalars in execution order: ``(t, alpha_ts, c_eps, sigma, a_q, b_q)`` (edm.py:616-672), evaluated on

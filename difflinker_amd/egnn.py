@@ -629,3 +629,118 @@ class DynamicsWithPockets(Dynamics):
         out, flags = self.launch(self.prepare(node_mask, linker_mask, edge_mask, context), t, xh)
         self._raise_on_flags(flags)
         return out
+
+
+# ---- training: the backward of the fully-connected denoiser (csrc/egnn_backward.hip) ------------------------------------
+def check_trainable(dyn):
+    """Raise ``NotImplementedError`` for a denoiser outside the backward's scope (the released FC configurations)."""
+    out = []
+    if isinstance(dyn, DynamicsWithPockets) or type(dyn) is not Dynamics:
+        out.append(f'{type(dyn).__name__} (pocket graphs)')
+    if getattr(dyn, 'graph_type', 'FC') != 'FC': out.append(f'graph_type={dyn.graph_type!r}')
+    if dyn.attention: out.append('attention=True')
+    if dyn.tanh: out.append('tanh=True')
+    if dyn.aggregation_method != 'sum': out.append(f'aggregation_method={dyn.aggregation_method!r}')
+    if dyn.sin_embedding: out.append('sin_embedding=True')
+    if dyn.dynamics.hidden_nf != HIDDEN_WIDTH: out.append(f'hidden_nf={dyn.dynamics.hidden_nf} (the backward is 128 wide)')
+    if out:
+        raise NotImplementedError('training (the HIP backward) covers fully-connected Dynamics with the released '
+                                  'hyper-parameters only; outside it: ' + ', '.join(out))
+
+
+def backward_args(dyn, B, N):
+    return _lib.DLBackwardArgs(B=int(B), N=int(N), in_node_nf=dyn.in_node_nf, context_node_nf=dyn.context_node_nf,
+                               condition_time=int(bool(dyn.condition_time)), hidden_nf=int(dyn.dynamics.hidden_nf),
+                               n_layers=int(dyn.n_layers), inv_sublayers=int(dyn.inv_sublayers),
+                               centering=int(bool(dyn.centering)), norm_constant=float(dyn.norm_constant),
+                               normalization_factor=float(dyn.normalization_factor))
+
+
+class _DenoiserFn(torch.autograd.Function):
+    """``Dynamics.forward`` with a HIP backward: the forward runs the unchanged inference kernels (its values are the
+    inference values bit for bit); the backward hands d eps_hat to ``dl_egnn_backward_fc`` and splits the flat gradient
+    (``Dynamics.parameters()`` order) over the parameters.  No gradient for the inputs (out of scope)."""
+
+    @staticmethod
+    def forward(ctx, dyn, t, xh, node_mask, linker_mask, edge_mask, context, *params):
+        out = dyn.forward(t=t, xh=xh, node_mask=node_mask, linker_mask=linker_mask, edge_mask=edge_mask, context=context)
+        ctx.dyn = dyn
+        ctx.save_for_backward(t, xh, node_mask, linker_mask, edge_mask, context)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        dyn = ctx.dyn
+        t, xh, node_mask, linker_mask, edge_mask, context = ctx.saved_tensors
+        grads = dyn.parameter_grad(t, xh, node_mask, linker_mask, edge_mask, context, grad_out)
+        return (None,) * 7 + tuple(grads)
+
+
+def _dynamics_parameter_grad(self, t, xh, node_mask, linker_mask, edge_mask, context, grad_out):
+    """Gradients of ``sum(grad_out * self.forward(...))`` for every parameter, in ``parameters()`` order (HIP backward)."""
+    check_trainable(self)
+    dev = xh.device
+    if dev.type != 'cuda':
+        raise _lib.HipLibraryError('the EGNN backward runs on the HIP device only (no CPU fallback): '
+                                   f'got tensors on {dev}')
+    lib = _lib.load()
+    bs, n = xh.shape[0], xh.shape[1]
+    params = list(self.parameters())
+    if bs == 0:
+        return [torch.zeros_like(p) for p in params]
+    limit = int(lib.dl_egnn_backward_max_atoms())
+    if n > limit:
+        raise ValueError(f'the EGNN backward takes molecules of at most {limit} atoms (padded width); got {n}')
+    f32 = lambda v: None if v is None else v.to(dev, torch.float32).contiguous()      # noqa: E731
+    flat = torch.cat([p.detach().reshape(-1).to(torch.float32) for p in params]).contiguous()
+    if not torch.is_tensor(t):
+        t = torch.tensor([float(t)], device=dev)
+    tt = f32(t).reshape(-1)
+    args = backward_args(self, bs, n)
+    want = int(lib.dl_egnn_backward_fc_num_params(ctypes.byref(args)))
+    if want != flat.numel():
+        raise ValueError(f'parameter count {flat.numel()} != the backward layout {want}')
+    need = int(lib.dl_egnn_backward_fc_workspace_bytes(ctypes.byref(args)))
+    ws = getattr(self, '_bwd_ws', None)
+    if ws is None or ws.numel() < need or ws.device != dev:
+        ws = self._bwd_ws = None
+        ws = self._bwd_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    xh_ = f32(xh)
+    nm = f32(node_mask.reshape(bs, n))
+    lm = f32(linker_mask.reshape(bs, n)) if linker_mask is not None else None
+    em = edge_mask.reshape(bs, n, n).to(dev, torch.int8).contiguous()
+    ctx_ = f32(context.reshape(bs, n, self.context_node_nf)) if context is not None and self.context_node_nf else None
+    go = f32(grad_out)
+    grad = torch.empty_like(flat)
+    args.params, args.n_params = flat.data_ptr(), flat.numel()
+    args.xh, args.t, args.t_is_scalar = xh_.data_ptr(), tt.data_ptr(), int(tt.numel() == 1)
+    args.node_mask, args.linker_mask, args.edge_mask = nm.data_ptr(), lm.data_ptr() if lm is not None else None, em.data_ptr()
+    args.context = ctx_.data_ptr() if ctx_ is not None else None
+    args.grad_out, args.grad_params = go.data_ptr(), grad.data_ptr()
+    args.workspace, args.workspace_bytes = ws.data_ptr(), need
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.dl_egnn_backward_fc(ctypes.byref(args), ctypes.c_void_p(stream)), 'dl_egnn_backward_fc')
+    out, k = [], 0
+    for p in params:
+        out.append(grad[k:k + p.numel()].view_as(p).to(p.dtype))
+        k += p.numel()
+    return out
+
+
+def _dynamics_training_forward(self, t, xh, node_mask, linker_mask, edge_mask, context):
+    """``forward`` whose output carries a gradient to the parameters (HIP backward).  Same values as ``forward``."""
+    check_trainable(self)
+    if xh.device.type != 'cuda':
+        raise _lib.HipLibraryError('Dynamics.training_forward runs on the HIP device only (no CPU fallback): '
+                                   f'got tensors on {xh.device}')
+    for name, v in (('t', t), ('xh', xh), ('context', context)):
+        if torch.is_tensor(v) and v.requires_grad:
+            raise NotImplementedError(f'gradients with respect to the input {name} are out of scope (parameters only)')
+    if not torch.is_tensor(t):
+        t = torch.tensor([float(t)], device=xh.device)
+    return _DenoiserFn.apply(self, t, xh, node_mask, linker_mask, edge_mask, context, *self.parameters())
+
+
+Dynamics.parameter_grad = _dynamics_parameter_grad
+Dynamics.training_forward = _dynamics_training_forward

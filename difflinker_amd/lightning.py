@@ -3,8 +3,9 @@
 Hyper-parameter wiring (lightning.py:39-112), ``load_from_checkpoint`` for Lightning-format checkpoints
 (``{'hyper_parameters', 'state_dict'}``), ``sample_chain`` (:405-463), and the evaluation of held-out data: ``forward``
 (:148-199) with ``training=False``, ``validation_step`` / ``test_step`` (:228-268) and ``aggregate_metric`` (:478-480).
-Training (backward, optimiser, data augmentation, ``training_step``), RDKit metrics, WandB and PL Trainer hooks are out
-of scope.
+Training: ``training_step`` (:201-226) with a differentiable ``loss`` (``EDM.training_forward``, HIP backward of the
+fully-connected denoiser), the random rotation of ``data_augmentation``, and ``configure_optimizers`` (:465-466);
+``python -m difflinker_amd.train`` is the training loop.  RDKit metrics, WandB and PL Trainer hooks are out of scope.
 Subclasses ``pytorch_lightning.LightningModule`` when that package is importable (it is not in the
 build image), else ``torch.nn.Module`` with the same surface the callers use
 (generate.py:101-175, sample.py:84-164).
@@ -190,6 +191,38 @@ class DDPM(_Base):
         utils.assert_partial_mean_zero_with_mask(x, node_mask, center_of_mass_mask)
         return self.edm.forward(x=x, h=h, node_mask=node_mask, fragment_mask=fragment_mask, linker_mask=linker_mask,
                                 edge_mask=edge_mask, context=context, mol_offset=mol_offset)
+
+    def _training_forward(self, data):
+        """``forward(data, training=True)`` (lightning.py:148-199): context, fragment centre of mass removed, the random
+        rotation when ``data_augmentation`` is on, then ``self.edm.training_forward`` (losses with a gradient)."""
+        x = data['positions']
+        node_mask = data['atom_mask']
+        fragment_mask = data['fragment_mask']
+        context, center_of_mass_mask = self._context_and_com_mask(data, node_mask, fragment_mask, data['anchors'])
+        x = utils.remove_partial_mean_with_mask(x, node_mask, center_of_mass_mask)
+        utils.assert_partial_mean_zero_with_mask(x, node_mask, center_of_mass_mask)
+        if self.data_augmentation:
+            x = utils.random_rotation(x)
+        return self.edm.training_forward(x=x, h=data['one_hot'], node_mask=node_mask, fragment_mask=fragment_mask,
+                                         linker_mask=data['linker_mask'], edge_mask=data['edge_mask'], context=context)
+
+    def training_step(self, data, *args):
+        """lightning.py:201-226: the 9 metrics of one batch; ``loss`` (``l2_loss`` or ``vlb_loss``) back-propagates to the
+        denoiser's parameters."""
+        delta_log_px, kl_prior, loss_term_t, loss_term_0, l2_loss, noise_t, noise_0 = self._training_forward(data)
+        vlb_loss = kl_prior + loss_term_t + loss_term_0 - delta_log_px
+        if self.loss_type == 'l2':
+            loss = l2_loss
+        elif self.loss_type == 'vlb':
+            loss = vlb_loss
+        else:
+            raise NotImplementedError(self.loss_type)
+        return {'loss': loss, 'delta_log_px': delta_log_px, 'kl_prior': kl_prior, 'loss_term_t': loss_term_t,
+                'loss_term_0': loss_term_0, 'l2_loss': l2_loss, 'vlb_loss': vlb_loss, 'noise_t': noise_t, 'noise_0': noise_0}
+
+    def configure_optimizers(self):
+        """lightning.py:465-466."""
+        return torch.optim.AdamW(self.edm.parameters(), lr=self.lr, amsgrad=True, weight_decay=1e-12)
 
     def _metrics(self, data, mol_offset=0):
         with torch.no_grad():

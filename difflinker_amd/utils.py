@@ -1,6 +1,7 @@
 """Hot-path helpers of the sampling loop (reference ``src/utils.py``: the six symbols
 SURVEY.md section 2 row 4 marks in scope).  Training utilities (EMA, grad-clip queue,
 rotation augmentation, stdout tee) are out of scope."""
+import math
 import random
 
 import numpy as np
@@ -111,3 +112,28 @@ def split_features(z, n_dims, num_classes, include_charges):
     if include_charges:
         h['integer'] = z[:, :, n_dims + num_classes:n_dims + num_classes + 1]
     return x, h
+
+
+def random_rotation(x):
+    """A random rotation per molecule, ``Rx Ry Rz`` of angles uniform in [-pi, pi) (reference ``utils.random_rotation``,
+    utils.py:303-363, 3-D), drawn and applied on ``x``'s device."""
+    bs, n_nodes, n_dims = x.size()
+    assert n_dims == 3
+    dev = x.device
+
+    def rot(a, b):
+        R = torch.eye(3, device=dev).unsqueeze(0).repeat(bs, 1, 1)
+        theta = torch.rand(bs, 1, 1, device=dev) * (2 * math.pi) - math.pi
+        cos, sin = torch.cos(theta), torch.sin(theta)
+        R[:, a:a + 1, a:a + 1] = cos
+        R[:, a:a + 1, b:b + 1] = sin
+        R[:, b:b + 1, a:a + 1] = -sin
+        R[:, b:b + 1, b:b + 1] = cos
+        return R
+    Rx = rot(1, 2)
+    Ry = rot(0, 2)
+    Ry[:, 0:1, 2:3], Ry[:, 2:3, 0:1] = -Ry[:, 0:1, 2:3], -Ry[:, 2:3, 0:1]      # utils.py:336-339: -sin above, sin below
+    Rz = rot(0, 1)
+    x = x.transpose(1, 2)
+    x = torch.matmul(Rz, torch.matmul(Ry, torch.matmul(Rx, x)))
+    return x.transpose(1, 2).contiguous()

@@ -362,6 +362,47 @@ typedef struct dl_loss_args {
 int32_t dl_edm_loss_prologue(const dl_loss_args* args, void* stream);
 int32_t dl_edm_loss_epilogue(const dl_loss_args* args, void* stream);
 
+/* d eps_hat of the loss terms (training; edm_loss.hip): for molecule b, atom i, component c, with m the noise mask,
+ * lm the linker mask (1 for inpainting), eh = eps_hat lm and d = eps - eh (eps read or drawn again as in the epilogue),
+ *   d_eps_hat = lm (-2 d w_err + eh w_noise / |eh|_F + [c < 3] d w_logpx)
+ * where (w_err, w_noise, w_logpx) = weights[b] are the upstream gradients of error_t, |eps_hat|_F and log p(x | z_0) (the
+ * row of dl_edm_loss_epilogue, whose |eps_hat|_F it reads from `rows`).  A zero w_noise adds nothing. */
+int32_t dl_edm_loss_grad(const dl_loss_args* args, const float* weights /* device f32 [B,3] */, float* d_eps_hat /* [B,N,3+nf] */,
+                         void* stream);
+
+/* ---- backward of the fully-connected denoiser (training; egnn_backward.hip) -------------------------------
+ * Gradient of sum(grad_out * Dynamics.forward(...)) with respect to every parameter of a fully-connected Dynamics
+ * (egnn_dynamics, hidden_nf = 128, SiLU, sum aggregation, no attention / tanh / sin_embedding; any n_layers, inv_sublayers
+ * 1..4, context width, norm_constant, normalization_factor, condition_time; centering = the velocity's mean removal of
+ * InpaintingEDM).  Parameters and gradient are ONE flat fp32 buffer each, in Dynamics.parameters() order (the raw, unpadded
+ * tensors of the state_dict; n_params must be dl_egnn_backward_fc_num_params).  The forward is recomputed in fp32 inside
+ * (x, h of every sublayer saved to the workspace, pair activations recomputed per tile, never stored).  Deterministic: per
+ * molecule partial gradients in the workspace, summed over molecules in a fixed order; no atomics.  The callee allocates
+ * nothing; argument checks (DL_ERR_BAD_ARG, DL_ERR_UNSUPPORTED) come before any device work; runs on `stream`. */
+typedef struct dl_backward_args {
+    int32_t B, N;
+    int32_t in_node_nf, context_node_nf, condition_time, hidden_nf, n_layers, inv_sublayers;
+    int32_t centering;              /* 1: d eps_hat passes through the velocity's mean removal (InpaintingEDM) */
+    float norm_constant, normalization_factor;
+    const float* params;            /* device f32 [n_params] */
+    int64_t n_params;
+    const float* xh;                /* device f32 [B,N,3+nf]: the denoiser's input z_t */
+    const float* t;                 /* device f32 [B] or [1] (t_is_scalar) */
+    int32_t t_is_scalar;
+    const float* node_mask;         /* device f32 [B,N] */
+    const float* linker_mask;       /* device f32 [B,N] or NULL */
+    const int8_t* edge_mask;        /* device int8 [B,N,N] as collate builds it (0 / -1 / -2, multiplied as-is) */
+    const float* context;           /* device f32 [B,N,context_node_nf] or NULL */
+    const float* grad_out;          /* device f32 [B,N,3+nf]: d eps_hat */
+    float* grad_params;             /* device f32 [n_params] out */
+    void* workspace;                /* device, >= dl_egnn_backward_fc_workspace_bytes */
+    size_t workspace_bytes;
+} dl_backward_args;
+int64_t dl_egnn_backward_fc_num_params(const dl_backward_args* args);          /* -1 outside the scope */
+size_t dl_egnn_backward_fc_workspace_bytes(const dl_backward_args* args);      /* reads B, N and the hyper-parameters; 0 outside */
+int32_t dl_egnn_backward_max_atoms(void);
+int32_t dl_egnn_backward_fc(const dl_backward_args* args, void* stream);
+
 /* Diagnostics (libraries built with -DDL_PROFILE only; dl_profile_max_events() returns 0 otherwise): when set
  * (device uint64 [8 waves][dl_profile_max_events()][2], or NULL to disable), the first workgroup of the next
  * launches logs (phase tag, shader clock) pairs of its first forward. */
