@@ -95,6 +95,18 @@ class DLBackwardArgs(ctypes.Structure):
     ]
 
 
+class DLSizeTrainArgs(ctypes.Structure):
+    _fields_ = [
+        ('B', ctypes.c_int32), ('N', ctypes.c_int32), ('in_node_nf', ctypes.c_int32), ('hidden_nf', ctypes.c_int32),
+        ('out_node_nf', ctypes.c_int32), ('n_layers', ctypes.c_int32), ('batch_norm', ctypes.c_int32),
+        ('params', ctypes.c_void_p), ('n_params', ctypes.c_int64), ('one_hot', ctypes.c_void_p),
+        ('positions', ctypes.c_void_p), ('fragment_mask', ctypes.c_void_p), ('edge_mask', ctypes.c_void_p),
+        ('logits', ctypes.c_void_p), ('batch_stats', ctypes.c_void_p), ('flags', ctypes.c_void_p),
+        ('grad_logits', ctypes.c_void_p), ('grad_params', ctypes.c_void_p), ('workspace', ctypes.c_void_p),
+        ('workspace_bytes', ctypes.c_size_t),
+    ]
+
+
 EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_string', 'dl_model_num_tensors',
            'dl_model_create', 'dl_model_destroy', 'dl_egnn_forward_fc', 'dl_sampler_step', 'dl_sample_chain_fc',
            'dl_set_profile_buffer', 'dl_profile_max_events', 'dl_pocket_workspace_bytes', 'dl_egnn_forward_pocket',
@@ -102,7 +114,8 @@ EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_stri
            'dl_size_gnn_forward', 'dl_philox_fill', 'dl_egnn_forward_fc_large', 'dl_inpaint_step', 'dl_workspace_bytes',
            'dl_team_max', 'dl_egnn_forward_fc_team', 'dl_team_max_atoms',
            'dl_edm_loss_prologue', 'dl_edm_loss_epilogue', 'dl_edm_loss_grad', 'dl_egnn_backward_fc_num_params',
-           'dl_egnn_backward_fc_workspace_bytes', 'dl_egnn_backward_max_atoms', 'dl_egnn_backward_fc')
+           'dl_egnn_backward_fc_workspace_bytes', 'dl_egnn_backward_max_atoms', 'dl_egnn_backward_fc',
+           'dl_size_train_num_params', 'dl_size_train_workspace_bytes', 'dl_size_train_forward', 'dl_size_train_backward')
 TEST_HOOK_EXPORTS = ('dl_debug_team_fault',)       # declared under #ifdef DL_TEST_HOOKS: the test-hooks build only
 
 _lib = None
@@ -201,6 +214,13 @@ def _open(path):
     lib.dl_egnn_backward_max_atoms.restype = i32
     lib.dl_egnn_backward_fc.restype = i32
     lib.dl_egnn_backward_fc.argtypes = [ctypes.POINTER(DLBackwardArgs), vp]
+    lib.dl_size_train_num_params.restype = ctypes.c_int64
+    lib.dl_size_train_num_params.argtypes = [ctypes.POINTER(DLSizeTrainArgs)]
+    lib.dl_size_train_workspace_bytes.restype = ctypes.c_size_t
+    lib.dl_size_train_workspace_bytes.argtypes = [ctypes.POINTER(DLSizeTrainArgs)]
+    for name in ('dl_size_train_forward', 'dl_size_train_backward'):
+        getattr(lib, name).restype = i32
+        getattr(lib, name).argtypes = [ctypes.POINTER(DLSizeTrainArgs), vp]
     lib.dl_size_model_num_tensors.restype = i32
     lib.dl_size_model_num_tensors.argtypes = [ctypes.POINTER(DLSizeConfig)]
     lib.dl_size_model_create.restype = i32

@@ -33,6 +33,9 @@
  *                                           SizeClassifier.forward at inference
  *                                           (src/linker_size_lightning.py:83-110): the `sample_fn`
  *                                           of generate.py:86-99 that runs once before a chain
+ *   dl_size_train_forward / dl_size_train_backward
+ *                                        <- SizeClassifier.forward in training mode + loss.backward()
+ *                                           (src/linker_size_lightning.py:83-117, :163-167)
  *
  * Conventions
  *   - every pointer marked "device" is a HIP device pointer owned by the caller (PyTorch-ROCm
@@ -450,6 +453,41 @@ int32_t dl_size_gnn_forward(const dl_size_model* m, int32_t B, int32_t N, const 
                             const float* positions, const float* fragment_mask, const float* edge_mask,
                             const float* distances, float* logits, int32_t* flags, void* stream);
 
+
+/* ---- training of the linker-size predictor (size_gnn_train.hip) -----------------------------------------
+ * SizeClassifier.forward in training mode (src/linker_size_lightning.py:83-117: BatchNorm1d normalising over ALL B*N rows,
+ * padding and linker rows included) and the gradient of sum(grad_logits * logits) with respect to every parameter.  Scope:
+ * hidden_nf = 128, normalization None (batch_norm = 0) or 'batch_norm' (1, eps 1e-5), any n_layers, in_node_nf <= 16,
+ * out_node_nf <= 64, at most dl_size_max_fragment_atoms() fragment atoms per molecule.  params / grad_params are ONE flat fp32
+ * buffer each in SizeGNN.parameters() order: the raw weights, BatchNorm affine weight and bias included (n_params must be
+ * dl_size_train_num_params).  The forward saves its state in the workspace; the backward reads the workspace of the matching
+ * forward (same args, same params, the workspace untouched in between).  Deterministic: fixed-order reductions, no atomics.
+ * The callee allocates nothing; null pointers, a wrong n_params, a too-small workspace and B*N < 2 with BatchNorm return
+ * DL_ERR_BAD_ARG, hyper-parameters outside the scope DL_ERR_UNSUPPORTED, all before any device work. */
+typedef struct dl_size_train_args {
+    int32_t B, N;
+    int32_t in_node_nf, hidden_nf, out_node_nf, n_layers;
+    int32_t batch_norm;             /* 0: normalization None, 1: 'batch_norm' */
+    const float* params;            /* device f32 [n_params] */
+    int64_t n_params;
+    const float* one_hot;           /* device f32 [B,N,in_node_nf] */
+    const float* positions;         /* device f32 [B,N,3] */
+    const float* fragment_mask;     /* device f32 [B,N]: the GNN's node mask */
+    const float* edge_mask;         /* device f32 [B,N,N]: an edge is kept where != 0 and |x_i - x_j|^2 < 6 */
+    float* logits;                  /* device f32 [B,out_node_nf] out (forward) */
+    float* batch_stats;             /* device f32 [n_layers][2: node_mlp.1, node_mlp.4][2: mean, biased var][128] out
+                                       (forward, batch_norm = 1 only) */
+    int32_t* flags;                 /* device int32 [B] out (forward): 4 = more fragment atoms than
+                                       dl_size_max_fragment_atoms() (that molecule's results are meaningless) */
+    const float* grad_logits;       /* device f32 [B,out_node_nf] (backward) */
+    float* grad_params;             /* device f32 [n_params] out (backward) */
+    void* workspace;                /* device, >= dl_size_train_workspace_bytes */
+    size_t workspace_bytes;
+} dl_size_train_args;
+int64_t dl_size_train_num_params(const dl_size_train_args* args);        /* -1 outside the scope */
+size_t dl_size_train_workspace_bytes(const dl_size_train_args* args);    /* reads B and the hyper-parameters; 0 outside */
+int32_t dl_size_train_forward(const dl_size_train_args* args, void* stream);
+int32_t dl_size_train_backward(const dl_size_train_args* args, void* stream);
 
 const char* dl_error_string(int32_t status);
 int32_t dl_last_hip_error(void);
