@@ -66,6 +66,13 @@ class DLChainArgs(ctypes.Structure):
     ]
 
 
+class DLJoinArgs(ctypes.Structure):
+    _fields_ = [
+        ('teams', ctypes.c_int32), ('team_of', ctypes.c_void_p), ('team_mol', ctypes.c_void_p),
+        ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_size_t), ('wait_ticks', ctypes.c_void_p),
+    ]
+
+
 LOSS_ROW = 8          # DL_LOSS_ROW: error_t, |eps_hat|, kl_prior, log p(x|z0), log p(h|z0), log constant, SNR weight, atoms
 
 
@@ -115,7 +122,8 @@ EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_stri
            'dl_team_max', 'dl_egnn_forward_fc_team', 'dl_team_max_atoms',
            'dl_edm_loss_prologue', 'dl_edm_loss_epilogue', 'dl_edm_loss_grad', 'dl_egnn_backward_fc_num_params',
            'dl_egnn_backward_fc_workspace_bytes', 'dl_egnn_backward_max_atoms', 'dl_egnn_backward_fc',
-           'dl_size_train_num_params', 'dl_size_train_workspace_bytes', 'dl_size_train_forward', 'dl_size_train_backward')
+           'dl_size_train_num_params', 'dl_size_train_workspace_bytes', 'dl_size_train_forward', 'dl_size_train_backward',
+           'dl_join_workspace_bytes', 'dl_sample_chain_fc_join')
 TEST_HOOK_EXPORTS = ('dl_debug_team_fault',)       # declared under #ifdef DL_TEST_HOOKS: the test-hooks build only
 
 _lib = None
@@ -198,6 +206,10 @@ def _open(path):
     lib.dl_egnn_forward_fc_large.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
     lib.dl_sample_chain_fc.restype = i32
     lib.dl_sample_chain_fc.argtypes = [vp, ctypes.POINTER(DLChainArgs), vp]
+    lib.dl_join_workspace_bytes.restype = ctypes.c_size_t
+    lib.dl_join_workspace_bytes.argtypes = [i32]
+    lib.dl_sample_chain_fc_join.restype = i32
+    lib.dl_sample_chain_fc_join.argtypes = [vp, ctypes.POINTER(DLChainArgs), ctypes.POINTER(DLJoinArgs), vp]
     lib.dl_inpaint_step.restype = i32
     lib.dl_inpaint_step.argtypes = [i32, i32, i32] + [vp] * 10 + [DLInpaintCoef, vp, vp]
     lib.dl_philox_fill.restype = i32

@@ -2448,79 +2448,70 @@ __device__ __forceinline__ bool chain_step2(const Lds& v, int q) {
     return true;
 }
 
-template <int PREC, bool TEAM, bool ATT>
-__global__ void __launch_bounds__(THREADS) sample_chain_fc_kernel(ChainArgs p) {
-    __shared__ __attribute__((aligned(16))) float lds_raw[L_TOTAL];   // static: every LDS address is a constant
-    const Lds v = lds_view(lds_raw);
-    int T, qb, qe;
-    {
-        const dl_chain_args& g = p.a;
-        const int tid = threadIdx.x;
-        int k = blockIdx.x, rank = 0, S = 1;
-        const int count = g.order_count > 0 ? g.order_count : g.B;        // molecules of THIS launch (a part of the batch, or all of it)
-        if constexpr (TEAM) {
-            const TeamSlot ts = team_slot(blockIdx.x, g.team);
-            if (ts.slot >= count) return;
-            k = ts.slot; rank = ts.rank; S = g.team;
-        }
-        const int b = g.order ? g.order[g.order_first + k] : k;
-        const int N = g.N, nf = p.md.nf, D = 3 + nf, K = g.keep_frames, B = g.B;
-        const int limit = TEAM ? NQMAX : NMAX;
-        T = g.T;
-        // a chain in two launches (dl_chain_args.q_begin / q_end): this launch's part of the T + 1 denoiser calls of molecule b
-        qb = g.q_begin ? g.q_begin[b] : 0;
-        qe = g.q_end ? g.q_end[b] : T + 1;
-        if (g.skip_flags && g.skip_flags[b] != 0) return;          // (it ended in the first launch; every member takes this branch)
-        const int8_t* nm = g.node_mask + size_t(b) * N;
-        const size_t frame = size_t(B) * N * D;
-        float* chain_b = g.chain + size_t(b) * N * D;
-        const int nb = compact_atoms(v, nm, N, tid);
-        if (rank == 0) {
-            if (tid == 0) {
-                if (TEAM) { if (nb > limit) atomicOr(&g.nan_flags[b], 4); }      // (a team's flags start at 0 / -1: set by the host)
-                else { g.nan_flags[b] = (nb > limit) ? 4 : 0; g.nan_step[b] = -1; }
-            }
-            // padded rows of every frame are zero (z is masked; chain starts from torch.zeros, edm.py:143)
-            for (int kf = 0; kf < K; ++kf)
-                for (int e = tid; e < N * D; e += THREADS)
-                    if (nm[e / D] == 0 || nb > limit) chain_b[kf * frame + e] = 0.0f;
-        }
-        if (nb > limit || nb == 0) return;
+// Start of a molecule's part of the chain (workgroup of molecule b, member `rank` of `S`): atoms, masks, receivers and the
+// state z of the own atoms in LDS - from x, h and draw 0, or from z_state when the part resumes (qb > 0).  `rows` / `flags`:
+// the team's exchange buffer and arrival words (TEAM).  false: nothing to sample (no atom, too many, or skipped).
+template <bool TEAM>
+__device__ __forceinline__ bool chain_begin(const ChainArgs& p, const Lds& v, int b, int rank, int S, int qb, char* rows,
+                                            unsigned* flags) {
+    const dl_chain_args& g = p.a;
+    const int tid = threadIdx.x;
+    const int N = g.N, nf = p.md.nf, D = 3 + nf, K = g.keep_frames, B = g.B;
+    const int limit = TEAM ? NQMAX : NMAX;
+    if (g.skip_flags && g.skip_flags[b] != 0) return false;        // (it ended in the first launch; every member takes this branch)
+    const int8_t* nm = g.node_mask + size_t(b) * N;
+    const size_t frame = size_t(B) * N * D;
+    float* chain_b = g.chain + size_t(b) * N * D;
+    const int nb = compact_atoms(v, nm, N, tid);
+    if (rank == 0) {
         if (tid == 0) {
-            if (TEAM) team_init(v, nb, S, rank, p.team_rows + size_t(k) * TEAM_MOL_BYTES, p.team_flags + size_t(k) * TEAM_MAX, p.team_fault);
-            ctx_store(v, p.md, N, g.edge_mask ? g.edge_mask + size_t(b) * N * N : nullptr, p.hsave + size_t(blockIdx.x) * HS_STRIDE,
-                      p.wpack, g.context ? g.context + size_t(b) * N * p.md.ctx : nullptr, 0.0f, b);
+            if (TEAM) { if (nb > limit) atomicOr(&g.nan_flags[b], 4); }      // (a team's flags start at 0 / -1: set by the host)
+            else { g.nan_flags[b] = (nb > limit) ? 4 : 0; g.nan_step[b] = -1; }
         }
-        __syncthreads();
-        const int nown = TEAM ? v.misc[TM_NOWN] : nb;
-        if (tid < nown) {
-            const size_t n = size_t(b) * N + v.idx[rank + tid * S];
-            v.lm[tid] = g.linker_mask[n];
-            v.frag[tid] = g.fragment_mask[n];
-        }
-        __syncthreads();
-        build_receivers(v, nown, tid);
-        const bool philox = (g.noise_x == nullptr);                // draws generated in place (pack_layout.h: philox_normal)
-        const unsigned gmol = unsigned(g.mol_offset + (g.mol_index ? g.mol_index[b] : b));     // global molecule index: the noise key
-        // z = normalize(x,h) * fragment_mask + noise_0 * linker_mask   (edm.py:132-137,347-350)
-        for (int e = tid; e < nown * D; e += THREADS) {
-            const int l = e / D, d = e - l * D;
-            const int pos = v.idx[rank + l * S];
-            const size_t n = size_t(b) * N + pos;
-            float val, eps0;
-            if (d < 3) { val = __fdiv_rn(g.x[n * 3 + d], g.norm_x); eps0 = philox ? 0.0f : g.noise_x[n * 3 + d]; }
-            else { val = __fdiv_rn(__fsub_rn(g.h[n * nf + d - 3], g.bias_h), g.norm_h); eps0 = philox ? 0.0f : g.noise_h[n * nf + d - 3]; }
-            if (philox) eps0 = philox_normal(g.noise_seed, gmol, unsigned(pos), 0u, unsigned(d));
-            const float lm = v.lm[l];
-            float z0 = __fadd_rn(__fmul_rn(val, v.frag[l]), __fmul_rn(__fmul_rn(eps0, lm), lm));
-            if (qb > 0) z0 = g.z_state[n * D + d];                 // resumed: the state the first launch left
-            v.z[l * DMAX + d] = z0;
-        }
-        __syncthreads();
+        // padded rows of every frame are zero (z is masked; chain starts from torch.zeros, edm.py:143)
+        for (int kf = 0; kf < K; ++kf)
+            for (int e = tid; e < N * D; e += THREADS)
+                if (nm[e / D] == 0 || nb > limit) chain_b[kf * frame + e] = 0.0f;
     }
-#pragma nounroll
-    for (int q = qb; q < qe; ++q)
-        if (!chain_step2<PREC, TEAM, ATT>(v, q)) return;
+    if (nb > limit || nb == 0) return false;
+    if (tid == 0) {
+        if (TEAM) team_init(v, nb, S, rank, rows, flags, p.team_fault);
+        ctx_store(v, p.md, N, g.edge_mask ? g.edge_mask + size_t(b) * N * N : nullptr, p.hsave + size_t(blockIdx.x) * HS_STRIDE,
+                  p.wpack, g.context ? g.context + size_t(b) * N * p.md.ctx : nullptr, 0.0f, b);
+    }
+    __syncthreads();
+    const int nown = TEAM ? v.misc[TM_NOWN] : nb;
+    if (tid < nown) {
+        const size_t n = size_t(b) * N + v.idx[rank + tid * S];
+        v.lm[tid] = g.linker_mask[n];
+        v.frag[tid] = g.fragment_mask[n];
+    }
+    __syncthreads();
+    build_receivers(v, nown, tid);
+    const bool philox = (g.noise_x == nullptr);                // draws generated in place (pack_layout.h: philox_normal)
+    const unsigned gmol = unsigned(g.mol_offset + (g.mol_index ? g.mol_index[b] : b));     // global molecule index: the noise key
+    // z = normalize(x,h) * fragment_mask + noise_0 * linker_mask   (edm.py:132-137,347-350)
+    for (int e = tid; e < nown * D; e += THREADS) {
+        const int l = e / D, d = e - l * D;
+        const int pos = v.idx[rank + l * S];
+        const size_t n = size_t(b) * N + pos;
+        float val, eps0;
+        if (d < 3) { val = __fdiv_rn(g.x[n * 3 + d], g.norm_x); eps0 = philox ? 0.0f : g.noise_x[n * 3 + d]; }
+        else { val = __fdiv_rn(__fsub_rn(g.h[n * nf + d - 3], g.bias_h), g.norm_h); eps0 = philox ? 0.0f : g.noise_h[n * nf + d - 3]; }
+        if (philox) eps0 = philox_normal(g.noise_seed, gmol, unsigned(pos), 0u, unsigned(d));
+        const float lm = v.lm[l];
+        float z0 = __fadd_rn(__fmul_rn(val, v.frag[l]), __fmul_rn(__fmul_rn(eps0, lm), lm));
+        if (qb > 0) z0 = g.z_state[n * D + d];                 // resumed: the state the first launch left
+        v.z[l * DMAX + d] = z0;
+    }
+    __syncthreads();
+    return true;
+}
+
+// End of a molecule's part of the chain after call qe - 1: stopped early (qe <= T), the state of the own atoms goes to z_state;
+// otherwise frame 0, the final sample [x, one_hot(h)] of the own atoms
+template <bool TEAM>
+__device__ __forceinline__ void chain_end(const Lds& v, int qe, int T) {
     if (qe <= T) {                                                 // stopped early: hand the state over (dl_chain_args.z_state)
         const auto* P = kargs<ChainArgs>();
         const int tid = lane_ids(v).tid;
@@ -2553,6 +2544,124 @@ __global__ void __launch_bounds__(THREADS) sample_chain_fc_kernel(ChainArgs p) {
         }
         if (TEAM && tid == 0 && v.misc[TM_FAIL] != 0) atomicOr(&P->a.nan_flags[b], 8);
     }
+}
+
+template <int PREC, bool TEAM, bool ATT>
+__global__ void __launch_bounds__(THREADS) sample_chain_fc_kernel(ChainArgs p) {
+    __shared__ __attribute__((aligned(16))) float lds_raw[L_TOTAL];   // static: every LDS address is a constant
+    const Lds v = lds_view(lds_raw);
+    int T, qb, qe;
+    {
+        const dl_chain_args& g = p.a;
+        int k = blockIdx.x, rank = 0, S = 1;
+        const int count = g.order_count > 0 ? g.order_count : g.B;        // molecules of THIS launch (a part of the batch, or all of it)
+        if constexpr (TEAM) {
+            const TeamSlot ts = team_slot(blockIdx.x, g.team);
+            if (ts.slot >= count) return;
+            k = ts.slot; rank = ts.rank; S = g.team;
+        }
+        const int b = g.order ? g.order[g.order_first + k] : k;
+        T = g.T;
+        // a chain in two launches (dl_chain_args.q_begin / q_end): this launch's part of the T + 1 denoiser calls of molecule b
+        qb = g.q_begin ? g.q_begin[b] : 0;
+        qe = g.q_end ? g.q_end[b] : T + 1;
+        if (!chain_begin<TEAM>(p, v, b, rank, S, qb, TEAM ? p.team_rows + size_t(k) * TEAM_MOL_BYTES : nullptr,
+                               TEAM ? p.team_flags + size_t(k) * TEAM_MAX : nullptr)) return;
+    }
+#pragma nounroll
+    for (int q = qb; q < qe; ++q)
+        if (!chain_step2<PREC, TEAM, ATT>(v, q)) return;
+    chain_end<TEAM>(v, qe, T);
+}
+
+// ---- the hand-over inside ONE launch (dl_sample_chain_fc_join).  Workgroup k samples molecule order[k] on its own compute unit
+// (TEAM = false) up to q_end[b]; then the molecules of the plan go on as TEAMS OF TWO: the OWNER (q_end[b] <= T) leaves z in
+// z_state and becomes member 0, a HELPER (a molecule whose own chain is over, a NaN included) becomes member 1 of the team it
+// was given (team_of[b]).  The two meet through one word each in the team's join block: the owner publishes JW_READY (or
+// JW_DEAD: its molecule ended - NaN - before the switch; the helper then leaves), the helper JW_HERE; each waits for the other's
+// word (relaxed agent-scope polls with s_sleep, bounded by the wall clock with room for a partner a whole chain late).  A member
+// that gives up publishes JW_POISON - a partner that sees it gives up too - and sets flag bit 3 on the team's molecule: the
+// host re-runs the chain with one compute unit per molecule.  The team phase is the team kernel's (chain_begin<true> from
+// z_state, chain_step2<PREC, true, ATT>, decode): a team molecule gets exactly the numbers of the two-launch hand-over at the
+// same switch call.  Every workgroup must be resident at once: a cooperative launch.
+constexpr unsigned JW_READY = 1u, JW_DEAD = 2u, JW_HERE = 3u, JW_POISON = 0xFFFFFFFFu;
+constexpr unsigned long long JOIN_WAIT_TICKS = 100000000ull * 20;    // 20 s of the 100 MHz wall clock (s_memrealtime)
+constexpr int JOIN_WORDS = 4;                                       // per team: [0] owner, [1] helper, [2..3] spare (16 bytes)
+
+struct JoinArgs {
+    ChainArgs c;                    // first: kargs<ChainArgs>() of the shared device code reads it at offset 0
+    const int32_t* team_of;
+    const int32_t* team_mol;
+    unsigned* words;                // [teams][JOIN_WORDS]
+    unsigned long long* wait_ticks; // [teams][2] or null
+};
+
+// member `rank` of team j is there: publish `mine`, wait for the partner's word (tid 0; the others wait at the barrier).  Returns
+// the partner's word (JW_POISON after a timeout of our own) and records how long we waited.
+__device__ __forceinline__ unsigned join_meet(const Lds& v, unsigned* words, int rank, unsigned mine, unsigned long long* wait) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // every storing wave: its stores (z_state) have left
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        typedef __attribute__((address_space(1))) unsigned gu32;
+        gu32* w = reinterpret_cast<gu32*>(reinterpret_cast<unsigned long long>(words));
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");            // (agent scope: z_state is visible before the word)
+        __hip_atomic_store(w + rank, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+        unsigned other = 0;
+        if (mine != JW_DEAD && mine != JW_POISON) {
+            for (;;) {
+                other = __hip_atomic_load(w + (1 - rank), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (other != 0) break;
+                if (__builtin_amdgcn_s_memrealtime() - t0 > JOIN_WAIT_TICKS) {
+                    __hip_atomic_store(w + rank, JW_POISON, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    other = JW_POISON;
+                    break;
+                }
+                __builtin_amdgcn_s_sleep(32);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");       // (the owner's z_state, for the helper)
+        }
+        if (wait) wait[rank] = __builtin_amdgcn_s_memrealtime() - t0;
+        v.misc[TM_FAIL] = int(other);
+    }
+    __syncthreads();
+    return unsigned(v.misc[TM_FAIL]);
+}
+
+template <int PREC, bool ATT>
+__global__ void __launch_bounds__(THREADS) sample_chain_fc_kernel_join(JoinArgs p) {
+    __shared__ __attribute__((aligned(16))) float lds_raw[L_TOTAL];   // static: every LDS address is a constant
+    const Lds v = lds_view(lds_raw);
+    const int k = blockIdx.x;
+    const int b = p.c.a.order ? p.c.a.order[k] : k;
+    const int T = p.c.a.T, qe = p.c.a.q_end[b];
+    // own molecule, one compute unit
+    bool alive = chain_begin<false>(p.c, v, b, 0, 1, 0, nullptr, nullptr);
+    if (alive) {
+#pragma nounroll
+        for (int q = 0; q < qe; ++q)
+            if (!chain_step2<PREC, false, ATT>(v, q)) { alive = false; break; }
+    }
+    if (alive) chain_end<false>(v, qe, T);
+    // team phase
+    const int j = p.team_of[b];
+    if (j < 0) return;
+    const int rank = qe <= T ? 0 : 1;
+    const int bo = rank == 0 ? b : p.team_mol[j];
+    const unsigned mine = rank == 1 ? JW_HERE : alive ? JW_READY : JW_DEAD;
+    const unsigned other = join_meet(v, p.words + size_t(j) * JOIN_WORDS, rank, mine,
+                                     p.wait_ticks ? p.wait_ticks + size_t(j) * 2 : nullptr);
+    if (mine == JW_DEAD || other == JW_DEAD) return;
+    if (other == JW_POISON) {                                  // the team did not assemble: the host re-runs the chain
+        if (threadIdx.x == 0) atomicOr(&p.c.a.nan_flags[bo], 8);
+        return;
+    }
+    const int qb = p.c.a.q_end[bo];
+    if (!chain_begin<true>(p.c, v, bo, rank, 2, qb, p.c.team_rows + size_t(j) * TEAM_MOL_BYTES,
+                           p.c.team_flags + size_t(j) * TEAM_MAX)) return;
+#pragma nounroll
+    for (int q = qb; q <= T; ++q) chain_step2<PREC, true, ATT>(v, q);
+    chain_end<true>(v, T + 1, T);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -3290,6 +3399,50 @@ int32_t dl_sample_chain_fc(const dl_model* m, const dl_chain_args* g, void* stre
         !hip_ok(hipMemsetAsync(g->nan_step, 0xFF, size_t(g->B) * sizeof(int32_t), st))) return DL_ERR_HIP;
     const hipError_t e = launch_team(kernel, ws.grid, st, &a);
     return hip_ok(e) ? DL_OK : DL_ERR_HIP;
+}
+
+// ---- the hand-over inside one launch (sample_chain_fc_kernel_join): [exchange buffers][arrival words][join words] per team
+size_t dl_join_workspace_bytes(int32_t teams) {
+    if (teams <= 0) return 0;
+    return size_t(teams) * (TEAM_MOL_BYTES + TEAM_MAX * sizeof(unsigned) + JOIN_WORDS * sizeof(unsigned));
+}
+
+int32_t dl_sample_chain_fc_join(const dl_model* m, const dl_chain_args* g, const dl_join_args* jn, void* stream) {
+    if (!m || !g || !jn) return DL_ERR_BAD_ARG;
+    if (!g->x || !g->h || !g->node_mask || !g->fragment_mask || !g->linker_mask ||
+        !g->coefs || !g->chain || !g->nan_flags || !g->nan_step) return DL_ERR_BAD_ARG;
+    if ((g->noise_x == nullptr) != (g->noise_h == nullptr)) return DL_ERR_BAD_ARG;
+    if (m->cfg.context_node_nf > 0 && !g->context) return DL_ERR_BAD_ARG;
+    if (g->B < 1 || g->N < 1 || g->T < 1 || g->keep_frames < 1 || g->keep_frames > g->T || g->team > 1 || g->team < 0) return DL_ERR_BAD_ARG;
+    // every molecule of the batch, each on its own workgroup: no part launches, no resumed molecules
+    if (g->order_first != 0 || g->order_count != 0 || g->q_begin || g->skip_flags || !g->q_end || !g->z_state) return DL_ERR_BAD_ARG;
+    if (jn->teams < 1 || 2 * jn->teams > g->B || !jn->team_of || !jn->team_mol) return DL_ERR_BAD_ARG;
+    if (!jn->workspace || jn->workspace_bytes < dl_join_workspace_bytes(jn->teams) ||
+        (reinterpret_cast<uintptr_t>(jn->workspace) & 15u) != 0) return DL_ERR_BAD_ARG;
+    if (m->cfg.sin_embedding) return DL_ERR_UNSUPPORTED;
+    int dev = 0, cus = 0;
+    if (!hip_ok(hipGetDevice(&dev)) || !hip_ok(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev))) return DL_ERR_HIP;
+    if (g->B > cus) return DL_ERR_BAD_ARG;                  // every workgroup resident at once: one per compute unit
+    JoinArgs a;
+    a.c.wpack = m->d_pack; a.c.md = dims_of(m); a.c.a = *g; a.c.a.team = 1; a.c.prof = g_prof_buf;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    FcWorkspace ws;
+    const int32_t rc = fc_workspace(g->B, 1, g->workspace, g->workspace_bytes, st, &ws);
+    if (rc != DL_OK) return rc;
+    char* w = static_cast<char*>(jn->workspace);
+    a.c.hsave = ws.hsave;
+    a.c.team_rows = w;
+    a.c.team_flags = reinterpret_cast<unsigned*>(w + size_t(jn->teams) * TEAM_MOL_BYTES);
+    a.words = a.c.team_flags + size_t(jn->teams) * TEAM_MAX;
+    a.c.team_fault = take_team_fault();
+    a.team_of = jn->team_of; a.team_mol = jn->team_mol;
+    a.wait_ticks = reinterpret_cast<unsigned long long*>(jn->wait_ticks);
+    if (!hip_ok(hipMemsetAsync(a.c.team_flags, 0, size_t(jn->teams) * (TEAM_MAX + JOIN_WORDS) * sizeof(unsigned), st))) return DL_ERR_HIP;
+    const bool f16 = m->cfg.precision != DL_PRECISION_FP32, att = m->cfg.attention != 0, two = m->cfg.precision == DL_PRECISION_F16X2 && !att;
+    const void* kernel = two ? (const void*)&sample_chain_fc_kernel_join<2, false>
+                       : f16 ? (att ? (const void*)&sample_chain_fc_kernel_join<1, true> : (const void*)&sample_chain_fc_kernel_join<1, false>)
+                             : (att ? (const void*)&sample_chain_fc_kernel_join<0, true> : (const void*)&sample_chain_fc_kernel_join<0, false>);
+    return hip_ok(launch_team(kernel, g->B, st, &a)) ? DL_OK : DL_ERR_HIP;
 }
 
 namespace {

@@ -129,6 +129,54 @@ def split_plan(sizes, linkers, n_calls, compute_units, n_layers, sublayers, min_
     return plan
 
 
+def join_plan(sizes, linkers, n_calls, compute_units, n_layers, sublayers, margin=0.03):
+    """The hand-over of split_plan inside ONE launch (dl_sample_chain_fc_join): the same molecules (OWNERS, split_plan's teams)
+    move to a team of two, but each as soon as a HELPER - a molecule that finished its own chain - is free, instead of all
+    together behind the slowest molecule of a first launch.  Helpers are the molecules that split_plan leaves on one compute
+    unit, matched in order: the earliest-finishing helper to the owner with the most work (pair i of both sorted lists).
+    The owner's switch call is the first one it reaches a fraction `margin` after its helper's predicted finish: the helper
+    usually arrives first and waits off the critical path, the owner seldom does.  A function of the sizes alone (cached).
+    Returns (q_end [B]: switch call of an owner, n_calls for everybody else, owners [teams], helpers [teams]) or None: no
+    split_plan, or fewer finished molecules than teams."""
+    split = split_plan(sizes, linkers, n_calls, compute_units, n_layers, sublayers)
+    if split is None:
+        return None
+    key = ('join', tuple(sizes), tuple(linkers), n_calls, compute_units, n_layers, sublayers, margin)
+    with _CACHE_LOCK:
+        if key in _PLAN_CACHE:
+            return _PLAN_CACHE[key]
+    owners = list(split[1])
+    in_team = set(owners)
+    rest = [b for b in range(len(sizes)) if b not in in_team]
+    plan = None
+    if len(rest) >= len(owners):
+        c1 = [forward_cost(n, l, n_layers, sublayers, 1) for n, l in zip(sizes, linkers)]
+        owners.sort(key=lambda b: (-c1[b], b))                     # most work first; ties by index: deterministic
+        rest.sort(key=lambda b: (c1[b], b))                         # earliest finish first
+        helpers = rest[:len(owners)]
+        q_end = [n_calls] * len(sizes)
+        for o, hp in zip(owners, helpers):
+            arrive = n_calls * c1[hp] * (1.0 + margin)
+            q_end[o] = int(min(max(-(-arrive // c1[o]), 1), n_calls - 1))
+        plan = (q_end, owners, helpers)
+    with _CACHE_LOCK:
+        if len(_PLAN_CACHE) > 64:
+            _PLAN_CACHE.clear()
+        _PLAN_CACHE[key] = plan
+    return plan
+
+
+def join_makespan(plan, sizes, linkers, n_calls, n_layers, sublayers):
+    """Makespan of a join_plan by the cost model (forward_cost units): a team starts when the later of owner and helper is there."""
+    q_end, owners, helpers = plan
+    c1 = [forward_cost(n, l, n_layers, sublayers, 1) for n, l in zip(sizes, linkers)]
+    end = [n_calls * c for c in c1]
+    for o, hp in zip(owners, helpers):
+        start = max(q_end[o] * c1[o], end[hp])
+        end[o] = start + (n_calls - q_end[o]) * forward_cost(sizes[o], linkers[o], n_layers, sublayers, 2)
+    return max(end)
+
+
 class EDM(torch.nn.Module):
     def __init__(
             self,
@@ -741,22 +789,28 @@ class EDM(torch.nn.Module):
                               f'the rest) use the chip evenly', RuntimeWarning, stacklevel=3)
         ws, ws_bytes = self.dynamics.workspace(bs - over, team, dev)
 
-        # the static hand-over inside a ragged batch that fills the chip (split_plan): two launches
+        # the hand-over inside a ragged batch that fills the chip: ONE launch in which split_plan's teams form as helpers free up
+        # (join_plan, dl_sample_chain_fc_join); two launches (split_plan) only when too few molecules finish early to help
         # (not for a shard of a batch - EDM.team_batch pinned, distributed.sample_chain_sharded: the plan follows the sizes of the
         # molecules at hand, and a molecule's sample must not depend on how its batch was split - SURVEY 8e)
-        plan = None
+        plan = join = None
         if team == 1 and over == 0 and self.split_chain and self.team_batch is None and not self.dynamics._no_teams \
                 and bs <= cus and T >= 20:
             counts = torch.stack([n_real, lm.ne(0).sum(1)]).cpu()             # ONE device-to-host copy: sizes and linker sizes
             sizes_h, linkers_h = counts[0].tolist(), counts[1].tolist()
             if max(sizes_h) <= int(lib.dl_max_atoms()) and min(sizes_h) > 0:
-                plan = split_plan(sizes_h, linkers_h, T + 1, cus, self.dynamics.n_layers,
-                                  int(getattr(self.dynamics, 'inv_sublayers', 2)))
+                sub = int(getattr(self.dynamics, 'inv_sublayers', 2))
+                plan = split_plan(sizes_h, linkers_h, T + 1, cus, self.dynamics.n_layers, sub)
                 if plan is not None and int(lib.dl_team_max(len(plan[1]))) < 2:
                     plan = None                                               # the teams would not fit at once
+                if plan is not None:
+                    # one launch: each of split_plan's teams forms as soon as a molecule that finished its chain can join it
+                    join = join_plan(sizes_h, linkers_h, T + 1, cus, self.dynamics.n_layers, sub)
+                    if join is not None:
+                        plan = None
         q_end_t = z_state = None
-        if plan is not None:
-            q_end_t = torch.tensor(plan[0], dtype=torch.int32, device=dev)
+        if plan is not None or join is not None:
+            q_end_t = torch.tensor((join or plan)[0], dtype=torch.int32, device=dev)
             z_state = torch.empty((bs, n, self.n_dims + nf), device=dev)
 
         def chain_args(flags_, steps_, team_, ws_, ws_bytes_, order_, first, count, q_begin=None, q_end=None, skip=None):
@@ -807,8 +861,22 @@ class EDM(torch.nn.Module):
             if over:
                 ready = torch.cuda.Event()
                 ready.record(cur)                          # inputs, coefficients, noise bank: enqueued on the current stream
-            _lib.check(lib.dl_sample_chain_fc(handle, ctypes.byref(args), ctypes.c_void_p(cur.cuda_stream)),
-                       'dl_sample_chain_fc')
+            if join is not None:
+                _, owners, helpers = join
+                team_of = [-1] * bs
+                for j_, (o_, hp_) in enumerate(zip(owners, helpers)):
+                    team_of[o_] = team_of[hp_] = j_
+                maps = torch.tensor(team_of + owners, dtype=torch.int32, device=dev)
+                need = int(lib.dl_join_workspace_bytes(len(owners)))
+                jws = self._side_workspace((dev.index, 'join'), need, dev)
+                jargs = _lib.DLJoinArgs(teams=len(owners), team_of=maps.data_ptr(), team_mol=maps.data_ptr() + 4 * bs,
+                                        workspace=jws.data_ptr(), workspace_bytes=need, wait_ticks=None)
+                _lib.check(lib.dl_sample_chain_fc_join(handle, ctypes.byref(args), ctypes.byref(jargs),
+                                                       ctypes.c_void_p(cur.cuda_stream)), 'dl_sample_chain_fc_join')
+                self.last_split_event = None
+            else:
+                _lib.check(lib.dl_sample_chain_fc(handle, ctypes.byref(args), ctypes.c_void_p(cur.cuda_stream)),
+                           'dl_sample_chain_fc')
             if over:
                 # the molecules beyond one per compute unit, on teams beside the first launch
                 flags, steps = side_launch(ready, team2, order, bs - over, over)

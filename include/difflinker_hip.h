@@ -268,6 +268,30 @@ typedef struct dl_chain_args {
 
 int32_t dl_sample_chain_fc(const dl_model* m, const dl_chain_args* args, void* stream);
 
+/* The hand-over of a ragged batch inside ONE launch (additive to ABI v7: dl_chain_args is unchanged).  Every molecule b of the
+ * batch (B <= compute units; workgroup k samples order[k], or k) starts on its own compute unit.  A molecule with
+ * args->q_end[b] <= T is an OWNER: after q_end[b] denoiser calls it leaves its state in z_state and finishes the chain on a
+ * team of two with a HELPER - a molecule whose own chain (q_end = T+1) is over, a NaN included - that joins it there; the
+ * others run their whole chain alone.  team_of [B]: the team a molecule owns or helps, or -1; team_mol [teams]: the owner
+ * molecule of each team (each team has exactly one owner and one helper).  A team molecule gets exactly the numbers of the
+ * two-launch hand-over at the same q_end (dl_sample_chain_fc twice, team = 2 for the second); every other molecule those of
+ * the single launch.  An owner that ends in a NaN before its switch call releases its helper.  Owner and helper wait for each
+ * other for at most 20 s; a member that gives up sets nan_flags bit 3 on the team's molecule (as a team that does not assemble).
+ * args: team 0 or 1, q_end and z_state given, q_begin / skip_flags NULL, order_first = order_count = 0, workspace of
+ * dl_workspace_bytes(B, 1).  The launch is cooperative.  wait_ticks (device [teams][2] or NULL): how long the owner / the
+ * helper of each team waited for the other, in ticks of the 100 MHz wall clock (diagnostics). */
+typedef struct dl_join_args {
+    int32_t teams;
+    const int32_t* team_of;     /* device [B]                                            */
+    const int32_t* team_mol;    /* device [teams]                                        */
+    void* workspace;            /* device scratch of dl_join_workspace_bytes(teams) bytes, 16-byte aligned */
+    size_t workspace_bytes;
+    uint64_t* wait_ticks;       /* device [teams][2] or NULL                             */
+} dl_join_args;
+
+size_t dl_join_workspace_bytes(int32_t teams);
+int32_t dl_sample_chain_fc_join(const dl_model* m, const dl_chain_args* args, const dl_join_args* join, void* stream);
+
 /* Teams.  A batch smaller than the chip leaves compute units idle when every molecule sits on one of them (the reference's
  * default sampling batch is 64, generate.py:145), and a molecule of more than dl_max_atoms() atoms does not fit one compute
  * unit's LDS at all.  With team = 2, 4 or 8 that many workgroups share a molecule: its atoms are dealt round-robin, a member
