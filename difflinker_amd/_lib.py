@@ -114,6 +114,20 @@ class DLSizeTrainArgs(ctypes.Structure):
     ]
 
 
+DL_BONDS_OVERFLOW, DL_BONDS_NONFINITE = 1, 2      # dl_bonds_args.status bits
+
+
+class DLBondsArgs(ctypes.Structure):
+    _fields_ = [
+        ('B', ctypes.c_int32), ('N', ctypes.c_int32), ('nf', ctypes.c_int32),
+        ('one_hot', ctypes.c_void_p), ('x', ctypes.c_void_p), ('node_mask', ctypes.c_void_p), ('table', ctypes.c_void_p),
+        ('table_len', ctypes.c_int32), ('capacity', ctypes.c_int32),
+        ('n_bonds', ctypes.c_void_p), ('bonds', ctypes.c_void_p), ('valence', ctypes.c_void_p),
+        ('n_components', ctypes.c_void_p), ('component', ctypes.c_void_p), ('status', ctypes.c_void_p),
+        ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_size_t),
+    ]
+
+
 EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_string', 'dl_model_num_tensors',
            'dl_model_create', 'dl_model_destroy', 'dl_egnn_forward_fc', 'dl_sampler_step', 'dl_sample_chain_fc',
            'dl_set_profile_buffer', 'dl_profile_max_events', 'dl_pocket_workspace_bytes', 'dl_egnn_forward_pocket',
@@ -123,7 +137,7 @@ EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_stri
            'dl_edm_loss_prologue', 'dl_edm_loss_epilogue', 'dl_edm_loss_grad', 'dl_egnn_backward_fc_num_params',
            'dl_egnn_backward_fc_workspace_bytes', 'dl_egnn_backward_max_atoms', 'dl_egnn_backward_fc',
            'dl_size_train_num_params', 'dl_size_train_workspace_bytes', 'dl_size_train_forward', 'dl_size_train_backward',
-           'dl_join_workspace_bytes', 'dl_sample_chain_fc_join')
+           'dl_join_workspace_bytes', 'dl_sample_chain_fc_join', 'dl_bonds_workspace_bytes', 'dl_perceive_bonds')
 TEST_HOOK_EXPORTS = ('dl_debug_team_fault',)       # declared under #ifdef DL_TEST_HOOKS: the test-hooks build only
 
 _lib = None
@@ -233,6 +247,10 @@ def _open(path):
     for name in ('dl_size_train_forward', 'dl_size_train_backward'):
         getattr(lib, name).restype = i32
         getattr(lib, name).argtypes = [ctypes.POINTER(DLSizeTrainArgs), vp]
+    lib.dl_bonds_workspace_bytes.restype = ctypes.c_size_t
+    lib.dl_bonds_workspace_bytes.argtypes = [i32, i32]
+    lib.dl_perceive_bonds.restype = i32
+    lib.dl_perceive_bonds.argtypes = [ctypes.POINTER(DLBondsArgs), vp]
     lib.dl_size_model_num_tensors.restype = i32
     lib.dl_size_model_num_tensors.argtypes = [ctypes.POINTER(DLSizeConfig)]
     lib.dl_size_model_create.restype = i32

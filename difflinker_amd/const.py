@@ -1,5 +1,7 @@
-"""Constants of the sampling boundary (reference ``src/const.py:6-61``; values restated,
-the RDKit-bound bond tables of the reference are post-processing and out of scope)."""
+"""Constants of the sampling boundary (reference ``src/const.py:6-61``; values restated) and of bond perception: the
+typical bond lengths behind ``get_bond_order`` (``src/const.py:64-139,175``) as matrices over this project's atom indices,
+from which ``bond_threshold_table`` builds the table of upper bounds the HIP kernel reads.  The RDKit enumerations of the
+reference (``BOND_DICT``, ``BOND2IDX``) have no counterpart: bond orders are the integers 1, 2, 3."""
 import torch
 
 TORCH_FLOAT = torch.float32
@@ -35,3 +37,57 @@ ZINC_TRAIN_LINKER_ID2SIZE = [3, 4, 5, 6, 7, 8, 9, 10, 11, 12]
 ZINC_TRAIN_LINKER_SIZE2ID = {size: idx for idx, size in enumerate(ZINC_TRAIN_LINKER_ID2SIZE)}
 GEOM_TRAIN_LINKER_ID2SIZE = list(range(3, 33)) + [36, 38, 41]
 GEOM_TRAIN_LINKER_SIZE2ID = {size: idx for idx, size in enumerate(GEOM_TRAIN_LINKER_ID2SIZE)}
+
+# typical bond lengths in pm (const.py:64-139) by GEOM atom index (C O N F S Cl Br I P; the ZINC vocabulary is the leading
+# 8 x 8 block), 0 = the reference has no entry.  The reference looks a pair up with the atom of the LOWER index first, so
+# entry [a][b] = [b][a] is what that lookup finds; Cl-I, Br-I and I-P have no single-bond length and never bond.
+BOND_LENGTHS = (
+    (   # single
+        (154, 143, 147, 135, 182, 177, 194, 214, 184),  # C
+        (143, 148, 140, 142, 151, 164, 172, 194, 163),  # O
+        (147, 140, 145, 136, 168, 175, 214, 222, 177),  # N
+        (135, 142, 136, 142, 158, 166, 178, 187, 156),  # F
+        (182, 151, 168, 158, 204, 207, 225, 234, 210),  # S
+        (177, 164, 175, 166, 207, 199, 214,   0, 203),  # Cl
+        (194, 172, 214, 178, 225, 214, 228,   0, 222),  # Br
+        (214, 194, 222, 187, 234,   0,   0, 266,   0),  # I
+        (184, 163, 177, 156, 210, 203, 222,   0, 221),  # P
+    ),
+    (   # double
+        (134, 120, 129,   0, 160,   0,   0,   0,   0),  # C
+        (120, 121, 121,   0,   0,   0,   0,   0, 150),  # O
+        (129, 121, 125,   0,   0,   0,   0,   0,   0),  # N
+        (  0,   0,   0,   0,   0,   0,   0,   0,   0),  # F
+        (160,   0,   0,   0,   0,   0,   0,   0, 186),  # S
+        (  0,   0,   0,   0,   0,   0,   0,   0,   0),  # Cl
+        (  0,   0,   0,   0,   0,   0,   0,   0,   0),  # Br
+        (  0,   0,   0,   0,   0,   0,   0,   0,   0),  # I
+        (  0, 150,   0,   0, 186,   0,   0,   0,   0),  # P
+    ),
+    (   # triple
+        (120, 113, 116,   0,   0,   0,   0,   0,   0),  # C
+        (113,   0,   0,   0,   0,   0,   0,   0,   0),  # O
+        (116,   0, 110,   0,   0,   0,   0,   0,   0),  # N
+        (  0,   0,   0,   0,   0,   0,   0,   0,   0),  # F
+        (  0,   0,   0,   0,   0,   0,   0,   0,   0),  # S
+        (  0,   0,   0,   0,   0,   0,   0,   0,   0),  # Cl
+        (  0,   0,   0,   0,   0,   0,   0,   0,   0),  # Br
+        (  0,   0,   0,   0,   0,   0,   0,   0,   0),  # I
+        (  0,   0,   0,   0,   0,   0,   0,   0,   0),  # P
+    ),
+)
+MARGINS_EDM = (10, 5, 2)            # pm added to the single / double / triple length (const.py:175)
+NO_BOND_THRESHOLD = -1.0            # "no such order": distances are >= 0, so `d < -1` never holds
+
+
+def bond_threshold_table(is_geom, margins=MARGINS_EDM):
+    """``[n_types][n_types][3]`` fp32 upper bounds in pm: a pair at ``d`` pm has order >= k + 1 when ``d < table[a][b][k]``
+    and every lower order holds too (the kernel and ``get_bond_order`` nest the comparisons)."""
+    n = GEOM_NUMBER_OF_ATOM_TYPES if is_geom else NUMBER_OF_ATOM_TYPES
+    table = torch.full((n, n, 3), NO_BOND_THRESHOLD, dtype=TORCH_FLOAT)
+    for k in range(3):
+        for a in range(n):
+            for b in range(n):
+                if BOND_LENGTHS[k][a][b]:
+                    table[a, b, k] = BOND_LENGTHS[k][a][b] + margins[k]
+    return table

@@ -2,12 +2,14 @@
 ``generate_with_pocket.py`` (:116-283) and ``generate_with_protein.py`` (:151-300) as importable functions on top of
 ``DDPM.sample_chain`` (HIP), ``SizeClassifier`` (HIP) and the RDKit-free I/O of ``io.py``.
 
-Differences from the scripts, all outside the sampling path: the ``obabel xyz -> sdf`` conversion is not run (no
-OpenBabel here; the ``.xyz`` files are what the reference's own post-processing starts from), and the functions
-return the list of written files instead of printing.  ``python -m difflinker_amd.generate --help`` exposes the same
+Differences from the scripts, all outside the sampling path: the functions return the list of written files instead of
+printing, and the ``obabel xyz -> sdf`` conversion (generate.py:179-180) is replaced by ``output_format='sdf'`` /
+``'both'``: bonds perceived on the GPU by the reference's own ``molecule_builder`` rule (``molecule_builder.py``, not
+OpenBabel's rules) and written by ``io.save_sdf_file``.  The default ``'xyz'`` writes what the scripts write before that call.  ``python -m difflinker_amd.generate --help`` exposes the same
 flags as the three scripts (``--pocket`` / ``--protein`` select the pocket-conditioned variants).
 """
 import argparse
+import json
 import os
 import random
 
@@ -16,9 +18,10 @@ import torch
 
 from . import const
 from .datasets import MOADDataset, collate_with_fragment_edges, collate_with_fragment_without_pocket_edges
-from .io import get_pocket, parse_molecule, pocket_arrays, read_molecule, read_pocket, save_xyz_file
+from .io import get_pocket, parse_molecule, pocket_arrays, read_molecule, read_pocket, save_sdf_file, save_xyz_file
 from .lightning import DDPM
 from .linker_size import SizeClassifier
+from .molecule_builder import perceive_all_bonds, summary
 from .utils import FoundNaNException
 
 
@@ -71,8 +74,14 @@ def _batches(dataset, batch_size, collate_fn):
         yield collate_fn(dataset[start:start + batch_size])
 
 
-def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_dir, name, com_key, hide_pocket):
-    written = []
+OUTPUT_FORMATS = ('xyz', 'sdf', 'both')
+
+
+def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_dir, name, com_key, hide_pocket,
+                     output_format='xyz'):
+    if output_format not in OUTPUT_FORMATS:
+        raise ValueError(f'output_format must be one of {OUTPUT_FORMATS}, got {output_format!r}')
+    written, found = [], []
     for batch_i, data in enumerate(_batches(dataset, batch_size, collate_fn)):
         n = len(data['positions'])
         chain = None
@@ -98,13 +107,23 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
             node_mask = node_mask.clone()
             width = data['pocket_mask'].shape[1]
             node_mask[:, :width][data['pocket_mask'].bool()] = 0
-        save_xyz_file(output_dir, h, x, node_mask, names=names, is_geom=ddpm.is_geom, suffix='')
-        written += [os.path.join(output_dir, f'{nm}_.xyz') for nm in names]
+        if output_format != 'sdf':
+            save_xyz_file(output_dir, h, x, node_mask, names=names, is_geom=ddpm.is_geom, suffix='')
+            written += [os.path.join(output_dir, f'{nm}_.xyz') for nm in names]
+        if output_format != 'xyz':                            # on the chain's output, before it leaves the device
+            found.append(perceive_all_bonds(h, x, node_mask, ddpm.is_geom))
+            save_sdf_file(output_dir, h, x, node_mask, found[-1].bonds, found[-1].n_bonds, names=names,
+                          is_geom=ddpm.is_geom, suffix='')
+            written += [os.path.join(output_dir, f'{nm}_.sdf') for nm in names]
+    if found:
+        print(json.dumps(summary(found)))
     return written
 
 
-def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anchors=None, device=None):
-    """``generate.py`` main(): fragments file -> ``n_samples`` molecules with a sampled linker, as ``.xyz`` files."""
+def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anchors=None, device=None, output_format='xyz'):
+    """``generate.py`` main(): fragments file -> ``n_samples`` molecules with a sampled linker, as ``.xyz`` files
+    (``output_format='sdf'``: ``.sdf`` files with perceived bonds instead, ``'both'``: both; one JSON line with the number of
+    molecules, the share in one piece and the mean bond count is printed then)."""
     device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
     os.makedirs(output_dir, exist_ok=True)
     sample_fn = make_sample_fn(linker_size, device)
@@ -124,10 +143,11 @@ def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anc
         'linker_mask': t(np.zeros_like(charges)), 'num_atoms': len(positions),
     }] * n_samples
     return _sample_and_save(ddpm, dataset, collate_with_fragment_edges, sample_fn, min(n_samples, 64), output_dir, name,
-                            com_key='fragment_mask', hide_pocket=False)
+                            com_key='fragment_mask', hide_pocket=False, output_format=output_format)
 
 
-def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size, device):
+def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size, device,
+                            output_format):
     frag_pos, frag_one_hot, frag_charges = frag
     pocket_pos, pocket_one_hot, pocket_charges = pocket
     positions = np.concatenate([frag_pos, pocket_pos], axis=0)
@@ -147,11 +167,11 @@ def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_s
     ddpm.val_dataset = dataset                            # centre-of-mass mask on the dataset type (lightning.py:443)
     return _sample_and_save(ddpm, dataset, collate_with_fragment_without_pocket_edges, sample_fn,
                             min(n_samples, max_batch_size), output_dir, name, com_key='fragment_only_mask',
-                            hide_pocket=True)
+                            hide_pocket=True, output_format=output_format)
 
 
 def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, output_dir, n_samples, n_steps, linker_size,
-                         anchors=None, max_batch_size=64, random_seed=None, device=None):
+                         anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz'):
     """``generate_with_pocket.py`` main(): the pocket is given as its own PDB file."""
     device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
     os.makedirs(output_dir, exist_ok=True)
@@ -171,11 +191,11 @@ def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, ou
     frag = parse_molecule(molecule, is_geom=ddpm.is_geom)
     pocket = pocket_arrays(read_pocket(pocket_path), backbone_atoms_only)
     return _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size,
-                                   device)
+                                   device, output_format)
 
 
 def generate_with_protein(input_path, protein_path, backbone_atoms_only, model, output_dir, n_samples, n_steps,
-                          linker_size, anchors=None, max_batch_size=64, random_seed=None, device=None):
+                          linker_size, anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz'):
     """``generate_with_protein.py`` main(): the pocket = residues of the protein within 6 A of the fragments."""
     device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
     os.makedirs(output_dir, exist_ok=True)
@@ -191,7 +211,7 @@ def generate_with_protein(input_path, protein_path, backbone_atoms_only, model, 
     frag = parse_molecule(molecule, is_geom=ddpm.is_geom)
     pocket = get_pocket(molecule, protein_path, backbone_atoms_only)
     return _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size,
-                                   device)
+                                   device, output_format)
 
 
 def main(argv=None):
@@ -209,16 +229,25 @@ def main(argv=None):
     p.add_argument('--anchors', default=None, help='comma-separated 1-based indices of the anchor atoms')
     p.add_argument('--max_batch_size', type=int, default=64)
     p.add_argument('--random_seed', type=int, default=None)
+    p.add_argument('--output_format', choices=OUTPUT_FORMATS, default='xyz',
+                   help='xyz: element symbols and coordinates; sdf: V2000 mol blocks with bonds perceived on the GPU '
+                        '(the molecule_builder rule of the reference, in place of its obabel call); both: both')
     a = p.parse_args(argv)
     if a.pocket is not None:
         files = generate_with_pocket(a.fragments, a.pocket, a.backbone_atoms_only, a.model, a.output, a.n_samples,
-                                     a.n_steps, a.linker_size, a.anchors, a.max_batch_size, a.random_seed)
+                                     a.n_steps, a.linker_size, a.anchors, a.max_batch_size, a.random_seed,
+                                     output_format=a.output_format)
     elif a.protein is not None:
         files = generate_with_protein(a.fragments, a.protein, a.backbone_atoms_only, a.model, a.output, a.n_samples,
-                                      a.n_steps, a.linker_size, a.anchors, a.max_batch_size, a.random_seed)
+                                      a.n_steps, a.linker_size, a.anchors, a.max_batch_size, a.random_seed,
+                                      output_format=a.output_format)
     else:
-        files = generate(a.fragments, a.model, a.output, a.n_samples, a.n_steps, a.linker_size, a.anchors)
-    print(f'Saved {len(files)} generated molecules in .xyz format in directory {a.output}')
+        files = generate(a.fragments, a.model, a.output, a.n_samples, a.n_steps, a.linker_size, a.anchors,
+                         output_format=a.output_format)
+    if a.output_format == 'xyz':
+        print(f'Saved {len(files)} generated molecules in .xyz format in directory {a.output}')
+    else:
+        print(f'Saved {len(files)} files ({a.output_format}) of generated molecules in directory {a.output}')
 
 
 if __name__ == '__main__':

@@ -1,0 +1,108 @@
+"""Bond perception of sampled batches — the reference's ``src/molecule_builder.py`` (``build_xae_molecule``,
+``get_bond_order``) for a whole batch in one HIP launch (``csrc/bonds.hip``), on the tensors ``sample_chain`` left on the
+device, plus the connectivity check of ``metrics.is_connected``.
+
+Atoms are numbered the way the reference numbers them: the rows with ``node_mask != 0`` in row order (it masks a molecule
+before it builds it), so atom ``k`` of ``bonds``, ``valence`` and ``component`` is the ``k``-th line of the ``.xyz`` / ``.sdf``
+file of the same molecule.  RDKit objects are not built: ``build_xae_molecules`` stops at the reference's ``(X, A, E)``
+triple, and validity is reported as numbers (valences, component counts), never as RDKit's sanitisation.
+"""
+import ctypes
+from collections import namedtuple
+
+import torch
+
+from . import _lib, const
+
+Bonds = namedtuple('Bonds', 'n_bonds bonds valence n_components component status')
+
+_TABLES = {}
+
+
+def _table(device, is_geom, margins):
+    key = (device, bool(is_geom), tuple(float(m) for m in margins))
+    if key not in _TABLES:
+        _TABLES[key] = const.bond_threshold_table(is_geom, margins).to(device).contiguous()
+    return _TABLES[key]
+
+
+def perceive_bonds(one_hot, x, node_mask, is_geom, margins=const.MARGINS_EDM, capacity=None):
+    """Bonds of every molecule of a batch: ``one_hot [B,N,nf]``, ``x [B,N,3]`` (Angstrom), ``node_mask [B,N,1]`` or ``[B,N]``
+    on the HIP device.  Returns device int32 tensors, without a host synchronisation:
+
+    ``n_bonds [B]``; ``bonds [B,capacity,3]`` rows ``(i, j, order)`` with ``j < i`` in row-major order of ``(i, j)``, valid up
+    to ``n_bonds``; ``valence [B,N]``; ``n_components [B]``; ``component [B,N]`` (smallest atom index of the atom's component,
+    -1 beyond the atom count); ``status [B]`` (``_lib.DL_BONDS_OVERFLOW``: more bonds than ``capacity``, ``n_bonds`` is
+    still the true count; ``_lib.DL_BONDS_NONFINITE``: a NaN / inf coordinate, which bonds to nothing).
+    ``capacity`` defaults to ``4 * N`` bonds per molecule (a valid heavy-atom graph has at most ``2 * N``)."""
+    if not (one_hot.is_cuda and x.is_cuda and node_mask.is_cuda):
+        raise _lib.HipLibraryError('perceive_bonds runs on the HIP device only (no CPU fallback): '
+                                   f'got tensors on {one_hot.device}, {x.device}, {node_mask.device}')
+    B, N, nf = one_hot.shape
+    if x.shape != (B, N, 3) or node_mask.numel() != B * N:
+        raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, x {tuple(x.shape)}, '
+                         f'node_mask {tuple(node_mask.shape)}')
+    dev = one_hot.device
+    f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()     # noqa: E731
+    one_hot, x, node_mask = f32(one_hot), f32(x), f32(node_mask)
+    table = _table(dev, is_geom, margins)
+    capacity = 4 * N if capacity is None else int(capacity)
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    out = Bonds(i32(B), i32(B, capacity, 3), i32(B, N), i32(B), i32(B, N), i32(B))
+    lib = _lib.load()
+    args = _lib.DLBondsArgs(B=B, N=N, nf=nf, one_hot=one_hot.data_ptr(), x=x.data_ptr(), node_mask=node_mask.data_ptr(),
+                            table=table.data_ptr(), table_len=table.numel(), capacity=capacity,
+                            n_bonds=out.n_bonds.data_ptr(), bonds=out.bonds.data_ptr() if capacity else None,
+                            valence=out.valence.data_ptr(), n_components=out.n_components.data_ptr(),
+                            component=out.component.data_ptr(), status=out.status.data_ptr(), workspace=None,
+                            workspace_bytes=0)
+    with torch.cuda.device(dev):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.dl_perceive_bonds(ctypes.byref(args), stream), 'dl_perceive_bonds')
+    return out
+
+
+def perceive_all_bonds(one_hot, x, node_mask, is_geom, margins=const.MARGINS_EDM):
+    """``perceive_bonds`` whose list holds every bond of every molecule: when the default capacity overflows (atoms piled
+    on one another, as an untrained model places them) the launch is repeated with the largest ``n_bonds`` as capacity.
+    Reads ``n_bonds`` on the host, so it synchronises; the writers and ``build_xae_molecules`` go through it."""
+    found = perceive_bonds(one_hot, x, node_mask, is_geom, margins)
+    most = int(found.n_bonds.max()) if found.n_bonds.numel() else 0
+    if most > found.bonds.shape[1]:
+        found = perceive_bonds(one_hot, x, node_mask, is_geom, margins, capacity=most)
+    return found
+
+
+def build_xae_molecules(one_hot, x, node_mask, is_geom, margins=const.MARGINS_EDM):
+    """Per molecule the reference's ``(X, A, E)`` of ``build_xae_molecule``: atom types ``[n]`` (int64), adjacency
+    ``[n,n]`` (bool) and bond orders ``[n,n]`` (int32), lower triangle only (the reference's graph is directed), dense, on
+    the host."""
+    found = perceive_all_bonds(one_hot, x, node_mask, is_geom, margins)
+    n_bonds, bonds = found.n_bonds.cpu(), found.bonds.cpu().long()
+    mask = node_mask.reshape(one_hot.shape[0], -1).cpu() != 0
+    types = one_hot.detach().cpu().argmax(dim=2)
+    out = []
+    for b in range(one_hot.shape[0]):
+        X = types[b][mask[b]]
+        n = X.shape[0]
+        E = torch.zeros((n, n), dtype=torch.int)
+        rows = bonds[b, :int(n_bonds[b])]
+        E[rows[:, 0], rows[:, 1]] = rows[:, 2].int()
+        out.append((X, E.bool(), E))
+    return out
+
+
+def is_connected(one_hot, x, node_mask, is_geom, margins=const.MARGINS_EDM):
+    """Device bool ``[B]``: the bond graph over the real atoms is one piece (``metrics.is_connected``:
+    ``len(GetMolFrags(mol)) == 1`` of the molecule ``build_molecule`` makes from the same bonds)."""
+    return perceive_bonds(one_hot, x, node_mask, is_geom, margins, capacity=0).n_components == 1
+
+
+def summary(found):
+    """The numbers the drivers print for a list of ``perceive_bonds`` results: molecules, the share in one piece and the
+    mean bond count."""
+    n_bonds = torch.cat([f.n_bonds for f in found]).float()
+    one_piece = torch.cat([f.n_components for f in found]) == 1
+    n = int(n_bonds.numel())
+    return {'molecules': n, 'connected': float(one_piece.float().mean()) if n else 0.0,
+            'mean_bonds': float(n_bonds.mean()) if n else 0.0}

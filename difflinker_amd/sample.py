@@ -8,15 +8,18 @@ is presentation and is not provided; the per-frame ``.xyz`` files it renders fro
 trajectory mode.
 """
 import argparse
+import json
 import os
 
 import torch
 
 from . import utils
 from .datasets import MOADDataset, collate, collate_with_fragment_edges, get_dataloader
-from .io import save_xyz_file
+from .generate import OUTPUT_FORMATS
+from .io import save_sdf_file, save_xyz_file
 from .lightning import DDPM
 from .linker_size import SizeClassifier
+from .molecule_builder import perceive_all_bonds, summary
 
 
 def check_if_generated(_output_dir, _uuids, n_samples):
@@ -51,8 +54,14 @@ def _prepare(checkpoint, prefix, data, n_steps, device):
     return model
 
 
-def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=None, linker_size_model=None):
-    """``sample.py``.  Returns the output directory."""
+def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=None, linker_size_model=None,
+           output_format='xyz'):
+    """``sample.py``.  Returns the output directory.  ``output_format`` 'sdf' / 'both' writes the sampled molecules (not
+    the ground truth, fragments or pocket) as ``<uuid>/<i>_.sdf`` with bonds perceived on the GPU, instead of / beside the
+    ``.xyz`` files, and prints one JSON line with the number of molecules, the share in one piece and the mean bond count."""
+    if output_format not in OUTPUT_FORMATS:
+        raise ValueError(f'output_format must be one of {OUTPUT_FORMATS}, got {output_format!r}')
+    found = []
     exp = 'model' if isinstance(checkpoint, DDPM) else checkpoint.split('/')[-1].replace('.ckpt', '')
     collate_fn, sample_fn = collate, None
     if linker_size_model is None:
@@ -107,7 +116,14 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 if pock.shape[1] < out_mask.shape[1]:          # template wider than the input (sampled sizes)
                     pock = torch.nn.functional.pad(pock, (0, 0, 0, out_mask.shape[1] - pock.shape[1]))
                 out_mask = out_mask - pock
-            save_xyz_file(output_dir, hs, xs, out_mask, [f'{u}/{i}' for u in uuids], is_geom=model.is_geom)
+            if output_format != 'sdf':
+                save_xyz_file(output_dir, hs, xs, out_mask, [f'{u}/{i}' for u in uuids], is_geom=model.is_geom)
+            if output_format != 'xyz':
+                found.append(perceive_all_bonds(hs, xs, out_mask, model.is_geom))
+                save_sdf_file(output_dir, hs, xs, out_mask, found[-1].bonds, found[-1].n_bonds, [f'{u}/{i}' for u in uuids],
+                              is_geom=model.is_geom)
+    if found:
+        print(json.dumps(summary(found)))
     return output_dir
 
 
@@ -152,11 +168,14 @@ def main(argv=None):
     p.add_argument('--linker_size_model', default=None)
     p.add_argument('--keep_frames', type=int, default=None, help='trajectory mode: frames kept per chain')
     p.add_argument('--device', default='cuda:0')
+    p.add_argument('--output_format', choices=OUTPUT_FORMATS, default='xyz',
+                   help='format of the sampled molecules: xyz, sdf (V2000 with bonds perceived on the GPU) or both')
     a = p.parse_args(argv)
     if a.keep_frames is not None:
         print(sample_trajectories(a.checkpoint, a.samples, a.prefix, a.keep_frames, a.device, a.data, a.n_steps))
     else:
-        print(sample(a.checkpoint, a.samples, a.prefix, a.n_samples, a.device, a.data, a.n_steps, a.linker_size_model))
+        print(sample(a.checkpoint, a.samples, a.prefix, a.n_samples, a.device, a.data, a.n_steps, a.linker_size_model,
+                     a.output_format))
 
 
 if __name__ == '__main__':

@@ -33,6 +33,9 @@
  *                                           SizeClassifier.forward at inference
  *                                           (src/linker_size_lightning.py:83-110): the `sample_fn`
  *                                           of generate.py:86-99 that runs once before a chain
+ *   dl_perceive_bonds                    <- build_xae_molecule / get_bond_order of a whole batch
+ *                                           (src/molecule_builder.py:44-102) and the fragment count behind
+ *                                           metrics.is_connected
  *   dl_size_train_forward / dl_size_train_backward
  *                                        <- SizeClassifier.forward in training mode + loss.backward()
  *                                           (src/linker_size_lightning.py:83-117, :163-167)
@@ -512,6 +515,42 @@ int64_t dl_size_train_num_params(const dl_size_train_args* args);        /* -1 o
 size_t dl_size_train_workspace_bytes(const dl_size_train_args* args);    /* reads B and the hyper-parameters; 0 outside */
 int32_t dl_size_train_forward(const dl_size_train_args* args, void* stream);
 int32_t dl_size_train_backward(const dl_size_train_args* args, void* stream);
+
+/* ---- bond perception of a sampled batch (bonds.hip) ----------------------------------------------------
+ * build_xae_molecule / get_bond_order (src/molecule_builder.py:44-102) for every molecule of a batch in ONE launch, one
+ * workgroup per molecule, plus the connected components of the bond graph (what metrics.is_connected asks of the molecule
+ * built from the same bonds).  Real atoms are the rows with node_mask != 0; atom k of every output is the k-th real row
+ * (the reference masks a molecule before it builds it); its type is the first maximum of its one-hot row.  For each pair
+ * j < i: d = 100 |x_i - x_j| in fp32, and with t = table[type_i][type_j]
+ *     order = d < t[0] ? (d < t[1] ? (d < t[2] ? 3 : 2) : 1) : 0
+ * `table` holds upper bounds in pm, symmetric in the two types; a negative entry means "no such order".  A non-finite
+ * coordinate bonds to nothing.  Deterministic: no global atomics, the same bits on every run.  The callee allocates nothing;
+ * N < 1, N > 1024, nf > 16 or table_len != nf * nf * 3 return DL_ERR_BAD_ARG; then B == 0 returns DL_OK without a launch (and
+ * without looking at the pointers); null pointers or a workspace below dl_bonds_workspace_bytes return DL_ERR_BAD_ARG, all
+ * before any device work. */
+#define DL_BONDS_OVERFLOW 1         /* status bit: n_bonds > capacity, the list holds the first `capacity` bonds */
+#define DL_BONDS_NONFINITE 2        /* status bit: a real atom has a NaN / inf coordinate */
+typedef struct dl_bonds_args {
+    int32_t B, N, nf;
+    const float* one_hot;           /* device f32 [B,N,nf] */
+    const float* x;                 /* device f32 [B,N,3], Angstrom */
+    const float* node_mask;         /* device f32 [B,N] */
+    const float* table;             /* device f32 [nf,nf,3] */
+    int32_t table_len;              /* number of floats in `table` */
+    int32_t capacity;               /* bonds the list holds per molecule */
+    int32_t* n_bonds;               /* device int32 [B] out: the true count, also beyond the capacity */
+    int32_t* bonds;                 /* device int32 [B,capacity,3] out: (i, j, order), j < i, row-major in (i, j); entries
+                                       from n_bonds on are not written */
+    int32_t* valence;               /* device int32 [B,N] out: sum of the bond orders of atom k; 0 from the atom count on */
+    int32_t* n_components;          /* device int32 [B] out */
+    int32_t* component;             /* device int32 [B,N] out: smallest atom index of atom k's component; -1 from the atom
+                                       count on */
+    int32_t* status;                /* device int32 [B] out: DL_BONDS_* bits */
+    void* workspace;                /* device, >= dl_bonds_workspace_bytes (may be NULL when that is 0) */
+    size_t workspace_bytes;
+} dl_bonds_args;
+size_t dl_bonds_workspace_bytes(int32_t B, int32_t N);      /* 0 today: every intermediate fits in LDS */
+int32_t dl_perceive_bonds(const dl_bonds_args* args, void* stream);
 
 const char* dl_error_string(int32_t status);
 int32_t dl_last_hip_error(void);
