@@ -128,6 +128,21 @@ class DLBondsArgs(ctypes.Structure):
     ]
 
 
+DL_KEYS_TOO_LARGE, DL_KEYS_BAD_BOND = 4, 8         # dl_mol_keys_args.status bits, beside the DL_BONDS_* bits carried forward
+
+
+class DLMolKeysArgs(ctypes.Structure):
+    _fields_ = [
+        ('B', ctypes.c_int32), ('N', ctypes.c_int32), ('nf', ctypes.c_int32),
+        ('one_hot', ctypes.c_void_p), ('node_mask', ctypes.c_void_p), ('drop_mask', ctypes.c_void_p),
+        ('capacity', ctypes.c_int32), ('n_bonds_in', ctypes.c_void_p), ('bonds', ctypes.c_void_p),
+        ('valence_in', ctypes.c_void_p), ('n_components_in', ctypes.c_void_p), ('status_in', ctypes.c_void_p),
+        ('max_valence', ctypes.c_void_p), ('max_valence_len', ctypes.c_int32),
+        ('n_atoms', ctypes.c_void_p), ('n_over', ctypes.c_void_p), ('n_components', ctypes.c_void_p),
+        ('n_bonds', ctypes.c_void_p), ('key', ctypes.c_void_p), ('colour', ctypes.c_void_p), ('status', ctypes.c_void_p),
+    ]
+
+
 EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_string', 'dl_model_num_tensors',
            'dl_model_create', 'dl_model_destroy', 'dl_egnn_forward_fc', 'dl_sampler_step', 'dl_sample_chain_fc',
            'dl_set_profile_buffer', 'dl_profile_max_events', 'dl_pocket_workspace_bytes', 'dl_egnn_forward_pocket',
@@ -137,7 +152,8 @@ EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_stri
            'dl_edm_loss_prologue', 'dl_edm_loss_epilogue', 'dl_edm_loss_grad', 'dl_egnn_backward_fc_num_params',
            'dl_egnn_backward_fc_workspace_bytes', 'dl_egnn_backward_max_atoms', 'dl_egnn_backward_fc',
            'dl_size_train_num_params', 'dl_size_train_workspace_bytes', 'dl_size_train_forward', 'dl_size_train_backward',
-           'dl_join_workspace_bytes', 'dl_sample_chain_fc_join', 'dl_bonds_workspace_bytes', 'dl_perceive_bonds')
+           'dl_join_workspace_bytes', 'dl_sample_chain_fc_join', 'dl_bonds_workspace_bytes', 'dl_perceive_bonds',
+           'dl_molecule_keys')
 TEST_HOOK_EXPORTS = ('dl_debug_team_fault',)       # declared under #ifdef DL_TEST_HOOKS: the test-hooks build only
 
 _lib = None
@@ -251,6 +267,8 @@ def _open(path):
     lib.dl_bonds_workspace_bytes.argtypes = [i32, i32]
     lib.dl_perceive_bonds.restype = i32
     lib.dl_perceive_bonds.argtypes = [ctypes.POINTER(DLBondsArgs), vp]
+    lib.dl_molecule_keys.restype = i32
+    lib.dl_molecule_keys.argtypes = [ctypes.POINTER(DLMolKeysArgs), vp]
     lib.dl_size_model_num_tensors.restype = i32
     lib.dl_size_model_num_tensors.argtypes = [ctypes.POINTER(DLSizeConfig)]
     lib.dl_size_model_create.restype = i32

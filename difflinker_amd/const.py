@@ -91,3 +91,15 @@ def bond_threshold_table(is_geom, margins=MARGINS_EDM):
                 if BOND_LENGTHS[k][a][b]:
                     table[a, b, k] = BOND_LENGTHS[k][a][b] + margins[k]
     return table
+
+# most bonds an atom may carry (const.py:156-171, ALLOWED_BONDS) by this project's atom indices; a list entry such as
+# P: [3, 5] keeps its alternatives.  Hydrogens are implicit in these data sets, so the valence rule of ``metrics`` is
+# "at most", not "exactly"
+ALLOWED_BONDS = {'C': 4, 'O': 2, 'N': 3, 'F': 1, 'S': 4, 'Cl': 1, 'Br': 1, 'I': 1, 'P': [3, 5]}
+
+
+def max_valence_table(is_geom):
+    """int32 ``[n_types]``: the largest allowed bond count of every element of the vocabulary, in index order."""
+    idx2atom = GEOM_IDX2ATOM if is_geom else IDX2ATOM
+    limits = [ALLOWED_BONDS[idx2atom[k]] for k in range(len(idx2atom))]
+    return torch.tensor([max(v) if isinstance(v, (list, tuple)) else v for v in limits], dtype=torch.int32)

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import const
+from . import metrics as mol_metrics
 from .datasets import MOADDataset, collate_with_fragment_edges, collate_with_fragment_without_pocket_edges
 from .io import get_pocket, parse_molecule, pocket_arrays, read_molecule, read_pocket, save_sdf_file, save_xyz_file
 from .lightning import DDPM
@@ -78,10 +79,10 @@ OUTPUT_FORMATS = ('xyz', 'sdf', 'both')
 
 
 def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_dir, name, com_key, hide_pocket,
-                     output_format='xyz'):
+                     output_format='xyz', metrics=False):
     if output_format not in OUTPUT_FORMATS:
         raise ValueError(f'output_format must be one of {OUTPUT_FORMATS}, got {output_format!r}')
-    written, found = [], []
+    written, found, scored = [], [], []
     for batch_i, data in enumerate(_batches(dataset, batch_size, collate_fn)):
         n = len(data['positions'])
         chain = None
@@ -115,15 +116,23 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
             save_sdf_file(output_dir, h, x, node_mask, found[-1].bonds, found[-1].n_bonds, names=names,
                           is_geom=ddpm.is_geom, suffix='')
             written += [os.path.join(output_dir, f'{nm}_.sdf') for nm in names]
+        if metrics:                                           # the molecules as written: without the pocket
+            types = h[:, :, :ddpm.num_classes]
+            scored += mol_metrics.to_host(mol_metrics.analyze(types, x, node_mask, ddpm.is_geom), types, node_mask)
     if found:
         print(json.dumps(summary(found)))
+    if metrics:                                               # no true molecule here: no novelty, no recovery
+        with open(os.path.join(output_dir, 'metrics.json'), 'w') as f:
+            json.dump(dict(mol_metrics.compute_metrics(scored), molecules=len(scored)), f, indent=1)
     return written
 
 
-def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anchors=None, device=None, output_format='xyz'):
+def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anchors=None, device=None, output_format='xyz',
+             metrics=False):
     """``generate.py`` main(): fragments file -> ``n_samples`` molecules with a sampled linker, as ``.xyz`` files
     (``output_format='sdf'``: ``.sdf`` files with perceived bonds instead, ``'both'``: both; one JSON line with the number of
-    molecules, the share in one piece and the mean bond count is printed then)."""
+    molecules, the share in one piece and the mean bond count is printed then).  ``metrics=True`` also writes
+    ``metrics.json`` to ``output_dir``: valence rule, connectivity and uniqueness of the samples (``metrics.compute_metrics``)."""
     device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
     os.makedirs(output_dir, exist_ok=True)
     sample_fn = make_sample_fn(linker_size, device)
@@ -143,11 +152,11 @@ def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anc
         'linker_mask': t(np.zeros_like(charges)), 'num_atoms': len(positions),
     }] * n_samples
     return _sample_and_save(ddpm, dataset, collate_with_fragment_edges, sample_fn, min(n_samples, 64), output_dir, name,
-                            com_key='fragment_mask', hide_pocket=False, output_format=output_format)
+                            com_key='fragment_mask', hide_pocket=False, output_format=output_format, metrics=metrics)
 
 
 def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size, device,
-                            output_format):
+                            output_format, metrics=False):
     frag_pos, frag_one_hot, frag_charges = frag
     pocket_pos, pocket_one_hot, pocket_charges = pocket
     positions = np.concatenate([frag_pos, pocket_pos], axis=0)
@@ -167,11 +176,12 @@ def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_s
     ddpm.val_dataset = dataset                            # centre-of-mass mask on the dataset type (lightning.py:443)
     return _sample_and_save(ddpm, dataset, collate_with_fragment_without_pocket_edges, sample_fn,
                             min(n_samples, max_batch_size), output_dir, name, com_key='fragment_only_mask',
-                            hide_pocket=True, output_format=output_format)
+                            hide_pocket=True, output_format=output_format, metrics=metrics)
 
 
 def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, output_dir, n_samples, n_steps, linker_size,
-                         anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz'):
+                         anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz',
+                         metrics=False):
     """``generate_with_pocket.py`` main(): the pocket is given as its own PDB file."""
     device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
     os.makedirs(output_dir, exist_ok=True)
@@ -191,11 +201,12 @@ def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, ou
     frag = parse_molecule(molecule, is_geom=ddpm.is_geom)
     pocket = pocket_arrays(read_pocket(pocket_path), backbone_atoms_only)
     return _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size,
-                                   device, output_format)
+                                   device, output_format, metrics)
 
 
 def generate_with_protein(input_path, protein_path, backbone_atoms_only, model, output_dir, n_samples, n_steps,
-                          linker_size, anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz'):
+                          linker_size, anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz',
+                          metrics=False):
     """``generate_with_protein.py`` main(): the pocket = residues of the protein within 6 A of the fragments."""
     device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
     os.makedirs(output_dir, exist_ok=True)
@@ -211,7 +222,7 @@ def generate_with_protein(input_path, protein_path, backbone_atoms_only, model, 
     frag = parse_molecule(molecule, is_geom=ddpm.is_geom)
     pocket = get_pocket(molecule, protein_path, backbone_atoms_only)
     return _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size,
-                                   device, output_format)
+                                   device, output_format, metrics)
 
 
 def main(argv=None):
@@ -232,18 +243,21 @@ def main(argv=None):
     p.add_argument('--output_format', choices=OUTPUT_FORMATS, default='xyz',
                    help='xyz: element symbols and coordinates; sdf: V2000 mol blocks with bonds perceived on the GPU '
                         '(the molecule_builder rule of the reference, in place of its obabel call); both: both')
+    p.add_argument('--metrics', action='store_true',
+                   help='score the generated molecules on the GPU (valence rule, connectivity, uniqueness) and write '
+                        'metrics.json to the output directory')
     a = p.parse_args(argv)
     if a.pocket is not None:
         files = generate_with_pocket(a.fragments, a.pocket, a.backbone_atoms_only, a.model, a.output, a.n_samples,
                                      a.n_steps, a.linker_size, a.anchors, a.max_batch_size, a.random_seed,
-                                     output_format=a.output_format)
+                                     output_format=a.output_format, metrics=a.metrics)
     elif a.protein is not None:
         files = generate_with_protein(a.fragments, a.protein, a.backbone_atoms_only, a.model, a.output, a.n_samples,
                                       a.n_steps, a.linker_size, a.anchors, a.max_batch_size, a.random_seed,
-                                      output_format=a.output_format)
+                                      output_format=a.output_format, metrics=a.metrics)
     else:
         files = generate(a.fragments, a.model, a.output, a.n_samples, a.n_steps, a.linker_size, a.anchors,
-                         output_format=a.output_format)
+                         output_format=a.output_format, metrics=a.metrics)
     if a.output_format == 'xyz':
         print(f'Saved {len(files)} generated molecules in .xyz format in directory {a.output}')
     else:

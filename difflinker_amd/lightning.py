@@ -5,7 +5,9 @@ Hyper-parameter wiring (lightning.py:39-112), ``load_from_checkpoint`` for Light
 (:148-199) with ``training=False``, ``validation_step`` / ``test_step`` (:228-268) and ``aggregate_metric`` (:478-480).
 Training: ``training_step`` (:201-226) with a differentiable ``loss`` (``EDM.training_forward``, HIP backward of the
 fully-connected denoiser), the random rotation of ``data_augmentation``, and ``configure_optimizers`` (:465-466);
-``python -m difflinker_amd.train`` is the training loop.  RDKit metrics, WandB and PL Trainer hooks are out of scope.
+``python -m difflinker_amd.train`` is the training loop.  Sample quality: ``sample_and_analyze`` (:322-403) with the
+RDKit-free scores of ``metrics.py``, ``validation_epoch_end`` / ``test_epoch_end`` (:276-304) and
+``compute_best_validation_metrics`` (:468-476).  RDKit metrics, animations, WandB and PL Trainer hooks are out of scope.
 Subclasses ``pytorch_lightning.LightningModule`` when that package is importable (it is not in the
 build image), else ``torch.nn.Module`` with the same surface the callers use
 (generate.py:101-175, sample.py:84-164).
@@ -13,6 +15,7 @@ build image), else ``torch.nn.Module`` with the same surface the callers use
 import torch
 import torch.nn as nn
 
+from . import metrics as mol_metrics
 from . import utils
 from .datasets import MOADDataset, create_templates_for_linker_generation
 from .edm import EDM, InpaintingEDM
@@ -95,6 +98,9 @@ class DDPM(_Base):
         from .const import LINKER_SIZE_DIST
         from .linker_size import DistributionNodes
         self.linker_size_sampler = DistributionNodes(LINKER_SIZE_DIST)          # lightning.py:113
+        self.metrics = {}                                                       # lightning.py:43: name -> value per epoch
+        if _Base is nn.Module:
+            self.current_epoch = 0              # Lightning's Trainer keeps this; here the training loop sets it
 
     # ---- checkpoints ----------------------------------------------------------------------------------
     @classmethod
@@ -259,6 +265,81 @@ class DDPM(_Base):
     def aggregate_metric(step_outputs, metric):
         """lightning.py:478-480: the mean of one metric over the step outputs."""
         return torch.tensor([float(out[metric]) for out in step_outputs]).mean()
+
+    # ---- sample quality -------------------------------------------------------------------------------
+    def _epoch_end(self, step_outputs, split, dataloader):
+        now = {}
+        for metric in (step_outputs[0].keys() if step_outputs else ()):
+            now[f'{metric}/{split}'] = float(self.aggregate_metric(step_outputs, metric))
+        if (self.current_epoch + 1) % self.test_epochs == 0:
+            for name, value in self.sample_and_analyze(dataloader()).items():
+                now[f'{name}/{split}'] = value
+        for name, value in now.items():
+            self.metrics.setdefault(name, []).append(value)
+        return now
+
+    def validation_epoch_end(self, validation_step_outputs):
+        """lightning.py:276-292: the means of the step metrics go to ``self.metrics['<name>/val']``; every ``test_epochs``
+        epochs the validation set is sampled and scored (``sample_and_analyze``) and those scores are stored the same way,
+        followed by the metrics of the best epoch so far.  ``self.log`` does not exist here: returns what the reference
+        logs, as a dict of floats."""
+        now = self._epoch_end(validation_step_outputs, 'val', self.val_dataloader)
+        if 'validity_and_connectivity/val' in now:
+            best_metrics, best_epoch = self.compute_best_validation_metrics()
+            now['best_epoch'] = int(best_epoch)
+            now.update({f'best_{name}': value for name, value in best_metrics.items()})
+        return now
+
+    def test_epoch_end(self, test_step_outputs):
+        """lightning.py:294-304: as ``validation_epoch_end`` on the test set, without the best-epoch lookup."""
+        return self._epoch_end(test_step_outputs, 'test', self.test_dataloader)
+
+    def compute_best_validation_metrics(self):
+        """lightning.py:468-476: the position of the largest ``validity_and_connectivity/val`` and every ``*/val`` metric at
+        that position.  As in the reference the position counts scored epochs, so with ``test_epochs > 1`` the step metrics
+        it picks belong to an earlier epoch; a list too short for the position is left out."""
+        scores = self.metrics['validity_and_connectivity/val']
+        best_epoch = max(range(len(scores)), key=lambda k: (scores[k], -k))        # np.argmax: the first of equal maxima
+        best_metrics = {name: values[best_epoch] for name, values in self.metrics.items()
+                        if name.endswith('/val') and len(values) > best_epoch}
+        return best_metrics, best_epoch
+
+    def sample_and_analyze(self, dataloader):
+        """lightning.py:322-403 with the scores of ``metrics.py`` in place of RDKit's: per batch ``n_stability_samples``
+        chains; a ``FoundNaNException`` is printed in the reference's three formats and that sample is skipped; pocket
+        models score the molecules without their pocket atoms; the true molecules and the final frames go through
+        ``metrics.analyze`` and the result is ``metrics.compute_metrics`` over all of them (which drops the predictions whose
+        true molecule is not valid and connected).  No animation, no WandB."""
+        pred, true, input_index = [], [], []
+        first = 0
+        for b, data in enumerate(dataloader):
+            drop = data['pocket_mask'] if self.pockets else None                   # lightning.py:331-334
+            n = len(data['positions'])
+            true_batch = mol_metrics.to_host(
+                mol_metrics.analyze(data['one_hot'], data['positions'], data['atom_mask'], self.is_geom, drop_mask=drop),
+                data['one_hot'], data['atom_mask'], drop)
+            for sample_idx in range(self.n_stability_samples):
+                try:
+                    chain_batch, node_mask = self.sample_chain(data, keep_frames=1)
+                except utils.FoundNaNException as e:
+                    for idx in e.x_h_nan_idx:
+                        print(f"FoundNaNException: [xh], e={self.current_epoch}, b={b}, i={idx}: {data['name'][idx]}")
+                    for idx in e.only_x_nan_idx:
+                        print(f"FoundNaNException: [x ], e={self.current_epoch}, b={b}, i={idx}: {data['name'][idx]}")
+                    for idx in e.only_h_nan_idx:
+                        print(f"FoundNaNException: [ h], e={self.current_epoch}, b={b}, i={idx}: {data['name'][idx]}")
+                    continue
+                x = chain_batch[0][:, :, :self.n_dims]
+                one_hot = chain_batch[0][:, :, self.n_dims:self.n_dims + self.num_classes]
+                out_drop = drop
+                if drop is not None and drop.shape[1] < node_mask.shape[1]:        # a template wider than the input
+                    out_drop = torch.nn.functional.pad(drop, (0, 0, 0, node_mask.shape[1] - drop.shape[1]))
+                pred += mol_metrics.to_host(mol_metrics.analyze(one_hot, x, node_mask, self.is_geom, drop_mask=out_drop),
+                                            one_hot, node_mask, out_drop)
+                true += true_batch
+                input_index += range(first, first + n)
+            first += n
+        return mol_metrics.compute_metrics(pred, true, input_index)
 
     # ---- sampling -------------------------------------------------------------------------------------
     def sample_chain(self, data, sample_fn=None, keep_frames=None):

@@ -13,6 +13,7 @@ import os
 
 import torch
 
+from . import metrics as mol_metrics
 from . import utils
 from .datasets import MOADDataset, collate, collate_with_fragment_edges, get_dataloader
 from .generate import OUTPUT_FORMATS
@@ -55,13 +56,15 @@ def _prepare(checkpoint, prefix, data, n_steps, device):
 
 
 def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=None, linker_size_model=None,
-           output_format='xyz'):
-    """``sample.py``.  Returns the output directory.  ``output_format`` 'sdf' / 'both' writes the sampled molecules (not
+           output_format='xyz', metrics=False):
+    """``sample.py``.  Returns the output directory.  ``metrics=True`` scores the molecules sampled in this call against
+    the data set's own (``metrics.compute_metrics``: valence rule, connectivity, uniqueness, novelty, recovery) and writes
+    the result to ``metrics.json`` in the output directory.  ``output_format`` 'sdf' / 'both' writes the sampled molecules (not
     the ground truth, fragments or pocket) as ``<uuid>/<i>_.sdf`` with bonds perceived on the GPU, instead of / beside the
     ``.xyz`` files, and prints one JSON line with the number of molecules, the share in one piece and the mean bond count."""
     if output_format not in OUTPUT_FORMATS:
         raise ValueError(f'output_format must be one of {OUTPUT_FORMATS}, got {output_format!r}')
-    found = []
+    found, pred, true, input_index = [], [], [], []
     exp = 'model' if isinstance(checkpoint, DDPM) else checkpoint.split('/')[-1].replace('.ckpt', '')
     collate_fn, sample_fn = collate, None
     if linker_size_model is None:
@@ -108,6 +111,8 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
             save_xyz_file(output_dir, h, x, batch['pocket_mask'], [f'{u}/pock' for u in uuids], is_geom=model.is_geom)
         save_xyz_file(output_dir, h, x, node_mask, [f'{u}/true' for u in uuids], is_geom=model.is_geom)
         save_xyz_file(output_dir, h, x, frag_mask, [f'{u}/frag' for u in uuids], is_geom=model.is_geom)
+        if metrics:                                            # the true molecules as the files show them: without the pocket
+            true_batch = mol_metrics.to_host(mol_metrics.analyze(h, x, node_mask, model.is_geom), h, node_mask)
         for i in range(starting_point, n_samples):
             chain, out_mask = model.sample_chain(batch, sample_fn=sample_fn, keep_frames=1)
             xs, hs = chain[0][:, :, :model.n_dims], chain[0][:, :, model.n_dims:]
@@ -122,8 +127,16 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 found.append(perceive_all_bonds(hs, xs, out_mask, model.is_geom))
                 save_sdf_file(output_dir, hs, xs, out_mask, found[-1].bonds, found[-1].n_bonds, [f'{u}/{i}' for u in uuids],
                               is_geom=model.is_geom)
+            if metrics:
+                types = hs[:, :, :model.num_classes]
+                pred += mol_metrics.to_host(mol_metrics.analyze(types, xs, out_mask, model.is_geom), types, out_mask)
+                true += true_batch
+                input_index += [(batch_idx, k) for k in range(len(uuids))]
     if found:
         print(json.dumps(summary(found)))
+    if metrics:
+        with open(os.path.join(output_dir, 'metrics.json'), 'w') as f:
+            json.dump(dict(mol_metrics.compute_metrics(pred, true, input_index), molecules=len(pred)), f, indent=1)
     return output_dir
 
 
@@ -170,12 +183,15 @@ def main(argv=None):
     p.add_argument('--device', default='cuda:0')
     p.add_argument('--output_format', choices=OUTPUT_FORMATS, default='xyz',
                    help='format of the sampled molecules: xyz, sdf (V2000 with bonds perceived on the GPU) or both')
+    p.add_argument('--metrics', action='store_true',
+                   help='score the sampled molecules on the GPU (valence rule, connectivity, uniqueness, novelty, recovery) '
+                        'and write metrics.json next to them')
     a = p.parse_args(argv)
     if a.keep_frames is not None:
         print(sample_trajectories(a.checkpoint, a.samples, a.prefix, a.keep_frames, a.device, a.data, a.n_steps))
     else:
         print(sample(a.checkpoint, a.samples, a.prefix, a.n_samples, a.device, a.data, a.n_steps, a.linker_size_model,
-                     a.output_format))
+                     a.output_format, a.metrics))
 
 
 if __name__ == '__main__':

@@ -9,10 +9,17 @@ options given explicitly override them.  Each step: ``training_step`` on a shuff
 (HIP), ``AdamW.step`` (``configure_optimizers``).  Every ``--val_every`` steps and at the end the mean ``validation_step``
 metrics are printed, and ``CKPT_DIR/last.ckpt`` is written in Lightning's format (``hyper_parameters``, ``state_dict``,
 plus ``optimizer_states``, ``global_step`` and ``epoch`` for ``--resume``); ``DDPM.load_from_checkpoint`` reads it.
+
+``--sample_every_epochs E`` (off by default) adds the reference's end-of-epoch scoring: after every epoch that the loop
+finishes, ``DDPM.validation_epoch_end`` aggregates the validation metrics and, every E-th epoch, samples
+``n_stability_samples`` linkers per validation molecule and scores them (``metrics.py``: valence rule, connectivity,
+uniqueness, novelty, recovery).  The result is printed as one JSON line, ``last.ckpt`` is written, and it is copied to
+``best.ckpt`` whenever ``validity_and_connectivity/val`` improves.  An epoch cut short by ``--max_steps`` is not scored.
 """
 import argparse
 import json
 import os
+import shutil
 
 import torch
 
@@ -55,9 +62,12 @@ def validate(model):
     return {k: float(DDPM.aggregate_metric(metrics, k)) for k in metrics[0]} if metrics else {}
 
 
-def save(model, opt, path, step, epoch):
+BEST_KEY = 'validity_and_connectivity/val'
+
+
+def save(model, opt, path, step, epoch, **extra):
     ckpt = model.checkpoint_dict()
-    ckpt.update(optimizer_states=[opt.state_dict()], global_step=step, epoch=epoch)
+    ckpt.update(optimizer_states=[opt.state_dict()], global_step=step, epoch=epoch, **extra)
     tmp = path + '.tmp'
     torch.save(ckpt, tmp)
     os.replace(tmp, path)
@@ -77,6 +87,9 @@ def main(argv=None):
     p.add_argument('--no_validation', action='store_true')
     p.add_argument('--resume', default=None, help='checkpoint of this loop to continue from')
     p.add_argument('--seed', type=int, default=None)
+    p.add_argument('--sample_every_epochs', type=int, default=0,
+                   help='score the validation set at the end of every epoch and sample it every E-th epoch; keeps best.ckpt '
+                        '(0: off)')
     a = p.parse_args(argv)
     cfg = dict(DEFAULTS)
     if a.config is not None:
@@ -105,6 +118,11 @@ def main(argv=None):
         opt.load_state_dict(ckpt['optimizer_states'][0])
     os.makedirs(a.checkpoints, exist_ok=True)
     path = os.path.join(a.checkpoints, 'last.ckpt')
+    best_path = os.path.join(a.checkpoints, 'best.ckpt')
+    best = float(ckpt.get('best_validity_and_connectivity', float('-inf'))) if ckpt is not None else float('-inf')
+    if a.sample_every_epochs:
+        model.test_epochs = a.sample_every_epochs
+    kept = lambda: {'best_validity_and_connectivity': best} if a.sample_every_epochs else {}   # noqa: E731
     step, epoch = start_step, start_epoch
     n_epochs = int(cfg['n_epochs'])
     done = False
@@ -121,15 +139,27 @@ def main(argv=None):
             if a.val_every and step % a.val_every == 0:
                 if not a.no_validation:
                     print(json.dumps({'step': step, 'val': validate(model)}), flush=True)
-                save(model, opt, path, step, epoch)
+                save(model, opt, path, step, epoch, **kept())
             if a.max_steps is not None and step >= a.max_steps:
                 done = True
                 break
         else:
+            if a.sample_every_epochs:
+                model.eval()
+                model.current_epoch = epoch
+                scores = model.validation_epoch_end([model.validation_step(data) for data in model.val_dataloader()])
+                print(json.dumps({'step': step, 'epoch': epoch, 'val_epoch': scores}), flush=True)
+                improved = BEST_KEY in scores and scores[BEST_KEY] > best
+                if improved:
+                    best = scores[BEST_KEY]
+                save(model, opt, path, step, epoch + 1, **kept())
+                if improved:
+                    shutil.copyfile(path, best_path + '.tmp')
+                    os.replace(best_path + '.tmp', best_path)
             epoch += 1
     if not a.no_validation:
         print(json.dumps({'step': step, 'val': validate(model)}), flush=True)
-    save(model, opt, path, step, epoch)
+    save(model, opt, path, step, epoch, **kept())
     print(json.dumps({'checkpoint': path, 'step': step}), flush=True)
     return path
 

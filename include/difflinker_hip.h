@@ -36,6 +36,9 @@
  *   dl_perceive_bonds                    <- build_xae_molecule / get_bond_order of a whole batch
  *                                           (src/molecule_builder.py:44-102) and the fragment count behind
  *                                           metrics.is_connected
+ *   dl_molecule_keys                     <- the questions metrics.py asks of a built molecule (src/metrics.py:12-54), put to
+ *                                           the bond graph instead of RDKit: valences within the element's limit,
+ *                                           one piece, and a renumbering-invariant key per molecule
  *   dl_size_train_forward / dl_size_train_backward
  *                                        <- SizeClassifier.forward in training mode + loss.backward()
  *                                           (src/linker_size_lightning.py:83-117, :163-167)
@@ -551,6 +554,59 @@ typedef struct dl_bonds_args {
 } dl_bonds_args;
 size_t dl_bonds_workspace_bytes(int32_t B, int32_t N);      /* 0 today: every intermediate fits in LDS */
 int32_t dl_perceive_bonds(const dl_bonds_args* args, void* stream);
+
+/* ---- molecule keys of a perceived batch (mol_keys.hip) ---------------------------------------------------
+ * Scores of the bond graph dl_perceive_bonds left on the device, one workgroup per molecule, ONE launch per batch, no host
+ * round trip between the two launches.  Atoms are numbered as dl_perceive_bonds numbers them (the k-th row with
+ * node_mask != 0 is atom k).  `drop_mask` (may be NULL; the reference's pocket_mask) removes atoms AFTER that numbering: a
+ * dropped atom and every bond that touches it are ignored; the atoms that stay are the "kept" atoms.
+ *
+ *   n_atoms       kept atoms
+ *   n_over        kept atoms whose valence (sum of the orders of their bonds to kept atoms) exceeds max_valence[type]
+ *   n_components  pieces of the graph over the kept atoms (recomputed when drop_mask is given, else `n_components_in`)
+ *   n_bonds       bonds between kept atoms (of the list as given: at most `capacity`)
+ *   colour        colour refinement (1-WL) with 64-bit integers, all arithmetic modulo 2^64:
+ *                     mix64(z): z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *                               z = (z ^ z >> 27) * 0x94D049BB133111EB; return z ^ z >> 31          (splitmix64)
+ *                     mix2(a, b) = mix64(a + b * 0xD6E8FEB86659FD93)
+ *                     c_0[i]   = mix2(0x243F6A8885A308D3, type_i + 1)
+ *                     c_r+1[i] = mix2(c_r[i], sum over the kept bonds (i, j, order) of mix2(c_r[j], order))
+ *                 for exactly n_atoms rounds (a partition of n atoms settles within n rounds; the count depends on nothing
+ *                 but n_atoms, so it is the same under every renumbering).  colour[b][k] is the final colour of atom k, 0 for
+ *                 a dropped atom and from the atom count on.
+ *   key           mix2(mix2(mix2(0x13198A2E03707344, n_atoms), n_bonds), sum over the kept atoms of mix64(colour))
+ *   status        the DL_BONDS_* bits of `status_in`, plus DL_KEYS_TOO_LARGE and DL_KEYS_BAD_BOND.  Any bit but
+ *                 DL_BONDS_NONFINITE means that key and colour do not describe the molecule (a cut list, an entry that is
+ *                 not a bond); with DL_KEYS_TOO_LARGE they are 0.
+ *
+ * An entry of the list is a bond when 0 <= i, j < atoms, i != j and 1 <= order <= 3; any other entry is skipped and sets
+ * DL_KEYS_BAD_BOND.  Sums are commutative and integer: the same bits on every run and under every order of the list.  Global
+ * memory is written with plain stores only.  Argument errors (null pointers, N < 1, nf < 1 or > 16, max_valence_len != nf,
+ * capacity < 0) return DL_ERR_BAD_ARG before any device work; B == 0 returns DL_OK without a launch. */
+#define DL_KEYS_TOO_LARGE 4         /* status bit: more than 1024 real atoms, or more kept bonds than the workgroup's LDS holds */
+#define DL_KEYS_BAD_BOND 8          /* status bit: a list entry that is not a bond of this molecule was skipped */
+typedef struct dl_mol_keys_args {
+    int32_t B, N, nf;
+    const float* one_hot;           /* device f32 [B,N,nf] */
+    const float* node_mask;         /* device f32 [B,N] */
+    const float* drop_mask;         /* device f32 [B,N] or NULL */
+    int32_t capacity;               /* bonds the list holds per molecule */
+    const int32_t* n_bonds_in;      /* device int32 [B]: dl_bonds_args.n_bonds */
+    const int32_t* bonds;           /* device int32 [B,capacity,3]: dl_bonds_args.bonds (may be NULL when capacity is 0) */
+    const int32_t* valence_in;      /* device int32 [B,N]: dl_bonds_args.valence (used when drop_mask is NULL) */
+    const int32_t* n_components_in; /* device int32 [B]: dl_bonds_args.n_components (used when drop_mask is NULL) */
+    const int32_t* status_in;       /* device int32 [B]: dl_bonds_args.status */
+    const int32_t* max_valence;     /* device int32 [nf]: most bonds an atom of each type may carry */
+    int32_t max_valence_len;
+    int32_t* n_atoms;               /* device int32 [B] out */
+    int32_t* n_over;                /* device int32 [B] out */
+    int32_t* n_components;          /* device int32 [B] out */
+    int32_t* n_bonds;               /* device int32 [B] out */
+    uint64_t* key;                  /* device 64-bit [B] out */
+    uint64_t* colour;               /* device 64-bit [B,N] out */
+    int32_t* status;                /* device int32 [B] out */
+} dl_mol_keys_args;
+int32_t dl_molecule_keys(const dl_mol_keys_args* args, void* stream);
 
 const char* dl_error_string(int32_t status);
 int32_t dl_last_hip_error(void);
