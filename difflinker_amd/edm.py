@@ -225,6 +225,11 @@ class EDM(torch.nn.Module):
         # rounding); the plan is a function of the batch's sizes alone, so a batch is sampled bit for bit the same every time.
         # False: one launch, every molecule on one compute unit for the whole chain.
         self.split_chain = SPLIT_CHAIN_DEFAULT
+        # the launch route of the LAST fused chain (_sample_chain_fused; a batch sampled in parts: of its last part), set before
+        # anything is launched: 'one' (dl_sample_chain_fc alone), 'join' (dl_sample_chain_fc_join: join_plan), 'two_launch' (the
+        # first launch plus the resumed teams on the side stream: split_plan without a join_plan) or 'overflow_teams' (the molecules
+        # beyond one per compute unit on teams beside the main launch).  An observable for tests and logs; nothing reads it.
+        self.last_route = None
 
     @staticmethod
     def _side_stream(dev):
@@ -808,6 +813,7 @@ class EDM(torch.nn.Module):
                     join = join_plan(sizes_h, linkers_h, T + 1, cus, self.dynamics.n_layers, sub)
                     if join is not None:
                         plan = None
+        self.last_route = 'join' if join is not None else 'two_launch' if plan is not None else 'overflow_teams' if over else 'one'
         q_end_t = z_state = None
         if plan is not None or join is not None:
             q_end_t = torch.tensor((join or plan)[0], dtype=torch.int32, device=dev)

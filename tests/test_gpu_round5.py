@@ -478,19 +478,54 @@ def test_non_finite_weights_reach_the_kernels_and_raise(bad):
 
 
 # ---- a chain in two phases: the static hand-over --------------------------------------------------------------------------
-def test_split_chain_hands_compute_units_over_and_samples_the_oracles_chain():
+# (route asked for, sizes, linker sizes, join_plan patched away).  The 12 molecules have a join_plan - six finished molecules for six
+# teams - so the chain as shipped takes the join launch; with join_plan patched to None it takes the two launches the hand-over
+# was written as.  The two batches of six have a split_plan (four / five teams) and too few finished molecules to help (two /
+# one): they take the two launches by themselves, nothing patched.
+HAND_OVER_12 = ([50, 48, 50, 47, 20, 22, 18, 25, 21, 19, 23, 20], [8, 7, 9, 6, 4, 5, 3, 6, 4, 4, 5, 4])
+HAND_OVER_CASES = [
+    pytest.param('join', *HAND_OVER_12, False, id='join-12-molecules'),
+    pytest.param('two_launch', *HAND_OVER_12, True, id='two_launch-forced-12-molecules'),
+    pytest.param('two_launch', [50, 48, 50, 47, 20, 22], [8, 7, 9, 6, 4, 5], False, id='two_launch-natural-4-teams'),
+    pytest.param('two_launch', [55, 54, 53, 52, 30, 12], [9, 8, 8, 7, 5, 3], False, id='two_launch-natural-5-teams'),
+]
+
+
+def _hand_over_plan(route, sizes, linkers, T, L, forced, monkeypatch):
+    """split_plan / join_plan of the batch for the DEVICE's compute units, asserted to lead to `route` (another chip fails here
+    instead of testing another route silently); `forced`: join_plan patched to None for EDM.  Returns (q_end, teams)."""
+    from difflinker_amd import edm as edm_mod
+    cus = torch.cuda.get_device_properties(P.dev()).multi_processor_count
+    plan = edm_mod.split_plan(sizes, linkers, T + 1, cus, L, 2)
+    assert plan is not None
+    join = edm_mod.join_plan(sizes, linkers, T + 1, cus, L, 2)
+    if forced:
+        assert join is not None, 'nothing to force'
+        monkeypatch.setattr(edm_mod, 'join_plan', lambda *a_, **k_: None)
+    elif route == 'two_launch':
+        assert join is None, 'the batch must take the two launches by itself'
+    else:
+        assert join is not None and sorted(join[1]) == sorted(plan[1])
+        return join[0], join[1]                      # the owners are split_plan's teams; their switch calls are join_plan's
+    return plan
+
+
+@pytest.mark.parametrize('route,sizes,linkers,forced', HAND_OVER_CASES)
+def test_split_chain_hands_compute_units_over_and_samples_the_oracles_chain(monkeypatch, route, sizes, linkers, forced):
     """``EDM.split_chain``: the small molecules of a ragged batch complete in the first launch, the others stop at the call where
     the small ones end (dl_chain_args.q_end), leave their state in HBM and finish in a second launch (q_begin, z_state) on teams
     of two.  The chain must be the oracle's - every kept frame - and agree with the one-launch chain to fp32 rounding (the steps
     on teams sum messages in the team's order); molecules that never run on a team are bit-identical; repeatable bit for bit;
-    the plan comes from the sizes alone."""
-    from difflinker_amd import edm as edm_mod
+    the plan comes from the sizes alone.
+    Routes (``EDM.last_route``, asserted on every run):
+      * ``join-12-molecules``: the chain as shipped - 'join', ONE launch (dl_sample_chain_fc_join), no second launch at all;
+      * ``two_launch-forced-12-molecules``: the same batch with ``edm.join_plan`` patched to None - 'two_launch', the second
+        launch on the side stream described above, ``last_split_event`` recorded between the two;
+      * ``two_launch-natural-4-teams`` / ``-5-teams``: batches whose join_plan is None by itself (four / five teams, two / one
+        finished molecules) - 'two_launch', nothing patched."""
     nf, L, T = 8, 2, 24
-    sizes, linkers = [50, 48, 50, 47, 20, 22, 18, 25, 21, 19, 23, 20], [8, 7, 9, 6, 4, 5, 3, 6, 4, 4, 5, 4]
     cus = torch.cuda.get_device_properties(P.dev()).multi_processor_count
-    plan = edm_mod.split_plan(sizes, linkers, T + 1, cus, L, 2)
-    assert plan is not None
-    q_end, teams = plan
+    q_end, teams = _hand_over_plan(route, sizes, linkers, T, L, forced, monkeypatch)
     assert teams and all(0 < q_end[b] < T + 1 for b in teams) and 2 * len(teams) <= cus
     untouched = sorted(set(range(len(sizes))) - set(teams))              # complete in the first launch
     dyn, sd, cfg = P.make_dynamics(nf, 1, L, seed=171)
@@ -507,6 +542,7 @@ def test_split_chain_hands_compute_units_over_and_samples_the_oracles_chain():
 
     def run(split, philox=False):
         edm.split_chain = split
+        edm.last_route = edm.last_split_event = None
         if philox:
             edm.noise_source, edm.noise_seed = 'philox', 9
             out = edm.sample_chain(g['x'], g['h'], g['node_mask'], g['fragment_mask'], g['linker_mask'], g['edge_mask'], g['context'],
@@ -516,32 +552,37 @@ def test_split_chain_hands_compute_units_over_and_samples_the_oracles_chain():
             out = edm.sample_chain(g['x'], g['h'], g['node_mask'], g['fragment_mask'], g['linker_mask'], g['edge_mask'], g['context'],
                                    keep_frames=6, noise_bank=bank.stacked())
         torch.cuda.synchronize()
+        assert edm.last_route == (route if split else 'one'), edm.last_route
+        assert (edm.last_split_event is not None) == (split and route == 'two_launch'), 'the event between the two launches'
         return out.cpu()
     got = run(True)
-    P.check_chain(f'split chain ({len(teams)} teams), T=24, 6 frames', got, want, inp)
+    P.check_chain(f'split chain, route {route} ({len(teams)} teams), T=24, 6 frames', got, want, inp)
     assert torch.equal(got, run(True)), 'bitwise repeatable'
     one = run(False)
     assert torch.equal(got[:, untouched], one[:, untouched]), 'molecules that never run on a team: the bits of the one-launch chain'
     lm = inp['linker_mask'][teams]
     err = rel_l2(got[0, teams, :, :3] * lm, one[0, teams, :, :3] * lm)
-    print(f'split vs one launch, the molecules that finish on teams: linker-x rel-L2 {err:.3e}')
+    print(f'split ({route}) vs one launch, the molecules that finish on teams: linker-x rel-L2 {err:.3e}')
     assert err <= 1e-5 and torch.equal(got[0, teams, :, 3:], one[0, teams, :, 3:])
     a, b = run(True, philox=True), run(False, philox=True)                       # in-kernel noise: resuming needs no generator state
     assert rel_l2(a[0, :, :, :3] * inp['linker_mask'], b[0, :, :, :3] * inp['linker_mask']) <= 1e-5
     assert torch.equal(a[:, untouched], b[:, untouched])
 
 
-def test_split_chain_reports_nans_of_either_launch_like_one_launch():
+@pytest.mark.parametrize('route,sizes,linkers,forced', HAND_OVER_CASES)
+def test_split_chain_reports_nans_of_either_launch_like_one_launch(monkeypatch, route, sizes, linkers, forced):
     """A NaN in a molecule that stops in the first launch of a split chain and resumes in the second: planted in a draw of the
     FIRST launch it ends the molecule there (the second launch skips it: dl_chain_args.skip_flags); planted in a draw of the
     SECOND launch it is found on the team.  Either way the exception carries what the one-launch chain reports: the same index
-    sets and the same denoiser call."""
-    from difflinker_amd import edm as edm_mod
+    sets and the same denoiser call.
+    Routes (``EDM.last_route``, asserted on every run - the chain sets it before it raises): ``two_launch-*`` run the two
+    launches this describes (forced: ``edm.join_plan`` patched to None; natural: a batch without a join_plan), where the flags of
+    both launches are merged; ``join-12-molecules`` is the chain as shipped, ONE join launch, where 'first launch' reads 'before
+    the molecule's switch call' and 'second launch' reads 'its team phase'."""
     from difflinker_amd.utils import FoundNaNException
     nf, L, T = 8, 1, 24
-    sizes, linkers = [50, 48, 50, 47, 20, 22, 18, 25, 21, 19, 23, 20], [8, 7, 9, 6, 4, 5, 3, 6, 4, 4, 5, 4]
-    q_end, teams = edm_mod.split_plan(sizes, linkers, T + 1, 256, L, 2)
-    assert 0 in teams and 2 in teams and 3 < q_end[0] < T - 3
+    q_end, teams = _hand_over_plan(route, sizes, linkers, T, L, forced, monkeypatch)
+    assert 0 in teams and 2 in teams and 3 < q_end[0] < T - 3 and q_end[2] + 2 <= T
     dyn, sd, cfg = P.make_dynamics(nf, 1, L, seed=181)
     dyn.team = 1
     inp, _, _ = P.ragged_inputs(sizes, linkers, nf, seed=182)
@@ -555,12 +596,15 @@ def test_split_chain_reports_nans_of_either_launch_like_one_launch():
         seen = {}
         for split in (False, True):
             edm.split_chain = split
+            edm.last_route = None
             with pytest.raises(FoundNaNException) as ei:
                 edm.sample_chain(g['x'], g['h'], g['node_mask'], g['fragment_mask'], g['linker_mask'], g['edge_mask'], g['context'],
                                  keep_frames=1, noise_bank=(nx, nh))
+            assert edm.last_route == (route if split else 'one'), edm.last_route
             e = ei.value
             seen[split] = (e.x_h_nan_idx, e.only_x_nan_idx, e.only_h_nan_idx, e.first_step)
-        print(f'NaN planted in draw {draw} of molecule {mol} (stops at call {q_end[mol]}): one launch {seen[False]}, split {seen[True]}')
+        print(f'NaN planted in draw {draw} of molecule {mol} (stops at call {q_end[mol]}, route {route}): one launch {seen[False]}, '
+              f'split {seen[True]}')
         assert seen[True] == seen[False] and (seen[True][0] | seen[True][1] | seen[True][2]) == {mol} and seen[True][3] == draw
 
 

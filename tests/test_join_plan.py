@@ -55,3 +55,27 @@ def test_join_plan_needs_split_plan_and_enough_finished_molecules():
     assert join_plan(sizes + [40], linkers + [5], 501, 256, 6, 2) is None    # more molecules than compute units
     # two big molecules, one small one: split_plan puts both big ones on teams, one finished molecule is too few
     assert join_plan([50, 50, 20], [8, 8, 4], 25, 256, 2, 2) is None
+
+
+def test_plans_of_the_batches_the_gpu_tests_name_their_routes_by():
+    """tests/test_gpu_round5.py / test_gpu_join.py assert the route of every chain (``EDM.last_route``); the plans behind those
+    routes, for one and two blocks on 256 and 304 compute units: the 12 molecules have a join_plan (six owners, six helpers ->
+    'join'; three GCLs per block move the switch calls), the two batches of six have a split_plan and NO join_plan (four / five
+    teams, two / one finished molecules -> 'two_launch')."""
+    from difflinker_amd.edm import join_plan, split_plan
+    T = 24
+    twelve = ([50, 48, 50, 47, 20, 22, 18, 25, 21, 19, 23, 20], [8, 7, 9, 6, 4, 5, 3, 6, 4, 4, 5, 4])
+    four_teams = ([50, 48, 50, 47, 20, 22], [8, 7, 9, 6, 4, 5])
+    five_teams = ([55, 54, 53, 52, 30, 12], [9, 8, 8, 7, 5, 3])
+    for L in (1, 2):
+        for cus in (256, 304):
+            q_end, owners, helpers = join_plan(*twelve, T + 1, cus, L, 2)
+            assert (owners, helpers) == ([0, 1, 2, 3, 7, 10], [4, 5, 6, 8, 9, 11])
+            assert q_end == [10, 10, 10, 10, 25, 25, 25, 22, 25, 25, 22, 25]
+            assert sorted(split_plan(*twelve, T + 1, cus, L, 2)[1]) == owners
+            q3, owners3, helpers3 = join_plan(*twelve, T + 1, cus, L, 3)
+            assert (owners3, helpers3) == (owners, helpers) and q3 == [9, 9, 9, 9, 25, 25, 25, 21, 25, 25, 21, 25]
+            assert split_plan(*four_teams, T + 1, cus, L, 2) == ([9, 9, 9, 9, 25, 25], [0, 1, 2, 3])
+            assert join_plan(*four_teams, T + 1, cus, L, 2) is None
+            assert split_plan(*five_teams, T + 1, cus, L, 2) == ([6, 6, 6, 6, 15, 25], [0, 1, 2, 3, 4])
+            assert join_plan(*five_teams, T + 1, cus, L, 2) is None
