@@ -143,6 +143,17 @@ class DLMolKeysArgs(ctypes.Structure):
     ]
 
 
+DL_RMSD_NONFINITE, DL_RMSD_NO_MAP, DL_RMSD_TOO_LARGE = 1, 2, 4      # dl_rmsd_args.status bits
+
+
+class DLRmsdArgs(ctypes.Structure):
+    _fields_ = [
+        ('P', ctypes.c_int32), ('n_max', ctypes.c_int32), ('xa', ctypes.c_void_p), ('xb', ctypes.c_void_p),
+        ('n_atoms', ctypes.c_void_p), ('map_offsets', ctypes.c_void_p), ('maps', ctypes.c_void_p),
+        ('maps_capacity', ctypes.c_int32), ('rmsd', ctypes.c_void_p), ('best', ctypes.c_void_p), ('status', ctypes.c_void_p),
+    ]
+
+
 EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_string', 'dl_model_num_tensors',
            'dl_model_create', 'dl_model_destroy', 'dl_egnn_forward_fc', 'dl_sampler_step', 'dl_sample_chain_fc',
            'dl_set_profile_buffer', 'dl_profile_max_events', 'dl_pocket_workspace_bytes', 'dl_egnn_forward_pocket',
@@ -153,7 +164,7 @@ EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_stri
            'dl_egnn_backward_fc_workspace_bytes', 'dl_egnn_backward_max_atoms', 'dl_egnn_backward_fc',
            'dl_size_train_num_params', 'dl_size_train_workspace_bytes', 'dl_size_train_forward', 'dl_size_train_backward',
            'dl_join_workspace_bytes', 'dl_sample_chain_fc_join', 'dl_bonds_workspace_bytes', 'dl_perceive_bonds',
-           'dl_molecule_keys')
+           'dl_molecule_keys', 'dl_best_rmsd')
 TEST_HOOK_EXPORTS = ('dl_debug_team_fault',)       # declared under #ifdef DL_TEST_HOOKS: the test-hooks build only
 
 _lib = None
@@ -269,6 +280,8 @@ def _open(path):
     lib.dl_perceive_bonds.argtypes = [ctypes.POINTER(DLBondsArgs), vp]
     lib.dl_molecule_keys.restype = i32
     lib.dl_molecule_keys.argtypes = [ctypes.POINTER(DLMolKeysArgs), vp]
+    lib.dl_best_rmsd.restype = i32
+    lib.dl_best_rmsd.argtypes = [ctypes.POINTER(DLRmsdArgs), vp]
     lib.dl_size_model_num_tensors.restype = i32
     lib.dl_size_model_num_tensors.argtypes = [ctypes.POINTER(DLSizeConfig)]
     lib.dl_size_model_create.restype = i32

@@ -99,6 +99,7 @@ class DDPM(_Base):
         from .linker_size import DistributionNodes
         self.linker_size_sampler = DistributionNodes(LINKER_SIZE_DIST)          # lightning.py:113
         self.metrics = {}                                                       # lightning.py:43: name -> value per epoch
+        self.geometry_metrics = False           # sample_and_analyze adds metrics.compute_geometry's RMSD keys (train --geometry)
         if _Base is nn.Module:
             self.current_epoch = 0              # Lightning's Trainer keeps this; here the training loop sets it
 
@@ -309,8 +310,11 @@ class DDPM(_Base):
         chains; a ``FoundNaNException`` is printed in the reference's three formats and that sample is skipped; pocket
         models score the molecules without their pocket atoms; the true molecules and the final frames go through
         ``metrics.analyze`` and the result is ``metrics.compute_metrics`` over all of them (which drops the predictions whose
-        true molecule is not valid and connected).  No animation, no WandB."""
+        true molecule is not valid and connected).  With ``self.geometry_metrics`` the symmetry-aware RMSD of the recovered
+        samples (``metrics.compute_geometry``) is added: ``rmsd`` (``None`` when nothing recovered), ``rmsd_molecules``,
+        ``rmsd_truncated``.  No animation, no WandB."""
         pred, true, input_index = [], [], []
+        pred_x, true_x, n_linker = [], [], []
         first = 0
         for b, data in enumerate(dataloader):
             drop = data['pocket_mask'] if self.pockets else None                   # lightning.py:331-334
@@ -318,6 +322,9 @@ class DDPM(_Base):
             true_batch = mol_metrics.to_host(
                 mol_metrics.analyze(data['one_hot'], data['positions'], data['atom_mask'], self.is_geom, drop_mask=drop),
                 data['one_hot'], data['atom_mask'], drop)
+            if self.geometry_metrics:
+                true_x_batch = list(mol_metrics.kept_positions(data['positions'], data['atom_mask'], drop)[0])
+                n_linker_batch = data['linker_mask'].reshape(n, -1).sum(1).long().tolist()
             for sample_idx in range(self.n_stability_samples):
                 try:
                     chain_batch, node_mask = self.sample_chain(data, keep_frames=1)
@@ -338,8 +345,15 @@ class DDPM(_Base):
                                             one_hot, node_mask, out_drop)
                 true += true_batch
                 input_index += range(first, first + n)
+                if self.geometry_metrics:
+                    pred_x += list(mol_metrics.kept_positions(x, node_mask, out_drop)[0])
+                    true_x += true_x_batch
+                    n_linker += n_linker_batch
             first += n
-        return mol_metrics.compute_metrics(pred, true, input_index)
+        scores = mol_metrics.compute_metrics(pred, true, input_index)
+        if self.geometry_metrics:
+            scores.update(mol_metrics.compute_geometry(pred, true, pred_x, true_x, n_linker))
+        return scores
 
     # ---- sampling -------------------------------------------------------------------------------------
     def sample_chain(self, data, sample_fn=None, keep_frames=None):

@@ -10,10 +10,16 @@ cannot tell decalin from bicyclopentyl), so ``same_molecule`` settles every key 
 What these numbers are NOT: RDKit's sanitisation (aromaticity, kekulisation, charges), canonical SMILES, stereo, energies.
 "Valid" here is the valence rule alone; "the same molecule" is an isomorphism of the graph labelled with elements and bond
 orders 1, 2, 3.
+
+``compute_geometry`` adds the reference's 3D score (compute_metrics.py:366-402): the RMSD of every recovered sample against
+its true molecule, the smallest over all isomorphisms of the two graphs (``isomorphisms`` on the host, the alignments of a
+whole list in one launch of ``dl_best_rmsd``, ``csrc/rmsd.hip``), times ``sqrt(n_atoms / n_linker)``.
 """
 import ctypes
+import math
 from collections import namedtuple
 
+import numpy as np
 import torch
 
 from . import _lib, const
@@ -179,6 +185,78 @@ def same_molecule(a, b):
     return depth == n
 
 
+def isomorphisms(a, b, limit=None):
+    """Every isomorphism of two ``Graph`` values, found with the pruning of ``same_molecule`` (final colour, element and
+    degree tags, the same visiting order, bond orders against matched neighbours), continuing after each complete assignment
+    instead of returning.  Returns ``(maps, truncated)``: ``maps[i][k]`` is the atom of ``b`` matched to atom ``k`` of ``a``;
+    at most ``limit`` maps are returned, and ``truncated`` says that there are more.  The first map is the one
+    ``same_molecule`` stops at, and ``bool(maps) == same_molecule(a, b)`` for every ``limit`` of at least 1 (or ``None``: no
+    limit); a ``limit`` below 1 asks for no map and gets ``([], False)`` without a search."""
+    n = len(a.types)
+    if n != len(b.types) or len(a.bonds) != len(b.bonds) or (limit is not None and limit < 1):
+        return [], False
+    coloured = a.colours is not None and b.colours is not None
+    adj_a, adj_b = _adjacency(a), _adjacency(b)
+    if sum(len(r) for r in adj_a) != 2 * len(a.bonds) or sum(len(r) for r in adj_b) != 2 * len(b.bonds):
+        raise ValueError('a bond is listed twice or joins an atom to itself')
+    tag_a = [(a.colours[k] if coloured else 0, a.types[k], len(adj_a[k])) for k in range(n)]
+    tag_b = [(b.colours[k] if coloured else 0, b.types[k], len(adj_b[k])) for k in range(n)]
+    if sorted(tag_a) != sorted(tag_b):
+        return [], False
+    if n == 0:
+        return [[]], False
+    order, seen = [], [False] * n
+    for root in range(n):
+        if seen[root]:
+            continue
+        seen[root] = True
+        queue = [root]
+        while queue:
+            u = queue.pop(0)
+            order.append(u)
+            for v in adj_a[u]:
+                if not seen[v]:
+                    seen[v] = True
+                    queue.append(v)
+    by_tag = {}
+    for v in range(n):
+        by_tag.setdefault(tag_b[v], []).append(v)
+    maps, image, used = [], [-1] * n, [False] * n
+    choice = [0] * n
+    depth = 0
+    while depth >= 0:
+        if depth == n:                                     # complete: record it and go on from the last atom's next candidate
+            if limit is not None and len(maps) == limit:
+                return maps, True
+            maps.append(list(image))
+            depth -= 1
+            used[image[order[depth]]] = False
+            image[order[depth]] = -1
+            continue
+        u = order[depth]
+        candidates = by_tag[tag_a[u]]
+        placed = False
+        while choice[depth] < len(candidates):
+            v = candidates[choice[depth]]
+            choice[depth] += 1
+            if used[v]:
+                continue
+            if all(image[w] < 0 or adj_b[v].get(image[w]) == o for w, o in adj_a[u].items()):
+                image[u], used[v] = v, True
+                placed = True
+                break
+        if placed:
+            depth += 1
+            if depth < n:
+                choice[depth] = 0
+        else:
+            depth -= 1
+            if depth >= 0:
+                used[image[order[depth]]] = False
+                image[order[depth]] = -1
+    return maps, False
+
+
 def group(keys, graphs):
     """The classes of identical molecules as lists of positions, in order of first appearance: buckets of equal ``keys``,
     each split by ``same_molecule``."""
@@ -244,3 +322,123 @@ def compute_metrics(pred, true=None, input_index=None):
             recovered.add(input_index[k])
     out['recovery'] = len(recovered) / len(inputs)
     return {name: float(out[name]) for name in names}
+
+
+def kept_positions(x, node_mask, drop_mask=None):
+    """The coordinates of the kept atoms of every molecule, compacted to the front in the numbering ``to_host`` gives a
+    ``Graph`` (real rows in row order, the dropped ones left out): ``x [B,N,3]`` and masks ``[B,N,1]`` or ``[B,N]`` in, the
+    compact fp32 ``[B,N,3]`` (zero from the count on) and the int32 counts ``[B]`` out.  Tensor ops on the tensors' own device,
+    no host synchronisation."""
+    B, N = x.shape[:2]
+    keep = node_mask.reshape(B, N) != 0
+    if drop_mask is not None:
+        keep = keep & (drop_mask.reshape(B, N) == 0)
+    order = torch.argsort((~keep).to(torch.int8), dim=1, stable=True)              # kept rows first, each group in row order
+    counts = keep.sum(1)
+    compact = torch.gather(x.to(torch.float32), 1, order[:, :, None].expand(B, N, 3))
+    compact = compact * (torch.arange(N, device=x.device)[None, :] < counts[:, None])[:, :, None]
+    return compact.contiguous(), counts.to(torch.int32)
+
+
+def pack_maps(maps, n_max):
+    """The map table of ``dl_best_rmsd`` on the host: ``maps[p]`` is the list of pair ``p``'s maps (each a list of its atom
+    count's length).  Returns ``(table, offsets)``: an int16 tensor of ``offsets[-1] * n_max`` 16-bit indices and the int32
+    offsets ``[P + 1]``; the block of pair ``p`` starts at ``offsets[p] * n_max`` and is atom-major (``include/difflinker_hip.h``)."""
+    if n_max > 32768:
+        raise ValueError(f'n_max {n_max}: the indices are packed through int16')
+    offsets = np.zeros(len(maps) + 1, dtype=np.int64)
+    offsets[1:] = np.cumsum([len(m) for m in maps])
+    if offsets[-1] >= 2 ** 31:
+        raise ValueError(f'{offsets[-1]} maps do not fit the 32-bit offsets of one launch')
+    table = np.zeros(int(offsets[-1]) * n_max, dtype=np.int16)
+    for p, rows in enumerate(maps):
+        if len(rows):
+            block = np.asarray(rows, dtype=np.int16).reshape(len(rows), -1).T      # [n, m]: atom-major
+            at = int(offsets[p]) * n_max
+            table[at:at + block.size] = block.reshape(-1)
+    return torch.from_numpy(table), torch.from_numpy(offsets.astype(np.int32))
+
+
+def best_rmsd(xa, xb, n_atoms, maps, offsets):
+    """``dl_best_rmsd`` on a list of pairs: ``xa``, ``xb`` fp32 ``[P,n_max,3]`` (``kept_positions`` rows), ``n_atoms`` int32
+    ``[P]``, and the table and offsets of ``pack_maps``, all on the HIP device.  Returns device tensors ``(rmsd, best,
+    status)``: fp32 ``[P]`` (NaN where ``status`` is not 0), the winning map's index within its pair (of equal ones the
+    lowest) and the ``_lib.DL_RMSD_*`` bits.  One launch, no host synchronisation."""
+    tensors = (xa, xb, n_atoms, maps, offsets)
+    if not all(t.is_cuda for t in tensors):
+        raise _lib.HipLibraryError('best_rmsd runs on the HIP device only (no CPU fallback): '
+                                   f'got tensors on {", ".join(str(t.device) for t in tensors)}')
+    P, n_max = xa.shape[:2]
+    if xa.shape != (P, n_max, 3) or xb.shape != xa.shape or n_atoms.numel() != P or offsets.numel() != P + 1 or n_max < 1 \
+            or maps.numel() % n_max:
+        raise ValueError(f'shapes disagree: xa {tuple(xa.shape)}, xb {tuple(xb.shape)}, n_atoms {tuple(n_atoms.shape)}, '
+                         f'offsets {tuple(offsets.shape)}, maps {tuple(maps.shape)}')
+    if maps.dtype not in (torch.int16, torch.uint16):
+        raise ValueError(f'maps must hold 16-bit indices, got {maps.dtype}')
+    dev = xa.device
+    xa, xb = (t.to(device=dev, dtype=torch.float32).contiguous() for t in (xa, xb))
+    n_atoms, offsets = (t.to(device=dev, dtype=torch.int32).contiguous() for t in (n_atoms, offsets))
+    maps = maps.to(dev).contiguous()
+    rmsd = torch.empty(P, dtype=torch.float32, device=dev)
+    best, status = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(2))
+    args = _lib.DLRmsdArgs(P=P, n_max=n_max, xa=xa.data_ptr(), xb=xb.data_ptr(), n_atoms=n_atoms.data_ptr(),
+                           map_offsets=offsets.data_ptr(), maps=maps.data_ptr() if maps.numel() else None,
+                           maps_capacity=maps.numel() // n_max, rmsd=rmsd.data_ptr(), best=best.data_ptr(),
+                           status=status.data_ptr())
+    with torch.cuda.device(dev):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.load().dl_best_rmsd(ctypes.byref(args), stream), 'dl_best_rmsd')
+    return rmsd, best, status
+
+
+def _stack_rows(rows, n_max):
+    """``[len(rows), n_max, 3]`` fp32 from per-molecule ``[>= n, 3]`` rows of any widths, in one padding op, not one copy per
+    row: views cut to ``n_max``, padded to the longest, then to ``n_max``.  Rows from an atom's count on are never read."""
+    out = torch.nn.utils.rnn.pad_sequence([r[:n_max].to(torch.float32) for r in rows], batch_first=True)
+    if out.shape[1] < n_max:
+        out = torch.nn.functional.pad(out, (0, 0, 0, n_max - out.shape[1]))
+    return out.contiguous()
+
+
+GEOMETRY_NAMES = ('rmsd', 'rmsd_molecules', 'rmsd_truncated')
+
+
+def compute_geometry(pred, true, pred_x, true_x, n_linker, max_matches=65536):
+    """The reference's RMSD score (compute_metrics.py:366-402) over the ``Molecule`` records ``pred`` and ``true`` of
+    ``compute_metrics``: every prediction that is valid, connected and the same molecule as its (valid, connected) true one
+    is aligned onto it under every isomorphism of the two graphs - at most ``max_matches`` of them - and the smallest RMSD,
+    times ``sqrt(n_atoms / n_linker[k])``, enters the mean.  ``pred_x[k]`` and ``true_x[k]`` are device tensors whose first
+    rows are the atoms' coordinates in the graphs' numbering (rows of ``kept_positions``).  Predictions with
+    ``n_linker[k] == 0`` are skipped.  All alignments run in ONE ``best_rmsd`` launch.
+
+    Returns ``rmsd`` (the mean as a float; ``None`` when no sample recovered its molecule, where the reference's mean of an
+    empty list is NaN, which JSON cannot hold), ``rmsd_molecules`` (how many samples it is over: recovered samples, as in the
+    reference, not inputs) and ``rmsd_truncated`` (how many of them have more than ``max_matches`` isomorphisms; they are
+    scored over the ones found).  A pair the kernel flags (``_lib.DL_RMSD_*``: more atoms than it takes) is left out of both.
+
+    What this is NOT: RDKit's GetBestRMS to the letter - no hydrogens (as in the reference, which strips them), no stereo
+    perception, and the correspondences come from the graph of elements and bond orders instead of RDKit's substructure match."""
+    if not (len(pred) == len(true) == len(pred_x) == len(true_x) == len(n_linker)):
+        raise ValueError(f'{len(pred)} predictions, {len(true)} true molecules, {len(pred_x)} and {len(true_x)} coordinate sets, '
+                         f'{len(n_linker)} linker sizes')
+    rows, maps, truncated = [], [], []
+    for k in range(len(pred)):
+        if not (_good(true[k]) and _good(pred[k]) and pred[k].key == true[k].key and int(n_linker[k]) > 0):
+            continue
+        found, cut = isomorphisms(pred[k].graph, true[k].graph, max_matches)
+        if found and len(found[0]):
+            rows.append(k)
+            maps.append(found)
+            truncated.append(cut)
+    if not rows:
+        return {'rmsd': None, 'rmsd_molecules': 0, 'rmsd_truncated': 0}
+    counts = [len(pred[k].graph.types) for k in rows]
+    n_max = max(counts)
+    dev = pred_x[rows[0]].device
+    xa, xb = (_stack_rows([xs[k] for k in rows], n_max) for xs in (pred_x, true_x))
+    table, offsets = pack_maps(maps, n_max)
+    rmsd, _, status = best_rmsd(xa, xb, torch.tensor(counts, dtype=torch.int32, device=dev), table.to(dev), offsets.to(dev))
+    rmsd, status = rmsd.cpu().tolist(), status.cpu().tolist()
+    scaled = [rmsd[p] * math.sqrt(counts[p] / int(n_linker[k])) for p, k in enumerate(rows) if status[p] == 0]
+    cut = sum(1 for p in range(len(rows)) if status[p] == 0 and truncated[p])
+    return {'rmsd': sum(scaled) / len(scaled) if scaled else None, 'rmsd_molecules': len(scaled), 'rmsd_truncated': cut}

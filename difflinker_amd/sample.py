@@ -56,15 +56,18 @@ def _prepare(checkpoint, prefix, data, n_steps, device):
 
 
 def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=None, linker_size_model=None,
-           output_format='xyz', metrics=False):
+           output_format='xyz', metrics=False, geometry=False):
     """``sample.py``.  Returns the output directory.  ``metrics=True`` scores the molecules sampled in this call against
     the data set's own (``metrics.compute_metrics``: valence rule, connectivity, uniqueness, novelty, recovery) and writes
-    the result to ``metrics.json`` in the output directory.  ``output_format`` 'sdf' / 'both' writes the sampled molecules (not
+    the result to ``metrics.json`` in the output directory; with ``geometry=True`` as well, the symmetry-aware RMSD of the
+    recovered samples (``metrics.compute_geometry``: ``rmsd``, ``rmsd_molecules``, ``rmsd_truncated``) joins it.  ``output_format`` 'sdf' / 'both' writes the sampled molecules (not
     the ground truth, fragments or pocket) as ``<uuid>/<i>_.sdf`` with bonds perceived on the GPU, instead of / beside the
     ``.xyz`` files, and prints one JSON line with the number of molecules, the share in one piece and the mean bond count."""
     if output_format not in OUTPUT_FORMATS:
         raise ValueError(f'output_format must be one of {OUTPUT_FORMATS}, got {output_format!r}')
     found, pred, true, input_index = [], [], [], []
+    pred_x, true_x, n_linker = [], [], []
+    geometry = geometry and metrics
     exp = 'model' if isinstance(checkpoint, DDPM) else checkpoint.split('/')[-1].replace('.ckpt', '')
     collate_fn, sample_fn = collate, None
     if linker_size_model is None:
@@ -113,6 +116,9 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
         save_xyz_file(output_dir, h, x, frag_mask, [f'{u}/frag' for u in uuids], is_geom=model.is_geom)
         if metrics:                                            # the true molecules as the files show them: without the pocket
             true_batch = mol_metrics.to_host(mol_metrics.analyze(h, x, node_mask, model.is_geom), h, node_mask)
+        if geometry:
+            true_x_batch = list(mol_metrics.kept_positions(x, node_mask)[0])
+            n_linker_batch = batch['linker_mask'].reshape(len(uuids), -1).sum(1).long().tolist()
         for i in range(starting_point, n_samples):
             chain, out_mask = model.sample_chain(batch, sample_fn=sample_fn, keep_frames=1)
             xs, hs = chain[0][:, :, :model.n_dims], chain[0][:, :, model.n_dims:]
@@ -132,11 +138,18 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 pred += mol_metrics.to_host(mol_metrics.analyze(types, xs, out_mask, model.is_geom), types, out_mask)
                 true += true_batch
                 input_index += [(batch_idx, k) for k in range(len(uuids))]
+            if geometry:
+                pred_x += list(mol_metrics.kept_positions(xs, out_mask)[0])
+                true_x += true_x_batch
+                n_linker += n_linker_batch
     if found:
         print(json.dumps(summary(found)))
     if metrics:
         with open(os.path.join(output_dir, 'metrics.json'), 'w') as f:
-            json.dump(dict(mol_metrics.compute_metrics(pred, true, input_index), molecules=len(pred)), f, indent=1)
+            scores = dict(mol_metrics.compute_metrics(pred, true, input_index), molecules=len(pred))
+            if geometry:
+                scores.update(mol_metrics.compute_geometry(pred, true, pred_x, true_x, n_linker))
+            json.dump(scores, f, indent=1)
     return output_dir
 
 
@@ -186,12 +199,15 @@ def main(argv=None):
     p.add_argument('--metrics', action='store_true',
                    help='score the sampled molecules on the GPU (valence rule, connectivity, uniqueness, novelty, recovery) '
                         'and write metrics.json next to them')
+    p.add_argument('--geometry', action='store_true',
+                   help='with --metrics: add the symmetry-aware RMSD of the recovered samples against their true molecules '
+                        '(rmsd, rmsd_molecules, rmsd_truncated)')
     a = p.parse_args(argv)
     if a.keep_frames is not None:
         print(sample_trajectories(a.checkpoint, a.samples, a.prefix, a.keep_frames, a.device, a.data, a.n_steps))
     else:
         print(sample(a.checkpoint, a.samples, a.prefix, a.n_samples, a.device, a.data, a.n_steps, a.linker_size_model,
-                     a.output_format, a.metrics))
+                     a.output_format, a.metrics, **({'geometry': True} if a.geometry else {})))
 
 
 if __name__ == '__main__':

@@ -90,6 +90,8 @@ def main(argv=None):
     p.add_argument('--sample_every_epochs', type=int, default=0,
                    help='score the validation set at the end of every epoch and sample it every E-th epoch; keeps best.ckpt '
                         '(0: off)')
+    p.add_argument('--geometry', action='store_true',
+                   help='with --sample_every_epochs: add the symmetry-aware RMSD of the recovered samples to the epoch scores')
     a = p.parse_args(argv)
     cfg = dict(DEFAULTS)
     if a.config is not None:
@@ -122,6 +124,7 @@ def main(argv=None):
     best = float(ckpt.get('best_validity_and_connectivity', float('-inf'))) if ckpt is not None else float('-inf')
     if a.sample_every_epochs:
         model.test_epochs = a.sample_every_epochs
+    model.geometry_metrics = bool(a.geometry)
     kept = lambda: {'best_validity_and_connectivity': best} if a.sample_every_epochs else {}   # noqa: E731
     step, epoch = start_step, start_epoch
     n_epochs = int(cfg['n_epochs'])

@@ -39,6 +39,9 @@
  *   dl_molecule_keys                     <- the questions metrics.py asks of a built molecule (src/metrics.py:12-54), put to
  *                                           the bond graph instead of RDKit: valences within the element's limit,
  *                                           one piece, and a renumbering-invariant key per molecule
+ *   dl_best_rmsd                         <- the RMSD block of compute_metrics.py:366-402: rdMolAlign.GetBestRMS of every
+ *                                           recovered sample against its true molecule, the minimum over the graph
+ *                                           isomorphisms the host enumerated, proper rotations only
  *   dl_size_train_forward / dl_size_train_backward
  *                                        <- SizeClassifier.forward in training mode + loss.backward()
  *                                           (src/linker_size_lightning.py:83-117, :163-167)
@@ -607,6 +610,54 @@ typedef struct dl_mol_keys_args {
     int32_t* status;                /* device int32 [B] out */
 } dl_mol_keys_args;
 int32_t dl_molecule_keys(const dl_mol_keys_args* args, void* stream);
+
+/* ---- symmetry-aware RMSD of a list of pairs (rmsd.hip) ------------------------------------------------------
+ * compute_metrics.py:366-402 scores every recovered sample with rdMolAlign.GetBestRMS(pred, true): the smallest RMSD after
+ * a rigid alignment (proper rotations only, no reflection) over all atom correspondences that are isomorphisms of the two
+ * graphs.  Here the host enumerates the correspondences ("maps", metrics.isomorphisms) and ONE launch scores the whole list,
+ * one 256-thread workgroup per pair.
+ *
+ * Atoms are the kept atoms of a molecule renumbered from 0, exactly as metrics.to_host numbers a Graph.  A map of pair p is a
+ * bijection image[0 .. n_atoms[p]): atom k of `xa` corresponds to atom image[k] of `xb`.
+ *
+ * LAYOUT OF THE MAP TABLE.  `maps` holds `maps_capacity` maps' worth of 16-bit atom indices, n_max to a map.  The maps of
+ * pair p are the m_p = map_offsets[p + 1] - map_offsets[p] maps from map_offsets[p] on, and their block starts at element
+ * map_offsets[p] * n_max.  INSIDE a block the entries are atom-major: image[k] of the pair's j-th map is
+ *     maps[map_offsets[p] * n_max + k * m_p + j],      0 <= k < n_atoms[p], 0 <= j < m_p
+ * so the 64 lanes of a wave, one map each, read 64 consecutive 16-bit words for every atom.  The rest of a block (from element
+ * n_atoms[p] * m_p on) is never read.
+ *
+ *   rmsd     sqrt(min over the maps of min over rotations R and translations t of mean_k |R a_k + t - b_image[k]|^2); the
+ *            factor sqrt(n_atoms / n_linker) of the reference is the caller's.  NaN when status is not 0.
+ *   best     index, within the pair, of the map that gives it; of equal candidates the lowest, so the same on every run;
+ *            -1 when status is not 0.
+ *   status   0, or DL_RMSD_* bits.  A pair with a bit set does not touch the other pairs of the launch.
+ *
+ * Candidates are compared as Ga + Gb - 2 lambda with lambda the largest eigenvalue of Horn's 4x4 quaternion matrix (cyclic
+ * Jacobi, fp64: safe for n = 1, 2, collinear, planar and coinciding sets); the winner's residual is then summed directly as
+ * sum |R a_k - b_image[k]|^2 in fp64, which does not cancel when the structures coincide.  Coordinates are centred in fp64 and
+ * held in fp32.  An index beyond the atom count is clamped (no fault; that map's value means nothing).
+ *
+ * Global memory is written with plain stores only; the callee allocates nothing.  A null `args`, P < 0, n_max < 1 or > 65536
+ * or maps_capacity < 0 return DL_ERR_BAD_ARG; then P == 0 returns DL_OK without a launch (and without looking at the
+ * pointers); then null pointers (`maps` may be NULL when maps_capacity is 0) return DL_ERR_BAD_ARG, all before any device
+ * work. */
+#define DL_RMSD_NONFINITE 1         /* status bit: a coordinate of the pair is NaN or infinite */
+#define DL_RMSD_NO_MAP 2            /* status bit: no map for this pair (or no atom, or offsets that leave the table) */
+#define DL_RMSD_TOO_LARGE 4         /* status bit: n_atoms above n_max or above the 1024 atoms the workgroup's LDS holds */
+typedef struct dl_rmsd_args {
+    int32_t P, n_max;               /* pairs; atoms per padded molecule */
+    const float* xa;                /* device f32 [P,n_max,3]: the predictions */
+    const float* xb;                /* device f32 [P,n_max,3]: the true molecules */
+    const int32_t* n_atoms;         /* device int32 [P] */
+    const int32_t* map_offsets;     /* device int32 [P+1]: first map of each pair, ascending */
+    const uint16_t* maps;           /* device 16-bit [maps_capacity * n_max], layout above */
+    int32_t maps_capacity;          /* maps the table holds (>= map_offsets[P]) */
+    float* rmsd;                    /* device f32 [P] out */
+    int32_t* best;                  /* device int32 [P] out */
+    int32_t* status;                /* device int32 [P] out */
+} dl_rmsd_args;
+int32_t dl_best_rmsd(const dl_rmsd_args* args, void* stream);
 
 const char* dl_error_string(int32_t status);
 int32_t dl_last_hip_error(void);
