@@ -1750,8 +1750,15 @@ __device__ __forceinline__ void stream_phase(const Lds& v, Prof& pf, const AggRe
         const float x2 = __uint_as_float(v.fmax[FM_X2]), x02 = __uint_as_float(v.fmax[FM_X02]);
         S1 = fminf(scale_for(4.0f * x2) * scale_for(cload(scn, 6)), scale_for(4.0f * x02) * scale_for(cload(scn, 7)));
     }
-    // (the columns of a tile's padding atoms - 14 of 64 at n = 50 - enter every GEMM as ZEROS: their operand scales are 0.  Nothing
-    // of them is ever read, and a zero column costs the matrix pipe less energy, which under the power cap is clock)
+    // (the columns of a tile's padding atoms - 14 of 64 at n = 50 - have operand scale 0: `live` multiplies rows that nobody ever
+    // wrote (hold and res2 from HBM scratch, the aggregate's LDS rows from nown on, the hv it stores back) by 0.  With a fresh allocation that is 0 - a
+    // zero column costs the matrix pipe less energy, which under the power cap is clock - but the workspace's contents on entry
+    // are unspecified (include/difflinker_hip.h): stale NaN / inf bits times 0 are NaN, and those columns then carry NaN
+    // through the whole MFMA chain and are stored back every pass.  So they MAY HOLD ANYTHING, and the results are right because
+    // NOTHING READS THEM: MFMA columns do not mix, and every consumer - hm / block_max, the P and Q stores, the flags - is guarded
+    // by `valid`.  A workgroup-wide maximum, NaN test or reduction that takes in a padding column breaks this; the guard is
+    // tests/test_gpu_scratch.py, which runs every launch route on workspaces pre-filled with NaN, inf and 3.4e38 patterns at
+    // n = 33 (31 padding columns) and n = 55 / 32 / 31 / 2 / 40 and compares bits with the zero-filled run)
     const float live = valid ? 1.0f : 0.0f;
     if (awave) {
         // the B operand of W3a' / of the projections from the fp32 node features

@@ -52,9 +52,16 @@
  *     asynchronous on that stream.
  *   - the library allocates NOTHING after dl_model_create (which uploads the packed weights): every compute entry
  *     point takes its scratch memory from the caller - `workspace` / `workspace_bytes`, sized by the matching
- *     dl_*_workspace_bytes query, 16-byte aligned, contents irrelevant on entry, free to reuse once the launch has
- *     completed on `stream`.  Two launches that run concurrently need two workspaces; a dl_model itself is
- *     immutable after creation and may be shared by any number of streams.
+ *     dl_*_workspace_bytes query, 16-byte aligned, free to reuse once the launch has completed on `stream`.  Two
+ *     launches that run concurrently need two workspaces; a dl_model itself is immutable after creation and may be
+ *     shared by any number of streams.
+ *   - THE WORKSPACE CONTRACT (every entry point that takes `workspace`): the contents of the workspace on entry are
+ *     unspecified - stale bytes of any earlier use, NaN, inf and huge integers included; the library initialises what it
+ *     needs (arrival words, counters, flag words) on `stream` before the kernels that read it; the contents on return are
+ *     unspecified.  The same holds for every output buffer: the defined part of every result, and every status flag, is
+ *     a function of the inputs alone, bit for bit, whatever workspace and outputs held on entry.  Outputs are written in
+ *     full unless their description says "up to" a returned count or "rows of real atoms" (tests/test_gpu_scratch.py
+ *     runs every entry point and launch route on buffers pre-filled with NaN, inf and 3.4e38 bit patterns).
  *   - all floating point is fp32; masks are int8 (node_mask, edge_mask) or fp32 (fragment /
  *     linker masks, context) exactly as the reference's collate produces them.
  *   - return value: 0 on success, a negative dl_status otherwise; dl_error_string() names it.
@@ -177,7 +184,9 @@ int32_t dl_egnn_forward_fc(const dl_model* m, int32_t B, int32_t N,
 /* Scratch of dl_egnn_forward_fc / dl_egnn_forward_fc_team / dl_sample_chain_fc for a batch of B molecules with `team`
  * compute units per molecule (0 or 1: one): per workgroup the node features and the pre-computed half of the node MLP that
  * cross the O(n^2) edge passes through L2 (124 KB: the T0 and residual tiles in accumulator order, the h fragment rows of a
- * 56..110-atom molecule across a coordinate pass), plus, for team > 1, the exchange buffers (116 KB per molecule) and arrival words. */
+ * 56..110-atom molecule across a coordinate pass), plus, for team > 1, the exchange buffers (116 KB per molecule) and arrival words.
+ * Contents on entry unspecified (the entry points zero the arrival words on `stream`; the tile columns of padding atoms are
+ * never written and never read for a result), contents on return unspecified.  `out` and `nan_flags` are written in full. */
 size_t dl_workspace_bytes(int32_t B, int32_t team);
 
 /* DynamicsWithPockets.forward (src/egnn.py:470-552): radius graph rebuilt on the GPU every call
@@ -186,7 +195,9 @@ size_t dl_workspace_bytes(int32_t B, int32_t team);
  *   graph_type  0: '4A', 1: 'FC-4A', 2: 'FC-10A-4A'
  *   linker_mask device f32 [B,N] (required: it defines the ligand atoms together with context[..., -2])
  *   context     device f32 [B,N,ctx], last two channels = fragment-only / pocket-only masks (:486-487)
- *   workspace   device scratch of at least dl_pocket_workspace_bytes(B, N) bytes, caller-owned
+ *   workspace   device scratch of at least dl_pocket_workspace_bytes(B, N) bytes, caller-owned; contents on entry
+ *               unspecified (the entry point zeroes its counters and batch-wide maxima on `stream`), contents on return
+ *               unspecified.  `out` (padded rows 0) and `nan_flags` are written in full
  * Molecule membership is positional (atom v belongs to molecule v / N), which is what the reference's batch-index
  * "edge_mask" vector encodes (src/datasets.py:359-364).  Both precisions are supported. */
 size_t dl_pocket_workspace_bytes(int32_t B, int32_t N);
@@ -201,7 +212,8 @@ int32_t dl_egnn_forward_pocket(const dl_model* m, int32_t B, int32_t N, int32_t 
  * diagonal included (value -2, src/datasets.py:366-369), each message weighted by that value.  Use it for batches with a
  * molecule of more than dl_max_atoms() atoms (dl_egnn_forward_fc flags those with bit 2); several times slower than
  * the LDS-resident kernel.  Arguments as dl_egnn_forward_fc (edge_mask required, linker_mask may be NULL);
- * workspace: dl_pocket_workspace_bytes(B, N). */
+ * workspace: dl_pocket_workspace_bytes(B, N), contents on entry and on return unspecified (initialised on `stream` as in
+ * dl_egnn_forward_pocket); `out` and `nan_flags` are written in full. */
 int32_t dl_egnn_forward_fc_large(const dl_model* m, int32_t B, int32_t N, const float* xh, const float* t,
                                  int32_t t_is_scalar, const int8_t* node_mask, const float* linker_mask,
                                  const int8_t* edge_mask, const float* context, float* out, int32_t* nan_flags,
@@ -243,14 +255,18 @@ typedef struct dl_chain_args {
     const dl_step_coef* coefs;  /* device [T]       execution order (s = T-1 first)            */
     float inv_alpha0, sigma0, sigma_x;      /* final decode scalars (src/edm.py:213-216,237-242) */
     float norm_x, norm_h, bias_h;           /* norm_values[0], norm_values[1], norm_biases[1]    */
-    float* chain;               /* device [keep_frames,B,N,3+nf]; frame 0 = final [x, one_hot(h)] */
+    float* chain;               /* device [keep_frames,B,N,3+nf]; frame 0 = final [x, one_hot(h)].  The rows of REAL atoms are
+                                 * written; padding rows (and the frames of a molecule that ended flagged) stay as the caller
+                                 * left them - EDM.sample_chain passes zeros */
     int32_t* nan_flags;         /* device [B]  bit0/bit1 as above (first offending forward only) */
     int32_t* nan_step;          /* device [B]  forward index (0..T) at which the flag was raised, or -1 */
     const int32_t* order;       /* device [B] or NULL: workgroup k samples molecule order[k].  One molecule occupies one
                                  * compute unit for the whole chain and workgroups are dispatched in index order, so a
                                  * batch larger than the chip finishes sooner when the big molecules go first
                                  * (longest-processing-time order); results are written at the molecule's own index. */
-    void* workspace;            /* device scratch of dl_workspace_bytes(B, team) bytes, 16-byte aligned */
+    void* workspace;            /* device scratch of dl_workspace_bytes(B, team) bytes, 16-byte aligned; contents on entry
+                                 * unspecified (arrival words zeroed on `stream` by the entry point), on return unspecified.
+                                 * nan_flags and nan_step are written for every molecule of the launch; z_state for those that stop early */
     size_t workspace_bytes;
     const int32_t* mol_index;   /* device [B] or NULL: entry b of this batch is molecule mol_offset + mol_index[b] of the
                                  * logical batch (NULL: mol_offset + b) - the key of the in-kernel noise; lets a caller
@@ -293,7 +309,9 @@ typedef struct dl_join_args {
     int32_t teams;
     const int32_t* team_of;     /* device [B]                                            */
     const int32_t* team_mol;    /* device [teams]                                        */
-    void* workspace;            /* device scratch of dl_join_workspace_bytes(teams) bytes, 16-byte aligned */
+    void* workspace;            /* device scratch of dl_join_workspace_bytes(teams) bytes, 16-byte aligned; contents on entry
+                                 * unspecified (arrival and join words zeroed on `stream` by the entry point), on return
+                                 * unspecified - as those of args->workspace */
     size_t workspace_bytes;
     uint64_t* wait_ticks;       /* device [teams][2] or NULL                             */
 } dl_join_args;
@@ -431,7 +449,9 @@ typedef struct dl_backward_args {
     const float* context;           /* device f32 [B,N,context_node_nf] or NULL */
     const float* grad_out;          /* device f32 [B,N,3+nf]: d eps_hat */
     float* grad_params;             /* device f32 [n_params] out */
-    void* workspace;                /* device, >= dl_egnn_backward_fc_workspace_bytes */
+    void* workspace;                /* device, >= dl_egnn_backward_fc_workspace_bytes; contents on entry unspecified (every saved
+                                     * activation and per-molecule partial is written before it is read, nothing accumulates
+                                     * across calls), on return unspecified; grad_params is written in full */
     size_t workspace_bytes;
 } dl_backward_args;
 int64_t dl_egnn_backward_fc_num_params(const dl_backward_args* args);          /* -1 outside the scope */
@@ -514,7 +534,9 @@ typedef struct dl_size_train_args {
                                        dl_size_max_fragment_atoms() (that molecule's results are meaningless) */
     const float* grad_logits;       /* device f32 [B,out_node_nf] (backward) */
     float* grad_params;             /* device f32 [n_params] out (backward) */
-    void* workspace;                /* device, >= dl_size_train_workspace_bytes */
+    void* workspace;                /* device, >= dl_size_train_workspace_bytes; contents unspecified on entry of the forward (it
+                                     * writes all the backward reads), the matching backward needs them untouched, unspecified
+                                     * after it; logits and grad_params are written in full */
     size_t workspace_bytes;
 } dl_size_train_args;
 int64_t dl_size_train_num_params(const dl_size_train_args* args);        /* -1 outside the scope */
@@ -552,7 +574,8 @@ typedef struct dl_bonds_args {
     int32_t* component;             /* device int32 [B,N] out: smallest atom index of atom k's component; -1 from the atom
                                        count on */
     int32_t* status;                /* device int32 [B] out: DL_BONDS_* bits */
-    void* workspace;                /* device, >= dl_bonds_workspace_bytes (may be NULL when that is 0) */
+    void* workspace;                /* device, >= dl_bonds_workspace_bytes (may be NULL when that is 0); contents on entry and
+                                     * on return unspecified.  Every output is written in full except `bonds`: up to n_bonds */
     size_t workspace_bytes;
 } dl_bonds_args;
 size_t dl_bonds_workspace_bytes(int32_t B, int32_t N);      /* 0 today: every intermediate fits in LDS */
