@@ -162,6 +162,7 @@ EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_stri
            'dl_team_max', 'dl_egnn_forward_fc_team', 'dl_team_max_atoms',
            'dl_edm_loss_prologue', 'dl_edm_loss_epilogue', 'dl_edm_loss_grad', 'dl_egnn_backward_fc_num_params',
            'dl_egnn_backward_fc_workspace_bytes', 'dl_egnn_backward_max_atoms', 'dl_egnn_backward_fc',
+           'dl_egnn_backward_pocket_workspace_bytes', 'dl_egnn_backward_pocket',
            'dl_size_train_num_params', 'dl_size_train_workspace_bytes', 'dl_size_train_forward', 'dl_size_train_backward',
            'dl_join_workspace_bytes', 'dl_sample_chain_fc_join', 'dl_bonds_workspace_bytes', 'dl_perceive_bonds',
            'dl_molecule_keys', 'dl_best_rmsd')
@@ -267,6 +268,10 @@ def _open(path):
     lib.dl_egnn_backward_max_atoms.restype = i32
     lib.dl_egnn_backward_fc.restype = i32
     lib.dl_egnn_backward_fc.argtypes = [ctypes.POINTER(DLBackwardArgs), vp]
+    lib.dl_egnn_backward_pocket_workspace_bytes.restype = ctypes.c_size_t
+    lib.dl_egnn_backward_pocket_workspace_bytes.argtypes = [ctypes.POINTER(DLBackwardArgs), i32]
+    lib.dl_egnn_backward_pocket.restype = i32
+    lib.dl_egnn_backward_pocket.argtypes = [ctypes.POINTER(DLBackwardArgs), i32, vp]
     lib.dl_size_train_num_params.restype = ctypes.c_int64
     lib.dl_size_train_num_params.argtypes = [ctypes.POINTER(DLSizeTrainArgs)]
     lib.dl_size_train_workspace_bytes.restype = ctypes.c_size_t

@@ -352,8 +352,9 @@ class EDM(torch.nn.Module):
         """``forward`` for TRAINING: the same draws and the same 7-tuple, bit for bit, and ``l2_loss``, ``loss_term_t``,
         ``loss_term_0``, ``noise_t`` and ``noise_0`` carry a gradient to the parameters of ``self.dynamics`` (the others do
         not depend on them).  The backward is HIP: ``dl_edm_loss_grad`` forms d eps_hat from the per-molecule weights of the
-        batch means, ``dl_egnn_backward_fc`` the parameter gradients (``Dynamics.training_forward``).  Fully-connected
-        ``Dynamics`` with the released hyper-parameters only (``egnn.check_trainable``; anything else raises
+        batch means, ``dl_egnn_backward_fc`` (pocket models: ``dl_egnn_backward_pocket``) the parameter gradients
+        (``Dynamics.training_forward``).  Fully-connected ``Dynamics`` and ``DynamicsWithPockets`` on the FC-4A / FC-10A-4A
+        graphs, with the released hyper-parameters only (``egnn.check_trainable``; anything else raises
         ``NotImplementedError``)."""
         from .egnn import check_trainable
         check_trainable(self.dynamics)

@@ -631,21 +631,35 @@ class DynamicsWithPockets(Dynamics):
         return out
 
 
-# ---- training: the backward of the fully-connected denoiser (csrc/egnn_backward.hip) ------------------------------------
+# ---- training: the backward of the denoiser (csrc/egnn_backward.hip: fully connected; csrc/egnn_backward_sparse.hip: pockets) ----
+TRAINABLE_POCKET_GRAPHS = ('FC-4A', 'FC-10A-4A')
+
+
 def check_trainable(dyn):
-    """Raise ``NotImplementedError`` for a denoiser outside the backward's scope (the released FC configurations)."""
+    """Raise ``NotImplementedError`` for a denoiser outside the backward's scope: fully-connected ``Dynamics`` and
+    ``DynamicsWithPockets`` on the ``FC-4A`` / ``FC-10A-4A`` radius graphs, with the released hyper-parameters."""
     out = []
-    if isinstance(dyn, DynamicsWithPockets) or type(dyn) is not Dynamics:
-        out.append(f'{type(dyn).__name__} (pocket graphs)')
-    if getattr(dyn, 'graph_type', 'FC') != 'FC': out.append(f'graph_type={dyn.graph_type!r}')
+    pocket = type(dyn) is DynamicsWithPockets
+    if not pocket and type(dyn) is not Dynamics:
+        out.append(f'{type(dyn).__name__}')
+    graph = getattr(dyn, 'graph_type', 'FC')
+    if pocket:
+        if graph not in TRAINABLE_POCKET_GRAPHS:
+            out.append(f'{type(dyn).__name__} with graph_type={graph!r} (pocket training covers {", ".join(TRAINABLE_POCKET_GRAPHS)})')
+    elif graph != 'FC':
+        out.append(f'graph_type={graph!r}')
     if dyn.attention: out.append('attention=True')
     if dyn.tanh: out.append('tanh=True')
     if dyn.aggregation_method != 'sum': out.append(f'aggregation_method={dyn.aggregation_method!r}')
     if dyn.sin_embedding: out.append('sin_embedding=True')
     if dyn.dynamics.hidden_nf != HIDDEN_WIDTH: out.append(f'hidden_nf={dyn.dynamics.hidden_nf} (the backward is 128 wide)')
     if out:
-        raise NotImplementedError('training (the HIP backward) covers fully-connected Dynamics with the released '
-                                  'hyper-parameters only; outside it: ' + ', '.join(out))
+        raise NotImplementedError('training (the HIP backward) covers fully-connected Dynamics and DynamicsWithPockets on the '
+                                  'FC-4A / FC-10A-4A graphs, with the released hyper-parameters only; outside it: '
+                                  + ', '.join(out))
+
+
+POCKET_BACKWARD_MAX_ATOMS = 2048      # dl_egnn_backward_pocket's limit on the padded width (include/difflinker_hip.h)
 
 
 def backward_args(dyn, B, N):
@@ -688,9 +702,11 @@ def _dynamics_parameter_grad(self, t, xh, node_mask, linker_mask, edge_mask, con
     params = list(self.parameters())
     if bs == 0:
         return [torch.zeros_like(p) for p in params]
-    limit = int(lib.dl_egnn_backward_max_atoms())
-    if n > limit:
-        raise ValueError(f'the EGNN backward takes molecules of at most {limit} atoms (padded width); got {n}')
+    pocket = isinstance(self, DynamicsWithPockets)
+    limit = POCKET_BACKWARD_MAX_ATOMS if pocket else int(lib.dl_egnn_backward_max_atoms())
+    if n > limit or (pocket and bs * n * n >= 2 ** 31):
+        raise ValueError(f'the EGNN backward takes molecules of at most {limit} atoms (padded width)'
+                         + (' and batches with B * N * N < 2^31' if pocket else '') + f'; got B = {bs}, N = {n}')
     f32 = lambda v: None if v is None else v.to(dev, torch.float32).contiguous()      # noqa: E731
     flat = torch.cat([p.detach().reshape(-1).to(torch.float32) for p in params]).contiguous()
     if not torch.is_tensor(t):
@@ -700,7 +716,11 @@ def _dynamics_parameter_grad(self, t, xh, node_mask, linker_mask, edge_mask, con
     want = int(lib.dl_egnn_backward_fc_num_params(ctypes.byref(args)))
     if want != flat.numel():
         raise ValueError(f'parameter count {flat.numel()} != the backward layout {want}')
-    need = int(lib.dl_egnn_backward_fc_workspace_bytes(ctypes.byref(args)))
+    if pocket:
+        graph = self.GRAPH_TYPES[self.graph_type]
+        need = int(lib.dl_egnn_backward_pocket_workspace_bytes(ctypes.byref(args), graph))
+    else:
+        need = int(lib.dl_egnn_backward_fc_workspace_bytes(ctypes.byref(args)))
     ws = getattr(self, '_bwd_ws', None)
     if ws is None or ws.numel() < need or ws.device != dev:
         ws = self._bwd_ws = None
@@ -708,19 +728,23 @@ def _dynamics_parameter_grad(self, t, xh, node_mask, linker_mask, edge_mask, con
     xh_ = f32(xh)
     nm = f32(node_mask.reshape(bs, n))
     lm = f32(linker_mask.reshape(bs, n)) if linker_mask is not None else None
-    em = edge_mask.reshape(bs, n, n).to(dev, torch.int8).contiguous()
+    em = None if pocket else edge_mask.reshape(bs, n, n).to(dev, torch.int8).contiguous()   # pockets: the batch-index vector, unused
     ctx_ = f32(context.reshape(bs, n, self.context_node_nf)) if context is not None and self.context_node_nf else None
     go = f32(grad_out)
     grad = torch.empty_like(flat)
     args.params, args.n_params = flat.data_ptr(), flat.numel()
     args.xh, args.t, args.t_is_scalar = xh_.data_ptr(), tt.data_ptr(), int(tt.numel() == 1)
-    args.node_mask, args.linker_mask, args.edge_mask = nm.data_ptr(), lm.data_ptr() if lm is not None else None, em.data_ptr()
+    args.node_mask, args.linker_mask = nm.data_ptr(), lm.data_ptr() if lm is not None else None
+    args.edge_mask = em.data_ptr() if em is not None else None
     args.context = ctx_.data_ptr() if ctx_ is not None else None
     args.grad_out, args.grad_params = go.data_ptr(), grad.data_ptr()
     args.workspace, args.workspace_bytes = ws.data_ptr(), need
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.dl_egnn_backward_fc(ctypes.byref(args), ctypes.c_void_p(stream)), 'dl_egnn_backward_fc')
+        if pocket:
+            _lib.check(lib.dl_egnn_backward_pocket(ctypes.byref(args), graph, ctypes.c_void_p(stream)), 'dl_egnn_backward_pocket')
+        else:
+            _lib.check(lib.dl_egnn_backward_fc(ctypes.byref(args), ctypes.c_void_p(stream)), 'dl_egnn_backward_fc')
     out, k = [], 0
     for p in params:
         out.append(grad[k:k + p.numel()].view_as(p).to(p.dtype))

@@ -459,6 +459,26 @@ size_t dl_egnn_backward_fc_workspace_bytes(const dl_backward_args* args);      /
 int32_t dl_egnn_backward_max_atoms(void);
 int32_t dl_egnn_backward_fc(const dl_backward_args* args, void* stream);
 
+/* ---- backward of the pocket-conditioned denoiser (training; egnn_backward_sparse.hip) --------------------------
+ * Gradient of sum(grad_out * DynamicsWithPockets.forward(...)) with respect to every parameter, on the radius graph of
+ * dl_egnn_forward_pocket (`graph_type` 0: '4A', 1: 'FC-4A', 2: 'FC-10A-4A'; the EGNN runs without an edge mask).  Same
+ * hyper-parameter scope, the same dl_backward_args and the same flat parameter layout as dl_egnn_backward_fc
+ * (dl_egnn_backward_fc_num_params answers for it), with these differences: `edge_mask` is ignored and may be NULL;
+ * `context` is required (context_node_nf >= 2) and its last two channels are the fragment-only and pocket-only masks;
+ * membership is positional (atom v belongs to molecule v / N).  The graph is rebuilt on the GPU from the masked coordinates
+ * of `xh` by the rule and the fp32 arithmetic of dl_egnn_forward_pocket, so it is the forward's edge set; the distance test
+ * carries no gradient.  All pair work follows the edge list in tiles of 32 edges spread over the chip; the pair GEMMs run on
+ * v_mfma_f32_32x32x2_f32 with fp32 accumulation.  Deterministic: no float atomics; node gradients are summed receiver-side
+ * over the neighbour lists, weight gradients through per-workgroup partials summed in a fixed order; a molecule's part of
+ * the gradient depends on that molecule alone.  An atom without neighbours and an empty molecule are legal.
+ * Limits: N <= 2048 padded atoms per molecule and B * N * N < 2^31; beyond them DL_ERR_TOO_MANY_ATOMS (workspace_bytes: 0).
+ * The workspace holds per-edge buffers sized for B * N * (N - 1) edges (520 bytes each) of which only the graph's edges are
+ * touched; its contents on entry are unspecified, grad_params is written in full.  The callee allocates nothing; argument
+ * checks (DL_ERR_BAD_ARG, DL_ERR_UNSUPPORTED, DL_ERR_TOO_MANY_ATOMS) come before any device work; B == 0 returns DL_OK
+ * without a launch; runs on `stream`. */
+size_t dl_egnn_backward_pocket_workspace_bytes(const dl_backward_args* args, int32_t graph_type);   /* 0 outside the scope */
+int32_t dl_egnn_backward_pocket(const dl_backward_args* args, int32_t graph_type, void* stream);
+
 /* Diagnostics (libraries built with -DDL_PROFILE only; dl_profile_max_events() returns 0 otherwise): when set
  * (device uint64 [8 waves][dl_profile_max_events()][2], or NULL to disable), the first workgroup of the next
  * launches logs (phase tag, shader clock) pairs of its first forward. */

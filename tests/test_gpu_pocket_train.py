@@ -1,0 +1,389 @@
+"""Training of the pocket-conditioned denoiser on the GPU: the edge-list HIP backward (csrc/egnn_backward_sparse.hip) against
+fp64 autograd of the oracle and against the unmodified reference's ``loss.backward()`` (tests/golden/pocket_grad.npz), the
+values of ``training_forward`` against ``forward``, determinism, stale scratch memory, an optimiser step, a short overfit and
+the ``python -m difflinker_amd.train`` loop on a toy MOAD dataset."""
+import ctypes
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from helpers import rel_l2, seeded_state_dict, trained_like_state_dict
+from oracle import egnn_oracle
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device('cuda:0')
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# The bars of the fully-connected backward (tests/test_gpu_train.py).  Measured on the pocket graphs (MI355X), worst of the cases
+# below: 5.8e-7 over all parameters and 1.9e-6 on one tensor (both 'trained_like'); fp32 eager autograd of the same oracle
+# reaches 1.6e-6 / 4.1e-6 ('c4_geometry'); the reference fixture: 1.7e-7 / 1.8e-6.  Below the FC bars, so these stay.
+BAR_ALL, BAR_TENSOR = 2e-6, 1e-5
+FP32_CLASS = 2.0                        # and within 2x the error of fp32 eager autograd against the same fp64 gradient
+GAP = 1e-3                              # Angstrom: no pair this close to a cut-off that applies to it
+
+
+def pocket_batch(batch, n_frag, n_pocket, linker, nf, seed, anchors=False, far_atom=False):
+    """``tests/test_gpu_parity.py::pocket_inputs`` (the denoiser's inputs for a collated synthetic pocket batch), optionally with
+    the anchors channel in front of the context or with molecule 0's last pocket atom moved 50 A away."""
+    from difflinker_amd import synthetic
+    from difflinker_amd.datasets import collate
+    mols = synthetic.pocket_molecules(batch, n_frag, n_pocket, linker, nf, seed)
+    if far_atom:
+        mols[0]['positions'][n_frag + n_pocket - 1] += torch.tensor([50.0, 0.0, 0.0])
+    inp = synthetic.sampler_inputs(collate(mols), pockets=True, anchors_context=anchors)
+    B, N = inp['x'].shape[:2]
+    g = torch.Generator().manual_seed(seed + 1)
+    z = torch.cat([inp['x'], inp['h']], dim=2) * inp['fragment_mask'] + \
+        torch.cat([2.0 * torch.randn((B, N, 3), generator=g), torch.randn((B, N, nf), generator=g)], dim=2) * inp['linker_mask']
+    t = torch.rand((B, 1), generator=g)
+    G = torch.randn((B, N, 3 + nf), generator=g)
+    return inp, z, t, G
+
+
+def assert_clear_of_cutoffs(z, inp, graph_type):
+    """The precondition of every comparison: in fp64 no same-molecule pair of real atoms lies within ``GAP`` of a cut-off that
+    applies to it, so the fp32 edge set of the kernels is the fp64 edge set of the oracle."""
+    x = (z[..., :3] * inp['node_mask']).double()
+    real = inp['node_mask'][..., 0] != 0
+    pock = (inp['context'][..., -1] != 0) & real
+    lig = real & ~pock
+    d = torch.cdist(x, x)
+    pp = pock[:, :, None] & pock[:, None, :]
+    cross = (lig[:, :, None] & pock[:, None, :]) | (pock[:, :, None] & lig[:, None, :])
+    cut = 4.0 if graph_type == 'FC-4A' else 10.0
+    near = (pp & ((d - 4.0).abs() < GAP)) | (cross & ((d - cut).abs() < GAP))
+    assert not bool(near.any()), f'{int(near.sum())} pairs within {GAP} A of a cut-off: choose another seed'
+
+
+def make_dyn(nf, ctx, L, S, wseed, graph_type, trained=False, centering=False):
+    from difflinker_amd import DynamicsWithPockets
+    dyn = DynamicsWithPockets(n_dims=3, in_node_nf=nf, context_node_nf=ctx, hidden_nf=128, n_layers=L, inv_sublayers=S,
+                              norm_constant=1e-6, normalization_factor=100, centering=centering, graph_type=graph_type)
+    sd = seeded_state_dict(nf + ctx + 1, 128, L, wseed, coord_gain=0.02, inv_sublayers=S)
+    if trained:
+        sd = trained_like_state_dict(sd, wseed)
+    dyn.load_state_dict({k: v.float() for k, v in sd.items()}, strict=True)
+    return dyn.to(DEV)
+
+
+def oracle_grads(dyn, t, z, inp, G, dtype=torch.float64):
+    cfg = egnn_oracle.EGNNConfig(in_node_nf=dyn.in_node_nf, context_node_nf=dyn.context_node_nf, n_layers=dyn.n_layers,
+                                 inv_sublayers=dyn.inv_sublayers, norm_constant=dyn.norm_constant,
+                                 normalization_factor=dyn.normalization_factor, centering=dyn.centering,
+                                 graph_type=dyn.graph_type)
+    p = {k: v.detach().cpu().to(dtype).requires_grad_(True) for k, v in dyn.state_dict().items()}
+    d = lambda v: v.detach().cpu().to(dtype)                                  # noqa: E731
+    out = egnn_oracle.dynamics_forward_pockets(p, cfg, d(t), d(z), d(inp['node_mask']), d(inp['linker_mask']),
+                                               inp['edge_mask'], d(inp['context']))
+    (out * d(G)).sum().backward()
+    return {k: v.grad for k, v in p.items()}
+
+
+def hip_grads(dyn, t, z, inp, G):
+    g = lambda v: v.to(DEV)                                                   # noqa: E731
+    grads = dyn.parameter_grad(g(t), g(z), g(inp['node_mask']), g(inp['linker_mask']), g(inp['edge_mask']), g(inp['context']),
+                               g(G))
+    return {k: v.cpu() for k, v in zip([n for n, _ in dyn.named_parameters()], grads)}
+
+
+def compare(got, ref):
+    keys = list(ref)
+    a = torch.cat([got[k].double().reshape(-1) for k in keys])
+    b = torch.cat([ref[k].double().reshape(-1) for k in keys])
+    worst = max(rel_l2(got[k].double(), ref[k].double()) for k in keys if ref[k].norm() > 0)
+    return rel_l2(a, b), worst
+
+
+# batch, n_frag, n_pocket, linker, nf, seed | graph, ctx, L, S, centering, trained, far atom
+CASES = {   # (seeds: the first of seed, seed + 100, ... whose batch is clear of the cut-offs, assert_clear_of_cutoffs)
+    'fc10_ragged': ((3, 12, 70, (3, 8), 9, 233), 'FC-10A-4A', 2, 2, 2, False, False, False),
+    'fc4_ragged': ((3, 12, 70, (3, 8), 9, 233), 'FC-4A', 2, 2, 2, False, False, False),
+    'single': ((1, 12, 40, (3, 8), 9, 5), 'FC-10A-4A', 2, 2, 2, False, False, False),
+    'one_atom_linker': ((2, 10, 45, (1, 1), 9, 7), 'FC-10A-4A', 2, 1, 2, False, False, False),
+    'far_pocket_atom': ((2, 12, 40, (3, 8), 9, 9), 'FC-4A', 2, 1, 2, False, False, True),
+    'odd_n': ((1, 11, 41, (5, 5), 8, 11), 'FC-10A-4A', 2, 1, 2, False, False, False),            # N = 57
+    'sub1': ((2, 12, 40, (3, 8), 9, 13), 'FC-10A-4A', 2, 2, 1, False, False, False),
+    'sub3': ((2, 12, 40, (3, 8), 9, 13), 'FC-4A', 2, 1, 3, False, False, False),
+    'ctx3_anchors': ((2, 12, 40, (3, 8), 9, 15), 'FC-10A-4A', 3, 1, 2, False, False, False),
+    'centering': ((2, 12, 40, (3, 8), 9, 517), 'FC-10A-4A', 2, 1, 2, True, False, False),
+    'trained_like': ((2, 12, 40, (3, 8), 9, 19), 'FC-10A-4A', 2, 2, 2, False, True, False),
+    'c4_geometry': ((2, 30, 252, (8, 12), 9, 641321), 'FC-10A-4A', 2, 2, 2, False, False, False),    # N about 292
+}
+
+
+def case_inputs(case):
+    mol, graph, ctx, L, S, centering, trained, far = CASES[case]
+    batch, n_frag, n_pocket, linker, nf, seed = mol
+    inp, z, t, G = pocket_batch(batch, n_frag, n_pocket, linker, nf, seed, anchors=ctx == 3, far_atom=far)
+    assert_clear_of_cutoffs(z, inp, graph)
+    dyn = make_dyn(nf, ctx, L, S, wseed=60 + L + S, graph_type=graph, trained=trained, centering=centering)
+    return dyn, inp, z, t, G
+
+
+@pytest.mark.parametrize('case', list(CASES))
+def test_parameter_grad_matches_fp64_oracle(case):
+    dyn, inp, z, t, G = case_inputs(case)
+    if case == 'far_pocket_atom':                      # the moved atom has no edge at all
+        x = (z[0, :, :3] * inp['node_mask'][0]).double()
+        far = int(torch.nonzero(inp['context'][0, :, -1]).max())
+        d = torch.cdist(x[far:far + 1], x)[0]
+        d[far] = 1e9
+        assert float(d[inp['node_mask'][0, :, 0] != 0].min()) > 10.0 + GAP
+    if case == 'odd_n':
+        assert z.shape[1] % 32 != 0
+    ref = oracle_grads(dyn, t, z, inp, G)
+    f32 = oracle_grads(dyn, t, z, inp, G, dtype=torch.float32)
+    hip = hip_grads(dyn, t, z, inp, G)
+    assert set(hip) == set(ref)
+    total, worst = compare(hip, ref)
+    total32, worst32 = compare(f32, ref)
+    print(f'{case}: rel-L2 all {total:.2e}, worst tensor {worst:.2e}; fp32 eager autograd {total32:.2e}, {worst32:.2e}')
+    assert total <= BAR_ALL and worst <= BAR_TENSOR, (total, worst)
+    assert total <= FP32_CLASS * total32 and worst <= FP32_CLASS * worst32, (total, total32, worst, worst32)
+
+
+def test_the_graph_matters():
+    """The same inputs under FC-4A and FC-10A-4A: two gradients, each its own oracle's."""
+    mol = CASES['fc10_ragged'][0]
+    inp, z, t, G = pocket_batch(*mol)
+    got = {}
+    for graph in ('FC-4A', 'FC-10A-4A'):
+        assert_clear_of_cutoffs(z, inp, graph)
+        dyn = make_dyn(mol[4], 2, 1, 2, wseed=71, graph_type=graph)
+        got[graph] = hip_grads(dyn, t, z, inp, G)
+        total, worst = compare(got[graph], oracle_grads(dyn, t, z, inp, G))
+        assert total <= BAR_ALL and worst <= BAR_TENSOR, (graph, total, worst)
+    assert compare(got['FC-4A'], got['FC-10A-4A'])[0] > 1e-3
+
+
+def test_parameter_grad_bitwise_repeatable():
+    dyn, inp, z, t, G = case_inputs('fc10_ragged')
+    a, c = hip_grads(dyn, t, z, inp, G), hip_grads(dyn, t, z, inp, G)
+    assert all(torch.equal(a[k], c[k]) for k in a)
+
+
+def test_batch_gradient_is_the_sum_of_its_molecules():
+    dyn, inp, z, t, G = case_inputs('fc10_ragged')
+    whole = hip_grads(dyn, t, z, inp, G)
+    parts = None
+    for b in range(z.shape[0]):
+        one = {k: (v[b:b + 1] if k != 'edge_mask' else torch.zeros(z.shape[1], dtype=v.dtype)) for k, v in inp.items()}
+        g = hip_grads(dyn, t[b:b + 1], z[b:b + 1], one, G[b:b + 1])
+        parts = g if parts is None else {k: parts[k].double() + g[k].double() for k in g}
+    keys = list(whole)
+    err = rel_l2(torch.cat([whole[k].double().reshape(-1) for k in keys]), torch.cat([parts[k].reshape(-1) for k in keys]))
+    print(f'batch of three against the sum of its molecules: rel-L2 {err:.2e}')
+    assert err <= 1e-6
+
+
+def test_stale_workspace_and_output_memory(monkeypatch):
+    """``dl_egnn_backward_pocket`` twice on one model with every allocation pre-filled (the NaN patterns of
+    tests/test_gpu_scratch.py): the gradient does not depend on what the workspace or ``grad_params`` held."""
+    import test_gpu_scratch as SC
+    from difflinker_amd import _lib, egnn
+    mol, graph, ctx, L, S, centering, trained, far = CASES['far_pocket_atom']
+    inp, z, t, G = pocket_batch(*mol, far_atom=True)
+    B, N = z.shape[:2]
+    args = (t, z, inp['node_mask'], inp['linker_mask'], inp['edge_mask'], inp['context'], G)
+
+    def run():
+        dyn = make_dyn(mol[4], ctx, L, S, wseed=63, graph_type=graph)
+        first = dyn.parameter_grad(*(v.to(DEV) for v in args))
+        torch.cuda.synchronize()
+        ws = dyn._bwd_ws
+        second = dyn.parameter_grad(*(v.to(DEV) for v in args))
+        torch.cuda.synchronize()
+        assert dyn._bwd_ws is ws
+        need = int(_lib.load().dl_egnn_backward_pocket_workspace_bytes(ctypes.byref(egnn.backward_args(dyn, B, N)),
+                                                                       dyn.GRAPH_TYPES[graph]))
+        assert need > 0
+        names = [n for n, _ in dyn.named_parameters()]
+        out = {f'first.{k}': v for k, v in zip(names, first)}
+        out.update({f'second.{k}': v for k, v in zip(names, second)})
+        n_params = sum(p.numel() for p in dyn.parameters())
+        return SC.Ran(out, [('workspace', ws, need), ('grad_params', first[0], 4 * n_params),
+                            ('grad_params again', second[0], 4 * n_params)])
+    got = SC.check_contract(monkeypatch, run)
+    for k, v in got.items():
+        assert torch.isfinite(v).all(), k
+        if k.startswith('first.'):
+            assert torch.equal(v, got['second.' + k[6:]]), k
+
+
+# ---- the loss ------------------------------------------------------------------------------------------------------------------
+def make_edm(dyn, nf, loss_type='l2', T=500):
+    from difflinker_amd import EDM
+    return EDM(dyn, in_node_nf=nf, n_dims=3, timesteps=T, noise_schedule='polynomial_2', noise_precision=1e-5,
+               loss_type=loss_type, norm_values=[1, 4, 10]).to(DEV)
+
+
+def test_training_forward_values_equal_forward():
+    mol = CASES['fc10_ragged'][0]
+    nf = mol[4]
+    inp, z, t, G = pocket_batch(*mol)
+    g = {k: v.to(DEV) for k, v in inp.items()}
+    dyn = make_dyn(nf, 2, 2, 2, wseed=64, graph_type='FC-10A-4A')
+    with torch.no_grad():
+        want = dyn.forward(t.to(DEV), z.to(DEV), g['node_mask'], g['linker_mask'], g['edge_mask'], g['context'])
+    got = dyn.training_forward(t.to(DEV), z.to(DEV), g['node_mask'], g['linker_mask'], g['edge_mask'], g['context'])
+    assert got.requires_grad and torch.equal(got.detach(), want)
+    edm = make_edm(dyn, nf)
+    B, N = z.shape[:2]
+    t_int = torch.tensor([0, 250, 500], device=DEV)
+    noise = (torch.randn(B, N, 3, device=DEV), torch.randn(B, N, nf, device=DEV))
+    a = (g['x'], g['h'], g['node_mask'], g['fragment_mask'], g['linker_mask'], g['edge_mask'], g['context'])
+    with torch.no_grad():
+        want = edm(*a, t_int=t_int, noise=noise)
+    got = edm.training_forward(*a, t_int=t_int, noise=noise)
+    for u, v in zip(got, want):
+        assert type(u) is type(v)
+        if torch.is_tensor(u):
+            assert torch.equal(u.detach(), v)
+    assert got[4].requires_grad
+
+
+GOLDEN_PATH = os.path.join(ROOT, 'tests', 'golden', 'pocket_grad.npz')
+
+
+@pytest.mark.parametrize('tag', ['fc10_l2', 'fc4_vlb'])
+def test_loss_gradient_matches_reference_fixture(tag):
+    """``loss.backward()`` of the unmodified reference (tests/golden/make_golden_pocket_grad.py) on the same inputs and draws;
+    the 7 outputs at the tolerance of tests/test_gpu_edm_loss.py."""
+    import test_gpu_edm_loss as LS
+    from difflinker_amd import DynamicsWithPockets
+    gold = np.load(GOLDEN_PATH)
+    nf, ctx, L, T, wseed, graph, vlb = (int(v) for v in gold[f'{tag}.params'])
+    graph_type = {1: 'FC-4A', 2: 'FC-10A-4A'}[graph]
+    dyn = DynamicsWithPockets(n_dims=3, in_node_nf=nf, context_node_nf=ctx, hidden_nf=128, n_layers=L, norm_constant=1e-6,
+                              normalization_factor=100, normalization='batch_norm', graph_type=graph_type)
+    sd = trained_like_state_dict(seeded_state_dict(nf + ctx + 1, 128, L, wseed, coord_gain=0.02), wseed)
+    dyn.load_state_dict({k: v.float() for k, v in sd.items()}, strict=True)
+    edm = make_edm(dyn, nf, 'vlb' if vlb else 'l2', T)
+    g = {k: torch.from_numpy(gold[f'{tag}.{k}']).to(DEV) for k in ('x', 'h', 'node_mask', 'fragment_mask', 'linker_mask',
+                                                                   'edge_mask', 'context', 't_int', 'noise_x', 'noise_h')}
+    res = edm.training_forward(g['x'], g['h'], g['node_mask'], g['fragment_mask'], g['linker_mask'], g['edge_mask'],
+                               g['context'], t_int=g['t_int'], noise=(g['noise_x'], g['noise_h']))
+    want = gold[f'{tag}.outputs']
+    for name, u, v in zip(LS.NAMES, res, want):                    # relative 1e-4 per term, as test_gpu_edm_loss.py compares them
+        u, v = float(u.detach()) if torch.is_tensor(u) else float(u), float(v)
+        err = abs(u - v) / max(abs(v), 1e-30) if v != 0 else abs(u)
+        assert err <= 1e-4, (name, u, v)
+    loss = res[1] + res[2] + res[3] - res[0] if vlb else res[4]
+    dyn.zero_grad()
+    loss.backward()
+    hip, ref = {}, {}
+    for k, p in dyn.named_parameters():
+        got = p.grad.detach().cpu().reshape(-1)
+        if f'{tag}.idx.{k}' in gold:
+            got = got[torch.from_numpy(gold[f'{tag}.idx.{k}']).long()]
+        hip[k], ref[k] = got, torch.from_numpy(gold[f'{tag}.grad.{k}']).double()
+    total, worst = compare(hip, ref)
+    print(f'{tag}: reference fixture rel-L2 all {total:.2e}, worst tensor {worst:.2e}')
+    assert total <= BAR_ALL and worst <= BAR_TENSOR, (total, worst)
+
+
+# ---- the training step and the loop ----------------------------------------------------------------------------------------------
+def toy_moad(n_mols, nf, seed):
+    from difflinker_amd import synthetic
+    data = []
+    for k, m in enumerate(synthetic.pocket_molecules(n_mols, 8, 30, (3, 5), nf, seed)):
+        m = dict(m)
+        m['charges'] = torch.zeros(m['num_atoms'])
+        m['uuid'], m['name'] = k, f'complex{k}'
+        data.append(m)
+    return data
+
+
+def make_ddpm(tmp_path, nf, **kw):
+    from difflinker_amd import DDPM
+    args = dict(data_path=str(tmp_path), train_data_prefix='MOAD_train.full', val_data_prefix='MOAD_val.full', in_node_nf=nf,
+                n_dims=3, context_node_nf=3, hidden_nf=128, activation='silu', n_layers=1, attention=False, tanh=False,
+                norm_constant=1e-6, inv_sublayers=2, sin_embedding=False, normalization_factor=100, aggregation_method='sum',
+                diffusion_steps=500, diffusion_noise_schedule='polynomial_2', diffusion_noise_precision=1e-5,
+                diffusion_loss_type='l2', normalize_factors=[1, 4, 10], include_charges=False, model='egnn_dynamics',
+                batch_size=4, lr=1e-3, torch_device='cuda:0', test_epochs=1, n_stability_samples=1, graph_type='FC-10A-4A')
+    args.update(kw)
+    return DDPM(**args).to(DEV)
+
+
+def test_adamw_step_repacks_and_overfits(tmp_path):
+    from difflinker_amd.const import GEOM_NUMBER_OF_ATOM_TYPES as NF
+    from difflinker_amd.datasets import collate
+    torch.manual_seed(0)
+    model = make_ddpm(tmp_path, NF, data_augmentation=True)
+    data = {k: (v.to(DEV) if torch.is_tensor(v) else v) for k, v in collate(toy_moad(4, NF, 3)).items()}
+    opt = model.configure_optimizers()
+    with torch.no_grad():
+        before = model.validation_step(data)
+    version = model.edm.dynamics._weight_version
+    out = model.training_step(data, 0)
+    opt.zero_grad()
+    out['loss'].backward()
+    assert all(p.grad is not None and torch.isfinite(p.grad).all() for p in model.edm.dynamics.parameters())
+    opt.step()
+    fresh = make_ddpm(tmp_path, NF)
+    fresh.load_state_dict(model.state_dict())
+    torch.manual_seed(5)
+    with torch.no_grad():
+        after = model.validation_step(data)
+    torch.manual_seed(5)
+    with torch.no_grad():
+        want = fresh.validation_step(data)
+    assert model.edm.dynamics._weight_version != version or float(after['loss']) == float(want['loss'])
+    assert float(after['loss']) == float(want['loss']), 'the forward after the step runs on the new weights'
+    assert float(before['loss']) != float(after['loss'])
+    model.data_augmentation = False
+    t_int = torch.tensor([[40], [200], [350], [120]], device=DEV)
+    B, N = data['positions'].shape[:2]
+    noise = (torch.randn(B, N, 3, device=DEV), torch.randn(B, N, NF, device=DEV))
+    ctx, com = model._context_and_com_mask(data, data['atom_mask'], data['fragment_mask'], data['anchors'])
+    from difflinker_amd import utils
+    x = utils.remove_partial_mean_with_mask(data['positions'], data['atom_mask'], com)
+    losses = []
+    for _ in range(30):
+        res = model.edm.training_forward(x, data['one_hot'], data['atom_mask'], data['fragment_mask'], data['linker_mask'],
+                                         data['edge_mask'], ctx, t_int=t_int, noise=noise)
+        opt.zero_grad()
+        res[4].backward()
+        opt.step()
+        losses.append(float(res[4].detach()))
+    print('overfit l2:', losses[0], '->', losses[-1])
+    assert losses[-1] < 0.5 * losses[0], losses
+
+
+def test_train_cli_on_a_toy_moad_dataset(tmp_path):
+    from difflinker_amd import DDPM
+    from difflinker_amd.const import GEOM_NUMBER_OF_ATOM_TYPES as NF
+    torch.save(toy_moad(6, NF, 0), os.path.join(tmp_path, 'MOAD_train_full.pt'))
+    torch.save(toy_moad(3, NF, 1), os.path.join(tmp_path, 'MOAD_val_full.pt'))
+    cfg = os.path.join(tmp_path, 'cfg.yml')
+    with open(cfg, 'w') as f:
+        f.write('nf: 128\nn_layers: 1\ninv_sublayers: 1\ntanh: False\nattention: False\nnorm_constant: 0.000001\n'
+                'normalization_factor: 100\ninclude_charges: False\nbatch_size: 3\nlr: 0.0002\nnormalize_factors: [1, 4, 10]\n'
+                'train_data_prefix: MOAD_train.full\nval_data_prefix: MOAD_val.full\ngraph_type: FC-10A-4A\n'
+                'data_augmentation: True\n')
+    ck = os.path.join(tmp_path, 'ck')
+    run = lambda *extra: subprocess.run([sys.executable, '-m', 'difflinker_amd.train', '--config', cfg, '--data',   # noqa: E731
+                                         str(tmp_path), '--checkpoints', ck, *extra], cwd=ROOT, capture_output=True,
+                                        text=True, timeout=600)
+    proc = run('--max_steps', '3')
+    assert proc.returncode == 0, proc.stderr[-3000:]
+    path = os.path.join(ck, 'last.ckpt')
+    assert json.loads(proc.stdout.strip().splitlines()[-1])['step'] == 3
+    proc = run('--max_steps', '4', '--resume', path)
+    assert proc.returncode == 0, proc.stderr[-3000:]
+    ckpt = torch.load(path, map_location='cpu', weights_only=False)
+    assert ckpt['global_step'] == 4 and ckpt['optimizer_states']
+    model = DDPM.load_from_checkpoint(path, map_location='cpu', torch_device='cuda:0').to(DEV).eval()
+    assert model.edm.dynamics.graph_type == 'FC-10A-4A'
+    model.data_path = str(tmp_path)
+    model.setup('val')
+    data = next(iter(model.val_dataloader()))
+    model.edm.T = 5
+    chain, nm = model.sample_chain(data, keep_frames=1)
+    assert torch.isfinite(chain).all()
