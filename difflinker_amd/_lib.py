@@ -154,6 +154,21 @@ class DLRmsdArgs(ctypes.Structure):
     ]
 
 
+DL_CLASH_NONFINITE, DL_CLASH_TOO_LARGE, DL_CLASH_BAD_TYPE = 1, 2, 4      # dl_clash_args.status bits
+
+
+class DLClashArgs(ctypes.Structure):
+    _fields_ = [
+        ('B', ctypes.c_int32), ('N', ctypes.c_int32), ('nf', ctypes.c_int32),
+        ('x', ctypes.c_void_p), ('one_hot', ctypes.c_void_p), ('query_mask', ctypes.c_void_p),
+        ('target_mask', ctypes.c_void_p), ('M', ctypes.c_int32), ('target_x', ctypes.c_void_p),
+        ('target_type', ctypes.c_void_p), ('threshold', ctypes.c_void_p), ('contact_cutoff', ctypes.c_float),
+        ('n_query', ctypes.c_void_p), ('n_target', ctypes.c_void_p), ('n_clashes', ctypes.c_void_p),
+        ('n_clash_atoms', ctypes.c_void_p), ('n_contacts', ctypes.c_void_p), ('min_dist2', ctypes.c_void_p),
+        ('status', ctypes.c_void_p), ('atom_clashes', ctypes.c_void_p), ('atom_min_dist2', ctypes.c_void_p),
+    ]
+
+
 EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_string', 'dl_model_num_tensors',
            'dl_model_create', 'dl_model_destroy', 'dl_egnn_forward_fc', 'dl_sampler_step', 'dl_sample_chain_fc',
            'dl_set_profile_buffer', 'dl_profile_max_events', 'dl_pocket_workspace_bytes', 'dl_egnn_forward_pocket',
@@ -165,7 +180,7 @@ EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_stri
            'dl_egnn_backward_pocket_workspace_bytes', 'dl_egnn_backward_pocket',
            'dl_size_train_num_params', 'dl_size_train_workspace_bytes', 'dl_size_train_forward', 'dl_size_train_backward',
            'dl_join_workspace_bytes', 'dl_sample_chain_fc_join', 'dl_bonds_workspace_bytes', 'dl_perceive_bonds',
-           'dl_molecule_keys', 'dl_best_rmsd')
+           'dl_molecule_keys', 'dl_clash_scores', 'dl_best_rmsd')
 TEST_HOOK_EXPORTS = ('dl_debug_team_fault',)       # declared under #ifdef DL_TEST_HOOKS: the test-hooks build only
 
 _lib = None
@@ -285,6 +300,8 @@ def _open(path):
     lib.dl_perceive_bonds.argtypes = [ctypes.POINTER(DLBondsArgs), vp]
     lib.dl_molecule_keys.restype = i32
     lib.dl_molecule_keys.argtypes = [ctypes.POINTER(DLMolKeysArgs), vp]
+    lib.dl_clash_scores.restype = i32
+    lib.dl_clash_scores.argtypes = [ctypes.POINTER(DLClashArgs), vp]
     lib.dl_best_rmsd.restype = i32
     lib.dl_best_rmsd.argtypes = [ctypes.POINTER(DLRmsdArgs), vp]
     lib.dl_size_model_num_tensors.restype = i32

@@ -103,3 +103,21 @@ def max_valence_table(is_geom):
     idx2atom = GEOM_IDX2ATOM if is_geom else IDX2ATOM
     limits = [ALLOWED_BONDS[idx2atom[k]] for k in range(len(idx2atom))]
     return torch.tensor([max(v) if isinstance(v, (list, tuple)) else v for v in limits], dtype=torch.int32)
+
+
+# Bondi's van der Waals radii in Angstrom (J. Phys. Chem. 68, 441 (1964)) by GEOM atom index (C O N F S Cl Br I P; the ZINC
+# vocabulary is the leading 8): what the clash rule of ``metrics.analyze_clashes`` is built from
+VDW_RADII = (1.70, 1.52, 1.55, 1.47, 1.80, 1.75, 1.85, 1.98, 1.80)
+
+
+def clash_threshold_table(is_geom, scale=0.75, tolerance=0.0):
+    """``[n_types][n_types]`` fp32 distances in Angstrom: a query atom of type ``a`` and a target atom of type ``b`` clash
+    when they are closer than ``table[a][b] = scale * (r[a] + r[b]) - tolerance`` (``VDW_RADII``; computed in fp64, rounded to
+    fp32 once) and that entry is positive.  Hydrogens are implicit in these data sets, so the plain sum (``scale = 1``) flags
+    ordinary contacts between heavy atoms; the default 0.75 is the usual heavy-atom convention."""
+    n = GEOM_NUMBER_OF_ATOM_TYPES if is_geom else NUMBER_OF_ATOM_TYPES
+    table = torch.zeros((n, n), dtype=torch.float64)
+    for a in range(n):
+        for b in range(n):
+            table[a, b] = float(scale) * (VDW_RADII[a] + VDW_RADII[b]) - float(tolerance)
+    return table.to(TORCH_FLOAT)

@@ -19,7 +19,7 @@ import torch
 from . import const
 from . import metrics as mol_metrics
 from .datasets import MOADDataset, collate_with_fragment_edges, collate_with_fragment_without_pocket_edges
-from .io import get_pocket, parse_molecule, pocket_arrays, read_molecule, read_pocket, save_sdf_file, save_xyz_file
+from .io import get_pocket, get_protein_atoms, parse_molecule, pocket_arrays, read_molecule, read_pocket, save_sdf_file, save_xyz_file
 from .lightning import DDPM
 from .linker_size import SizeClassifier
 from .molecule_builder import perceive_all_bonds, summary
@@ -79,10 +79,10 @@ OUTPUT_FORMATS = ('xyz', 'sdf', 'both')
 
 
 def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_dir, name, com_key, hide_pocket,
-                     output_format='xyz', metrics=False):
+                     output_format='xyz', metrics=False, clashes=False, protein=None):
     if output_format not in OUTPUT_FORMATS:
         raise ValueError(f'output_format must be one of {OUTPUT_FORMATS}, got {output_format!r}')
-    written, found, scored = [], [], []
+    written, found, scored, clash_records = [], [], [], []
     for batch_i, data in enumerate(_batches(dataset, batch_size, collate_fn)):
         n = len(data['positions'])
         chain = None
@@ -104,6 +104,15 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
         x = x + mean * node_mask
         offset = batch_i * batch_size
         names = [f'output_{offset + i}_{name}' for i in range(n)]
+        if clashes:                                           # in the input frame, where the protein's atoms are: the template's
+            pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, x.shape[1] - m.shape[1]))     # noqa: E731
+            generated = node_mask * (1 - pad(data['fragment_mask']))                        # linker rows against the pocket rows,
+            pocket_rows = pad(data['pocket_mask']) if protein is None else None            # or against the whole protein
+            scored_x = x
+            if pocket_rows is not None:                       # the pocket atoms where the file has them, not where the trip
+                scored_x = torch.where(pocket_rows.bool(), pad(data['positions']), x)      # through the COM frame left them
+            clash_records += mol_metrics.clashes_to_host(mol_metrics.analyze_clashes(
+                h[:, :, :ddpm.num_classes], scored_x, generated, pocket_rows, protein=protein, is_geom=ddpm.is_geom))
         if hide_pocket:                                       # generate_with_pocket.py:272
             node_mask = node_mask.clone()
             width = data['pocket_mask'].shape[1]
@@ -121,18 +130,32 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
             scored += mol_metrics.to_host(mol_metrics.analyze(types, x, node_mask, ddpm.is_geom), types, node_mask)
     if found:
         print(json.dumps(summary(found)))
-    if metrics:                                               # no true molecule here: no novelty, no recovery
+    if metrics or clashes:
+        scores = {}
+        if metrics:                                           # no true molecule here: no novelty, no recovery
+            scores = dict(mol_metrics.compute_metrics(scored), molecules=len(scored))
+        if clashes:
+            scores.update(mol_metrics.compute_clashes(clash_records))
         with open(os.path.join(output_dir, 'metrics.json'), 'w') as f:
-            json.dump(dict(mol_metrics.compute_metrics(scored), molecules=len(scored)), f, indent=1)
+            json.dump(scores, f, indent=1)
+    if clashes:                                               # one record per written file, by its name
+        by_name = {f'output_{i}_{name}': m for i, m in enumerate(clash_records)}
+        finite = lambda d: d if np.isfinite(d) else None      # noqa: E731  (no pair, or a flagged molecule: JSON has no inf / NaN)
+        with open(os.path.join(output_dir, 'clashes.json'), 'w') as f:
+            json.dump({os.path.basename(path): {'n_clashes': m.n_clashes, 'n_clash_atoms': m.n_clash_atoms,
+                                                'min_distance': finite(m.min_distance)}
+                       for path in written for m in [by_name[os.path.basename(path).rsplit('_.', 1)[0]]]}, f, indent=1)
     return written
 
 
 def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anchors=None, device=None, output_format='xyz',
-             metrics=False):
+             metrics=False, clashes=False):
     """``generate.py`` main(): fragments file -> ``n_samples`` molecules with a sampled linker, as ``.xyz`` files
     (``output_format='sdf'``: ``.sdf`` files with perceived bonds instead, ``'both'``: both; one JSON line with the number of
     molecules, the share in one piece and the mean bond count is printed then).  ``metrics=True`` also writes
     ``metrics.json`` to ``output_dir``: valence rule, connectivity and uniqueness of the samples (``metrics.compute_metrics``)."""
+    if clashes:
+        raise ValueError('clashes are scored against a protein: pass a pocket or a protein file (--pocket / --protein)')
     device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
     os.makedirs(output_dir, exist_ok=True)
     sample_fn = make_sample_fn(linker_size, device)
@@ -156,7 +179,7 @@ def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anc
 
 
 def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size, device,
-                            output_format, metrics=False):
+                            output_format, metrics=False, clashes=False, protein=None):
     frag_pos, frag_one_hot, frag_charges = frag
     pocket_pos, pocket_one_hot, pocket_charges = pocket
     positions = np.concatenate([frag_pos, pocket_pos], axis=0)
@@ -176,13 +199,15 @@ def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_s
     ddpm.val_dataset = dataset                            # centre-of-mass mask on the dataset type (lightning.py:443)
     return _sample_and_save(ddpm, dataset, collate_with_fragment_without_pocket_edges, sample_fn,
                             min(n_samples, max_batch_size), output_dir, name, com_key='fragment_only_mask',
-                            hide_pocket=True, output_format=output_format, metrics=metrics)
+                            hide_pocket=True, output_format=output_format, metrics=metrics, clashes=clashes, protein=protein)
 
 
 def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, output_dir, n_samples, n_steps, linker_size,
                          anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz',
-                         metrics=False):
-    """``generate_with_pocket.py`` main(): the pocket is given as its own PDB file."""
+                         metrics=False, clashes=False):
+    """``generate_with_pocket.py`` main(): the pocket is given as its own PDB file.  ``clashes=True`` scores every sample's
+    generated atoms against the pocket atoms (``metrics.analyze_clashes``), adds the ``metrics.compute_clashes`` keys to
+    ``metrics.json`` and writes ``clashes.json``: ``n_clashes``, ``n_clash_atoms`` and ``min_distance`` per written file."""
     device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
     os.makedirs(output_dir, exist_ok=True)
     if random_seed is not None:
@@ -201,13 +226,16 @@ def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, ou
     frag = parse_molecule(molecule, is_geom=ddpm.is_geom)
     pocket = pocket_arrays(read_pocket(pocket_path), backbone_atoms_only)
     return _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size,
-                                   device, output_format, metrics)
+                                   device, output_format, metrics, clashes)
 
 
 def generate_with_protein(input_path, protein_path, backbone_atoms_only, model, output_dir, n_samples, n_steps,
                           linker_size, anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz',
-                          metrics=False):
-    """``generate_with_protein.py`` main(): the pocket = residues of the protein within 6 A of the fragments."""
+                          metrics=False, clashes=False):
+    """``generate_with_protein.py`` main(): the pocket = residues of the protein within 6 A of the fragments.
+    ``clashes=True`` as in ``generate_with_pocket``, but against ALL protein atoms whose element is in the vocabulary
+    (``io.get_protein_atoms``), residues outside the pocket the model saw included; the pocket rows of the batch are then not
+    targets, so no atom counts twice."""
     device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
     os.makedirs(output_dir, exist_ok=True)
     if random_seed is not None:
@@ -221,8 +249,13 @@ def generate_with_protein(input_path, protein_path, backbone_atoms_only, model, 
     name = '.'.join(input_path.split('/')[-1].split('.')[:-1])
     frag = parse_molecule(molecule, is_geom=ddpm.is_geom)
     pocket = get_pocket(molecule, protein_path, backbone_atoms_only)
+    protein = None
+    if clashes:
+        positions, types = get_protein_atoms(protein_path, ddpm.is_geom)
+        protein = (torch.tensor(positions, dtype=const.TORCH_FLOAT, device=device),
+                   torch.tensor(types, dtype=torch.int32, device=device))
     return _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size,
-                                   device, output_format, metrics)
+                                   device, output_format, metrics, clashes, protein)
 
 
 def main(argv=None):
@@ -246,15 +279,22 @@ def main(argv=None):
     p.add_argument('--metrics', action='store_true',
                    help='score the generated molecules on the GPU (valence rule, connectivity, uniqueness) and write '
                         'metrics.json to the output directory')
+    p.add_argument('--clashes', action='store_true',
+                   help='with --pocket / --protein: count the steric clashes of the generated atoms with the pocket atoms / '
+                        'with all protein atoms on the GPU (0.75 x the sum of the van der Waals radii), add the scores to '
+                        'metrics.json and write clashes.json with one record per written file')
     a = p.parse_args(argv)
+    if a.clashes and a.pocket is None and a.protein is None:
+        raise ValueError('--clashes scores the generated atoms against a protein: pass --pocket or --protein')
+    extra = {'clashes': True} if a.clashes else {}
     if a.pocket is not None:
         files = generate_with_pocket(a.fragments, a.pocket, a.backbone_atoms_only, a.model, a.output, a.n_samples,
                                      a.n_steps, a.linker_size, a.anchors, a.max_batch_size, a.random_seed,
-                                     output_format=a.output_format, metrics=a.metrics)
+                                     output_format=a.output_format, metrics=a.metrics, **extra)
     elif a.protein is not None:
         files = generate_with_protein(a.fragments, a.protein, a.backbone_atoms_only, a.model, a.output, a.n_samples,
                                       a.n_steps, a.linker_size, a.anchors, a.max_batch_size, a.random_seed,
-                                      output_format=a.output_format, metrics=a.metrics)
+                                      output_format=a.output_format, metrics=a.metrics, **extra)
     else:
         files = generate(a.fragments, a.model, a.output, a.n_samples, a.n_steps, a.linker_size, a.anchors,
                          output_format=a.output_format, metrics=a.metrics)

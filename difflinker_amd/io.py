@@ -261,6 +261,21 @@ def get_pocket(mol, pdb_path, backbone_atoms_only=False):
     return np.array(pos), np.array(one_hot), np.array(charges)
 
 
+def get_protein_atoms(pdb_path, is_geom=True):
+    """``(positions [M,3], types [M] int32)`` of ALL atoms of a PDB file whose element is in the vocabulary, in the file's own
+    frame and in ``_walk_pdb`` order: the shared target list of ``metrics.analyze_clashes``.  Unlike ``get_pocket`` nothing
+    is cut to the 6 A neighbourhood - a generated linker can run into residues the model never saw - and other elements
+    (hydrogens, metals) are left out as ``get_pocket`` leaves them out."""
+    atom2idx = const.GEOM_ATOM2IDX if is_geom else const.ATOM2IDX
+    pos, types = [], []
+    for a in _walk_pdb(pdb_path):
+        key = a.element if a.element in atom2idx else _symbol(a.element)
+        if key in atom2idx:
+            pos.append(a.coord)
+            types.append(atom2idx[key])
+    return np.array(pos, dtype=np.float64).reshape(-1, 3), np.array(types, dtype=np.int32)
+
+
 def pocket_arrays(pocket_data, backbone_atoms_only):
     """One-hot / charges of a ``read_pocket`` dictionary (generate_with_pocket.py:200-209); unknown elements raise like
     the reference's dictionary lookup does."""

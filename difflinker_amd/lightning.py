@@ -100,6 +100,7 @@ class DDPM(_Base):
         self.linker_size_sampler = DistributionNodes(LINKER_SIZE_DIST)          # lightning.py:113
         self.metrics = {}                                                       # lightning.py:43: name -> value per epoch
         self.geometry_metrics = False           # sample_and_analyze adds metrics.compute_geometry's RMSD keys (train --geometry)
+        self.clash_metrics = False              # pocket models: it adds metrics.compute_clashes' keys as well (train --clashes)
         if _Base is nn.Module:
             self.current_epoch = 0              # Lightning's Trainer keeps this; here the training loop sets it
 
@@ -312,9 +313,13 @@ class DDPM(_Base):
         ``metrics.analyze`` and the result is ``metrics.compute_metrics`` over all of them (which drops the predictions whose
         true molecule is not valid and connected).  With ``self.geometry_metrics`` the symmetry-aware RMSD of the recovered
         samples (``metrics.compute_geometry``) is added: ``rmsd`` (``None`` when nothing recovered), ``rmsd_molecules``,
-        ``rmsd_truncated``.  No animation, no WandB."""
+        ``rmsd_truncated``.  With ``self.clash_metrics`` a pocket model also gets the ``metrics.compute_clashes`` keys: the
+        samples' linker atoms against the pocket atoms, and the data set's own linkers in the same pockets as ``true``.
+        No animation, no WandB."""
         pred, true, input_index = [], [], []
         pred_x, true_x, n_linker = [], [], []
+        clashes = self.clash_metrics and self.pockets
+        pred_clashes, true_clashes = [], []
         first = 0
         for b, data in enumerate(dataloader):
             drop = data['pocket_mask'] if self.pockets else None                   # lightning.py:331-334
@@ -322,6 +327,9 @@ class DDPM(_Base):
             true_batch = mol_metrics.to_host(
                 mol_metrics.analyze(data['one_hot'], data['positions'], data['atom_mask'], self.is_geom, drop_mask=drop),
                 data['one_hot'], data['atom_mask'], drop)
+            if clashes:
+                true_clash_batch = mol_metrics.clashes_to_host(mol_metrics.analyze_clashes(
+                    data['one_hot'][:, :, :self.num_classes], data['positions'], data['linker_mask'], drop, is_geom=self.is_geom))
             if self.geometry_metrics:
                 true_x_batch = list(mol_metrics.kept_positions(data['positions'], data['atom_mask'], drop)[0])
                 n_linker_batch = data['linker_mask'].reshape(n, -1).sum(1).long().tolist()
@@ -345,6 +353,11 @@ class DDPM(_Base):
                                             one_hot, node_mask, out_drop)
                 true += true_batch
                 input_index += range(first, first + n)
+                if clashes:                                                        # the template's linker rows
+                    frag = torch.nn.functional.pad(data['fragment_mask'], (0, 0, 0, node_mask.shape[1] - data['fragment_mask'].shape[1]))
+                    pred_clashes += mol_metrics.clashes_to_host(mol_metrics.analyze_clashes(
+                        one_hot, x, node_mask * (1 - frag), out_drop, is_geom=self.is_geom))
+                    true_clashes += true_clash_batch
                 if self.geometry_metrics:
                     pred_x += list(mol_metrics.kept_positions(x, node_mask, out_drop)[0])
                     true_x += true_x_batch
@@ -353,6 +366,8 @@ class DDPM(_Base):
         scores = mol_metrics.compute_metrics(pred, true, input_index)
         if self.geometry_metrics:
             scores.update(mol_metrics.compute_geometry(pred, true, pred_x, true_x, n_linker))
+        if clashes:
+            scores.update(mol_metrics.compute_clashes(pred_clashes, true_clashes))
         return scores
 
     # ---- sampling -------------------------------------------------------------------------------------

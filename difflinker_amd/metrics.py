@@ -14,6 +14,10 @@ orders 1, 2, 3.
 ``compute_geometry`` adds the reference's 3D score (compute_metrics.py:366-402): the RMSD of every recovered sample against
 its true molecule, the smallest over all isomorphisms of the two graphs (``isomorphisms`` on the host, the alignments of a
 whole list in one launch of ``dl_best_rmsd``, ``csrc/rmsd.hip``), times ``sqrt(n_atoms / n_linker)``.
+
+``analyze_clashes`` / ``compute_clashes`` answer what none of the above can, because they all drop the pocket first: does the
+generated linker fit, or does it sit inside the protein?  Generated atoms against protein atoms under a van der Waals rule
+(``dl_clash_scores``, ``csrc/clash.hip``); the reference has no code for it, the rule is stated in ``analyze_clashes``.
 """
 import ctypes
 import math
@@ -442,3 +446,131 @@ def compute_geometry(pred, true, pred_x, true_x, n_linker, max_matches=65536):
     scaled = [rmsd[p] * math.sqrt(counts[p] / int(n_linker[k])) for p, k in enumerate(rows) if status[p] == 0]
     cut = sum(1 for p in range(len(rows)) if status[p] == 0 and truncated[p])
     return {'rmsd': sum(scaled) / len(scaled) if scaled else None, 'rmsd_molecules': len(scaled), 'rmsd_truncated': cut}
+
+
+Clashes = namedtuple('Clashes', 'n_query n_target n_clashes n_clash_atoms n_contacts min_dist2 status atom_clashes '
+                                'atom_min_dist2 query_mask')
+ClashRecord = namedtuple('ClashRecord', 'n_query n_target n_clashes n_clash_atoms n_contacts min_distance status atom_clashes '
+                                        'atom_min_distance')
+CLASH_NAMES = ('clash_molecules', 'clash_flagged', 'clash_free', 'clashes_per_molecule', 'clash_atoms_share',
+               'contacts_per_molecule', 'min_distance')
+CLASH_TRUE_NAMES = ('true_clashes_per_molecule', 'true_clash_free', 'clash_excess')
+
+
+def analyze_clashes(one_hot, x, query_mask, target_mask=None, protein=None, is_geom=True, scale=0.75, tolerance=0.0,
+                    contact_cutoff=4.0, thresholds=None):
+    """Steric clashes of generated atoms with the protein, for every molecule of a batch in one launch of
+    ``dl_clash_scores`` on the HIP device.
+
+    THE RULE (this project's own: the reference reports clash counts in its paper and has no code for them).  Atoms are heavy
+    atoms, hydrogens are implicit.  A pair is one QUERY atom - a row of ``query_mask [B,N]`` or ``[B,N,1]``, the generated
+    atoms - and one TARGET atom - a row of ``target_mask`` (the batch's ``pocket_mask``) that is not a query row, or an atom
+    of ``protein = (positions [M,3], types [M])``, a list shared by all molecules and given in the frame of ``x``.  An atom's
+    type is the first largest entry of its ``one_hot [B,N,nf]`` row.  With ``t = threshold[query type][target type]``
+    (``const.clash_threshold_table(is_geom, scale, tolerance)``: ``scale * (r_vdw[a] + r_vdw[b]) - tolerance`` over Bondi's
+    radii, fp32, or the caller's ``thresholds [nf,nf]``) a pair CLASHES when ``d2 < t * t`` and ``t > 0``, and is a CONTACT
+    when ``d2 < contact_cutoff * contact_cutoff``; ``d2 = ((dx*dx) + (dy*dy)) + (dz*dz)`` in fp32 without fused
+    multiply-adds, the comparisons strict.  ``scale = 1`` is the plain sum of the radii; with implicit hydrogens that flags
+    ordinary contacts, hence the default 0.75.
+
+    Returns a ``Clashes`` of device tensors: ``n_query``, ``n_target``, ``n_clashes`` (pairs), ``n_clash_atoms`` (query atoms
+    with a clash), ``n_contacts`` (int32 ``[B]``), ``min_dist2`` (fp32 ``[B]``: the smallest SQUARED distance, ``+inf``
+    without a pair), ``status`` (int32 ``[B]``: ``_lib.DL_CLASH_*`` bits; with ``NONFINITE`` or ``TOO_LARGE`` the counts are
+    0 and the minima NaN), ``atom_clashes`` (int32 ``[B,N]``, 0 on non-query rows), ``atom_min_dist2`` (fp32 ``[B,N]``,
+    ``+inf`` on non-query rows and without targets) and the ``query_mask`` it was given.  No host synchronisation.
+
+    What this is NOT: no hydrogens, no clashes inside the ligand, no energy or docking score."""
+    shared = () if protein is None else tuple(protein)
+    tensors = (one_hot, x, query_mask) + (() if target_mask is None else (target_mask,)) + shared + \
+        (() if thresholds is None else (thresholds,))
+    if not all(t.is_cuda for t in tensors):
+        raise _lib.HipLibraryError('analyze_clashes runs on the HIP device only (no CPU fallback): '
+                                   f'got tensors on {", ".join(str(t.device) for t in tensors)}')
+    B, N, nf = one_hot.shape
+    if x.shape != (B, N, 3) or query_mask.numel() != B * N or (target_mask is not None and target_mask.numel() != B * N):
+        raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, x {tuple(x.shape)}, query_mask '
+                         f'{tuple(query_mask.shape)}')
+    dev = one_hot.device
+    f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()     # noqa: E731
+    one_hot, x, qm = f32(one_hot), f32(x), f32(query_mask).reshape(B, N)
+    tm = None if target_mask is None else f32(target_mask).reshape(B, N)
+    M, px, pt = 0, None, None
+    if protein is not None:
+        px, pt = f32(shared[0]), shared[1].to(device=dev, dtype=torch.int32).contiguous()
+        M = pt.numel()
+        if px.shape != (M, 3):
+            raise ValueError(f'shapes disagree: protein positions {tuple(px.shape)}, types {tuple(pt.shape)}')
+    if thresholds is None:
+        thresholds = const.clash_threshold_table(is_geom, scale, tolerance).to(dev)
+    thresholds = f32(thresholds)
+    if thresholds.shape != (nf, nf):
+        raise ValueError(f'thresholds {tuple(thresholds.shape)} for {nf} atom types')
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    out = Clashes(i32(B), i32(B), i32(B), i32(B), i32(B), torch.empty(B, dtype=torch.float32, device=dev), i32(B), i32(B, N),
+                  torch.empty(B, N, dtype=torch.float32, device=dev), qm)
+    args = _lib.DLClashArgs(
+        B=B, N=N, nf=nf, x=x.data_ptr(), one_hot=one_hot.data_ptr(), query_mask=qm.data_ptr(),
+        target_mask=None if tm is None else tm.data_ptr(), M=M, target_x=px.data_ptr() if M else None,
+        target_type=pt.data_ptr() if M else None, threshold=thresholds.data_ptr(), contact_cutoff=float(contact_cutoff),
+        n_query=out.n_query.data_ptr(), n_target=out.n_target.data_ptr(), n_clashes=out.n_clashes.data_ptr(),
+        n_clash_atoms=out.n_clash_atoms.data_ptr(), n_contacts=out.n_contacts.data_ptr(), min_dist2=out.min_dist2.data_ptr(),
+        status=out.status.data_ptr(), atom_clashes=out.atom_clashes.data_ptr(), atom_min_dist2=out.atom_min_dist2.data_ptr())
+    with torch.cuda.device(dev):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.load().dl_clash_scores(ctypes.byref(args), stream), 'dl_clash_scores')
+    return out
+
+
+def clashes_to_host(result):
+    """The ``ClashRecord`` values ``compute_clashes`` reads, one per molecule of a ``Clashes``, on the host: the counts as
+    ints, ``min_distance`` in Angstrom (the fp64 square root of ``min_dist2``: ``inf`` without a pair, NaN for a flagged molecule),
+    ``status``, and ``atom_clashes`` / ``atom_min_distance`` as lists over the QUERY atoms only, in row order."""
+    cols = [getattr(result, name).cpu().tolist() for name in ('n_query', 'n_target', 'n_clashes', 'n_clash_atoms', 'n_contacts')]
+    root = lambda t: np.sqrt(t.cpu().numpy().astype(np.float64))      # noqa: E731  (numpy's square root is correctly rounded)
+    closest = root(result.min_dist2).tolist()
+    status = result.status.cpu().tolist()
+    rows = result.query_mask.cpu() != 0
+    atom_c, atom_d = result.atom_clashes.cpu(), root(result.atom_min_dist2)
+    return [ClashRecord(cols[0][b], cols[1][b], cols[2][b], cols[3][b], cols[4][b], closest[b], status[b],
+                        atom_c[b][rows[b]].tolist(), atom_d[b][rows[b].numpy()].tolist()) for b in range(len(status))]
+
+
+def _clash_scored(record):
+    return not record.status & (_lib.DL_CLASH_NONFINITE | _lib.DL_CLASH_TOO_LARGE)
+
+
+def compute_clashes(pred, true=None):
+    """Scores of the ``ClashRecord`` values ``pred`` (``clashes_to_host``), plain numbers:
+
+    ``clash_molecules``        records scored: the flagged ones (``DL_CLASH_NONFINITE`` / ``DL_CLASH_TOO_LARGE``: their counts
+                               mean nothing) are left out of everything below
+    ``clash_flagged``          how many were left out
+    ``clash_free``             share of the scored records with ``n_clashes == 0``
+    ``clashes_per_molecule``   mean number of clashing pairs
+    ``clash_atoms_share``      clashing query atoms over query atoms, both summed over the scored records
+    ``contacts_per_molecule``  mean number of contact pairs
+    ``min_distance``           mean of the per-molecule smallest distance in Angstrom; records without a pair are left out,
+                               ``None`` when that leaves none
+
+    With ``true`` - one record per prediction: the data set's own linker scored in the same pocket - three more keys, over the
+    positions where both records are scored: ``true_clashes_per_molecule``, ``true_clash_free`` and ``clash_excess`` (the
+    mean of ``pred - true`` clashing pairs).  Without ``true`` they are absent.  Nothing scored: every share and mean is 0."""
+    if true is not None and len(true) != len(pred):
+        raise ValueError(f'{len(pred)} predictions, {len(true)} true records')
+    good = [m for m in pred if _clash_scored(m)]
+    n = len(good)
+    mean = lambda values: float(sum(values) / len(values)) if values else 0.0      # noqa: E731
+    queries = sum(m.n_query for m in good)
+    closest = [m.min_distance for m in good if math.isfinite(m.min_distance)]
+    out = {'clash_molecules': n, 'clash_flagged': len(pred) - n,
+           'clash_free': mean([m.n_clashes == 0 for m in good]),
+           'clashes_per_molecule': mean([m.n_clashes for m in good]),
+           'clash_atoms_share': float(sum(m.n_clash_atoms for m in good) / queries) if queries else 0.0,
+           'contacts_per_molecule': mean([m.n_contacts for m in good]),
+           'min_distance': mean(closest) if closest else None}
+    if true is not None:
+        both = [(p, t) for p, t in zip(pred, true) if _clash_scored(p) and _clash_scored(t)]
+        out['true_clashes_per_molecule'] = mean([t.n_clashes for _, t in both])
+        out['true_clash_free'] = mean([t.n_clashes == 0 for _, t in both])
+        out['clash_excess'] = mean([p.n_clashes - t.n_clashes for p, t in both])
+    return out

@@ -56,17 +56,22 @@ def _prepare(checkpoint, prefix, data, n_steps, device):
 
 
 def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=None, linker_size_model=None,
-           output_format='xyz', metrics=False, geometry=False):
+           output_format='xyz', metrics=False, geometry=False, clashes=False):
     """``sample.py``.  Returns the output directory.  ``metrics=True`` scores the molecules sampled in this call against
     the data set's own (``metrics.compute_metrics``: valence rule, connectivity, uniqueness, novelty, recovery) and writes
     the result to ``metrics.json`` in the output directory; with ``geometry=True`` as well, the symmetry-aware RMSD of the
     recovered samples (``metrics.compute_geometry``: ``rmsd``, ``rmsd_molecules``, ``rmsd_truncated``) joins it.  ``output_format`` 'sdf' / 'both' writes the sampled molecules (not
     the ground truth, fragments or pocket) as ``<uuid>/<i>_.sdf`` with bonds perceived on the GPU, instead of / beside the
-    ``.xyz`` files, and prints one JSON line with the number of molecules, the share in one piece and the mean bond count."""
+    ``.xyz`` files, and prints one JSON line with the number of molecules, the share in one piece and the mean bond count.
+    ``clashes=True`` (pocket data sets only; others raise ``ValueError``) counts the steric clashes of every sample's linker
+    atoms with its pocket atoms, and of the data set's own linker in the same pocket as ``true``
+    (``metrics.analyze_clashes`` / ``compute_clashes``); the keys go into ``metrics.json``, beside the ``metrics`` keys when
+    both are asked for and alone otherwise."""
     if output_format not in OUTPUT_FORMATS:
         raise ValueError(f'output_format must be one of {OUTPUT_FORMATS}, got {output_format!r}')
     found, pred, true, input_index = [], [], [], []
     pred_x, true_x, n_linker = [], [], []
+    pred_clashes, true_clashes = [], []
     geometry = geometry and metrics
     exp = 'model' if isinstance(checkpoint, DDPM) else checkpoint.split('/')[-1].replace('.ckpt', '')
     collate_fn, sample_fn = collate, None
@@ -91,6 +96,8 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
 
     model = _prepare(checkpoint, prefix, data, n_steps, device)
     moad = isinstance(model.val_dataset, MOADDataset)
+    if clashes and not (len(model.val_dataset) and 'pocket_mask' in model.val_dataset[0]):
+        raise ValueError('clashes are scored against the pocket atoms: this data set has no pocket_mask')
     for batch_idx, batch in enumerate(model.val_dataloader(collate_fn=collate_fn)):
         uuids = [str(u) for u in batch['uuid']]
         for u in uuids:
@@ -116,12 +123,21 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
         save_xyz_file(output_dir, h, x, frag_mask, [f'{u}/frag' for u in uuids], is_geom=model.is_geom)
         if metrics:                                            # the true molecules as the files show them: without the pocket
             true_batch = mol_metrics.to_host(mol_metrics.analyze(h, x, node_mask, model.is_geom), h, node_mask)
+        if clashes:                                            # the data set's own linker in the same pocket
+            true_clash_batch = mol_metrics.clashes_to_host(mol_metrics.analyze_clashes(
+                h[:, :, :model.num_classes], x, batch['linker_mask'], batch['pocket_mask'], is_geom=model.is_geom))
         if geometry:
             true_x_batch = list(mol_metrics.kept_positions(x, node_mask)[0])
             n_linker_batch = batch['linker_mask'].reshape(len(uuids), -1).sum(1).long().tolist()
         for i in range(starting_point, n_samples):
             chain, out_mask = model.sample_chain(batch, sample_fn=sample_fn, keep_frames=1)
             xs, hs = chain[0][:, :, :model.n_dims], chain[0][:, :, model.n_dims:]
+            if clashes:                                        # the template's linker rows against its pocket rows
+                pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, out_mask.shape[1] - m.shape[1]))      # noqa: E731
+                pred_clashes += mol_metrics.clashes_to_host(mol_metrics.analyze_clashes(
+                    hs[:, :, :model.num_classes], xs, out_mask * (1 - pad(batch['fragment_mask'])), pad(batch['pocket_mask']),
+                    is_geom=model.is_geom))
+                true_clashes += true_clash_batch
             if moad:
                 pock = batch['pocket_mask']
                 if pock.shape[1] < out_mask.shape[1]:          # template wider than the input (sampled sizes)
@@ -144,11 +160,15 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 n_linker += n_linker_batch
     if found:
         print(json.dumps(summary(found)))
-    if metrics:
+    if metrics or clashes:
         with open(os.path.join(output_dir, 'metrics.json'), 'w') as f:
-            scores = dict(mol_metrics.compute_metrics(pred, true, input_index), molecules=len(pred))
+            scores = {}
+            if metrics:
+                scores = dict(mol_metrics.compute_metrics(pred, true, input_index), molecules=len(pred))
             if geometry:
                 scores.update(mol_metrics.compute_geometry(pred, true, pred_x, true_x, n_linker))
+            if clashes:
+                scores.update(mol_metrics.compute_clashes(pred_clashes, true_clashes))
             json.dump(scores, f, indent=1)
     return output_dir
 
@@ -202,12 +222,16 @@ def main(argv=None):
     p.add_argument('--geometry', action='store_true',
                    help='with --metrics: add the symmetry-aware RMSD of the recovered samples against their true molecules '
                         '(rmsd, rmsd_molecules, rmsd_truncated)')
+    p.add_argument('--clashes', action='store_true',
+                   help='pocket data sets: count the steric clashes of the sampled linkers (and of the true ones) with the '
+                        'pocket atoms on the GPU and write the scores to metrics.json')
     a = p.parse_args(argv)
     if a.keep_frames is not None:
         print(sample_trajectories(a.checkpoint, a.samples, a.prefix, a.keep_frames, a.device, a.data, a.n_steps))
     else:
         print(sample(a.checkpoint, a.samples, a.prefix, a.n_samples, a.device, a.data, a.n_steps, a.linker_size_model,
-                     a.output_format, a.metrics, **({'geometry': True} if a.geometry else {})))
+                     a.output_format, a.metrics, **({'geometry': True} if a.geometry else {}),
+                     **({'clashes': True} if a.clashes else {})))
 
 
 if __name__ == '__main__':

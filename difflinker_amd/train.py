@@ -92,6 +92,9 @@ def main(argv=None):
                         '(0: off)')
     p.add_argument('--geometry', action='store_true',
                    help='with --sample_every_epochs: add the symmetry-aware RMSD of the recovered samples to the epoch scores')
+    p.add_argument('--clashes', action='store_true',
+                   help='with --sample_every_epochs, pocket models: add the steric clashes of the sampled linkers with the '
+                        'pocket atoms to the epoch scores')
     a = p.parse_args(argv)
     cfg = dict(DEFAULTS)
     if a.config is not None:
@@ -125,6 +128,7 @@ def main(argv=None):
     if a.sample_every_epochs:
         model.test_epochs = a.sample_every_epochs
     model.geometry_metrics = bool(a.geometry)
+    model.clash_metrics = bool(a.clashes)
     kept = lambda: {'best_validity_and_connectivity': best} if a.sample_every_epochs else {}   # noqa: E731
     step, epoch = start_step, start_epoch
     n_epochs = int(cfg['n_epochs'])

@@ -42,6 +42,9 @@
  *   dl_best_rmsd                         <- the RMSD block of compute_metrics.py:366-402: rdMolAlign.GetBestRMS of every
  *                                           recovered sample against its true molecule, the minimum over the graph
  *                                           isomorphisms the host enumerated, proper rotations only
+ *   dl_clash_scores                      <- (no reference counterpart: the paper reports clash counts of pocket samples, the
+ *                                           scripts do not compute them) generated atoms against protein atoms under a
+ *                                           van der Waals rule stated below, one launch per batch
  *   dl_size_train_forward / dl_size_train_backward
  *                                        <- SizeClassifier.forward in training mode + loss.backward()
  *                                           (src/linker_size_lightning.py:83-117, :163-167)
@@ -701,6 +704,71 @@ typedef struct dl_rmsd_args {
     int32_t* status;                /* device int32 [P] out */
 } dl_rmsd_args;
 int32_t dl_best_rmsd(const dl_rmsd_args* args, void* stream);
+
+/* ---- steric clashes of generated atoms with the protein (clash.hip) -------------------------------------------
+ * Does the linker fit, or does it sit inside the protein?  The reference has no code for this question, so the rule is this
+ * project's own; tests/clash_ref.py restates it in numpy float32 and gives the same bits as the kernel.
+ *
+ * THE RULE.  Atoms are heavy atoms of the project's vocabularies, hydrogens are implicit.  A pair is one QUERY atom (a
+ * generated atom) and one TARGET atom (a protein atom).  The host builds threshold[a][b] in fp32 Angstrom, a the query's type
+ * and b the target's (const.clash_threshold_table: scale * (r[a] + r[b]) - tolerance over Bondi's van der Waals radii,
+ * computed in fp64 and rounded once; defaults scale 0.75, tolerance 0).  An atom's type is the index of the first largest
+ * entry of its one-hot row, as dl_perceive_bonds reads it.  With dx = xq - xt (dy, dz alike)
+ *     d2 = ((dx*dx) + (dy*dy)) + (dz*dz)
+ * every operation a separate fp32 round-to-nearest operation in exactly this order, no fused multiply-add, and the pair
+ *     CLASHES       when d2 < t * t and t > 0, t = threshold[a][b]    (t * t one fp32 multiply; the comparison is strict)
+ *     is a CONTACT  when d2 < c * c, c = contact_cutoff               (same arithmetic)
+ *
+ * A molecule's query atoms are its rows with query_mask != 0.  Its targets are its rows with target_mask != 0 that are not
+ * query rows (a row set in both masks counts as a query only), followed by the SHARED list target_x / target_type, the same
+ * for every molecule of the launch (the whole protein of `generate --protein`).  Masks may be interleaved with padding rows
+ * in any order; rows in neither mask are never read.
+ *
+ *   n_query, n_target   atoms on either side (in-batch targets plus the shared atoms with a type in [0, nf))
+ *   n_clashes           clashing pairs
+ *   n_clash_atoms       query atoms with at least one clash
+ *   n_contacts          contact pairs
+ *   min_dist2           smallest d2 over the pairs, +inf without a pair (the caller takes the square root)
+ *   atom_clashes        per row: clashing pairs of this query atom; 0 on non-query rows
+ *   atom_min_dist2      per row: smallest d2 of this query atom; +inf on non-query rows and without targets
+ *   status              0, or DL_CLASH_* bits.  A molecule with a bit set does not touch the other molecules of the launch.
+ *
+ * With DL_CLASH_NONFINITE or DL_CLASH_TOO_LARGE every integer output of the molecule but `status` is 0 (n_query and n_target
+ * included), min_dist2 is NaN and atom_min_dist2 is NaN on its query rows.  DL_CLASH_TOO_LARGE is decided first and such a
+ * molecule is not looked at further (its status is exactly that bit).  A shared atom with a type outside [0, nf) is skipped,
+ * coordinates and all, and sets DL_CLASH_BAD_TYPE on every molecule; the other outputs stay valid.
+ *
+ * One 256-thread workgroup per molecule, ONE launch per batch.  Integer sums and minima only: no floating-point
+ * accumulation, no atomics, the same bits on every run.  Global memory is written with plain stores only and every output is
+ * written in full; the callee allocates nothing.  A null `args`, B < 0, N < 1, nf < 1 or > 16 or M < 0 return DL_ERR_BAD_ARG;
+ * then B == 0 returns DL_OK without a launch (and without looking at the pointers); then null pointers (`target_mask` may
+ * always be NULL: no in-batch targets; `target_x` and `target_type` may be NULL when M is 0) return DL_ERR_BAD_ARG, all before
+ * any device work. */
+#define DL_CLASH_NONFINITE 1        /* status bit: a query or target coordinate of the molecule or of the shared list is NaN or infinite */
+#define DL_CLASH_TOO_LARGE 2        /* status bit: more than 1024 query atoms */
+#define DL_CLASH_BAD_TYPE 4         /* status bit: a target_type outside [0, nf) was skipped */
+typedef struct dl_clash_args {
+    int32_t B, N, nf;
+    const float* x;                 /* device f32 [B,N,3], Angstrom */
+    const float* one_hot;           /* device f32 [B,N,nf] */
+    const float* query_mask;        /* device f32 [B,N] */
+    const float* target_mask;       /* device f32 [B,N] or NULL: in-batch targets (the reference's pocket_mask) */
+    int32_t M;                      /* atoms of the shared target list, may be 0 */
+    const float* target_x;          /* device f32 [M,3], in the frame of `x` */
+    const int32_t* target_type;     /* device int32 [M] */
+    const float* threshold;         /* device f32 [nf,nf]: [query type][target type], Angstrom */
+    float contact_cutoff;           /* Angstrom */
+    int32_t* n_query;               /* device int32 [B] out */
+    int32_t* n_target;              /* device int32 [B] out */
+    int32_t* n_clashes;             /* device int32 [B] out */
+    int32_t* n_clash_atoms;         /* device int32 [B] out */
+    int32_t* n_contacts;            /* device int32 [B] out */
+    float* min_dist2;               /* device f32 [B] out */
+    int32_t* status;                /* device int32 [B] out */
+    int32_t* atom_clashes;          /* device int32 [B,N] out */
+    float* atom_min_dist2;          /* device f32 [B,N] out */
+} dl_clash_args;
+int32_t dl_clash_scores(const dl_clash_args* args, void* stream);
 
 const char* dl_error_string(int32_t status);
 int32_t dl_last_hip_error(void);
