@@ -169,6 +169,21 @@ class DLClashArgs(ctypes.Structure):
     ]
 
 
+DL_SHAPE_NONFINITE, DL_SHAPE_OUT_OF_RANGE, DL_SHAPE_TOO_LARGE = 1, 2, 4  # dl_shape_args.status: one of these, or 0
+
+
+class DLShapeArgs(ctypes.Structure):
+    _fields_ = [
+        ('B', ctypes.c_int32), ('Na', ctypes.c_int32), ('Nb', ctypes.c_int32), ('nf', ctypes.c_int32),
+        ('x_a', ctypes.c_void_p), ('one_hot_a', ctypes.c_void_p), ('mask_a', ctypes.c_void_p),
+        ('x_b', ctypes.c_void_p), ('one_hot_b', ctypes.c_void_p), ('mask_b', ctypes.c_void_p),
+        ('r2', ctypes.c_void_p),
+        ('vol_a', ctypes.c_void_p), ('vol_b', ctypes.c_void_p), ('vol_min', ctypes.c_void_p),
+        ('core_a', ctypes.c_void_p), ('core_b', ctypes.c_void_p), ('core_both', ctypes.c_void_p),
+        ('n_a', ctypes.c_void_p), ('n_b', ctypes.c_void_p), ('status', ctypes.c_void_p),
+    ]
+
+
 EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_string', 'dl_model_num_tensors',
            'dl_model_create', 'dl_model_destroy', 'dl_egnn_forward_fc', 'dl_sampler_step', 'dl_sample_chain_fc',
            'dl_set_profile_buffer', 'dl_profile_max_events', 'dl_pocket_workspace_bytes', 'dl_egnn_forward_pocket',
@@ -180,7 +195,7 @@ EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_stri
            'dl_egnn_backward_pocket_workspace_bytes', 'dl_egnn_backward_pocket',
            'dl_size_train_num_params', 'dl_size_train_workspace_bytes', 'dl_size_train_forward', 'dl_size_train_backward',
            'dl_join_workspace_bytes', 'dl_sample_chain_fc_join', 'dl_bonds_workspace_bytes', 'dl_perceive_bonds',
-           'dl_molecule_keys', 'dl_clash_scores', 'dl_best_rmsd')
+           'dl_molecule_keys', 'dl_clash_scores', 'dl_shape_scores', 'dl_best_rmsd')
 TEST_HOOK_EXPORTS = ('dl_debug_team_fault',)       # declared under #ifdef DL_TEST_HOOKS: the test-hooks build only
 
 _lib = None
@@ -302,6 +317,8 @@ def _open(path):
     lib.dl_molecule_keys.argtypes = [ctypes.POINTER(DLMolKeysArgs), vp]
     lib.dl_clash_scores.restype = i32
     lib.dl_clash_scores.argtypes = [ctypes.POINTER(DLClashArgs), vp]
+    lib.dl_shape_scores.restype = i32
+    lib.dl_shape_scores.argtypes = [ctypes.POINTER(DLShapeArgs), vp]
     lib.dl_best_rmsd.restype = i32
     lib.dl_best_rmsd.argtypes = [ctypes.POINTER(DLRmsdArgs), vp]
     lib.dl_size_model_num_tensors.restype = i32

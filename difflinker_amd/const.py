@@ -121,3 +121,13 @@ def clash_threshold_table(is_geom, scale=0.75, tolerance=0.0):
         for b in range(n):
             table[a, b] = float(scale) * (VDW_RADII[a] + VDW_RADII[b]) - float(tolerance)
     return table.to(TORCH_FLOAT)
+
+
+def shape_radius_table(is_geom, scale=0.8, step=0.25):
+    """``[n_types][3]`` fp32 SQUARED radii in Angstrom^2 of the three levels of the shape rule (``metrics.analyze_shapes``):
+    ``r_k = scale * VDW_RADII[type] + k * step`` for ``k = 0, 1, 2`` in fp64, rounded to fp32 once, then ``r_k * r_k`` as one
+    fp32 multiplication.  The defaults follow RDKit's shape encoding (``vdwScale`` 0.8, ``stepSize`` 0.25, two layers)."""
+    n = GEOM_NUMBER_OF_ATOM_TYPES if is_geom else NUMBER_OF_ATOM_TYPES
+    radii = torch.tensor([[float(scale) * VDW_RADII[t] + k * float(step) for k in range(3)] for t in range(n)],
+                         dtype=torch.float64).to(TORCH_FLOAT)
+    return radii * radii

@@ -101,6 +101,7 @@ class DDPM(_Base):
         self.metrics = {}                                                       # lightning.py:43: name -> value per epoch
         self.geometry_metrics = False           # sample_and_analyze adds metrics.compute_geometry's RMSD keys (train --geometry)
         self.clash_metrics = False              # pocket models: it adds metrics.compute_clashes' keys as well (train --clashes)
+        self.shape_metrics = False              # it adds metrics.compute_shapes' keys: every sample against its true molecule (train --shape)
         if _Base is nn.Module:
             self.current_epoch = 0              # Lightning's Trainer keeps this; here the training loop sets it
 
@@ -315,8 +316,11 @@ class DDPM(_Base):
         samples (``metrics.compute_geometry``) is added: ``rmsd`` (``None`` when nothing recovered), ``rmsd_molecules``,
         ``rmsd_truncated``.  With ``self.clash_metrics`` a pocket model also gets the ``metrics.compute_clashes`` keys: the
         samples' linker atoms against the pocket atoms, and the data set's own linkers in the same pockets as ``true``.
-        No animation, no WandB."""
+        With ``self.shape_metrics`` every sample's gridded van der Waals volume is compared with its true molecule's in the
+        frame the two share (``metrics.compute_shapes``; pocket rows left out, once over all ligand rows and once over the
+        linker rows).  No animation, no WandB."""
         pred, true, input_index = [], [], []
+        shapes, linker_shapes = [], []
         pred_x, true_x, n_linker = [], [], []
         clashes = self.clash_metrics and self.pockets
         pred_clashes, true_clashes = [], []
@@ -358,6 +362,9 @@ class DDPM(_Base):
                     pred_clashes += mol_metrics.clashes_to_host(mol_metrics.analyze_clashes(
                         one_hot, x, node_mask * (1 - frag), out_drop, is_geom=self.is_geom))
                     true_clashes += true_clash_batch
+                if self.shape_metrics:
+                    shapes += self._shape_records(data, one_hot, x, node_mask, drop, out_drop, linker=False)
+                    linker_shapes += self._shape_records(data, one_hot, x, node_mask, drop, out_drop, linker=True)
                 if self.geometry_metrics:
                     pred_x += list(mol_metrics.kept_positions(x, node_mask, out_drop)[0])
                     true_x += true_x_batch
@@ -368,7 +375,33 @@ class DDPM(_Base):
             scores.update(mol_metrics.compute_geometry(pred, true, pred_x, true_x, n_linker))
         if clashes:
             scores.update(mol_metrics.compute_clashes(pred_clashes, true_clashes))
+        if self.shape_metrics:
+            scores.update(mol_metrics.compute_shapes(shapes, linker_shapes, pred))
         return scores
+
+    def _shape_records(self, data, one_hot, x, node_mask, drop, out_drop, linker):
+        """``metrics.ShapeRecord`` per molecule of a sampled batch against the data set's molecule.  ``sample_chain`` centres
+        its input on ``center_of_mass`` and the data set's positions are not centred, so the true molecule is moved the same
+        way first: the two then share the fragments' coordinates.  Pocket rows take part on neither side."""
+        if self.inpainting:                                                        # the conditions of ``sample_chain``
+            com_mask = data['atom_mask']
+        elif isinstance(self.val_dataset, MOADDataset) and self.center_of_mass == 'fragments':
+            com_mask = data['fragment_only_mask']
+        elif self.center_of_mass == 'fragments':
+            com_mask = data['fragment_mask']
+        elif self.center_of_mass == 'anchors':
+            com_mask = data['anchors']
+        else:
+            raise NotImplementedError(self.center_of_mass)
+        true_x = utils.remove_partial_mean_with_mask(data['positions'], data['atom_mask'], com_mask)
+        pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, node_mask.shape[1] - m.shape[1]))      # noqa: E731
+        if linker:
+            mask, true_mask = node_mask * (1 - pad(data['fragment_mask'])), data['linker_mask']
+        else:
+            mask = node_mask if out_drop is None else node_mask * (1 - out_drop)
+            true_mask = data['atom_mask'] if drop is None else data['atom_mask'] * (1 - drop)
+        return mol_metrics.shapes_to_host(mol_metrics.analyze_shapes(
+            one_hot, x, mask, data['one_hot'][:, :, :self.num_classes], true_x, true_mask, is_geom=self.is_geom))
 
     # ---- sampling -------------------------------------------------------------------------------------
     def sample_chain(self, data, sample_fn=None, keep_frames=None):

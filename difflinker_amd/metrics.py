@@ -18,6 +18,10 @@ whole list in one launch of ``dl_best_rmsd``, ``csrc/rmsd.hip``), times ``sqrt(n
 ``analyze_clashes`` / ``compute_clashes`` answer what none of the above can, because they all drop the pocket first: does the
 generated linker fit, or does it sit inside the protein?  Generated atoms against protein atoms under a van der Waals rule
 (``dl_clash_scores``, ``csrc/clash.hip``); the reference has no code for it, the rule is stated in ``analyze_clashes``.
+
+``analyze_shapes`` / ``compute_shapes`` score EVERY sample in 3D, recovered or not: the gridded van der Waals volume it shares
+with its true molecule, in place (``dl_shape_scores``, ``csrc/shape.hip``).  This stands where the reference has the shape
+half of SC-RDKit; the grid rule is this project's own after RDKit's defaults, not RDKit's, and the numbers are not RDKit's.
 """
 import ctypes
 import math
@@ -573,4 +577,108 @@ def compute_clashes(pred, true=None):
         out['true_clashes_per_molecule'] = mean([t.n_clashes for _, t in both])
         out['true_clash_free'] = mean([t.n_clashes == 0 for _, t in both])
         out['clash_excess'] = mean([p.n_clashes - t.n_clashes for p, t in both])
+    return out
+
+
+Shapes = namedtuple('Shapes', 'vol_a vol_b vol_min core_a core_b core_both n_a n_b status')
+ShapeRecord = namedtuple('ShapeRecord', Shapes._fields)
+SHAPE_NAMES = ('shape_molecules', 'shape_flagged', 'shape_similarity', 'shape_tanimoto', 'shape_similarity_7',
+               'shape_similarity_8', 'shape_similarity_9')
+SHAPE_R2_MAX = 400.0                             # the largest squared radius dl_shape_scores admits: 20 A
+
+
+def analyze_shapes(one_hot_a, x_a, mask_a, one_hot_b, x_b, mask_b, is_geom=True, scale=0.8, step=0.25):
+    """Gridded van der Waals overlap of molecule A and molecule B of every pair of a batch, in the frame the two share, in
+    one launch of ``dl_shape_scores`` on the HIP device.
+
+    THE RULE (this project's own.  Spacing, scale and layering follow RDKit's shape encoding - ``gridSpacing`` 0.5,
+    ``vdwScale`` 0.8, ``stepSize`` 0.25, two bits per point, heavy atoms only - but the grid is not RDKit's and neither are
+    the numbers).  A row takes part when its mask (``[B,N]`` or ``[B,N,1]``) is non-zero; its type is the first largest entry
+    of its one-hot row.  Lattice points sit at ``(0.5 i, 0.5 j, 0.5 k)`` for all integers, in the frame of the coordinates.
+    With ``r2 = const.shape_radius_table(is_geom, scale, step)`` an atom of type ``t`` gives a point
+    ``(d2 < r2[t][0]) + (d2 < r2[t][1]) + (d2 < r2[t][2])``, ``d2 = ((dx*dx) + (dy*dy)) + (dz*dz)`` in fp32 without fused
+    multiply-adds, the comparisons strict; a point's LEVEL for a molecule is the maximum over the molecule's atoms: 3 inside
+    the scaled van der Waals sphere, 2 and 1 in two layers of ``step`` around it.  ``Na`` and ``Nb`` may differ.
+
+    Returns a ``Shapes`` of int32 device tensors ``[B]``: ``vol_a`` / ``vol_b`` (sum of the levels), ``vol_min`` (sum of
+    ``min(level_A, level_B)``), ``core_a`` / ``core_b`` / ``core_both`` (points at level 3), ``n_a`` / ``n_b`` (rows that took
+    part) and ``status``: 0, or one of ``_lib.DL_SHAPE_NONFINITE`` (a participating coordinate is NaN or infinite),
+    ``DL_SHAPE_OUT_OF_RANGE`` (beyond 4096 A), ``DL_SHAPE_TOO_LARGE`` (the pair spans more than 120 A), decided in this
+    order; a flagged pair has every other output 0.  No host synchronisation.
+
+    What this is NOT: no alignment (the molecules are compared where they are), no pharmacophore features (the other half
+    of SC-RDKit), no hydrogens, not RDKit's numbers.  The lattice is fixed in space: a common shift of both molecules by
+    less than the spacing moves the counts a little."""
+    tensors = (one_hot_a, x_a, mask_a, one_hot_b, x_b, mask_b)
+    if not all(t.is_cuda for t in tensors):
+        raise _lib.HipLibraryError('analyze_shapes runs on the HIP device only (no CPU fallback): '
+                                   f'got tensors on {", ".join(str(t.device) for t in tensors)}')
+    B, Na, nf = one_hot_a.shape
+    Nb = one_hot_b.shape[1]
+    if (one_hot_b.shape != (B, Nb, nf) or x_a.shape != (B, Na, 3) or x_b.shape != (B, Nb, 3) or mask_a.numel() != B * Na
+            or mask_b.numel() != B * Nb):
+        raise ValueError(f'shapes disagree: one_hot_a {tuple(one_hot_a.shape)}, x_a {tuple(x_a.shape)}, mask_a '
+                         f'{tuple(mask_a.shape)}, one_hot_b {tuple(one_hot_b.shape)}, x_b {tuple(x_b.shape)}, mask_b '
+                         f'{tuple(mask_b.shape)}')
+    r2 = const.shape_radius_table(is_geom, scale, step)
+    if r2.shape != (nf, 3):
+        raise ValueError(f'radius table {tuple(r2.shape)} for {nf} atom types')
+    if not bool((torch.isfinite(r2) & (r2 <= SHAPE_R2_MAX)).all()):
+        raise ValueError(f'scale {scale} and step {step} give a radius that is not finite or is above 20 A')
+    dev = one_hot_a.device
+    f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()     # noqa: E731
+    one_hot_a, x_a, ma = f32(one_hot_a), f32(x_a), f32(mask_a).reshape(B, Na)
+    one_hot_b, x_b, mb = f32(one_hot_b), f32(x_b), f32(mask_b).reshape(B, Nb)
+    r2 = r2.to(dev).contiguous()
+    out = Shapes(*(torch.empty(B, dtype=torch.int32, device=dev) for _ in Shapes._fields))
+    args = _lib.DLShapeArgs(B=B, Na=Na, Nb=Nb, nf=nf, x_a=x_a.data_ptr(), one_hot_a=one_hot_a.data_ptr(), mask_a=ma.data_ptr(),
+                            x_b=x_b.data_ptr(), one_hot_b=one_hot_b.data_ptr(), mask_b=mb.data_ptr(), r2=r2.data_ptr(),
+                            **{name: getattr(out, name).data_ptr() for name in Shapes._fields})
+    with torch.cuda.device(dev):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.load().dl_shape_scores(ctypes.byref(args), stream), 'dl_shape_scores')
+    return out
+
+
+def shapes_to_host(result):
+    """One ``ShapeRecord`` of plain ints per pair of a ``Shapes``, on the host."""
+    cols = [getattr(result, name).cpu().tolist() for name in Shapes._fields]
+    return [ShapeRecord(*row) for row in zip(*cols)]
+
+
+def _shape_scored(record):
+    return record.status == 0 and record.vol_a > 0
+
+
+def _tanimoto(record):
+    return record.vol_min / (record.vol_a + record.vol_b - record.vol_min)
+
+
+def compute_shapes(records, linker_records=None, pred=None):
+    """Scores of the ``ShapeRecord`` values ``records`` (``shapes_to_host``; A the sample, B its true molecule), in fp64:
+
+    ``shape_molecules``         pairs scored: unflagged, with ``vol_a > 0``; the others are left out of everything below
+    ``shape_flagged``           pairs with a status flag
+    ``shape_similarity``        mean of ``vol_min / vol_a``: the share of the sample's gridded volume that lies inside the true
+                                molecule's, 1 - the protrude distance - the term SC-RDKit weighs by 0.5, on this project's grid
+    ``shape_tanimoto``          mean of ``vol_min / (vol_a + vol_b - vol_min)``
+    ``shape_similarity_7/8/9``  percent of the scored pairs with ``shape_similarity`` above 0.7 / 0.8 / 0.9, as the reference
+                                reports SC-RDKit
+
+    With ``linker_records`` (the same pairs scored over their linker rows only) ``shape_tanimoto_linker``, the mean over those
+    records.  With ``pred`` (the ``to_host`` records of ``analyze`` for the same samples) ``shape_tanimoto_valid``, the mean
+    over the samples that are valid and in one piece.  A mean or a percentage over nothing is ``None``, as ``rmsd`` is."""
+    if pred is not None and len(pred) != len(records):
+        raise ValueError(f'{len(records)} shape records, {len(pred)} molecules')
+    mean = lambda values: float(sum(values) / len(values)) if values else None      # noqa: E731
+    good = [m for m in records if _shape_scored(m)]
+    similarity = [m.vol_min / m.vol_a for m in good]
+    above = lambda bar: 100.0 * sum(v > bar for v in similarity) / len(similarity) if similarity else None   # noqa: E731
+    out = {'shape_molecules': len(good), 'shape_flagged': sum(1 for m in records if m.status != 0),
+           'shape_similarity': mean(similarity), 'shape_tanimoto': mean([_tanimoto(m) for m in good]),
+           'shape_similarity_7': above(0.7), 'shape_similarity_8': above(0.8), 'shape_similarity_9': above(0.9)}
+    if linker_records is not None:
+        out['shape_tanimoto_linker'] = mean([_tanimoto(m) for m in linker_records if _shape_scored(m)])
+    if pred is not None:
+        out['shape_tanimoto_valid'] = mean([_tanimoto(m) for m, mol in zip(records, pred) if _shape_scored(m) and _good(mol)])
     return out

@@ -56,7 +56,7 @@ def _prepare(checkpoint, prefix, data, n_steps, device):
 
 
 def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=None, linker_size_model=None,
-           output_format='xyz', metrics=False, geometry=False, clashes=False):
+           output_format='xyz', metrics=False, geometry=False, clashes=False, shape=False):
     """``sample.py``.  Returns the output directory.  ``metrics=True`` scores the molecules sampled in this call against
     the data set's own (``metrics.compute_metrics``: valence rule, connectivity, uniqueness, novelty, recovery) and writes
     the result to ``metrics.json`` in the output directory; with ``geometry=True`` as well, the symmetry-aware RMSD of the
@@ -66,12 +66,16 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
     ``clashes=True`` (pocket data sets only; others raise ``ValueError``) counts the steric clashes of every sample's linker
     atoms with its pocket atoms, and of the data set's own linker in the same pocket as ``true``
     (``metrics.analyze_clashes`` / ``compute_clashes``); the keys go into ``metrics.json``, beside the ``metrics`` keys when
-    both are asked for and alone otherwise."""
+    both are asked for and alone otherwise.  ``shape=True`` scores EVERY sample's gridded van der Waals volume against its
+    true molecule's, in the centred frame the two share and without the pocket rows (``metrics.analyze_shapes`` /
+    ``compute_shapes``: once over the ligand rows, once over the linker rows alone); its keys go into ``metrics.json`` in the
+    same way, with ``shape_tanimoto_valid`` when ``metrics`` is asked for as well."""
     if output_format not in OUTPUT_FORMATS:
         raise ValueError(f'output_format must be one of {OUTPUT_FORMATS}, got {output_format!r}')
     found, pred, true, input_index = [], [], [], []
     pred_x, true_x, n_linker = [], [], []
     pred_clashes, true_clashes = [], []
+    shapes, linker_shapes = [], []
     geometry = geometry and metrics
     exp = 'model' if isinstance(checkpoint, DDPM) else checkpoint.split('/')[-1].replace('.ckpt', '')
     collate_fn, sample_fn = collate, None
@@ -143,6 +147,14 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 if pock.shape[1] < out_mask.shape[1]:          # template wider than the input (sampled sizes)
                     pock = torch.nn.functional.pad(pock, (0, 0, 0, out_mask.shape[1] - pock.shape[1]))
                 out_mask = out_mask - pock
+            if shape:                                          # the sample against the true molecule, where both lie
+                types, true_types = hs[:, :, :model.num_classes], h[:, :, :model.num_classes]
+                pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, out_mask.shape[1] - m.shape[1]))      # noqa: E731
+                shapes += mol_metrics.shapes_to_host(mol_metrics.analyze_shapes(
+                    types, xs, out_mask, true_types, x, node_mask, is_geom=model.is_geom))
+                linker_shapes += mol_metrics.shapes_to_host(mol_metrics.analyze_shapes(
+                    types, xs, out_mask * (1 - pad(batch['fragment_mask'])), true_types, x, batch['linker_mask'],
+                    is_geom=model.is_geom))
             if output_format != 'sdf':
                 save_xyz_file(output_dir, hs, xs, out_mask, [f'{u}/{i}' for u in uuids], is_geom=model.is_geom)
             if output_format != 'xyz':
@@ -160,7 +172,7 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 n_linker += n_linker_batch
     if found:
         print(json.dumps(summary(found)))
-    if metrics or clashes:
+    if metrics or clashes or shape:
         with open(os.path.join(output_dir, 'metrics.json'), 'w') as f:
             scores = {}
             if metrics:
@@ -169,6 +181,8 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 scores.update(mol_metrics.compute_geometry(pred, true, pred_x, true_x, n_linker))
             if clashes:
                 scores.update(mol_metrics.compute_clashes(pred_clashes, true_clashes))
+            if shape:
+                scores.update(mol_metrics.compute_shapes(shapes, linker_shapes, pred if metrics else None))
             json.dump(scores, f, indent=1)
     return output_dir
 
@@ -225,13 +239,16 @@ def main(argv=None):
     p.add_argument('--clashes', action='store_true',
                    help='pocket data sets: count the steric clashes of the sampled linkers (and of the true ones) with the '
                         'pocket atoms on the GPU and write the scores to metrics.json')
+    p.add_argument('--shape', action='store_true',
+                   help='score every sample\'s gridded van der Waals volume against its true molecule on the GPU (this '
+                        'project\'s grid after RDKit\'s defaults, not SC-RDKit) and write the scores to metrics.json')
     a = p.parse_args(argv)
     if a.keep_frames is not None:
         print(sample_trajectories(a.checkpoint, a.samples, a.prefix, a.keep_frames, a.device, a.data, a.n_steps))
     else:
         print(sample(a.checkpoint, a.samples, a.prefix, a.n_samples, a.device, a.data, a.n_steps, a.linker_size_model,
                      a.output_format, a.metrics, **({'geometry': True} if a.geometry else {}),
-                     **({'clashes': True} if a.clashes else {})))
+                     **({'clashes': True} if a.clashes else {}), **({'shape': True} if a.shape else {})))
 
 
 if __name__ == '__main__':

@@ -95,6 +95,9 @@ def main(argv=None):
     p.add_argument('--clashes', action='store_true',
                    help='with --sample_every_epochs, pocket models: add the steric clashes of the sampled linkers with the '
                         'pocket atoms to the epoch scores')
+    p.add_argument('--shape', action='store_true',
+                   help='with --sample_every_epochs: add the gridded shape overlap of every sample with its true molecule to '
+                        'the epoch scores')
     a = p.parse_args(argv)
     cfg = dict(DEFAULTS)
     if a.config is not None:
@@ -129,6 +132,7 @@ def main(argv=None):
         model.test_epochs = a.sample_every_epochs
     model.geometry_metrics = bool(a.geometry)
     model.clash_metrics = bool(a.clashes)
+    model.shape_metrics = bool(a.shape)
     kept = lambda: {'best_validity_and_connectivity': best} if a.sample_every_epochs else {}   # noqa: E731
     step, epoch = start_step, start_epoch
     n_epochs = int(cfg['n_epochs'])

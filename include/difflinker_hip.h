@@ -45,6 +45,10 @@
  *   dl_clash_scores                      <- (no reference counterpart: the paper reports clash counts of pocket samples, the
  *                                           scripts do not compute them) generated atoms against protein atoms under a
  *                                           van der Waals rule stated below, one launch per batch
+ *   dl_shape_scores                      <- the shape half of SC-RDKit (src/delinker_utils/calc_SC_RDKit.py:36-38,
+ *                                           1 - rdShapeHelpers.ShapeProtrudeDist, compute_metrics.py:404-441): the gridded
+ *                                           van der Waals overlap of every sample with its true molecule.  The rule stated
+ *                                           below is this project's own after RDKit's defaults, NOT RDKit's grid
  *   dl_size_train_forward / dl_size_train_backward
  *                                        <- SizeClassifier.forward in training mode + loss.backward()
  *                                           (src/linker_size_lightning.py:83-117, :163-167)
@@ -769,6 +773,77 @@ typedef struct dl_clash_args {
     float* atom_min_dist2;          /* device f32 [B,N] out */
 } dl_clash_args;
 int32_t dl_clash_scores(const dl_clash_args* args, void* stream);
+
+/* ---- gridded shape overlap of two molecules in one frame (shape.hip) ---------------------------------------------
+ * Where does a sample lie in space, compared with the molecule it was sampled for?  The reference answers with SC-RDKit; half
+ * of that is 1 - ShapeProtrudeDist(pred, true), a gridded van der Waals volume overlap.  RDKit is absent here and its numbers
+ * cannot be pinned, so spacing, scale and layering follow RDKit's defaults (gridSpacing 0.5, vdwScale 0.8, stepSize 0.25, two
+ * bits per point, ignoreHs) and past that THE RULE IS THIS PROJECT'S OWN: not RDKit's grid, not RDKit's numbers, and not
+ * "SC-RDKit" (no pharmacophore features, no alignment).  tests/shape_ref.py restates it in numpy float32 and gives the same
+ * integers as the kernel.  DiffLinker's samples share the fragments' coordinates with the data set's molecule, so the two
+ * molecules are compared in place.
+ *
+ * THE RULE.  A launch scores B pairs.  Pair b is molecule A (x_a [B,Na,3], one_hot_a [B,Na,nf], mask_a [B,Na]) and molecule
+ * B (x_b [B,Nb,3], one_hot_b, mask_b); Na and Nb are independent.  A row takes part when its mask is non-zero; its type is
+ * the index of the first largest entry of its one-hot row, as dl_perceive_bonds and dl_clash_scores read it.  Rows that do not
+ * take part are never read, whatever they hold.
+ *   Radii.     The host builds r2[type][k], k = 0, 1, 2 (const.shape_radius_table): r_k = scale * vdw[type] + k * step in fp64
+ *              over Bondi's radii (const.VDW_RADII), defaults scale 0.8 and step 0.25; r_k is rounded to fp32 once and
+ *              r2 = r_k * r_k is one fp32 multiplication.  scale and step are arguments of the table, not of the kernel.
+ *   Lattice.   Points sit at p = (0.5f*i, 0.5f*j, 0.5f*k) for ALL integers i, j, k, in the frame of the input coordinates
+ *              (exact in fp32).  The lattice is fixed in that frame: moving both molecules by a multiple of 0.5 A changes
+ *              nothing, moving them by less does (one C at the origin has volume 431, at (0.25, 0, 0) 460).
+ *   Distance.  dx = px - xa (dy, dz alike),  d2 = ((dx*dx) + (dy*dy)) + (dz*dz), every operation a separate fp32
+ *              round-to-nearest operation in exactly this order, no fused multiply-add.  Comparisons are strict.
+ *   Level.     An atom of type t gives a point (d2 < r2[t][0]) + (d2 < r2[t][1]) + (d2 < r2[t][2]); the LEVEL of a point for
+ *              a molecule is the maximum of that over the molecule's participating atoms: 3 inside the scaled van der Waals
+ *              sphere, 2 and 1 in the two layers around it, 0 outside.
+ *   Outputs    per pair, all int32, sums over the whole lattice (only finitely many points are non-zero, so which box an
+ *              implementation walks is not part of the rule, and no output depends on the order of anything):
+ *                vol_a = sum level_A      vol_b = sum level_B      vol_min = sum min(level_A, level_B)
+ *                core_a = #{level_A = 3}  core_b = #{level_B = 3}  core_both = #{level_A = 3 and level_B = 3}
+ *                n_a, n_b   participating rows of either molecule
+ *                status     0 or ONE DL_SHAPE_* flag
+ *   Flags.     Decided in this order, the first that holds is the status and the pair is not looked at further; a flagged
+ *              pair has every integer output except `status` set to 0 (n_a and n_b included) and leaves the other pairs of
+ *              the launch alone.
+ *                DL_SHAPE_NONFINITE     a participating coordinate is NaN or infinite
+ *                DL_SHAPE_OUT_OF_RANGE  a participating |coordinate| > 4096
+ *                DL_SHAPE_TOO_LARGE     with lo = floor(2*min) and hi = floor(2*max) per axis over the participating atoms of
+ *                                       BOTH molecules (2*x and floor are exact in fp32): hi - lo > 240 on any axis, about 120 A
+ *              A pair with n_a = 0 or n_b = 0 is not an error: its sums are what the rule gives.
+ * The score the callers form: vol_min / vol_a is 1 - (protrude distance of A from B), the term SC-RDKit weighs by 0.5;
+ * vol_min / (vol_a + vol_b - vol_min) is a Tanimoto overlap.
+ *
+ * One 256-thread workgroup per pair, ONE launch per batch; the levels live as bit planes in LDS (shape.hip).  Integer sums
+ * only, the same bits on every run.  Global memory is written with plain stores only, no global atomics, and every output
+ * element is written; the callee allocates nothing.  Every r2 entry must be finite and at most 400 (a 20 A radius): the host
+ * wrapper checks it; the kernel stays inside its memory with any table, but its sums are the rule's only within that limit.
+ * A null `args`, B < 0, Na < 1, Nb < 1, nf < 1 or > 16 return DL_ERR_BAD_ARG; then B == 0 returns DL_OK without a launch (and
+ * without looking at the pointers); then a null pointer returns DL_ERR_BAD_ARG, all before any device work. */
+#define DL_SHAPE_NONFINITE 1        /* status: a participating coordinate is NaN or infinite */
+#define DL_SHAPE_OUT_OF_RANGE 2     /* status: a participating |coordinate| > 4096 */
+#define DL_SHAPE_TOO_LARGE 4        /* status: the two molecules together span more than 240 lattice steps on an axis */
+typedef struct dl_shape_args {
+    int32_t B, Na, Nb, nf;
+    const float* x_a;               /* device f32 [B,Na,3], Angstrom */
+    const float* one_hot_a;         /* device f32 [B,Na,nf] */
+    const float* mask_a;            /* device f32 [B,Na] */
+    const float* x_b;               /* device f32 [B,Nb,3], in the frame of x_a */
+    const float* one_hot_b;         /* device f32 [B,Nb,nf] */
+    const float* mask_b;            /* device f32 [B,Nb] */
+    const float* r2;                /* device f32 [nf,3]: squared radii of the three levels, Angstrom^2 */
+    int32_t* vol_a;                 /* device int32 [B] out */
+    int32_t* vol_b;                 /* device int32 [B] out */
+    int32_t* vol_min;               /* device int32 [B] out */
+    int32_t* core_a;                /* device int32 [B] out */
+    int32_t* core_b;                /* device int32 [B] out */
+    int32_t* core_both;             /* device int32 [B] out */
+    int32_t* n_a;                   /* device int32 [B] out */
+    int32_t* n_b;                   /* device int32 [B] out */
+    int32_t* status;                /* device int32 [B] out */
+} dl_shape_args;
+int32_t dl_shape_scores(const dl_shape_args* args, void* stream);
 
 const char* dl_error_string(int32_t status);
 int32_t dl_last_hip_error(void);
