@@ -184,6 +184,22 @@ class DLShapeArgs(ctypes.Structure):
     ]
 
 
+DL_RINGS_MAX_ATOMS, DL_RING_BINS = 256, 7             # dl_rings_args: kept atoms per molecule; bins of ring_hist
+DL_RINGS_TOO_LARGE, DL_RINGS_BAD_BOND = 4, 8          # dl_rings_args.status bits, beside the DL_BONDS_* bits carried forward
+
+
+class DLRingsArgs(ctypes.Structure):
+    _fields_ = [
+        ('B', ctypes.c_int32), ('N', ctypes.c_int32),
+        ('node_mask', ctypes.c_void_p), ('drop_mask', ctypes.c_void_p), ('mark_mask', ctypes.c_void_p),
+        ('capacity', ctypes.c_int32),
+        ('n_bonds_in', ctypes.c_void_p), ('bonds', ctypes.c_void_p), ('status_in', ctypes.c_void_p),
+        ('n_atoms', ctypes.c_void_p), ('n_bonds', ctypes.c_void_p), ('n_components', ctypes.c_void_p),
+        ('n_rings', ctypes.c_void_p), ('bond_ring', ctypes.c_void_p), ('atom_ring', ctypes.c_void_p),
+        ('ring_hist', ctypes.c_void_p), ('status', ctypes.c_void_p),
+    ]
+
+
 EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_string', 'dl_model_num_tensors',
            'dl_model_create', 'dl_model_destroy', 'dl_egnn_forward_fc', 'dl_sampler_step', 'dl_sample_chain_fc',
            'dl_set_profile_buffer', 'dl_profile_max_events', 'dl_pocket_workspace_bytes', 'dl_egnn_forward_pocket',
@@ -195,7 +211,8 @@ EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_stri
            'dl_egnn_backward_pocket_workspace_bytes', 'dl_egnn_backward_pocket',
            'dl_size_train_num_params', 'dl_size_train_workspace_bytes', 'dl_size_train_forward', 'dl_size_train_backward',
            'dl_join_workspace_bytes', 'dl_sample_chain_fc_join', 'dl_bonds_workspace_bytes', 'dl_perceive_bonds',
-           'dl_molecule_keys', 'dl_clash_scores', 'dl_shape_scores', 'dl_best_rmsd')
+           'dl_molecule_keys', 'dl_clash_scores', 'dl_shape_scores', 'dl_ring_scores',
+           'dl_best_rmsd')
 TEST_HOOK_EXPORTS = ('dl_debug_team_fault',)       # declared under #ifdef DL_TEST_HOOKS: the test-hooks build only
 
 _lib = None
@@ -319,6 +336,8 @@ def _open(path):
     lib.dl_clash_scores.argtypes = [ctypes.POINTER(DLClashArgs), vp]
     lib.dl_shape_scores.restype = i32
     lib.dl_shape_scores.argtypes = [ctypes.POINTER(DLShapeArgs), vp]
+    lib.dl_ring_scores.restype = i32
+    lib.dl_ring_scores.argtypes = [ctypes.POINTER(DLRingsArgs), vp]
     lib.dl_best_rmsd.restype = i32
     lib.dl_best_rmsd.argtypes = [ctypes.POINTER(DLRmsdArgs), vp]
     lib.dl_size_model_num_tensors.restype = i32

@@ -79,10 +79,10 @@ OUTPUT_FORMATS = ('xyz', 'sdf', 'both')
 
 
 def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_dir, name, com_key, hide_pocket,
-                     output_format='xyz', metrics=False, clashes=False, protein=None):
+                     output_format='xyz', metrics=False, clashes=False, protein=None, rings=False):
     if output_format not in OUTPUT_FORMATS:
         raise ValueError(f'output_format must be one of {OUTPUT_FORMATS}, got {output_format!r}')
-    written, found, scored, clash_records = [], [], [], []
+    written, found, scored, clash_records, ring_records = [], [], [], [], []
     for batch_i, data in enumerate(_batches(dataset, batch_size, collate_fn)):
         n = len(data['positions'])
         chain = None
@@ -128,14 +128,20 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
         if metrics:                                           # the molecules as written: without the pocket
             types = h[:, :, :ddpm.num_classes]
             scored += mol_metrics.to_host(mol_metrics.analyze(types, x, node_mask, ddpm.is_geom), types, node_mask)
+        if rings:                                             # likewise without the pocket; the linker rows marked
+            pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, x.shape[1] - m.shape[1]))     # noqa: E731
+            ring_records += mol_metrics.rings_to_host(*mol_metrics.analyze_rings(
+                h[:, :, :ddpm.num_classes], x, node_mask, ddpm.is_geom, node_mask * (1 - pad(data['fragment_mask']))))
     if found:
         print(json.dumps(summary(found)))
-    if metrics or clashes:
+    if metrics or clashes or rings:
         scores = {}
         if metrics:                                           # no true molecule here: no novelty, no recovery
             scores = dict(mol_metrics.compute_metrics(scored), molecules=len(scored))
         if clashes:
             scores.update(mol_metrics.compute_clashes(clash_records))
+        if rings:                                             # no true molecule here either
+            scores.update(mol_metrics.compute_rings(ring_records))
         with open(os.path.join(output_dir, 'metrics.json'), 'w') as f:
             json.dump(scores, f, indent=1)
     if clashes:                                               # one record per written file, by its name
@@ -149,11 +155,13 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
 
 
 def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anchors=None, device=None, output_format='xyz',
-             metrics=False, clashes=False):
+             metrics=False, clashes=False, rings=False):
     """``generate.py`` main(): fragments file -> ``n_samples`` molecules with a sampled linker, as ``.xyz`` files
     (``output_format='sdf'``: ``.sdf`` files with perceived bonds instead, ``'both'``: both; one JSON line with the number of
     molecules, the share in one piece and the mean bond count is printed then).  ``metrics=True`` also writes
-    ``metrics.json`` to ``output_dir``: valence rule, connectivity and uniqueness of the samples (``metrics.compute_metrics``)."""
+    ``metrics.json`` to ``output_dir``: valence rule, connectivity and uniqueness of the samples (``metrics.compute_metrics``).
+    ``rings=True`` adds the ring scores of the samples to ``metrics.json`` (``metrics.analyze_rings`` / ``compute_rings``: the
+    linker's ring count, small rings, macrocycles; the pocket variants take it as well)."""
     if clashes:
         raise ValueError('clashes are scored against a protein: pass a pocket or a protein file (--pocket / --protein)')
     device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
@@ -175,11 +183,12 @@ def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anc
         'linker_mask': t(np.zeros_like(charges)), 'num_atoms': len(positions),
     }] * n_samples
     return _sample_and_save(ddpm, dataset, collate_with_fragment_edges, sample_fn, min(n_samples, 64), output_dir, name,
-                            com_key='fragment_mask', hide_pocket=False, output_format=output_format, metrics=metrics)
+                            com_key='fragment_mask', hide_pocket=False, output_format=output_format, metrics=metrics,
+                            rings=rings)
 
 
 def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size, device,
-                            output_format, metrics=False, clashes=False, protein=None):
+                            output_format, metrics=False, clashes=False, protein=None, rings=False):
     frag_pos, frag_one_hot, frag_charges = frag
     pocket_pos, pocket_one_hot, pocket_charges = pocket
     positions = np.concatenate([frag_pos, pocket_pos], axis=0)
@@ -199,12 +208,13 @@ def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_s
     ddpm.val_dataset = dataset                            # centre-of-mass mask on the dataset type (lightning.py:443)
     return _sample_and_save(ddpm, dataset, collate_with_fragment_without_pocket_edges, sample_fn,
                             min(n_samples, max_batch_size), output_dir, name, com_key='fragment_only_mask',
-                            hide_pocket=True, output_format=output_format, metrics=metrics, clashes=clashes, protein=protein)
+                            hide_pocket=True, output_format=output_format, metrics=metrics, clashes=clashes, protein=protein,
+                            rings=rings)
 
 
 def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, output_dir, n_samples, n_steps, linker_size,
                          anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz',
-                         metrics=False, clashes=False):
+                         metrics=False, clashes=False, rings=False):
     """``generate_with_pocket.py`` main(): the pocket is given as its own PDB file.  ``clashes=True`` scores every sample's
     generated atoms against the pocket atoms (``metrics.analyze_clashes``), adds the ``metrics.compute_clashes`` keys to
     ``metrics.json`` and writes ``clashes.json``: ``n_clashes``, ``n_clash_atoms`` and ``min_distance`` per written file."""
@@ -226,12 +236,12 @@ def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, ou
     frag = parse_molecule(molecule, is_geom=ddpm.is_geom)
     pocket = pocket_arrays(read_pocket(pocket_path), backbone_atoms_only)
     return _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size,
-                                   device, output_format, metrics, clashes)
+                                   device, output_format, metrics, clashes, rings=rings)
 
 
 def generate_with_protein(input_path, protein_path, backbone_atoms_only, model, output_dir, n_samples, n_steps,
                           linker_size, anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz',
-                          metrics=False, clashes=False):
+                          metrics=False, clashes=False, rings=False):
     """``generate_with_protein.py`` main(): the pocket = residues of the protein within 6 A of the fragments.
     ``clashes=True`` as in ``generate_with_pocket``, but against ALL protein atoms whose element is in the vocabulary
     (``io.get_protein_atoms``), residues outside the pocket the model saw included; the pocket rows of the batch are then not
@@ -255,7 +265,7 @@ def generate_with_protein(input_path, protein_path, backbone_atoms_only, model, 
         protein = (torch.tensor(positions, dtype=const.TORCH_FLOAT, device=device),
                    torch.tensor(types, dtype=torch.int32, device=device))
     return _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size,
-                                   device, output_format, metrics, clashes, protein)
+                                   device, output_format, metrics, clashes, protein, rings=rings)
 
 
 def main(argv=None):
@@ -283,21 +293,25 @@ def main(argv=None):
                    help='with --pocket / --protein: count the steric clashes of the generated atoms with the pocket atoms / '
                         'with all protein atoms on the GPU (0.75 x the sum of the van der Waals radii), add the scores to '
                         'metrics.json and write clashes.json with one record per written file')
+    p.add_argument('--rings', action='store_true',
+                   help='perceive the rings of the generated molecules on the GPU (ring count of the linker, small rings, '
+                        'macrocycles; the cyclomatic number, no aromaticity) and add the scores to metrics.json')
     a = p.parse_args(argv)
     if a.clashes and a.pocket is None and a.protein is None:
         raise ValueError('--clashes scores the generated atoms against a protein: pass --pocket or --protein')
     extra = {'clashes': True} if a.clashes else {}
+    more = {'rings': True} if a.rings else {}
     if a.pocket is not None:
         files = generate_with_pocket(a.fragments, a.pocket, a.backbone_atoms_only, a.model, a.output, a.n_samples,
                                      a.n_steps, a.linker_size, a.anchors, a.max_batch_size, a.random_seed,
-                                     output_format=a.output_format, metrics=a.metrics, **extra)
+                                     output_format=a.output_format, metrics=a.metrics, **extra, **more)
     elif a.protein is not None:
         files = generate_with_protein(a.fragments, a.protein, a.backbone_atoms_only, a.model, a.output, a.n_samples,
                                       a.n_steps, a.linker_size, a.anchors, a.max_batch_size, a.random_seed,
-                                      output_format=a.output_format, metrics=a.metrics, **extra)
+                                      output_format=a.output_format, metrics=a.metrics, **extra, **more)
     else:
         files = generate(a.fragments, a.model, a.output, a.n_samples, a.n_steps, a.linker_size, a.anchors,
-                         output_format=a.output_format, metrics=a.metrics)
+                         output_format=a.output_format, metrics=a.metrics, **more)
     if a.output_format == 'xyz':
         print(f'Saved {len(files)} generated molecules in .xyz format in directory {a.output}')
     else:

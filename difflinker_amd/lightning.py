@@ -102,6 +102,7 @@ class DDPM(_Base):
         self.geometry_metrics = False           # sample_and_analyze adds metrics.compute_geometry's RMSD keys (train --geometry)
         self.clash_metrics = False              # pocket models: it adds metrics.compute_clashes' keys as well (train --clashes)
         self.shape_metrics = False              # it adds metrics.compute_shapes' keys: every sample against its true molecule (train --shape)
+        self.ring_metrics = False               # it adds metrics.compute_rings' keys: ring count of the linker, small rings, macrocycles (train --rings)
         if _Base is nn.Module:
             self.current_epoch = 0              # Lightning's Trainer keeps this; here the training loop sets it
 
@@ -318,8 +319,11 @@ class DDPM(_Base):
         samples' linker atoms against the pocket atoms, and the data set's own linkers in the same pockets as ``true``.
         With ``self.shape_metrics`` every sample's gridded van der Waals volume is compared with its true molecule's in the
         frame the two share (``metrics.compute_shapes``; pocket rows left out, once over all ligand rows and once over the
-        linker rows).  No animation, no WandB."""
+        linker rows).  With ``self.ring_metrics`` the rings of every sample and of its true molecule are perceived
+        (``metrics.analyze_rings`` / ``compute_rings``; pocket rows dropped): the linker's ring count, small rings,
+        macrocycles.  No animation, no WandB."""
         pred, true, input_index = [], [], []
+        pred_rings, true_rings = [], []
         shapes, linker_shapes = [], []
         pred_x, true_x, n_linker = [], [], []
         clashes = self.clash_metrics and self.pockets
@@ -334,6 +338,10 @@ class DDPM(_Base):
             if clashes:
                 true_clash_batch = mol_metrics.clashes_to_host(mol_metrics.analyze_clashes(
                     data['one_hot'][:, :, :self.num_classes], data['positions'], data['linker_mask'], drop, is_geom=self.is_geom))
+            if self.ring_metrics:
+                true_ring_batch = mol_metrics.rings_to_host(*mol_metrics.analyze_rings(
+                    data['one_hot'][:, :, :self.num_classes], data['positions'], data['atom_mask'], self.is_geom,
+                    data['linker_mask'], drop_mask=drop))
             if self.geometry_metrics:
                 true_x_batch = list(mol_metrics.kept_positions(data['positions'], data['atom_mask'], drop)[0])
                 n_linker_batch = data['linker_mask'].reshape(n, -1).sum(1).long().tolist()
@@ -365,6 +373,11 @@ class DDPM(_Base):
                 if self.shape_metrics:
                     shapes += self._shape_records(data, one_hot, x, node_mask, drop, out_drop, linker=False)
                     linker_shapes += self._shape_records(data, one_hot, x, node_mask, drop, out_drop, linker=True)
+                if self.ring_metrics:                                              # the template's linker rows marked
+                    frag = torch.nn.functional.pad(data['fragment_mask'], (0, 0, 0, node_mask.shape[1] - data['fragment_mask'].shape[1]))
+                    pred_rings += mol_metrics.rings_to_host(*mol_metrics.analyze_rings(
+                        one_hot, x, node_mask, self.is_geom, node_mask * (1 - frag), drop_mask=out_drop))
+                    true_rings += true_ring_batch
                 if self.geometry_metrics:
                     pred_x += list(mol_metrics.kept_positions(x, node_mask, out_drop)[0])
                     true_x += true_x_batch
@@ -377,6 +390,8 @@ class DDPM(_Base):
             scores.update(mol_metrics.compute_clashes(pred_clashes, true_clashes))
         if self.shape_metrics:
             scores.update(mol_metrics.compute_shapes(shapes, linker_shapes, pred))
+        if self.ring_metrics:
+            scores.update(mol_metrics.compute_rings(pred_rings, true_rings))
         return scores
 
     def _shape_records(self, data, one_hot, x, node_mask, drop, out_drop, linker):

@@ -22,6 +22,11 @@ generated linker fit, or does it sit inside the protein?  Generated atoms agains
 ``analyze_shapes`` / ``compute_shapes`` score EVERY sample in 3D, recovered or not: the gridded van der Waals volume it shares
 with its true molecule, in place (``dl_shape_scores``, ``csrc/shape.hip``).  This stands where the reference has the shape
 half of SC-RDKit; the grid rule is this project's own after RDKit's defaults, not RDKit's, and the numbers are not RDKit's.
+
+``analyze_rings`` / ``compute_rings`` score ring topology, which none of the above sees: the number of rings of the linker
+(the reference's ``rings_n``, compute_metrics.py:128-145), three- and four-membered rings, and macrocycles closed through a
+fragment (``dl_ring_scores``, ``csrc/rings.hip``).  The ring count is the cyclomatic number, not RDKit's symmetrised count;
+there is no aromaticity, so the reference's ring filter is not reproduced.
 """
 import ctypes
 import math
@@ -681,4 +686,129 @@ def compute_shapes(records, linker_records=None, pred=None):
         out['shape_tanimoto_linker'] = mean([_tanimoto(m) for m in linker_records if _shape_scored(m)])
     if pred is not None:
         out['shape_tanimoto_valid'] = mean([_tanimoto(m) for m, mol in zip(records, pred) if _shape_scored(m) and _good(mol)])
+    return out
+
+
+Rings = namedtuple('Rings', 'n_atoms n_bonds n_components n_rings bond_ring atom_ring ring_hist status bonds')
+RingRecord = namedtuple('RingRecord', 'n_rings n_rings_ligand marked_hist status')
+RING_NAMES = ('ring_molecules', 'ring_flagged', 'rings_n', 'rings_n_ligand', 'ring_free', 'small_ring', 'macrocycle',
+              'ring_bonds_3', 'ring_bonds_4', 'ring_bonds_5', 'ring_bonds_6', 'ring_bonds_7', 'ring_bonds_8plus')
+
+
+def ring_scores(node_mask, found, drop_mask=None, mark_mask=None):
+    """``dl_ring_scores`` on the result ``found`` of ``perceive_bonds`` for the same ``node_mask`` (``[B,N]`` or ``[B,N,1]``;
+    ``drop_mask`` and ``mark_mask`` alike, by row): device tensors in, a ``Rings`` of int32 device tensors out, no host
+    synchronisation.
+
+    THE RULE, over the simple graph of the kept atoms (real rows that ``drop_mask`` leaves) and the distinct bonds between
+    them: ``n_atoms``, ``n_bonds``, ``n_components`` ``[B]``; ``n_rings = n_bonds - n_atoms + n_components`` ``[B]``, the
+    cyclomatic number - RDKit's ring count except for cages such as cubane, where RDKit's symmetrised set has more;
+    ``bond_ring [B,capacity]``: for every list entry that is a kept bond the number of atoms of the smallest ring through
+    it, 0 for a bridge and for every other entry; ``atom_ring [B,N]`` by atom number (the k-th real row is atom k): the
+    smallest ring the atom lies in, 0 for none, for dropped atoms and from the atom count on; ``ring_hist [B,2,7]``: the kept
+    bonds by smallest ring (bin 0 none, bins 1-5 rings of 3-7 atoms, bin 6 of 8 or more), row 0 all of them, row 1 those
+    with a ``mark_mask`` end (zero without ``mark_mask``); ``status [B]``: the ``_lib.DL_BONDS_*`` bits of ``found``,
+    ``DL_RINGS_BAD_BOND`` and ``DL_RINGS_TOO_LARGE`` (more than 256 kept atoms: everything but ``n_atoms`` is 0); ``bonds``
+    is ``found``."""
+    masks = (node_mask,) + tuple(m for m in (drop_mask, mark_mask) if m is not None)
+    if not (all(m.is_cuda for m in masks) and found.bonds.is_cuda):
+        raise _lib.HipLibraryError('ring_scores runs on the HIP device only (no CPU fallback): '
+                                   f'got tensors on {", ".join(str(m.device) for m in masks)}, {found.bonds.device}')
+    B = found.n_bonds.shape[0]
+    if node_mask.numel() % max(B, 1) or (B == 0 and node_mask.dim() < 2):
+        raise ValueError(f'shapes disagree: node_mask {tuple(node_mask.shape)}, {B} bond lists')
+    N = node_mask.numel() // B if B else node_mask.shape[1]
+    if any(m.numel() != B * N for m in masks) or found.bonds.dim() != 3 or found.bonds.shape[0] != B:
+        raise ValueError(f'shapes disagree: masks {[tuple(m.shape) for m in masks]}, bonds {tuple(found.bonds.shape)}')
+    dev = node_mask.device
+    f32 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()     # noqa: E731
+    node_mask, drop_mask, mark_mask = f32(node_mask), f32(drop_mask), f32(mark_mask)
+    capacity = found.bonds.shape[1]
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    out = Rings(i32(B), i32(B), i32(B), i32(B), i32(B, capacity), i32(B, N), i32(B, 2, _lib.DL_RING_BINS), i32(B), found)
+    opt = lambda t: None if t is None else t.data_ptr()                     # noqa: E731
+    args = _lib.DLRingsArgs(
+        B=B, N=N, node_mask=node_mask.data_ptr(), drop_mask=opt(drop_mask), mark_mask=opt(mark_mask), capacity=capacity,
+        n_bonds_in=found.n_bonds.data_ptr(), bonds=found.bonds.data_ptr() if capacity else None,
+        status_in=found.status.data_ptr(), n_atoms=out.n_atoms.data_ptr(), n_bonds=out.n_bonds.data_ptr(),
+        n_components=out.n_components.data_ptr(), n_rings=out.n_rings.data_ptr(),
+        bond_ring=out.bond_ring.data_ptr() if capacity else None, atom_ring=out.atom_ring.data_ptr(),
+        ring_hist=out.ring_hist.data_ptr(), status=out.status.data_ptr())
+    with torch.cuda.device(dev):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.load().dl_ring_scores(ctypes.byref(args), stream), 'dl_ring_scores')
+    return out
+
+
+def analyze_rings(one_hot, x, node_mask, is_geom, linker_mask, drop_mask=None, margins=const.MARGINS_EDM):
+    """Rings of every molecule of a batch on the HIP device, in two views of ONE bond perception (``perceive_all_bonds``,
+    which synchronises; the two ``dl_ring_scores`` launches do not): ``(ligand, linker)``, both ``Rings``.
+
+    ``ligand``  the molecule without the ``drop_mask`` rows (the pocket of a pocket model), the ``linker_mask`` rows marked:
+                row 1 of its ``ring_hist`` holds the rings that linker bonds take part in, those closed through a fragment
+                included
+    ``linker``  everything that is not a linker row dropped: the linker as a molecule of its own, as the reference takes it
+                for ``rings_n`` (compute_metrics.py:128-145).  A ring closed through a fragment atom is absent here."""
+    if not (one_hot.is_cuda and x.is_cuda and node_mask.is_cuda and linker_mask.is_cuda):
+        raise _lib.HipLibraryError('analyze_rings runs on the HIP device only (no CPU fallback): '
+                                   f'got tensors on {one_hot.device}, {x.device}, {node_mask.device}, {linker_mask.device}')
+    B, N = one_hot.shape[:2]
+    if linker_mask.numel() != B * N:
+        raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, linker_mask {tuple(linker_mask.shape)}')
+    found = perceive_all_bonds(one_hot, x, node_mask, is_geom, margins)
+    linker = linker_mask.reshape(B, N).to(torch.float32)
+    ligand = ring_scores(node_mask, found, drop_mask, linker)
+    return ligand, ring_scores(node_mask, found, (linker == 0).to(torch.float32))
+
+
+def rings_to_host(ligand, linker):
+    """One ``RingRecord`` of plain values per molecule of the two views ``analyze_rings`` returns: ``n_rings`` of the linker
+    view, ``n_rings_ligand``, ``marked_hist`` (row 1 of the ligand view's ``ring_hist``: the linker's bonds by smallest ring)
+    and ``status``, the bits of both views."""
+    rings, rings_ligand = linker.n_rings.cpu().tolist(), ligand.n_rings.cpu().tolist()
+    marked = ligand.ring_hist[:, 1].cpu().tolist()
+    status = (ligand.status | linker.status).cpu().tolist()
+    return [RingRecord(*row) for row in zip(rings, rings_ligand, marked, status)]
+
+
+def _ring_scored(record):
+    return not record.status & ~_lib.DL_BONDS_NONFINITE
+
+
+def compute_rings(pred, true=None):
+    """Scores of the ``RingRecord`` values ``pred`` (``rings_to_host``), in fp64:
+
+    ``ring_molecules``    records scored; those with any status bit other than ``DL_BONDS_NONFINITE`` (a cut list, an entry
+                          that is no bond, more than 256 atoms) are left out of everything below
+    ``ring_flagged``      how many were left out
+    ``rings_n``           mean number of rings of the linker taken as a molecule of its own - the reference's column; the
+                          cyclomatic number, which is RDKit's count except for cages
+    ``rings_n_ligand``    the same over the whole ligand
+    ``ring_free``         share of the scored records whose linker has no ring
+    ``small_ring``        share with a linker bond in a three- or four-membered ring of the ligand
+    ``macrocycle``        share with a linker bond whose smallest ring in the ligand has 8 or more atoms
+    ``ring_bonds_3`` ... ``ring_bonds_7``, ``ring_bonds_8plus``
+                          the linker bonds that lie in a ring, summed over the scored records, split by the size of their
+                          smallest ring: shares that add up to 1
+
+    With ``true`` - one record per prediction, the data set's own molecule - over the positions where both are scored:
+    ``true_rings_n`` and ``rings_n_match``, the share of samples whose linker has as many rings as the data set's linker.
+    Shares are in [0, 1]; a mean or a share over nothing is ``None``, as in ``compute_shapes``."""
+    if true is not None and len(true) != len(pred):
+        raise ValueError(f'{len(pred)} predictions, {len(true)} true records')
+    mean = lambda values: float(sum(values) / len(values)) if values else None      # noqa: E731
+    good = [m for m in pred if _ring_scored(m)]
+    bins = [sum(m.marked_hist[k] for m in good) for k in range(_lib.DL_RING_BINS)]
+    in_rings = sum(bins[1:])
+    out = {'ring_molecules': len(good), 'ring_flagged': len(pred) - len(good),
+           'rings_n': mean([m.n_rings for m in good]), 'rings_n_ligand': mean([m.n_rings_ligand for m in good]),
+           'ring_free': mean([m.n_rings == 0 for m in good]),
+           'small_ring': mean([m.marked_hist[1] + m.marked_hist[2] > 0 for m in good]),
+           'macrocycle': mean([m.marked_hist[_lib.DL_RING_BINS - 1] > 0 for m in good])}
+    for k, name in enumerate(RING_NAMES[7:], start=1):
+        out[name] = float(bins[k] / in_rings) if in_rings else None
+    if true is not None:
+        both = [(p, t) for p, t in zip(pred, true) if _ring_scored(p) and _ring_scored(t)]
+        out['true_rings_n'] = mean([t.n_rings for _, t in both])
+        out['rings_n_match'] = mean([p.n_rings == t.n_rings for p, t in both])
     return out

@@ -56,7 +56,7 @@ def _prepare(checkpoint, prefix, data, n_steps, device):
 
 
 def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=None, linker_size_model=None,
-           output_format='xyz', metrics=False, geometry=False, clashes=False, shape=False):
+           output_format='xyz', metrics=False, geometry=False, clashes=False, shape=False, rings=False):
     """``sample.py``.  Returns the output directory.  ``metrics=True`` scores the molecules sampled in this call against
     the data set's own (``metrics.compute_metrics``: valence rule, connectivity, uniqueness, novelty, recovery) and writes
     the result to ``metrics.json`` in the output directory; with ``geometry=True`` as well, the symmetry-aware RMSD of the
@@ -69,13 +69,16 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
     both are asked for and alone otherwise.  ``shape=True`` scores EVERY sample's gridded van der Waals volume against its
     true molecule's, in the centred frame the two share and without the pocket rows (``metrics.analyze_shapes`` /
     ``compute_shapes``: once over the ligand rows, once over the linker rows alone); its keys go into ``metrics.json`` in the
-    same way, with ``shape_tanimoto_valid`` when ``metrics`` is asked for as well."""
+    same way, with ``shape_tanimoto_valid`` when ``metrics`` is asked for as well.  ``rings=True`` perceives the rings of
+    every sample and of its true molecule, pocket rows left out (``metrics.analyze_rings`` / ``compute_rings``: the linker's
+    ring count ``rings_n``, small rings, macrocycles), and writes those keys in the same way."""
     if output_format not in OUTPUT_FORMATS:
         raise ValueError(f'output_format must be one of {OUTPUT_FORMATS}, got {output_format!r}')
     found, pred, true, input_index = [], [], [], []
     pred_x, true_x, n_linker = [], [], []
     pred_clashes, true_clashes = [], []
     shapes, linker_shapes = [], []
+    pred_rings, true_rings = [], []
     geometry = geometry and metrics
     exp = 'model' if isinstance(checkpoint, DDPM) else checkpoint.split('/')[-1].replace('.ckpt', '')
     collate_fn, sample_fn = collate, None
@@ -130,6 +133,9 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
         if clashes:                                            # the data set's own linker in the same pocket
             true_clash_batch = mol_metrics.clashes_to_host(mol_metrics.analyze_clashes(
                 h[:, :, :model.num_classes], x, batch['linker_mask'], batch['pocket_mask'], is_geom=model.is_geom))
+        if rings:                                              # the data set's own molecule, without the pocket
+            true_ring_batch = mol_metrics.rings_to_host(*mol_metrics.analyze_rings(
+                h[:, :, :model.num_classes], x, node_mask, model.is_geom, batch['linker_mask']))
         if geometry:
             true_x_batch = list(mol_metrics.kept_positions(x, node_mask)[0])
             n_linker_batch = batch['linker_mask'].reshape(len(uuids), -1).sum(1).long().tolist()
@@ -155,6 +161,11 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 linker_shapes += mol_metrics.shapes_to_host(mol_metrics.analyze_shapes(
                     types, xs, out_mask * (1 - pad(batch['fragment_mask'])), true_types, x, batch['linker_mask'],
                     is_geom=model.is_geom))
+            if rings:                                          # out_mask holds no pocket row here
+                pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, out_mask.shape[1] - m.shape[1]))      # noqa: E731
+                pred_rings += mol_metrics.rings_to_host(*mol_metrics.analyze_rings(
+                    hs[:, :, :model.num_classes], xs, out_mask, model.is_geom, out_mask * (1 - pad(batch['fragment_mask']))))
+                true_rings += true_ring_batch
             if output_format != 'sdf':
                 save_xyz_file(output_dir, hs, xs, out_mask, [f'{u}/{i}' for u in uuids], is_geom=model.is_geom)
             if output_format != 'xyz':
@@ -172,7 +183,7 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 n_linker += n_linker_batch
     if found:
         print(json.dumps(summary(found)))
-    if metrics or clashes or shape:
+    if metrics or clashes or shape or rings:
         with open(os.path.join(output_dir, 'metrics.json'), 'w') as f:
             scores = {}
             if metrics:
@@ -183,6 +194,8 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 scores.update(mol_metrics.compute_clashes(pred_clashes, true_clashes))
             if shape:
                 scores.update(mol_metrics.compute_shapes(shapes, linker_shapes, pred if metrics else None))
+            if rings:
+                scores.update(mol_metrics.compute_rings(pred_rings, true_rings))
             json.dump(scores, f, indent=1)
     return output_dir
 
@@ -242,13 +255,17 @@ def main(argv=None):
     p.add_argument('--shape', action='store_true',
                    help='score every sample\'s gridded van der Waals volume against its true molecule on the GPU (this '
                         'project\'s grid after RDKit\'s defaults, not SC-RDKit) and write the scores to metrics.json')
+    p.add_argument('--rings', action='store_true',
+                   help='perceive the rings of every sample and of its true molecule on the GPU (ring count of the linker, '
+                        'small rings, macrocycles; the cyclomatic number, no aromaticity) and write the scores to metrics.json')
     a = p.parse_args(argv)
     if a.keep_frames is not None:
         print(sample_trajectories(a.checkpoint, a.samples, a.prefix, a.keep_frames, a.device, a.data, a.n_steps))
     else:
         print(sample(a.checkpoint, a.samples, a.prefix, a.n_samples, a.device, a.data, a.n_steps, a.linker_size_model,
                      a.output_format, a.metrics, **({'geometry': True} if a.geometry else {}),
-                     **({'clashes': True} if a.clashes else {}), **({'shape': True} if a.shape else {})))
+                     **({'clashes': True} if a.clashes else {}), **({'shape': True} if a.shape else {}),
+                     **({'rings': True} if a.rings else {})))
 
 
 if __name__ == '__main__':

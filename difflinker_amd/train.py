@@ -98,6 +98,9 @@ def main(argv=None):
     p.add_argument('--shape', action='store_true',
                    help='with --sample_every_epochs: add the gridded shape overlap of every sample with its true molecule to '
                         'the epoch scores')
+    p.add_argument('--rings', action='store_true',
+                   help='with --sample_every_epochs: add the ring scores of the samples (ring count of the linker, small rings, '
+                        'macrocycles) to the epoch scores')
     a = p.parse_args(argv)
     cfg = dict(DEFAULTS)
     if a.config is not None:
@@ -133,6 +136,7 @@ def main(argv=None):
     model.geometry_metrics = bool(a.geometry)
     model.clash_metrics = bool(a.clashes)
     model.shape_metrics = bool(a.shape)
+    model.ring_metrics = bool(a.rings)
     kept = lambda: {'best_validity_and_connectivity': best} if a.sample_every_epochs else {}   # noqa: E731
     step, epoch = start_step, start_epoch
     n_epochs = int(cfg['n_epochs'])

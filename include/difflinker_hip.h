@@ -49,6 +49,10 @@
  *                                           1 - rdShapeHelpers.ShapeProtrudeDist, compute_metrics.py:404-441): the gridded
  *                                           van der Waals overlap of every sample with its true molecule.  The rule stated
  *                                           below is this project's own after RDKit's defaults, NOT RDKit's grid
+ *   dl_ring_scores                       <- rings_n of compute_metrics.py:128-145 (CalcNumRings of the linker) and the ring
+ *                                           perception under its ring filter (:269-298), asked of the bond graph: the
+ *                                           cyclomatic number and the smallest ring through every bond.  No aromaticity,
+ *                                           so the filter itself is not reproduced
  *   dl_size_train_forward / dl_size_train_backward
  *                                        <- SizeClassifier.forward in training mode + loss.backward()
  *                                           (src/linker_size_lightning.py:83-117, :163-167)
@@ -844,6 +848,66 @@ typedef struct dl_shape_args {
     int32_t* status;                /* device int32 [B] out */
 } dl_shape_args;
 int32_t dl_shape_scores(const dl_shape_args* args, void* stream);
+
+/* ---- ring perception of a perceived batch (rings.hip) -------------------------------------------------------
+ * Ring topology of the bond graph dl_perceive_bonds left on the device: one workgroup per molecule, ONE launch per batch, no
+ * host round trip.  The list is read with the conventions of dl_molecule_keys: atom k is the k-th row with node_mask != 0;
+ * `drop_mask` (may be NULL) removes atoms AFTER that numbering, together with every bond that touches them; an entry
+ * (i, j, order) is a bond when 0 <= i, j < atoms, i != j and 1 <= order <= 3, in either orientation; any other entry is
+ * skipped and sets DL_RINGS_BAD_BOND.  `mark_mask` (may be NULL; [B,N] by row like drop_mask) marks atoms; the callers pass
+ * the linker mask.  Everything below is over the SIMPLE graph of the kept atoms and the distinct kept pairs; orders play no
+ * part beyond the validity of an entry.
+ *
+ *   n_atoms       kept atoms
+ *   n_bonds       distinct kept pairs
+ *   n_components  pieces of that graph
+ *   n_rings       n_bonds - n_atoms + n_components: the cyclomatic number, the size of a smallest set of smallest rings.
+ *                 It equals RDKit's ring count (CalcNumRings, RingInfo.NumRings) except for cages such as cubane, where
+ *                 RDKit's symmetrised set has more rings (6 for cubane; 5 here).
+ *   bond_ring     [B,capacity], written in full.  For list entry e that is a kept bond (u, v): the number of atoms of the
+ *                 smallest cycle through that bond, that is 1 + the length in bonds of the shortest path from u to v that
+ *                 does not use the bond itself; 0 when there is none (a bridge).  0 for every skipped entry, every entry
+ *                 with a dropped end, and every e >= min(n_bonds_in, capacity).  Repeated entries of one pair (in either
+ *                 orientation) all get that pair's value and set DL_RINGS_BAD_BOND; dl_perceive_bonds never emits them.
+ *   atom_ring     [B,N] by atom number: the smallest non-zero bond_ring over atom k's kept bonds; 0 when the atom is in no
+ *                 ring, when it is dropped, and from the atom count on.
+ *   ring_hist     [B,2,DL_RING_BINS].  Row 0 counts the list entries that are kept bonds by the bin of their bond_ring
+ *                 (bin 0: in no ring; bins 1..5: smallest ring of 3..7 atoms; bin 6: of 8 or more); row 1 counts the same
+ *                 only for bonds with at least one marked end, and is all zero when mark_mask is NULL.
+ *   status        the bits of `status_in`, plus DL_BONDS_OVERFLOW when n_bonds_in > capacity (a negative n_bonds_in counts
+ *                 as 0), DL_RINGS_BAD_BOND, and DL_RINGS_TOO_LARGE for more than DL_RINGS_MAX_ATOMS KEPT atoms: every
+ *                 output of that molecule except `status` and `n_atoms` is then 0 (its list is not looked at) and the other
+ *                 molecules of the launch are untouched.  N itself may be up to 1024: pockets are dropped, not counted.
+ *
+ * Integer work only: the same bits on every run and under every order of the list (bond_ring permuted with it).  Global
+ * memory is written with plain stores only, every output element is written, the callee allocates nothing.  A null `args`,
+ * B < 0, N < 1, N > 1024 or capacity < 0 return DL_ERR_BAD_ARG; then B == 0 returns DL_OK without a launch; then a null
+ * pointer (other than drop_mask, mark_mask, and `bonds` / `bond_ring` when capacity is 0) returns DL_ERR_BAD_ARG, all before
+ * any device work.
+ * Not here: aromaticity, enumerating the rings or counting them by size, fused / spiro / bridged classes. */
+#define DL_RINGS_MAX_ATOMS 256      /* kept atoms per molecule */
+#define DL_RING_BINS 7              /* 0: in no ring; 1..5: smallest ring of 3..7 atoms; 6: of 8 or more */
+#define DL_RINGS_TOO_LARGE 4        /* status bit, same value as DL_KEYS_TOO_LARGE */
+#define DL_RINGS_BAD_BOND 8         /* status bit, same value as DL_KEYS_BAD_BOND */
+typedef struct dl_rings_args {
+    int32_t B, N;
+    const float* node_mask;         /* device f32 [B,N] */
+    const float* drop_mask;         /* device f32 [B,N] or NULL */
+    const float* mark_mask;         /* device f32 [B,N] or NULL */
+    int32_t capacity;               /* bonds the list holds per molecule */
+    const int32_t* n_bonds_in;      /* device int32 [B]: dl_bonds_args.n_bonds */
+    const int32_t* bonds;           /* device int32 [B,capacity,3]: dl_bonds_args.bonds (may be NULL when capacity is 0) */
+    const int32_t* status_in;       /* device int32 [B]: dl_bonds_args.status */
+    int32_t* n_atoms;               /* device int32 [B] out */
+    int32_t* n_bonds;               /* device int32 [B] out */
+    int32_t* n_components;          /* device int32 [B] out */
+    int32_t* n_rings;               /* device int32 [B] out */
+    int32_t* bond_ring;             /* device int32 [B,capacity] out (may be NULL when capacity is 0) */
+    int32_t* atom_ring;             /* device int32 [B,N] out */
+    int32_t* ring_hist;             /* device int32 [B,2,DL_RING_BINS] out */
+    int32_t* status;                /* device int32 [B] out */
+} dl_rings_args;
+int32_t dl_ring_scores(const dl_rings_args* args, void* stream);
 
 const char* dl_error_string(int32_t status);
 int32_t dl_last_hip_error(void);
