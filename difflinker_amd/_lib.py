@@ -200,6 +200,25 @@ class DLRingsArgs(ctypes.Structure):
     ]
 
 
+DL_FRAG_MAX_ATOMS, DL_FRAG_CUT_FIELDS = 256, 10        # dl_fragment_args: atoms per molecule; int32 values per cut record
+DL_FRAG_TOO_LARGE, DL_FRAG_BAD_BOND = 4, 8            # dl_fragment_args.status bits, beside the DL_BONDS_* bits carried forward
+DL_FRAG_DISCONNECTED, DL_FRAG_TRUNCATED = 16, 32
+
+
+class DLFragmentArgs(ctypes.Structure):
+    _fields_ = [
+        ('B', ctypes.c_int32), ('N', ctypes.c_int32), ('nf', ctypes.c_int32),
+        ('one_hot', ctypes.c_void_p), ('node_mask', ctypes.c_void_p), ('charge', ctypes.c_void_p),
+        ('carbon_type', ctypes.c_int32), ('capacity', ctypes.c_int32),
+        ('n_bonds_in', ctypes.c_void_p), ('bonds', ctypes.c_void_p), ('status_in', ctypes.c_void_p),
+        ('min_linker', ctypes.c_int32), ('min_fragment', ctypes.c_int32), ('min_path_atoms', ctypes.c_int32),
+        ('linker_leq_frags', ctypes.c_int32), ('R', ctypes.c_int32),
+        ('n_atoms', ctypes.c_void_p), ('n_bonds', ctypes.c_void_p), ('n_cuttable', ctypes.c_void_p),
+        ('n_cuts', ctypes.c_void_p), ('status', ctypes.c_void_p), ('bond_side', ctypes.c_void_p),
+        ('cuts', ctypes.c_void_p), ('labels', ctypes.c_void_p),
+    ]
+
+
 EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_string', 'dl_model_num_tensors',
            'dl_model_create', 'dl_model_destroy', 'dl_egnn_forward_fc', 'dl_sampler_step', 'dl_sample_chain_fc',
            'dl_set_profile_buffer', 'dl_profile_max_events', 'dl_pocket_workspace_bytes', 'dl_egnn_forward_pocket',
@@ -211,7 +230,7 @@ EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_stri
            'dl_egnn_backward_pocket_workspace_bytes', 'dl_egnn_backward_pocket',
            'dl_size_train_num_params', 'dl_size_train_workspace_bytes', 'dl_size_train_forward', 'dl_size_train_backward',
            'dl_join_workspace_bytes', 'dl_sample_chain_fc_join', 'dl_bonds_workspace_bytes', 'dl_perceive_bonds',
-           'dl_molecule_keys', 'dl_clash_scores', 'dl_shape_scores', 'dl_ring_scores',
+           'dl_molecule_keys', 'dl_clash_scores', 'dl_shape_scores', 'dl_ring_scores', 'dl_fragment_cuts',
            'dl_best_rmsd')
 TEST_HOOK_EXPORTS = ('dl_debug_team_fault',)       # declared under #ifdef DL_TEST_HOOKS: the test-hooks build only
 
@@ -338,6 +357,8 @@ def _open(path):
     lib.dl_shape_scores.argtypes = [ctypes.POINTER(DLShapeArgs), vp]
     lib.dl_ring_scores.restype = i32
     lib.dl_ring_scores.argtypes = [ctypes.POINTER(DLRingsArgs), vp]
+    lib.dl_fragment_cuts.restype = i32
+    lib.dl_fragment_cuts.argtypes = [ctypes.POINTER(DLFragmentArgs), vp]
     lib.dl_best_rmsd.restype = i32
     lib.dl_best_rmsd.argtypes = [ctypes.POINTER(DLRmsdArgs), vp]
     lib.dl_size_model_num_tensors.restype = i32

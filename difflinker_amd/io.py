@@ -8,6 +8,7 @@ symbols and coordinates, so the few record types involved are parsed here direct
 * ``read_molecule``: first molecule of an ``.sdf`` / ``.mol`` (V2000 and V3000 atom blocks), ``.pdb`` (first model,
   first alternate location), ``.mol2`` (``@<TRIPOS>ATOM``) or ``.xyz`` file, hydrogens removed
   (``removeHs=True`` + ``Chem.RemoveAllHs``, generate.py:53-59,117);
+* ``read_sdf_molecules``: EVERY record of an ``.sdf`` with its bond block and formal charges, for ``difflinker_amd.prepare``;
 * ``parse_molecule``: positions / one-hot / charges with the reference's vocabularies (src/datasets.py:22-37);
 * ``read_pocket`` / ``get_pocket``: the pocket dictionaries of the two pocket scripts, including their quirks
   (every model is walked, the highest-occupancy alternate location is kept, contact residues are matched by residue
@@ -158,6 +159,101 @@ def read_molecule(path):
     if not symbols:
         raise ValueError(f'no atoms found in {path}')
     return _without_hydrogens(symbols, coords, name or base)
+
+
+@dataclass
+class BondedMolecule(Molecule):
+    """A record of ``read_sdf_molecules``: heavy atoms with their bonds ``(i, j, order)`` (0-based, as the file orients them,
+    order 4 aromatic), formal ``charges`` per atom, and whether the record has 3D coordinates."""
+    bonds: List[tuple] = field(default_factory=list)
+    charges: List[int] = field(default_factory=list)
+    is_3d: bool = True
+
+
+_V2000_CHARGE = {0: 0, 1: 3, 2: 2, 3: 1, 4: 0, 5: -1, 6: -2, 7: -3}     # the atom block's charge column (4: a radical)
+
+
+def _read_bonded_molblock(lines):
+    """One whole CTfile record (V2000 or V3000): ``(symbols, coords, charges, bonds, name, flat)``, hydrogens included."""
+    if len(lines) < 4:
+        raise ValueError('truncated mol block')
+    name, counts = lines[0].strip(), lines[3]
+    symbols, coords, charges, bonds = [], [], [], []
+    if 'V3000' in counts:
+        section, index, n_atoms, n_bonds = None, {}, None, None
+        for ln in lines[4:]:
+            t = ln.strip()
+            if not t.startswith('M  V30'):
+                continue
+            parts = t.split()[2:]
+            if parts[:1] == ['COUNTS']:
+                n_atoms, n_bonds = int(parts[1]), int(parts[2])
+            elif parts[:1] in (['BEGIN'], ['END']):
+                section = parts[1] if parts[0] == 'BEGIN' else None
+            elif section == 'ATOM':
+                index[int(parts[0])] = len(symbols)
+                symbols.append(_symbol(parts[1]))
+                coords.append([float(parts[2]), float(parts[3]), float(parts[4])])
+                charges.append(sum(int(p[4:]) for p in parts[6:] if p.startswith('CHG=')))
+            elif section == 'BOND':
+                bonds.append((index[int(parts[2])], index[int(parts[3])], int(parts[1])))
+        if n_atoms != len(symbols) or n_bonds != len(bonds):
+            raise ValueError('the V3000 counts line and the blocks disagree')
+    else:
+        n_atoms, n_bonds = int(counts[0:3]), int(counts[3:6])
+        if len(lines) < 4 + n_atoms + n_bonds:
+            raise ValueError('truncated atom or bond block')
+        for ln in lines[4:4 + n_atoms]:
+            coords.append([float(ln[0:10]), float(ln[10:20]), float(ln[20:30])])
+            symbols.append(_symbol(ln[31:34]))
+            charges.append(_V2000_CHARGE[int(ln[36:39].strip() or 0)])
+        for ln in lines[4 + n_atoms:4 + n_atoms + n_bonds]:
+            i, j, order = int(ln[0:3]), int(ln[3:6]), int(ln[6:9])
+            if not (1 <= i <= n_atoms and 1 <= j <= n_atoms):
+                raise ValueError(f'bond {i}-{j} of {n_atoms} atoms')
+            bonds.append((i - 1, j - 1, order))
+        listed = [ln for ln in lines[4 + n_atoms + n_bonds:] if ln.startswith('M  CHG') or ln.startswith('M  RAD')]
+        if listed:                               # property lines replace the whole charge column
+            charges = [0] * n_atoms
+        for ln in listed:
+            if ln.startswith('M  CHG'):
+                parts = ln.split()
+                for k in range(int(parts[2])):
+                    charges[int(parts[3 + 2 * k]) - 1] = int(parts[4 + 2 * k])
+    flat = lines[1][20:22] == '2D' or all(c[2] == 0.0 for c in coords)
+    return symbols, coords, charges, bonds, name, flat
+
+
+def read_sdf_molecules(path):
+    """EVERY record of an SDF file as a ``BondedMolecule``: atom AND bond blocks of V2000 and V3000 records, formal charges
+    from ``M  CHG`` lines, the atom block's charge column or ``CHG=``.  Hydrogens are removed together with their bonds and
+    the bond indices renumbered.  A malformed record is skipped and counted: returns ``(molecules, n_malformed)``.
+    ``read_molecule`` (first record, atoms only) stays what the generation scripts use."""
+    with open(path) as f:
+        lines = f.read().splitlines()
+    records, start = [], 0
+    for k, ln in enumerate(lines):
+        if ln.strip() == '$$$$':
+            records.append(lines[start:k])
+            start = k + 1
+    if any(ln.strip() for ln in lines[start:]):
+        records.append(lines[start:])            # a last record without its terminator
+    molecules, malformed = [], 0
+    for number, record in enumerate(records):
+        try:
+            symbols, coords, charges, bonds, name, flat = _read_bonded_molblock(record)
+            if not symbols:
+                raise ValueError('no atoms')
+        except (ValueError, IndexError, KeyError):
+            malformed += 1
+            continue
+        keep = [i for i, s in enumerate(symbols) if s not in ('H', 'D', 'T')]
+        new = {old: k for k, old in enumerate(keep)}
+        pos = np.asarray([coords[i] for i in keep], dtype=np.float64).reshape(len(keep), 3)
+        molecules.append(BondedMolecule([symbols[i] for i in keep], pos, name or f'record_{number}',
+                                        bonds=[(new[i], new[j], order) for i, j, order in bonds if i in new and j in new],
+                                        charges=[charges[i] for i in keep], is_3d=not flat))
+    return molecules, malformed
 
 
 def get_one_hot(atom, atoms_dict):

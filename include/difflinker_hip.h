@@ -53,6 +53,9 @@
  *                                           perception under its ring filter (:269-298), asked of the bond graph: the
  *                                           cyclomatic number and the smallest ring through every bond.  No aromaticity,
  *                                           so the filter itself is not reproduced
+ *   dl_fragment_cuts                     <- FragmentMol(minCuts = maxCuts = 2) with DeLinker's pattern
+ *                                           (data/geom/generate_geom_multifrag.py:199-206) and the re-assembly of
+ *                                           data/zinc/prepare_dataset.py, src/datasets.py:56-100
  *   dl_size_train_forward / dl_size_train_backward
  *                                        <- SizeClassifier.forward in training mode + loss.backward()
  *                                           (src/linker_size_lightning.py:83-117, :163-167)
@@ -908,6 +911,83 @@ typedef struct dl_rings_args {
     int32_t* status;                /* device int32 [B] out */
 } dl_rings_args;
 int32_t dl_ring_scores(const dl_rings_args* args, void* stream);
+
+/* ---- matched-pair double cuts: linker-design examples from molecules (fragment.hip) --------------------------
+ * Every way to cut a molecule at two bonds into fragment 1, linker and fragment 2: one workgroup per molecule, ONE launch
+ * per batch.  This project's statement of DeLinker's preparation rule, after RDKit's FragmentMol with minCuts = maxCuts = 2
+ * and the pattern [#6+0;!$(*=,#[!#6])]!@!=!#[*], over heavy atoms.
+ *
+ * INPUT.  Atom k is the k-th row with node_mask != 0; its type is the FIRST largest entry of its one_hot row; `charge`
+ * ([B,N] by row; NULL: 0 everywhere) is its formal charge.  The bond list has the layout of dl_perceive_bonds: an entry
+ * (i, j, order) is a bond when 0 <= i, j < atoms, i != j and 1 <= order <= 4 (4: aromatic), in either orientation; any
+ * other entry is skipped and sets DL_FRAG_BAD_BOND.  A repeated pair counts once, as its FIRST entry (position and order),
+ * and sets DL_FRAG_BAD_BOND.  Entries from min(n_bonds_in, capacity) on are not read.
+ *
+ * CUTTABLE.  A bond is cuttable when (1) its order is 1, (2) it lies in no ring: removing it disconnects its ends, and
+ * (3) at least one end is a carbon (type == carbon_type) with charge 0 that has no order-2 or order-3 bond to a non-carbon
+ * atom.  The other end is any atom.  So C(=O)-N and C(=O)-O are not cuttable, C(=O)-C is (through its other end), and N-O
+ * never is.
+ *
+ * CUTS.  The molecule must be one piece, otherwise DL_FRAG_DISCONNECTED and no cuts (a molecule without atoms is no piece
+ * and has no cuts either).  Every unordered pair of cuttable bonds e1 < e2 (list positions of their first entries) splits it
+ * into three pieces: the LINKER touches both bonds, fragment 1 lies beyond e1, fragment 2 beyond e2.  anchor_k is the
+ * fragment atom of bond e_k, exit_k its linker atom.  path_atoms is the number of atoms on the shortest path from exit_1 to
+ * exit_2, both counted (1 when they are one atom); both bonds are bridges, so that path stays inside the linker.  A pair is
+ * KEPT when n_linker >= min_linker, n_frag_1 >= min_fragment, n_frag_2 >= min_fragment, path_atoms >= min_path_atoms and,
+ * when linker_leq_frags != 0, n_linker <= min(n_frag_1, n_frag_2).  DeLinker's values are 3, 5, 2, 1.  Kept pairs are
+ * numbered in lexicographic order of (e1, e2).
+ *
+ *   n_atoms     atoms (real rows)
+ *   n_bonds     distinct pairs of the list
+ *   n_cuttable  cuttable bonds (also reported for a molecule of several pieces)
+ *   n_cuts      ALL kept pairs, also those beyond R
+ *   bond_side   [B,capacity], written in full: for the first entry of a cuttable bond the number of atoms on the side of its
+ *               atom i; 0 for every other entry
+ *   cuts        [B,R,DL_FRAG_CUT_FIELDS]: the first min(n_cuts, R) records (e1, e2, anchor_1, exit_1, anchor_2, exit_2,
+ *               n_frag_1, n_frag_2, n_linker, path_atoms); zeros after them
+ *   labels      uint8 [B,R,N] by atom number: 0 fragment 1, 1 fragment 2, 2 linker; 255 from the atom count on and in
+ *               every unused record
+ *   status      the bits of `status_in` (NULL: none), plus DL_BONDS_OVERFLOW when n_bonds_in > capacity (a negative
+ *               n_bonds_in counts as 0), DL_FRAG_BAD_BOND, DL_FRAG_DISCONNECTED, DL_FRAG_TRUNCATED (n_cuts > R) and
+ *               DL_FRAG_TOO_LARGE for more than DL_FRAG_MAX_ATOMS atoms: every count of that molecule except n_atoms is
+ *               then 0, its bond_side and cuts are 0 and its labels 255 (no record is used; its list is not looked at),
+ *               and the other molecules of the launch are untouched.
+ *
+ * Integer work only: the same bits on every run.  Global memory is written with plain stores only, every output element is
+ * written, the callee allocates nothing.  A null `args`, B < 0, N < 1, N > 1024, nf < 1, carbon_type outside [0, nf),
+ * capacity < 0 or R < 0 return DL_ERR_BAD_ARG; then B == 0 returns DL_OK without a launch; then a null pointer (other than
+ * charge, status_in, `bonds` / `bond_side` when capacity is 0 and `cuts` / `labels` when R is 0) returns DL_ERR_BAD_ARG, all
+ * before any device work.
+ * Not here: SMILES (so symmetric cuts are not merged), conformers, BRICS, cuts at three or more bonds, pockets, aromaticity
+ * perception beyond the list's orders, hydrogens. */
+#define DL_FRAG_MAX_ATOMS 256       /* atoms per molecule */
+#define DL_FRAG_CUT_FIELDS 10       /* int32 values per record of `cuts` */
+#define DL_FRAG_TOO_LARGE 4         /* status bit, same value as DL_KEYS_TOO_LARGE */
+#define DL_FRAG_BAD_BOND 8          /* status bit, same value as DL_KEYS_BAD_BOND */
+#define DL_FRAG_DISCONNECTED 16     /* status bit: the molecule is not one piece; no cuts */
+#define DL_FRAG_TRUNCATED 32        /* status bit: n_cuts > R; `cuts` and `labels` hold the first R */
+typedef struct dl_fragment_args {
+    int32_t B, N, nf;
+    const float* one_hot;           /* device f32 [B,N,nf] */
+    const float* node_mask;         /* device f32 [B,N] */
+    const int32_t* charge;          /* device int32 [B,N] by row, or NULL */
+    int32_t carbon_type;            /* index of carbon in the type table */
+    int32_t capacity;               /* bonds the list holds per molecule */
+    const int32_t* n_bonds_in;      /* device int32 [B] */
+    const int32_t* bonds;           /* device int32 [B,capacity,3] (may be NULL when capacity is 0) */
+    const int32_t* status_in;       /* device int32 [B]: dl_bonds_args.status, or NULL */
+    int32_t min_linker, min_fragment, min_path_atoms, linker_leq_frags;
+    int32_t R;                      /* records `cuts` and `labels` hold per molecule */
+    int32_t* n_atoms;               /* device int32 [B] out */
+    int32_t* n_bonds;               /* device int32 [B] out */
+    int32_t* n_cuttable;            /* device int32 [B] out */
+    int32_t* n_cuts;                /* device int32 [B] out */
+    int32_t* status;                /* device int32 [B] out */
+    int32_t* bond_side;             /* device int32 [B,capacity] out (may be NULL when capacity is 0) */
+    int32_t* cuts;                  /* device int32 [B,R,DL_FRAG_CUT_FIELDS] out (may be NULL when R is 0) */
+    uint8_t* labels;                /* device uint8 [B,R,N] out (may be NULL when R is 0) */
+} dl_fragment_args;
+int32_t dl_fragment_cuts(const dl_fragment_args* args, void* stream);
 
 const char* dl_error_string(int32_t status);
 int32_t dl_last_hip_error(void);
