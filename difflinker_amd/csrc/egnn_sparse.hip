@@ -8,15 +8,21 @@
 //   * the radius graph is rebuilt on the GPU every forward (count -> scan -> fill), one wave per atom; each
 //     atom's neighbour list is padded to whole QUADS of 8 edge slots and the lists follow each other, so an MFMA tile
 //     (32 consecutive slots = 4 quads) holds the edges of up to four receiving atoms (padding: 5 % of the slots at
-//     the pocket configuration; whole tiles per atom cost 22 %);
+//     the pocket configuration; whole tiles per atom cost 22 %); every MOLECULE's quads start on a tile boundary (up to
+//     three padding quads behind its last atom), so no tile holds atoms of two molecules;
 //   * the edge pass runs over tiles: first layer generated as MFMA A-fragments from gathered P_i, Q_j rows,
 //     second layer [32x128]x[128x128] on v_mfma_f32_32x32x2_f32 with the weights in LDS, SiLU, and the sum
 //     over the edges of each quad reduced IN REGISTERS; quads of one atom inside a tile are merged, so a tile writes
 //     one partial row per receiving atom it holds (no atomics: the node kernel adds an atom's partial rows in a
 //     fixed order, so the result is deterministic);
-//   * the node MLP (+ the next pass's projections) is one kernel per pass over 32-atom row tiles.
+//   * the node MLP (+ the next pass's projections) is one kernel per pass over 32-atom row tiles, cut per molecule.
 // Arithmetic: fp32 MFMA or the f16x3 split scheme of egnn_fc.hip (template PREC); on this path the fp16 scales are
 // local: every node-kernel workgroup scales its own 32-row tiles, every edge tile is scaled by its own max |u|.
+// Batch independence: edge tiles and row tiles belong to ONE molecule, and an atom's partial sums are grouped by the
+// position of its quads inside its molecule's tiles - so the output rows of molecule b are a function of molecule b and
+// the padded width N alone: the same bits alone, in any batch, at any position in it, next to any neighbours
+// (tests/test_gpu_batch_independence.py).  What stays batch-wide (the maxima behind the coordinate pass's widening test,
+// TW_FULL) decides which tiles are computed, never a value.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -46,15 +52,21 @@ struct PkWs {
     int *flags, *ntile, *tile_off, *tile_row, *col, *total;   // ntile / tile_off / tile_row count QUADS (8 edge slots)
     int* deg;                                                 // edges per receiving atom ('mean' divides by it, egnn.py:315-319)
     int* eq_tiles;                                            // tiles with a receiving atom the coordinate update keeps; count: total[1]
+    int *mol_q, *mol_adj;                                     // pk_scan_kernel: per molecule, quads in front of it without / the shift to its padded start
+    int* range;                                               // nan_flags of the call: a molecule whose f16-mode scale left the fp16 range is reported there
     size_t bytes;
 };
 
 __host__ __device__ inline size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
 
+// upper bound of the quad count: every atom pads its list to a multiple of 8 slots, every molecule its quads to a multiple of 4
+__host__ __device__ inline size_t quad_cap(int B, int N) { return size_t(B) * N * (N / 8 + 1) + size_t(B) * 3 + 4; }
+__host__ __device__ inline size_t tile_cap(int B, int N) { return quad_cap(B, N) / 4 + 1; }                 // MFMA tiles of 32 slots
+
 inline PkWs carve(void* base, int B, int N) {
     const size_t V = size_t(B) * N;
-    const size_t QMAX = V * (N / 8 + 1) + 4;                       // quads: every atom pads its list to a multiple of 8 slots
-    const size_t TMAX = QMAX / 4 + 1;                               // MFMA tiles of 32 slots
+    const size_t QMAX = quad_cap(B, N);
+    const size_t TMAX = tile_cap(B, N);
     char* p = static_cast<char*>(base);
     size_t off = 0;
     auto take = [&](size_t bytes) { char* r = p ? p + off : nullptr; off += al256(bytes); return r; };
@@ -71,6 +83,9 @@ inline PkWs carve(void* base, int B, int N) {
     w.deg = reinterpret_cast<int*>(take(V * 4));
     w.tile_off = reinterpret_cast<int*>(take((V + 1) * 4));
     w.total = reinterpret_cast<int*>(take(256));
+    w.mol_q = reinterpret_cast<int*>(take((size_t(B) + 1) * 4));
+    w.mol_adj = reinterpret_cast<int*>(take((size_t(B) + 1) * 4));
+    w.range = nullptr;                                             // (not scratch: run_sparse points it at the call's nan_flags)
     w.tile_row = reinterpret_cast<int*>(take(QMAX * 4));
     w.eq_tiles = reinterpret_cast<int*>(take(TMAX * 4));
     w.col = reinterpret_cast<int*>(take(TMAX * 32 * 4));
@@ -89,9 +104,10 @@ inline PkWs carve(void* base, int B, int N) {
 // edge kernel, read by pk_xupdate_kernel), [4..6] float bits of the batch-wide maxima of |h|, |x|^2, |x0|^2 (atomicMax; never reset
 // inside a forward: conservative) - what the proof behind skipping the masked coordinate sums needs (pk_edge_kernel<EQUIV>)
 constexpr int TW_FULL = 2, TW_HMAX = 4, TW_X2 = 5, TW_X02 = 6;
-// [7]: some f16-mode scale of this forward came from a bound beyond the fp16 range (pack_layout.h: beyond_f16_range) - the scales
-// here belong to tiles, not to molecules, so pk_out_kernel reports every molecule of the call (NAN_RANGE | x | h)
-constexpr int TW_RANGE = 7;
+// An f16-mode scale that came from a bound beyond the fp16 range (pack_layout.h: beyond_f16_range): every tile, of rows or of
+// edges, belongs to one molecule, and that molecule alone is reported (NAN_RANGE | x | h in its nan_flags word, which run_sparse
+// zeroes before the first kernel)
+__device__ __forceinline__ void report_range(int* range, int mol) { atomicOr(range + mol, NAN_RANGE | 3); }
 // batch-wide maximum of non-negative floats (as bits: they order like the values, NaN above all): the atomic is issued only when
 // the word - read relaxed, possibly stale, i.e. LOWER - does not already hold as much; after the first few waves of a kernel nobody
 // issues one (19 k atoms x 128 features of atomics on ONE address cost a forward of the pocket configuration a third of its time)
@@ -204,37 +220,71 @@ __global__ void pk_edges_kernel(PkDims d, PkWs w) {
     if (!FILL) {
         if (lane == 0) { w.ntile[v] = nt; w.deg[v] = count; }
     } else {
-        for (int e = count + lane; e < nt * 8; e += 64) {                                           // padding
+        // the quads up to the next atom's first one: this atom's own and, behind the LAST atom of a molecule, the padding quads that
+        // complete the molecule's last tile (pk_scan_kernel) - empty slots of this atom as far as the edge kernel is concerned,
+        // and outside [tile_off, tile_off + ntile), the quads the node kernel and the coordinate update add up
+        const int na = w.tile_off[v + 1] - base_tile;
+        for (int e = count + lane; e < na * 8; e += 64) {                                           // padding
             w.col[size_t(base_tile) * 8 + e] = -1;
             w.wgt[size_t(base_tile) * 8 + e] = 0.0f;
         }
-        for (int k = lane; k < nt; k += 64) w.tile_row[base_tile + k] = v;
+        for (int k = lane; k < na; k += 64) w.tile_row[base_tile + k] = v;
     }
 }
 
-// 3. exclusive scan of ntile[0..V) -> tile_off, total quad count (single workgroup)
-// (also marks the slots between the last quad and the end of its tile as padding: nothing else ever writes them)
-__global__ void pk_scan_kernel(int V, const int* __restrict__ ntile, int* __restrict__ tile_off, int* __restrict__ total,
-                               int* __restrict__ col, float* __restrict__ wgt) {
+// 3. exclusive scan of ntile[0..V) -> tile_off, total quad count (single workgroup), with every molecule's first quad moved up
+//    to the next tile boundary (a multiple of 4 quads): a molecule's tiles, the grouping of its atoms' partial sums and the
+//    scales of its edge tiles then do not depend on the molecules in front of it.  Three passes: the plain scan (which notes
+//    the count in front of every molecule), a scan of the molecules' padded totals, the shifted offsets.
+__global__ void pk_scan_kernel(int B, int N, const int* __restrict__ ntile, int* __restrict__ tile_off, int* __restrict__ total,
+                               int* __restrict__ mol_q, int* __restrict__ mol_adj) {
     __shared__ int part[1024];
+    const int V = B * N;
     const int tid = threadIdx.x, nth = blockDim.x;
+    auto block_scan = [&](int s) {                                  // inclusive scan of one value per thread
+        part[tid] = s;
+        __syncthreads();
+        for (int off = 1; off < nth; off <<= 1) {
+            const int add = (tid >= off) ? part[tid - off] : 0;
+            __syncthreads();
+            part[tid] += add;
+            __syncthreads();
+        }
+        return part[tid];
+    };
     const int per = (V + nth - 1) / nth;
     const int lo = min(tid * per, V), hi = min(lo + per, V);
     int s = 0;
     for (int i = lo; i < hi; ++i) s += ntile[i];
-    part[tid] = s;
-    __syncthreads();
-    for (int off = 1; off < nth; off <<= 1) {
-        const int add = (tid >= off) ? part[tid - off] : 0;
-        __syncthreads();
-        part[tid] += add;
-        __syncthreads();
+    const int run0 = block_scan(s) - s;
+    if (lo < hi) {
+        int run = run0, next = ((lo + N - 1) / N) * N;              // the first molecule boundary at or behind lo
+        for (int i = lo; i < hi; ++i) {
+            if (i == next) { mol_q[i / N] = run; next += N; }
+            run += ntile[i];
+        }
     }
-    int run = part[tid] - s;
-    for (int i = lo; i < hi; ++i) { tile_off[i] = run; run += ntile[i]; }
-    if (tid == nth - 1) { tile_off[V] = part[tid]; total[0] = part[tid]; total[1] = 0; }   // total[1]: pk_eqtiles_kernel's counter
-    const int nq = part[nth - 1];                                   // every quad of every atom
-    for (int e = nq * 8 + tid; e < ((nq + 3) >> 2) * 32; e += nth) { col[e] = -1; wgt[e] = 0.0f; }
+    if (tid == nth - 1) mol_q[B] = part[tid];
+    __syncthreads();                                                // mol_q is complete (one workgroup: the barrier orders its global writes)
+    const int perb = (B + nth - 1) / nth;
+    const int blo = min(tid * perb, B), bhi = min(blo + perb, B);
+    int sb = 0;
+    for (int b = blo; b < bhi; ++b) sb += (mol_q[b + 1] - mol_q[b] + 3) & ~3;
+    int runb = block_scan(sb) - sb;
+    for (int b = blo; b < bhi; ++b) { mol_adj[b] = runb - mol_q[b]; runb += (mol_q[b + 1] - mol_q[b] + 3) & ~3; }
+    if (tid == nth - 1) {                                           // the padded total: a whole number of tiles
+        mol_adj[B] = part[tid] - mol_q[B];
+        tile_off[V] = part[tid]; total[0] = part[tid]; total[1] = 0;   // total[1]: pk_eqtiles_kernel's counter
+    }
+    __syncthreads();
+    if (lo < hi) {
+        int run = run0, b = lo / N, next = (b + 1) * N, adj = mol_adj[b];
+        for (int i = lo; i < hi; ++i) {
+            if (i == next) { ++b; next += N; adj = mol_adj[b]; }
+            tile_off[i] = run + adj;
+            run += ntile[i];
+        }
+    }
 }
 
 // 4b. the tiles of the coordinate pass: the reference multiplies the coordinate sum of every atom outside the linker mask
@@ -300,7 +350,8 @@ __device__ __forceinline__ void wg_max(unsigned* slot, float val, int lane) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// 5. node kernel, one workgroup (4 waves = 4 feature tiles) per 32-atom row tile:
+// 5. node kernel, one workgroup (4 waves = 4 feature tiles) per 32-atom row tile; the tiles are cut per molecule (ceil(N / 32)
+//    each, the last one short), so the fp16 scales a workgroup takes from its rows' maxima are those of one molecule:
 //    POST: agg = (sum of the atom's tile partials), t = SiLU(W3a' h + W3b' agg + b3'), h += W4' t + b4, masked
 //          (GCL.node_model egnn.py:62-72,78-79);   PRE: P = W1a' h + b1', Q = W1b' h for the NEXT pass.
 // ---------------------------------------------------------------------------------------------------
@@ -316,7 +367,10 @@ pk_node_kernel(PkDims d, PkWs w, const float* __restrict__ post, const float* __
     const int tid = threadIdx.x;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63, c = lane & 31, hh = lane >> 5;
-    const int row0 = blockIdx.x * 32;
+    const int tpm = (d.N + 31) >> 5;                                // row tiles per molecule
+    const int mol = blockIdx.x / tpm, mt = blockIdx.x - mol * tpm;
+    const int row0 = mol * d.N + 32 * mt;
+    const int nrows = min(32, d.N - 32 * mt);                       // rows of this tile: the molecule's, never its neighbour's
     if (tid < 4) mx[tid] = 0u;
     if (tid < 64) rowmx[tid >> 5][tid & 31] = 0u;
     __syncthreads();
@@ -326,7 +380,7 @@ pk_node_kernel(PkDims d, PkWs w, const float* __restrict__ post, const float* __
         const int r = e >> 5, q = e & 31;
         const int v = row0 + r;
         float4 hv = make_float4(0.f, 0.f, 0.f, 0.f), av = hv;
-        if (v < d.V) {
+        if (r < nrows) {
             hv = *reinterpret_cast<const float4*>(w.H + size_t(v) * HID + 4 * q);
             if (post) {
                 const int q0 = w.tile_off[v], nq = w.ntile[v];      // the atom's quads
@@ -365,7 +419,7 @@ pk_node_kernel(PkDims d, PkWs w, const float* __restrict__ post, const float* __
         if (PREC == 1) {
             const float sw3a = sc[GS_SW_W3A + nt], sw3b = sc[GS_SW_W3B + nt];     // one weight scale per output tile (balanced packing)
             const float S = fminf(s_h * sw3a, scale_for(__uint_as_float(mx[1])) * sw3b);
-            if (tid == 0 && (beyond_f16_range(__uint_as_float(mx[0])) || beyond_f16_range(__uint_as_float(mx[1])))) w.total[TW_RANGE] = 1;
+            if (tid == 0 && (beyond_f16_range(__uint_as_float(mx[0])) || beyond_f16_range(__uint_as_float(mx[1])))) report_range(w.range, mol);
             s1 = S * inv_pow2(sw3a); s2 = S * inv_pow2(sw3b); inv = inv_pow2(S);
         }
         floatx16 acc = splat16(PREC == 0 ? b3 : 0.0f);
@@ -392,7 +446,7 @@ pk_node_kernel(PkDims d, PkWs w, const float* __restrict__ post, const float* __
         float s_t = 1.0f, inv4 = 1.0f;
         if (PREC == 1) {
             s_t = scale_for(__uint_as_float(mx[2])); inv4 = inv_pow2(s_t * sc[4]);
-            if (tid == 0 && beyond_f16_range(__uint_as_float(mx[2]))) w.total[TW_RANGE] = 1;
+            if (tid == 0 && beyond_f16_range(__uint_as_float(mx[2]))) report_range(w.range, mol);
         }
         floatx16 hn;
 #pragma unroll
@@ -411,16 +465,16 @@ pk_node_kernel(PkDims d, PkWs w, const float* __restrict__ post, const float* __
         for (int reg = 0; reg < 16; ++reg) {
             const int r = acc_row(reg, hh);
             const int v = row0 + r;
-            const float val = (v < d.V && (w.flags[v] & F_REAL)) ? hn[reg] : 0.0f;   // h * node_mask
+            const float val = (r < nrows && (w.flags[v] & F_REAL)) ? hn[reg] : 0.0f;   // h * node_mask
             hL[r * LDT + 32 * nt + c] = val;
-            if (v < d.V) w.H[size_t(v) * HID + 32 * nt + c] = val;
+            if (r < nrows) w.H[size_t(v) * HID + 32 * nt + c] = val;
             nmax = fmaxf(nmax, fabsf(val));
         }
         wg_max(&mx[3], nmax, lane);
         __syncthreads();
         if (PREC == 1) {
             s_h = scale_for(__uint_as_float(mx[3]));
-            if (tid == 0 && beyond_f16_range(__uint_as_float(mx[3]))) w.total[TW_RANGE] = 1;
+            if (tid == 0 && beyond_f16_range(__uint_as_float(mx[3]))) report_range(w.range, mol);
         }
         if (tid == 0) gmax_update(w.total, TW_HMAX, __uint_as_float(mx[3]));       // batch-wide max |h| (pk_edge_kernel<EQUIV>)
     }
@@ -440,7 +494,7 @@ pk_node_kernel(PkDims d, PkWs w, const float* __restrict__ post, const float* __
                 const int r = acc_row(reg, hh);
                 const int v = row0 + r;
                 const float val = (PREC == 0) ? acc[reg] : fmaf(acc[reg], inv, bias);
-                if (v < d.V) dst[size_t(v) * HID + 32 * nt + c] = val;
+                if (r < nrows) dst[size_t(v) * HID + 32 * nt + c] = val;
                 if (PREC == 1) {
                     // max over this wave's 32 features of row r (lanes of one half), then across the 4 waves in LDS
                     float m = fabsf(val) * efac;
@@ -456,7 +510,7 @@ pk_node_kernel(PkDims d, PkWs w, const float* __restrict__ post, const float* __
             __syncthreads();
             if (tid < 64) {
                 const int v = row0 + (tid & 31);
-                if (v < d.V) (tid < 32 ? w.pmax : w.qmax)[v] = __uint_as_float(rowmx[tid >> 5][tid & 31]);
+                if ((tid & 31) < nrows) (tid < 32 ? w.pmax : w.qmax)[v] = __uint_as_float(rowmx[tid >> 5][tid & 31]);
             }
         }
     }
@@ -532,12 +586,13 @@ pk_edge_kernel(PkDims d, PkWs w, const float* __restrict__ wimg, const float* __
     // every L2 seeing every molecule's rows
     const int xcd = blockIdx.x & 7, nblk = (int(gridDim.x) + 7 - xcd) >> 3;
     const int gw = (blockIdx.x >> 3) * (EDGE_THREADS / 64) + wv, GW = nblk * (EDGE_THREADS / 64);
-    // receiving atom and sender of this lane's slot in tile tt (slots past the last quad: padding of the last atom)
+    // receiving atom and sender of this lane's slot in tile tt (the quad count is a multiple of 4: every slot of a tile is some
+    // atom's, the padding quads behind a molecule its last atom's)
     auto tile_atoms = [&](int tt, int& ii, int& jj) {
         const int qd = 4 * tt + qg;
         const bool in = qd < nquads;
         ii = w.tile_row[in ? qd : nquads - 1];
-        jj = w.col[size_t(tt) * 32 + c];                             // (-1 past the last quad: pk_scan_kernel)
+        jj = w.col[size_t(tt) * 32 + c];                             // (-1 on padding: pk_edges_kernel<true>)
     };
 
     // Software-pipelined tile loop.  Every global access of a tile is a dependent chain (tile -> atoms -> coordinates ->
@@ -690,7 +745,7 @@ pk_edge_kernel(PkDims d, PkWs w, const float* __restrict__ wimg, const float* __
             // tests/test_gpu_round5.py::test_hbm_resident_kernels_over_twenty_binades_of_magnitude)
             const float bound_u = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(bound)));
             const float sa = scale_for(bound_u);
-            if (beyond_f16_range(bound_u) && lane == 0) w.total[TW_RANGE] = 1;
+            if (beyond_f16_range(bound_u) && lane == 0) report_range(w.range, ra0 / d.N);   // the tile's molecule
             const float accs = sa * sc[sw_index], inv = inv_pow2(accs);
             // accumulators start from the inline constant 0; the bias joins in the (exact) rescaling fma
             acc0 = splat16(0.0f); acc1 = splat16(0.0f); acc2 = splat16(0.0f); acc3 = splat16(0.0f);
@@ -907,7 +962,6 @@ __global__ void pk_out_kernel(PkDims d, PkWs w, const float* __restrict__ wp, fl
     }
     out[size_t(v) * d.D + k] = val;
     if (val != val) atomicOr(&nan_flags[v / d.N], bit);
-    if (k == 0 && v % d.N == 0 && w.total[TW_RANGE] != 0) atomicOr(&nan_flags[v / d.N], NAN_RANGE | 3);
 }
 
 thread_local int g_sparse_last_hip = 0;
@@ -940,7 +994,8 @@ int32_t run_sparse(const dl_model* m, int32_t B, int32_t N, int32_t graph_type, 
     d.B = B; d.N = N; d.V = B * N; d.nf = md.nf; d.ctx = md.ctx; d.fin = md.fin; d.D = 3 + md.nf; d.ct = md.ct;
     d.graph_type = graph_type; d.norm_constant = md.norm_constant; d.emask = emask;
     const bool weighted = graph_type == 3;
-    const PkWs w = carve(workspace, B, N);
+    PkWs w = carve(workspace, B, N);
+    w.range = nan_flags;
     const float* wp = m->d_pack;
     const int V = d.V;
 
@@ -949,14 +1004,14 @@ int32_t run_sparse(const dl_model* m, int32_t B, int32_t N, int32_t graph_type, 
     hipLaunchKernelGGL(pk_init_kernel, dim3((V * HID + 255) / 256), dim3(256), 0, st, d, w, wp, xh, t,
                        t_is_scalar ? 0 : 1, node_mask, linker_mask, context);
     hipLaunchKernelGGL(pk_edges_kernel<false>, dim3((V + 3) / 4), dim3(256), 0, st, d, w);
-    hipLaunchKernelGGL(pk_scan_kernel, dim3(1), dim3(1024), 0, st, V, w.ntile, w.tile_off, w.total, w.col, w.wgt);
+    hipLaunchKernelGGL(pk_scan_kernel, dim3(1), dim3(1024), 0, st, B, N, w.ntile, w.tile_off, w.total, w.mol_q, w.mol_adj);
     hipLaunchKernelGGL(pk_edges_kernel<true>, dim3((V + 3) / 4), dim3(256), 0, st, d, w);
     {
-        const int tmax = int((size_t(V) * (N / 8 + 1) + 4) / 4 + 1);          // upper bound of the tile count (carve)
+        const int tmax = int(tile_cap(B, N));                                  // upper bound of the tile count (carve)
         hipLaunchKernelGGL(pk_eqtiles_kernel, dim3((tmax + 255) / 256), dim3(256), 0, st, w);
     }
 
-    const int row_tiles = (V + 31) / 32;
+    const int row_tiles = B * ((N + 31) / 32);                     // cut per molecule (pk_node_kernel)
     const int edge_grid = 512;                                     // 2 workgroups per CU (64 KB LDS each)
     const bool f16 = m->cfg.precision != DL_PRECISION_FP32, two = m->cfg.precision == DL_PRECISION_F16X2;
     // `pre`: the pass whose projections the kernel ends with (a GCL, or the equivariant update: `pre_equiv`)

@@ -11,6 +11,15 @@ in ONE launch on one compute unit per molecule - the two-launch hand-over of ``E
 ``EDM.overflow_teams`` follow the sizes of the molecules at hand and are for unsharded batches only (they change the order in
 which a molecule's messages are summed: ~1e-8 on the final coordinates).  The unsharded call of a batch BEYOND one GPU's compute
 units runs one launch per chain too, so world = 1 / 2 / 4 / 8 sample the same bits (tests/test_gpu_round6.py, C3 shape).
+
+The radius-graph paths keep the same promise - ``DynamicsWithPockets`` and the HBM-resident kernels of fully-connected molecules
+beyond the LDS-resident limit (csrc/egnn_sparse.hip): their edge tiles and node row tiles are cut per molecule, so the denoiser
+output of molecule b is a function of molecule b and the padded width N alone; the host-driven chain keys its draws by
+``mol_offset``, and ``shard_sampler_inputs`` re-bases the pockets' batch-id ``edge_mask``.  Chains, loss rows and single forwards
+of a pocket batch equal those of its shards (2 x 2, 4 x 1, 2 + 2 + 1), of each molecule alone, of the batch reversed and of the
+molecule among other neighbours, bit for bit, in every arithmetic mode (tests/test_gpu_batch_independence.py; its preconditions:
+tests/test_batch_independence_host.py).  Out of scope: independence of the padded width N - a shard keeps the batch's N, and
+rows may sit anywhere in it (tests/test_gpu_round5.py::test_pocket_atoms_anywhere_among_the_padding_rows).
 """
 import time
 

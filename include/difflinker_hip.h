@@ -188,7 +188,7 @@ int32_t dl_max_atoms(void);
  *                                   bit4 (f16 modes only, always with bit0 | bit1): a magnitude bound of this molecule's
  *                                   activations reached 2^75 (3.8e22) - beyond the scales' range the fp16 operands would
  *                                   saturate silently, so `out` is void; DL_PRECISION_FP32 has no such limit.  The radius-graph
- *                                   kernels scale per tile, not per molecule: they report every molecule of the call */
+ *                                   kernels scale per tile, and a tile belongs to one molecule: they too report that molecule alone */
 int32_t dl_egnn_forward_fc(const dl_model* m, int32_t B, int32_t N,
                            const float* xh, const float* t, int32_t t_is_scalar,
                            const int8_t* node_mask, const float* linker_mask, const int8_t* edge_mask,
@@ -213,7 +213,10 @@ size_t dl_workspace_bytes(int32_t B, int32_t team);
  *               unspecified (the entry point zeroes its counters and batch-wide maxima on `stream`), contents on return
  *               unspecified.  `out` (padded rows 0) and `nan_flags` are written in full
  * Molecule membership is positional (atom v belongs to molecule v / N), which is what the reference's batch-index
- * "edge_mask" vector encodes (src/datasets.py:359-364).  Both precisions are supported. */
+ * "edge_mask" vector encodes (src/datasets.py:359-364).  Both precisions are supported.
+ * The rows of molecule b in `out` and nan_flags[b] are a function of molecule b's inputs and N alone, bit for bit: not of B, of
+ * the molecule's position in the batch or of the other molecules (edge and row tiles are cut per molecule; the workspace holds
+ * up to 3 padding quads of 8 edge slots per molecule for it).  The same holds for dl_egnn_forward_fc_large. */
 size_t dl_pocket_workspace_bytes(int32_t B, int32_t N);
 int32_t dl_egnn_forward_pocket(const dl_model* m, int32_t B, int32_t N, int32_t graph_type,
                                const float* xh, const float* t, int32_t t_is_scalar,

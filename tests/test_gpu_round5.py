@@ -676,7 +676,8 @@ def test_coordinates_beyond_the_f16_range_are_reported_not_saturated(sizes, link
 
 
 def test_pocket_coordinates_beyond_the_f16_range_are_reported():
-    """The same on the radius-graph kernels: their scales belong to tiles, so the report names every molecule of the call."""
+    """The same on the radius-graph kernels: their scales belong to tiles, and a tile to one molecule - both molecules are
+    beyond the range here, so the report names both (one alone: tests/test_gpu_batch_independence.py)."""
     from difflinker_amd.utils import FoundNaNException
     nf = 9
     dyn, sd, cfg = P.make_pocket_dynamics(nf, 2, seed=221)
