@@ -219,6 +219,22 @@ class DLFragmentArgs(ctypes.Structure):
     ]
 
 
+DL_POCKET_MAX_LIGAND, DL_POCKET_MAX_GROUPS = 256, 32768                     # dl_pocket_args: ligand atoms per pair; groups per protein
+DL_POCKET_NONFINITE, DL_POCKET_TOO_LARGE, DL_POCKET_TOO_MANY_GROUPS = 1, 2, 4  # dl_pocket_args.status bits
+DL_POCKET_BAD_PROTEIN, DL_POCKET_TRUNCATED = 8, 32
+
+
+class DLPocketArgs(ctypes.Structure):
+    _fields_ = [
+        ('B', ctypes.c_int32), ('L', ctypes.c_int32), ('P', ctypes.c_int32), ('M_total', ctypes.c_int32),
+        ('protein_x', ctypes.c_void_p), ('protein_group', ctypes.c_void_p), ('protein_offset', ctypes.c_void_p),
+        ('pair_protein', ctypes.c_void_p), ('ligand_x', ctypes.c_void_p), ('ligand_mask', ctypes.c_void_p),
+        ('cutoff', ctypes.c_double), ('Mmax', ctypes.c_int32), ('capacity', ctypes.c_int32),
+        ('n_ligand', ctypes.c_void_p), ('n_contact_atoms', ctypes.c_void_p), ('n_groups_selected', ctypes.c_void_p),
+        ('n_pocket', ctypes.c_void_p), ('status', ctypes.c_void_p), ('member', ctypes.c_void_p), ('index', ctypes.c_void_p),
+    ]
+
+
 EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_string', 'dl_model_num_tensors',
            'dl_model_create', 'dl_model_destroy', 'dl_egnn_forward_fc', 'dl_sampler_step', 'dl_sample_chain_fc',
            'dl_set_profile_buffer', 'dl_profile_max_events', 'dl_pocket_workspace_bytes', 'dl_egnn_forward_pocket',
@@ -231,7 +247,7 @@ EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_stri
            'dl_size_train_num_params', 'dl_size_train_workspace_bytes', 'dl_size_train_forward', 'dl_size_train_backward',
            'dl_join_workspace_bytes', 'dl_sample_chain_fc_join', 'dl_bonds_workspace_bytes', 'dl_perceive_bonds',
            'dl_molecule_keys', 'dl_clash_scores', 'dl_shape_scores', 'dl_ring_scores', 'dl_fragment_cuts',
-           'dl_best_rmsd')
+           'dl_pocket_select', 'dl_best_rmsd')
 TEST_HOOK_EXPORTS = ('dl_debug_team_fault',)       # declared under #ifdef DL_TEST_HOOKS: the test-hooks build only
 
 _lib = None
@@ -359,6 +375,8 @@ def _open(path):
     lib.dl_ring_scores.argtypes = [ctypes.POINTER(DLRingsArgs), vp]
     lib.dl_fragment_cuts.restype = i32
     lib.dl_fragment_cuts.argtypes = [ctypes.POINTER(DLFragmentArgs), vp]
+    lib.dl_pocket_select.restype = i32
+    lib.dl_pocket_select.argtypes = [ctypes.POINTER(DLPocketArgs), vp]
     lib.dl_best_rmsd.restype = i32
     lib.dl_best_rmsd.argtypes = [ctypes.POINTER(DLRmsdArgs), vp]
     lib.dl_size_model_num_tensors.restype = i32

@@ -22,8 +22,8 @@ class ZincDataset(torch.utils.data.Dataset):
     def __init__(self, data_path, prefix, device):
         dataset_path = os.path.join(data_path, f'{prefix}.pt')
         if not os.path.exists(dataset_path):
-            raise FileNotFoundError(f'{dataset_path} not found: preprocess the dataset with the reference tooling '
-                                    '(RDKit) first')
+            raise FileNotFoundError(f'{dataset_path} not found: build it with python -m difflinker_amd.prepare --proteins, or '
+                                    'preprocess the dataset with the reference tooling (RDKit) first')
         self.data = torch.load(dataset_path, map_location=device, weights_only=False)
 
     def __len__(self):
@@ -49,8 +49,8 @@ class MOADDataset(torch.utils.data.Dataset):
             prefix, pocket_mode = '_'.join(parts[:-1]), parts[-1]
         dataset_path = os.path.join(data_path, f'{prefix}_{pocket_mode}.pt')
         if not os.path.exists(dataset_path):
-            raise FileNotFoundError(f'{dataset_path} not found: preprocess the dataset with the reference tooling '
-                                    '(RDKit) first')
+            raise FileNotFoundError(f'{dataset_path} not found: build it with python -m difflinker_amd.prepare --proteins, or '
+                                    'preprocess the dataset with the reference tooling (RDKit) first')
         self.data = torch.load(dataset_path, map_location=device, weights_only=False)
 
     def __len__(self):

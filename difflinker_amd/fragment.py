@@ -4,7 +4,8 @@
 In place of the reference's two RDKit steps: fragmentation by ``FragmentMol`` with ``minCuts = maxCuts = 2`` and DeLinker's
 pattern (``data/geom/generate_geom_multifrag.py:199-206``), and the re-assembly of fragments, linker and anchors per example
 (``data/zinc/prepare_dataset.py``, ``src/datasets.py:56-100``).  Not here: SMILES (symmetric cuts are not merged: every kept
-pair is its own example), conformers, BRICS, cuts at three or more bonds, pockets, aromaticity perception, hydrogens."""
+pair is its own example), conformers, BRICS, cuts at three or more bonds, aromaticity perception, hydrogens.  Pockets around the molecules:
+``difflinker_amd.pocket``."""
 import ctypes
 from collections import namedtuple
 

@@ -13,12 +13,15 @@ symbols and coordinates, so the few record types involved are parsed here direct
 * ``read_pocket`` / ``get_pocket``: the pocket dictionaries of the two pocket scripts, including their quirks
   (every model is walked, the highest-occupancy alternate location is kept, contact residues are matched by residue
   NUMBER only, the 'full' atom list keeps whatever elements the file has);
+* ``read_pdb_arrays`` / ``groups``: a protein parsed ONCE into arrays and the dense residue ids of its atoms, for the batched
+  pocket selection of ``difflinker_amd.pocket`` and ``difflinker_amd.prepare --proteins``;
 * ``save_xyz_file`` / ``load_xyz_files`` / ``load_molecule_xyz``: byte-compatible with src/visualizer.py:14-59;
 * ``save_sdf_file``: V2000 mol blocks from the bond lists of ``molecule_builder.perceive_bonds``, in place of the
   reference's ``obabel xyz -> sdf`` call (generate.py:179-180).  The bonds are the reference's own ``molecule_builder``
   rule, not OpenBabel's.
 """
 import os
+from collections import namedtuple
 from dataclasses import dataclass, field
 from typing import List
 
@@ -284,6 +287,8 @@ class _PdbAtom:
     coord: List[float]
     resseq: int
     occupancy: float
+    chain: str = ' '
+    icode: str = ' '
 
 
 def _walk_pdb(path):
@@ -305,7 +310,7 @@ def _walk_pdb(path):
             except ValueError:
                 occ = 1.0
             atom = _PdbAtom(name, _pdb_element(ln).upper(), [float(ln[30:38]), float(ln[38:46]), float(ln[46:54])],
-                            int(ln[22:26]), occ)
+                            int(ln[22:26]), occ, ln[21], ln[26])
             key = (model, ln[21], ln[22:27], ln[17:20], name)      # chain, resseq + icode, resname, atom
             if ln[16] != ' ' and key in index:
                 if occ > atoms[index[key]].occupancy:
@@ -355,6 +360,33 @@ def get_pocket(mol, pdb_path, backbone_atoms_only=False):
         one_hot.append(get_one_hot(key, const.GEOM_ATOM2IDX))
         charges.append(const.GEOM_CHARGES[key])
     return np.array(pos), np.array(one_hot), np.array(charges)
+
+
+PdbArrays = namedtuple('PdbArrays', 'coords resseq chain icode name element')
+
+
+def read_pdb_arrays(path):
+    """One PDB file, parsed once, per atom in ``_walk_pdb`` order: ``coords [M,3]`` fp32 (Bio.PDB keeps float32 coordinates, and
+    ``get_pocket`` measures from them), ``resseq [M]`` residue numbers (int64), and the lists ``chain``, ``icode`` (insertion
+    code, ``' '`` for none), ``name`` (atom name) and ``element`` (upper case, as ``_walk_pdb`` keeps it).  What
+    ``pocket.select_pockets`` and ``pocket.pocket_atoms`` need of a protein; ``get_pocket`` parses the file again for every
+    ligand."""
+    atoms = _walk_pdb(path)
+    return PdbArrays(np.array([a.coord for a in atoms], dtype=np.float32).reshape(len(atoms), 3),
+                     np.array([a.resseq for a in atoms], dtype=np.int64), [a.chain for a in atoms], [a.icode for a in atoms],
+                     [a.name for a in atoms], [a.element for a in atoms])
+
+
+def groups(arrays, by='number'):
+    """Dense group ids ``[M]`` int32 of a ``PdbArrays``, numbered ``0 .. G - 1`` in order of first appearance: the residues
+    ``dl_pocket_select`` selects as a whole.  ``by='number'`` groups by the residue NUMBER alone, the reference's rule
+    (``get_pocket``): equal numbers in other chains, and with other insertion codes, are one group.  ``by='residue'`` groups by
+    ``(chain, number, insertion code)``."""
+    if by not in ('number', 'residue'):
+        raise ValueError(f"groups by {by!r}: 'number' or 'residue'")
+    keys = arrays.resseq.tolist() if by == 'number' else list(zip(arrays.chain, arrays.resseq.tolist(), arrays.icode))
+    ids = {}
+    return np.array([ids.setdefault(key, len(ids)) for key in keys], dtype=np.int32)
 
 
 def get_protein_atoms(pdb_path, is_geom=True):

@@ -56,6 +56,8 @@
  *   dl_fragment_cuts                     <- FragmentMol(minCuts = maxCuts = 2) with DeLinker's pattern
  *                                           (data/geom/generate_geom_multifrag.py:199-206) and the re-assembly of
  *                                           data/zinc/prepare_dataset.py, src/datasets.py:56-100
+ *   dl_pocket_select                     <- get_pocket of data/pocket/prepare_dataset.py (residues with an atom within 6 A
+ *                                           of the ligand), for every (ligand, protein) pair of a batch
  *   dl_size_train_forward / dl_size_train_backward
  *                                        <- SizeClassifier.forward in training mode + loss.backward()
  *                                           (src/linker_size_lightning.py:83-117, :163-167)
@@ -961,8 +963,8 @@ int32_t dl_ring_scores(const dl_rings_args* args, void* stream);
  * capacity < 0 or R < 0 return DL_ERR_BAD_ARG; then B == 0 returns DL_OK without a launch; then a null pointer (other than
  * charge, status_in, `bonds` / `bond_side` when capacity is 0 and `cuts` / `labels` when R is 0) returns DL_ERR_BAD_ARG, all
  * before any device work.
- * Not here: SMILES (so symmetric cuts are not merged), conformers, BRICS, cuts at three or more bonds, pockets, aromaticity
- * perception beyond the list's orders, hydrogens. */
+ * Not here: SMILES (so symmetric cuts are not merged), conformers, BRICS, cuts at three or more bonds, aromaticity
+ * perception beyond the list's orders, hydrogens.  Pockets: dl_pocket_select below. */
 #define DL_FRAG_MAX_ATOMS 256       /* atoms per molecule */
 #define DL_FRAG_CUT_FIELDS 10       /* int32 values per record of `cuts` */
 #define DL_FRAG_TOO_LARGE 4         /* status bit, same value as DL_KEYS_TOO_LARGE */
@@ -991,6 +993,72 @@ typedef struct dl_fragment_args {
     uint8_t* labels;                /* device uint8 [B,R,N] out (may be NULL when R is 0) */
 } dl_fragment_args;
 int32_t dl_fragment_cuts(const dl_fragment_args* args, void* stream);
+
+/* ---- pockets: the protein atoms around every ligand of a batch (pocket.hip) -----------------------------------
+ * For every (ligand, protein) pair the protein atoms whose GROUP holds an atom within `cutoff` of some ligand atom: one
+ * workgroup per pair, ONE launch per batch.  With the residue number as the group and cutoff 6 this is get_pocket of the
+ * reference's data/pocket/prepare_dataset.py and generate_with_protein.py (:85-148).
+ *
+ * INPUT.  Proteins are concatenated: protein p owns the atoms protein_offset[p] .. protein_offset[p + 1] - 1 of protein_x
+ * and protein_group, in file order; protein_group holds dense ids 0 .. G_p - 1 within its protein, assigned by the host.
+ * Pair b is the protein pair_protein[b] (one protein serves any number of pairs) and the ligand rows i with
+ * ligand_mask[b, i] != 0; rows with mask 0 are never read, whatever they hold.
+ *
+ * THE RULE.  For protein atom j and ligand atom i:  dx = (double)xp - xl (dy, dz alike),
+ * d2 = ((dx*dx) + (dy*dy)) + (dz*dz), each operation a separate fp64 round-to-nearest operation in this order.  Atom j is a
+ * CONTACT atom when d2 <= cutoff * cutoff for some i (one fp64 multiply, the comparison not strict); a group is SELECTED
+ * when it holds a contact atom; atom j is a POCKET atom when its group is selected.
+ *
+ *   n_ligand            real ligand rows
+ *   n_contact_atoms     contact atoms
+ *   n_groups_selected   selected groups
+ *   n_pocket            ALL pocket atoms, also those beyond `capacity`
+ *   member              uint8 [B,Mmax] by position within the protein: bit 0 contact atom, bit 1 pocket atom; 0 from the
+ *                       protein's size on
+ *   index               [B,capacity]: the positions within the protein of the first min(n_pocket, capacity) pocket atoms, in
+ *                       file order; -1 after them
+ *   status              DL_POCKET_TRUNCATED (n_pocket > capacity), or the reasons a pair has no answer:
+ *                       DL_POCKET_TOO_LARGE (more than DL_POCKET_MAX_LIGAND ligand atoms; alone, nothing else is looked at),
+ *                       DL_POCKET_BAD_PROTEIN (pair_protein outside [0, P), offsets that do not ascend inside [0, M_total],
+ *                       or a protein of more than Mmax atoms; alone, no atom is looked at), DL_POCKET_TOO_MANY_GROUPS (a
+ *                       group id < 0 or >= DL_POCKET_MAX_GROUPS) and DL_POCKET_NONFINITE (a non-finite coordinate among the
+ *                       protein's atoms or the real ligand rows).  Such a pair has n_ligand, every other count 0, member 0
+ *                       and index -1; the other pairs of the launch are untouched.
+ *
+ * The same bits on every run.  Global memory is written with plain stores only, every output element is written, the callee
+ * allocates nothing.  A null `args`, a negative B, L, P, M_total, Mmax or capacity, or a cutoff that is not >= 0 return
+ * DL_ERR_BAD_ARG; then B == 0 returns DL_OK without a launch; then a null pointer (other than protein_x / protein_group when
+ * M_total is 0, ligand_x / ligand_mask when L is 0, `member` when Mmax is 0 and `index` when capacity is 0) returns
+ * DL_ERR_BAD_ARG, all before any device work.
+ * Not here: parsing, hydrogens, protein cleaning, and the choice of the atoms a data set keeps (pocket.py does that). */
+#define DL_POCKET_MAX_LIGAND 256    /* ligand atoms per pair */
+#define DL_POCKET_MAX_GROUPS 32768  /* groups per protein */
+#define DL_POCKET_NONFINITE 1       /* status bit, same value as DL_CLASH_NONFINITE */
+#define DL_POCKET_TOO_LARGE 2       /* status bit, same value as DL_CLASH_TOO_LARGE */
+#define DL_POCKET_TOO_MANY_GROUPS 4 /* status bit */
+#define DL_POCKET_BAD_PROTEIN 8     /* status bit */
+#define DL_POCKET_TRUNCATED 32      /* status bit, same value as DL_FRAG_TRUNCATED */
+typedef struct dl_pocket_args {
+    int32_t B, L;                   /* pairs; ligand rows per pair */
+    int32_t P, M_total;             /* proteins; atoms of all proteins together */
+    const float* protein_x;         /* device f32 [M_total,3] (may be NULL when M_total is 0) */
+    const int32_t* protein_group;   /* device int32 [M_total] (may be NULL when M_total is 0) */
+    const int32_t* protein_offset;  /* device int32 [P+1] */
+    const int32_t* pair_protein;    /* device int32 [B] */
+    const double* ligand_x;         /* device f64 [B,L,3] (may be NULL when L is 0) */
+    const float* ligand_mask;       /* device f32 [B,L] (may be NULL when L is 0) */
+    double cutoff;                  /* Angstrom */
+    int32_t Mmax;                   /* row width of `member`: at least the largest protein of the launch */
+    int32_t capacity;               /* R: positions `index` holds per pair */
+    int32_t* n_ligand;              /* device int32 [B] out */
+    int32_t* n_contact_atoms;       /* device int32 [B] out */
+    int32_t* n_groups_selected;     /* device int32 [B] out */
+    int32_t* n_pocket;              /* device int32 [B] out */
+    int32_t* status;                /* device int32 [B] out */
+    uint8_t* member;                /* device uint8 [B,Mmax] out (may be NULL when Mmax is 0) */
+    int32_t* index;                 /* device int32 [B,capacity] out (may be NULL when capacity is 0) */
+} dl_pocket_args;
+int32_t dl_pocket_select(const dl_pocket_args* args, void* stream);
 
 const char* dl_error_string(int32_t status);
 int32_t dl_last_hip_error(void);
