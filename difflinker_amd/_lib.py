@@ -219,6 +219,25 @@ class DLFragmentArgs(ctypes.Structure):
     ]
 
 
+DL_FRAG_MULTI_FIELDS, DL_FRAG_MULTI_MIN_CUTS, DL_FRAG_MULTI_MAX_CUTS = 22, 3, 5     # dl_fragment_multi_args: ints per record; k
+DL_FRAG_MULTI_MAX_CUTTABLE, DL_FRAG_MULTI_LINKER = 64, 5                        # cuttable bonds of a molecule that is cut; a label
+DL_FRAG_MANY_CUTTABLE = 64                                                      # dl_fragment_multi_args.status bit
+
+
+class DLFragmentMultiArgs(ctypes.Structure):
+    _fields_ = [
+        ('B', ctypes.c_int32), ('N', ctypes.c_int32), ('nf', ctypes.c_int32),
+        ('one_hot', ctypes.c_void_p), ('node_mask', ctypes.c_void_p), ('charge', ctypes.c_void_p),
+        ('carbon_type', ctypes.c_int32), ('capacity', ctypes.c_int32),
+        ('n_bonds_in', ctypes.c_void_p), ('bonds', ctypes.c_void_p), ('status_in', ctypes.c_void_p),
+        ('min_cuts', ctypes.c_int32), ('max_cuts', ctypes.c_int32), ('min_linker', ctypes.c_int32),
+        ('min_fragment', ctypes.c_int32), ('max_atoms', ctypes.c_int32), ('min_rings', ctypes.c_int32), ('R', ctypes.c_int32),
+        ('n_atoms', ctypes.c_void_p), ('n_bonds', ctypes.c_void_p), ('n_cuttable', ctypes.c_void_p),
+        ('n_cuts', ctypes.c_void_p), ('status', ctypes.c_void_p), ('n_cuts_k', ctypes.c_void_p),
+        ('cuts', ctypes.c_void_p), ('labels', ctypes.c_void_p),
+    ]
+
+
 DL_POCKET_MAX_LIGAND, DL_POCKET_MAX_GROUPS = 256, 32768                     # dl_pocket_args: ligand atoms per pair; groups per protein
 DL_POCKET_NONFINITE, DL_POCKET_TOO_LARGE, DL_POCKET_TOO_MANY_GROUPS = 1, 2, 4  # dl_pocket_args.status bits
 DL_POCKET_BAD_PROTEIN, DL_POCKET_TRUNCATED = 8, 32
@@ -247,7 +266,7 @@ EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_stri
            'dl_size_train_num_params', 'dl_size_train_workspace_bytes', 'dl_size_train_forward', 'dl_size_train_backward',
            'dl_join_workspace_bytes', 'dl_sample_chain_fc_join', 'dl_bonds_workspace_bytes', 'dl_perceive_bonds',
            'dl_molecule_keys', 'dl_clash_scores', 'dl_shape_scores', 'dl_ring_scores', 'dl_fragment_cuts',
-           'dl_pocket_select', 'dl_best_rmsd')
+           'dl_pocket_select', 'dl_fragment_multicuts', 'dl_best_rmsd')
 TEST_HOOK_EXPORTS = ('dl_debug_team_fault',)       # declared under #ifdef DL_TEST_HOOKS: the test-hooks build only
 
 _lib = None
@@ -375,6 +394,8 @@ def _open(path):
     lib.dl_ring_scores.argtypes = [ctypes.POINTER(DLRingsArgs), vp]
     lib.dl_fragment_cuts.restype = i32
     lib.dl_fragment_cuts.argtypes = [ctypes.POINTER(DLFragmentArgs), vp]
+    lib.dl_fragment_multicuts.restype = i32
+    lib.dl_fragment_multicuts.argtypes = [ctypes.POINTER(DLFragmentMultiArgs), vp]
     lib.dl_pocket_select.restype = i32
     lib.dl_pocket_select.argtypes = [ctypes.POINTER(DLPocketArgs), vp]
     lib.dl_best_rmsd.restype = i32

@@ -3,6 +3,7 @@
     python -m difflinker_amd.prepare --sdf mols.sdf --out DIR --prefix NAME [--geom] [--min_linker 3 --min_fragment 5
         --min_path_atoms 2 --no_linker_leq_frags] [--max_per_molecule K] [--val_fraction F --seed S] [--device cuda:0]
         [--proteins PDB_DIR [--pocket_cutoff 6.0] [--pocket_by number|residue]]
+        [--multi_cuts MIN MAX [--multi_min_size 3] [--multi_max_atoms 40] [--multi_min_rings 3]]
 
 The molecules are batched, padded to the batch's largest, and cut by one ``dl_fragment_cuts`` launch per batch
 (``fragment.fragment_all``); every kept double cut becomes one example (``fragment.examples``).  ``DIR/NAME.pt`` is the list of
@@ -17,7 +18,14 @@ protein is parsed ONCE per run (``io.read_pdb_arrays``), and the pocket of every
 ``--pocket_cutoff`` of one of its atoms - is selected by one ``dl_pocket_select`` launch per batch (``pocket.select_all``).
 ``DIR/NAME_full.pt`` and ``DIR/NAME_bb.pt`` are the lists ``MOADDataset`` loads as ``NAME.full`` and ``NAME.bb``, and the table
 gains the reference's columns ``pocket_full_size, pocket_bb_size, molecule_size, fragments_size, linker_size``.  In place of
-``data/pocket/prepare_dataset.py`` and ``MOADDataset.preprocess``; see ``pocket`` for what this is not."""
+``data/pocket/prepare_dataset.py`` and ``MOADDataset.preprocess``; see ``pocket`` for what this is not.
+
+With ``--multi_cuts MIN MAX`` (3 <= MIN <= MAX <= 5) the run writes the MULTI-fragment set only, as
+``data/geom/generate_geom_multifrag.py:227-231`` does: every molecule of at most ``--multi_max_atoms`` atoms with at least
+``--multi_min_rings`` rings (the cyclomatic number) is cut at MIN to MAX bonds by one ``dl_fragment_multicuts`` launch per batch
+(``fragment.multi_all``), a linker and every fragment of at least ``--multi_min_size`` atoms; the double-cut options do not
+apply.  Every kept star becomes one example (``fragment.multi_examples``), and the table has the columns ``uuid, molecule,
+n_cuts, anchors, n_frags, n_linker``, the anchors and the fragment sizes joined by ``-`` like the reference's ``anchors``."""
 import argparse
 import csv
 import json
@@ -29,13 +37,14 @@ import numpy as np
 import torch
 
 from . import _lib, const
-from .fragment import examples, fragment_all
+from .fragment import examples, fragment_all, multi_all, multi_examples
 from .io import groups, read_pdb_arrays, read_sdf_molecules
 from .pocket import DEAD, pocket_atoms, pocket_examples, select_all
 
 SKIP_REASONS = ('malformed', 'unknown_element', 'too_large', 'not_one_piece', 'no_3d')
 POCKET_SKIP_REASONS = ('no_protein_file', 'empty_pocket')         # with --proteins, beside SKIP_REASONS
 TABLE_COLUMNS = ('uuid', 'molecule', 'anchor_1', 'anchor_2', 'n_frag_1', 'n_frag_2', 'n_linker')
+MULTI_TABLE_COLUMNS = ('uuid', 'molecule', 'n_cuts', 'anchors', 'n_frags', 'n_linker')    # with --multi_cuts
 POCKET_TABLE_COLUMNS = TABLE_COLUMNS + ('pocket_full_size', 'pocket_bb_size', 'molecule_size', 'fragments_size', 'linker_size')
 
 
@@ -76,10 +85,12 @@ class _Clock:
         return now
 
 
-def prepare(molecules, is_geom, device, batch_size=256, max_per_molecule=None, seconds=None, **rule):
+def prepare(molecules, is_geom, device, batch_size=256, max_per_molecule=None, seconds=None, multi=False, **rule):
     """Examples of a list of ``BondedMolecule``: ``(dicts, rows, skipped)``; ``rows`` as ``fragment.examples`` gives them with
     the molecule index into ``molecules``, ``skipped`` a count per reason of ``SKIP_REASONS``.  A dict given as ``seconds``
-    gathers the time of the shares ``'gpu'`` (upload, launches, until the device is idle) and ``'assembly'``."""
+    gathers the time of the shares ``'gpu'`` (upload, launches, until the device is idle) and ``'assembly'``.  With ``multi``
+    the cuts are those of ``fragment.multi_all``, ``rule`` is its rule and the rows are those of ``fragment.multi_examples``."""
+    cut_all, assemble = (multi_all, multi_examples) if multi else (fragment_all, examples)
     clock = _Clock(device, seconds)
     atom2idx = const.GEOM_ATOM2IDX if is_geom else const.ATOM2IDX
     skipped = {reason: 0 for reason in SKIP_REASONS}
@@ -98,10 +109,10 @@ def prepare(molecules, is_geom, device, batch_size=256, max_per_molecule=None, s
         batch = [molecules[i] for i in usable[start:start + batch_size]]
         began = time.perf_counter()
         one_hot, mask, bonds, n_bonds, charge = pad_batch(batch, is_geom, device)
-        found = fragment_all(one_hot, mask, bonds, n_bonds, is_geom=is_geom, charge=charge, **rule)
+        found = cut_all(one_hot, mask, bonds, n_bonds, is_geom=is_geom, charge=charge, **rule)
         began = clock.lap('gpu', began)
         skipped['not_one_piece'] += int((found.status & _lib.DL_FRAG_DISCONNECTED != 0).sum())
-        got, got_rows = examples(found, [m.symbols for m in batch], [m.positions for m in batch], [m.name for m in batch],
+        got, got_rows = assemble(found, [m.symbols for m in batch], [m.positions for m in batch], [m.name for m in batch],
                                  is_geom, with_rows=True)
         taken = {}
         for item, row in zip(got, got_rows):
@@ -189,8 +200,9 @@ def prepare_pockets(molecules, proteins_dir, device, batch_size=256, max_per_mol
     return full, bb, rows, skipped
 
 
-def write(out, prefix, data, rows, bb=None):
-    """``prefix.pt`` and ``prefix_table.csv``; with ``bb`` (a pocket set) ``prefix_full.pt`` and ``prefix_bb.pt`` instead."""
+def write(out, prefix, data, rows, bb=None, multi=False):
+    """``prefix.pt`` and ``prefix_table.csv``; with ``bb`` (a pocket set) ``prefix_full.pt`` and ``prefix_bb.pt`` instead; with
+    ``multi`` the rows are those of ``fragment.multi_examples`` and the table has ``MULTI_TABLE_COLUMNS``."""
     if bb is None:
         torch.save(data, os.path.join(out, f'{prefix}.pt'))
     else:
@@ -198,8 +210,10 @@ def write(out, prefix, data, rows, bb=None):
         torch.save(bb, os.path.join(out, f'{prefix}_bb.pt'))
     with open(os.path.join(out, f'{prefix}_table.csv'), 'w', newline='') as f:
         table = csv.writer(f)
-        table.writerow(TABLE_COLUMNS if bb is None else POCKET_TABLE_COLUMNS)
+        table.writerow(MULTI_TABLE_COLUMNS if multi else TABLE_COLUMNS if bb is None else POCKET_TABLE_COLUMNS)
         for item, row in zip(data, rows):
+            if multi:
+                row = (row[0], row[1], '-'.join(map(str, row[2])), '-'.join(map(str, row[3])), row[4])
             table.writerow((item['uuid'], item['name']) + tuple(row[1:]))
 
 
@@ -224,13 +238,28 @@ def main(argv=None):
     p.add_argument('--pocket_by', choices=('number', 'residue'), default='number',
                    help="what is selected as a whole: all atoms with a residue NUMBER (the reference's rule), or one residue "
                         'of one chain')
+    p.add_argument('--multi_cuts', type=int, nargs=2, metavar=('MIN', 'MAX'), default=None,
+                   help='write the multi-fragment set instead: one linker joined to MIN..MAX fragments, 3 <= MIN <= MAX <= 5')
+    p.add_argument('--multi_min_size', type=int, default=3, help='with --multi_cuts: atoms of the linker and of every fragment')
+    p.add_argument('--multi_max_atoms', type=int, default=40, help='with --multi_cuts: larger molecules are not cut')
+    p.add_argument('--multi_min_rings', type=int, default=3, help='with --multi_cuts: molecules with fewer rings are not cut')
     args = p.parse_args(argv)
+    multi = args.multi_cuts is not None
+    if multi and args.proteins is not None:
+        p.error('--multi_cuts writes no pocket-conditioned sets: it cannot go with --proteins')
+    if multi and not _lib.DL_FRAG_MULTI_MIN_CUTS <= args.multi_cuts[0] <= args.multi_cuts[1] <= _lib.DL_FRAG_MULTI_MAX_CUTS:
+        p.error(f'--multi_cuts MIN MAX: {_lib.DL_FRAG_MULTI_MIN_CUTS} <= MIN <= MAX <= {_lib.DL_FRAG_MULTI_MAX_CUTS}')
 
     molecules, malformed = read_sdf_molecules(args.sdf)
     rule = dict(min_linker=args.min_linker, min_fragment=args.min_fragment, min_path_atoms=args.min_path_atoms,
                 linker_leq_frags=not args.no_linker_leq_frags)
     bb = None
-    if args.proteins is None:
+    if multi:
+        data, rows, skipped = prepare(molecules, args.geom, torch.device(args.device), args.batch_size, args.max_per_molecule,
+                                      multi=True, min_cuts=args.multi_cuts[0], max_cuts=args.multi_cuts[1],
+                                      min_linker=args.multi_min_size, min_fragment=args.multi_min_size,
+                                      max_atoms=args.multi_max_atoms, min_rings=args.multi_min_rings)
+    elif args.proteins is None:
         data, rows, skipped = prepare(molecules, args.geom, torch.device(args.device), args.batch_size, args.max_per_molecule, **rule)
     else:
         data, bb, rows, skipped = prepare_pockets(molecules, args.proteins, torch.device(args.device), args.batch_size,
@@ -239,6 +268,9 @@ def main(argv=None):
     os.makedirs(args.out, exist_ok=True)
     summary = {'molecules_read': len(molecules) + malformed, 'molecules_skipped': skipped, 'examples': len(data),
                'molecules_with_examples': len({row[0] for row in rows}), 'files': {}}
+    if multi:
+        summary['examples_by_cuts'] = {str(k): sum(row[1] == k for row in rows)
+                                       for k in range(args.multi_cuts[0], args.multi_cuts[1] + 1)}
     if args.val_fraction > 0:
         order = sorted({row[0] for row in rows})
         random.Random(args.seed).shuffle(order)
@@ -247,10 +279,10 @@ def main(argv=None):
             chosen = [k for k, row in enumerate(rows) if (row[0] in held_out) == wanted]
             part, part_bb = ([dict(items[k], uuid=uuid) for uuid, k in enumerate(chosen)] if items is not None else None
                              for items in (data, bb))
-            write(args.out, f'{args.prefix}_{name}', part, [rows[k] for k in chosen], part_bb)
+            write(args.out, f'{args.prefix}_{name}', part, [rows[k] for k in chosen], part_bb, multi)
             summary['files'][f'{args.prefix}_{name}'] = len(part)
     else:
-        write(args.out, args.prefix, data, rows, bb)
+        write(args.out, args.prefix, data, rows, bb, multi)
         summary['files'][args.prefix] = len(data)
     print(json.dumps(summary))
     return summary

@@ -56,6 +56,9 @@
  *   dl_fragment_cuts                     <- FragmentMol(minCuts = maxCuts = 2) with DeLinker's pattern
  *                                           (data/geom/generate_geom_multifrag.py:199-206) and the re-assembly of
  *                                           data/zinc/prepare_dataset.py, src/datasets.py:56-100
+ *   dl_fragment_multicuts                <- fragment_by_mmpa(min_cuts=3, max_cuts=5, min_frag_size=3) on molecules of at
+ *                                           most 40 atoms with three rings (data/geom/generate_geom_multifrag.py:227-231):
+ *                                           one linker joined to three, four or five fragments
  *   dl_pocket_select                     <- get_pocket of data/pocket/prepare_dataset.py (residues with an atom within 6 A
  *                                           of the ligand), for every (ligand, protein) pair of a batch
  *   dl_size_train_forward / dl_size_train_backward
@@ -963,8 +966,8 @@ int32_t dl_ring_scores(const dl_rings_args* args, void* stream);
  * capacity < 0 or R < 0 return DL_ERR_BAD_ARG; then B == 0 returns DL_OK without a launch; then a null pointer (other than
  * charge, status_in, `bonds` / `bond_side` when capacity is 0 and `cuts` / `labels` when R is 0) returns DL_ERR_BAD_ARG, all
  * before any device work.
- * Not here: SMILES (so symmetric cuts are not merged), conformers, BRICS, cuts at three or more bonds, aromaticity
- * perception beyond the list's orders, hydrogens.  Pockets: dl_pocket_select below. */
+ * Not here: SMILES (so symmetric cuts are not merged), conformers, BRICS, aromaticity perception beyond the list's orders,
+ * hydrogens.  Cuts at three to five bonds: dl_fragment_multicuts below.  Pockets: dl_pocket_select below. */
 #define DL_FRAG_MAX_ATOMS 256       /* atoms per molecule */
 #define DL_FRAG_CUT_FIELDS 10       /* int32 values per record of `cuts` */
 #define DL_FRAG_TOO_LARGE 4         /* status bit, same value as DL_KEYS_TOO_LARGE */
@@ -993,6 +996,74 @@ typedef struct dl_fragment_args {
     uint8_t* labels;                /* device uint8 [B,R,N] out (may be NULL when R is 0) */
 } dl_fragment_args;
 int32_t dl_fragment_cuts(const dl_fragment_args* args, void* stream);
+
+/* ---- multi-cuts: one linker joined to three, four or five fragments (fragment.hip) ----------------------------
+ * Every way to cut a molecule at k = 3, 4 or 5 bonds into ONE linker and k fragments, the examples a multi-fragment data set is
+ * made of: one workgroup per molecule, ONE launch per batch.  This project's statement of what the reference asks of RDKit's
+ * FragmentMol with minCuts = 3, maxCuts = 5 (data/geom/generate_geom_multifrag.py:227-231), over heavy atoms.  No run of the
+ * reference pins it (RDKit is no dependency of this project): this text is the authority, restated in tests/multicut_ref.py.
+ *
+ * Atoms, bond entries, DL_FRAG_BAD_BOND, "first entry of a repeated pair", CUTTABLE, "one piece" (DL_FRAG_DISCONNECTED: no
+ * cuts) and DL_FRAG_TOO_LARGE are exactly those of dl_fragment_cuts above.  Cuttable bonds are numbered in list order.
+ *
+ * GATES.  A molecule is cut only when n_atoms <= max_atoms and n_bonds - n_atoms + 1 >= min_rings (the cyclomatic number
+ * of dl_ring_scores; the reference asks NumRings() >= 3 of at most 40 atoms, the same except for cages).  A molecule that
+ * fails a gate has no cuts, and the gate sets no status bit; its other outputs are what they would be without the gates.
+ *
+ * MANY.  A molecule that passes the gates and has more than DL_FRAG_MULTI_MAX_CUTTABLE cuttable bonds sets
+ * DL_FRAG_MANY_CUTTABLE and has no cuts (a molecule of 40 atoms has at most 39; the reference itself stops at 100).
+ *
+ * STARS.  Removing a set of k cuttable bonds e_1 < ... < e_k (list positions) leaves k + 1 pieces.  The set is a STAR when one
+ * piece touches all k bonds: that piece is the LINKER, fragment q is the piece beyond e_q, anchor_q is the fragment atom of
+ * e_q and exit_q its linker atom (exits may coincide).  A star is KEPT when n_linker >= min_linker and every fragment has at
+ * least min_fragment atoms; the reference's values are 3 and 3.  There is no path rule and no linker-versus-fragments rule.
+ * Kept stars are numbered by k ascending, min_cuts <= k <= max_cuts, and within a k in lexicographic order of (e_1, ..., e_k).
+ *
+ *   n_atoms, n_bonds, n_cuttable   as dl_fragment_cuts (n_cuttable is the whole count, also beyond 64 and behind a gate)
+ *   n_cuts      ALL kept stars, also those beyond R
+ *   n_cuts_k    [B,3]: the kept stars of 3, 4 and 5 bonds (0 for a k outside min_cuts..max_cuts)
+ *   cuts        [B,R,DL_FRAG_MULTI_FIELDS]: the first min(n_cuts, R) records (k, n_linker, e[5], anchor[5], exit[5],
+ *               n_frag[5]), the slots q >= k of every row of five hold -1; unused records are all 0
+ *   labels      uint8 [B,R,N] by atom number: q for fragment q (0..4), DL_FRAG_MULTI_LINKER for the linker; 255 from the atom
+ *               count on and in every unused record
+ *   status      as dl_fragment_cuts, plus DL_FRAG_MANY_CUTTABLE; DL_FRAG_TRUNCATED when n_cuts > R.  DL_FRAG_TOO_LARGE: every
+ *               count except n_atoms is 0, cuts 0, labels 255.
+ *
+ * Integer work only: the same bits on every run.  Global memory is written with plain stores only, every output element is
+ * written, the callee allocates nothing.  Arguments are checked as by dl_fragment_cuts, and min_cuts < 3, max_cuts > 5 or
+ * min_cuts > max_cuts return DL_ERR_BAD_ARG as well; n_cuts_k may not be null.  max_atoms and min_rings are any integers
+ * (256 and 0 switch the gates off).
+ * Not here: SMILES (symmetric cuts are not merged), conformers, BRICS, hydrogens, pockets. */
+#define DL_FRAG_MULTI_FIELDS 22         /* int32 values per record of `cuts`: k, n_linker, 4 x 5 */
+#define DL_FRAG_MULTI_MIN_CUTS 3
+#define DL_FRAG_MULTI_MAX_CUTS 5
+#define DL_FRAG_MULTI_MAX_CUTTABLE 64   /* cuttable bonds of a molecule that is cut */
+#define DL_FRAG_MULTI_LINKER 5          /* value of `labels` for a linker atom */
+#define DL_FRAG_MANY_CUTTABLE 64        /* status bit: more than DL_FRAG_MULTI_MAX_CUTTABLE cuttable bonds; no cuts */
+typedef struct dl_fragment_multi_args {
+    int32_t B, N, nf;
+    const float* one_hot;           /* device f32 [B,N,nf] */
+    const float* node_mask;         /* device f32 [B,N] */
+    const int32_t* charge;          /* device int32 [B,N] by row, or NULL */
+    int32_t carbon_type;            /* index of carbon in the type table */
+    int32_t capacity;               /* bonds the list holds per molecule */
+    const int32_t* n_bonds_in;      /* device int32 [B] */
+    const int32_t* bonds;           /* device int32 [B,capacity,3] (may be NULL when capacity is 0) */
+    const int32_t* status_in;       /* device int32 [B]: dl_bonds_args.status, or NULL */
+    int32_t min_cuts, max_cuts;     /* 3 <= min_cuts <= max_cuts <= 5 */
+    int32_t min_linker, min_fragment;
+    int32_t max_atoms, min_rings;   /* the gates */
+    int32_t R;                      /* records `cuts` and `labels` hold per molecule */
+    int32_t* n_atoms;               /* device int32 [B] out */
+    int32_t* n_bonds;               /* device int32 [B] out */
+    int32_t* n_cuttable;            /* device int32 [B] out */
+    int32_t* n_cuts;                /* device int32 [B] out */
+    int32_t* status;                /* device int32 [B] out */
+    int32_t* n_cuts_k;              /* device int32 [B,3] out */
+    int32_t* cuts;                  /* device int32 [B,R,DL_FRAG_MULTI_FIELDS] out (may be NULL when R is 0) */
+    uint8_t* labels;                /* device uint8 [B,R,N] out (may be NULL when R is 0) */
+} dl_fragment_multi_args;
+int32_t dl_fragment_multicuts(const dl_fragment_multi_args* args, void* stream);
 
 /* ---- pockets: the protein atoms around every ligand of a batch (pocket.hip) -----------------------------------
  * For every (ligand, protein) pair the protein atoms whose GROUP holds an atom within `cutoff` of some ligand atom: one
