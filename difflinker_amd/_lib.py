@@ -267,7 +267,7 @@ EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_stri
            'dl_join_workspace_bytes', 'dl_sample_chain_fc_join', 'dl_bonds_workspace_bytes', 'dl_perceive_bonds',
            'dl_molecule_keys', 'dl_clash_scores', 'dl_shape_scores', 'dl_ring_scores', 'dl_fragment_cuts',
            'dl_pocket_select', 'dl_fragment_multicuts', 'dl_best_rmsd')
-TEST_HOOK_EXPORTS = ('dl_debug_team_fault',)       # declared under #ifdef DL_TEST_HOOKS: the test-hooks build only
+TEST_HOOK_EXPORTS = ('dl_debug_team_fault', 'dl_debug_slot_order')       # declared under #ifdef DL_TEST_HOOKS: the test-hooks build only
 
 _lib = None
 
@@ -286,7 +286,7 @@ def load():
 
 class test_hooks:
     """Context manager for the fault-injection tests: inside it ``load()`` returns the ``-DDL_TEST_HOOKS`` build of the
-    library (``dl_debug_team_fault`` exists there and nowhere else).  Handles (``dl_model``) are plain structs of device
+    library (``dl_debug_team_fault`` and ``dl_debug_slot_order`` exist there and nowhere else).  Handles (``dl_model``) are plain structs of device
     pointers and work across the two builds, but the tests create their models inside the context anyway."""
 
     def __enter__(self):
@@ -295,6 +295,8 @@ class test_hooks:
         lib = _open(TEST_HOOKS_LIB_PATH)
         lib.dl_debug_team_fault.restype = None
         lib.dl_debug_team_fault.argtypes = [ctypes.c_int32]
+        lib.dl_debug_slot_order.restype = ctypes.c_int32
+        lib.dl_debug_slot_order.argtypes = [ctypes.c_int32]
         _lib = lib
         return lib
 

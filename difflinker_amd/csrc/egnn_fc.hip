@@ -36,6 +36,7 @@
 
 #include "../../include/difflinker_hip.h"
 #include "pack_layout.h"
+#include "slot_order.h"
 
 
 namespace {
@@ -298,26 +299,15 @@ __device__ __forceinline__ float geo_scale(const Lds& v, const float* __restrict
 //   EQUIV = true : aggx[i]    = sum_j cdiff_ij * (w7'.u2_ij) * m_ij (coordinate head)      -> partial triples
 // The partials of the g slots of an atom are written to LDS (over P, Q, H and W2', dead by then) after the barrier that
 // ends the loop; pair_reduce_* adds them in chunk order.
-constexpr int NSLOT = 32 * GWAVES;
+static_assert(SLOT_WAVES == GWAVES, "slot_order.h plans for the workgroup's waves");
 constexpr int PB_STRIDE = LDH;                        // partial rows [NSLOT][132] from L_A on: 135 KB <= A + B + C + W
 static_assert(NSLOT * PB_STRIDE <= L_W + UNIT, "partial-sum buffer must fit the P, Q, H, W2' regions");
+// slot_plan (chunks per receiver, steps) and the lane -> (receiver, chunk) map with the short last chunks gathered into the
+// last waves: slot_order.h
 
-struct SlotPlan {
-    int g, q;
-};
-// nrec receivers share the 256 slots (all n_b atoms of the molecule, or this workgroup's part of them in a team)
-__device__ __forceinline__ SlotPlan slot_plan(int nrec, int nb) {
-    SlotPlan sp;
-    sp.g = min(NSLOT / max(nrec, 1), nb);
-    sp.q = (nb + sp.g - 1) / sp.g;
-    // ... and of the plans with that many steps the one with the FEWEST slots: a wave without slots skips the loop (8 linker atoms
-    // as receivers of 50 senders: 25 instead of 32 slots each, 7 waves instead of 8; 36 atoms: 6 instead of 7, 7 waves) - a step
-    // costs its energy per ACTIVE wave, and under the power cap energy is time (round 6)
-    sp.g = (nb + sp.q - 1) / max(sp.q, 1);
-    // (one or two MORE steps where that takes fewer wave-steps still - 38 atoms: 6 waves x 8 instead of 8 x 7 - measured slower, +5 %:
-    // the number of steps is the critical path; profiles/r06/ab_fewest_slots_plan.log)
-    return sp;
-}
+#ifdef DL_TEST_HOOKS
+__device__ int g_slots_receiver_major = 0;            // tests only (dl_debug_slot_order): every plan numbers its slots il g + c
+#endif
 
 // fp16 hi (truncated) / lo (nearest) fragments of 8 scaled values; the hi part as fp32 is the value with its low 13
 // mantissa bits cleared (v_and), which equals what v_cvt_pkrtz keeps for everything in the normal fp16 range
@@ -346,17 +336,21 @@ __device__ __forceinline__ void pair_phase(const Lds& v, int nb, int w, int lane
     // of every other atom by zero (egnn.py:113-116) - i.e. the entries of the list v.rcv.  Senders: every atom of the molecule.
     const int nrec = EQUIV ? v.misc[MS_NRCV] : (TEAM ? v.misc[TM_NOWN] : nb);
     const int S = TEAM ? v.misc[TM_S] : 1, rank = TEAM ? v.misc[TM_RANK] : 0;
-    const SlotPlan pl = slot_plan(nrec, nb);
-    const int q = pl.q;
-    const int slot = 32 * w + c;
-    const bool slot_ok = slot < nrec * pl.g;
-    const int il = slot_ok ? slot / pl.g : 0;
+#ifdef DL_TEST_HOOKS
+    const SlotOrder so = slot_order(nrec, nb, g_slots_receiver_major != 0);
+#else
+    const SlotOrder so = slot_order(nrec, nb);
+#endif
+    const SlotLane sl = slot_lane(so, nb, 32 * w + c);
+    const int q = so.q;
+    const int nt = slot_wave_steps(so, w);                        // steps of this wave: q, or r < q where it holds short last chunks only
+    const bool slot_ok = sl.ok;
+    const int il = sl.il;
     const int li = EQUIV ? (slot_ok ? v.rcv[il] : 0) : il;        // the receiving atom among the own atoms: its row of P
     const int i = rank + li * S;                                  // ... and in the molecule: coordinates, row of the edge mask
-    const int j0 = slot_ok ? (slot - il * pl.g) * q : 0;
-    const int jn = slot_ok ? min(q, nb - j0) : 0;                 // senders this slot really has (may be <= 0)
-    const bool wave_active = 32 * w < nrec * pl.g;                // wave-uniform
-    float* pb = v.A + slot * PB_STRIDE;
+    const int j0 = sl.j0;
+    const int jn = sl.jn;                                         // senders this slot really has (0: no slot)
+    const bool wave_active = nt > 0;                              // wave-uniform
 
     floatx16 agg[4];
     float ax = 0.0f, ay = 0.0f, az = 0.0f;
@@ -419,7 +413,7 @@ __device__ __forceinline__ void pair_phase(const Lds& v, int nb, int w, int lane
         typedef volatile __attribute__((address_space(3))) int* lds_vint_t;
         lds_vint_t prog = (lds_vint_t)(reinterpret_cast<int*>(v.A - L_A + L_PROG));
 
-        for (int t = 0; t < q; ++t) {
+        for (int t = 0; t < nt; ++t) {
             // the P row, the bias vectors and all of W2' do not depend on t: without an opaque offset the compiler hoists
             // ~100 LDS reads out of the loop into registers it does not have (= scratch) and reloads them every iteration
             int opq = 0;
@@ -731,12 +725,22 @@ __device__ __forceinline__ void pair_phase(const Lds& v, int nb, int w, int lane
                 ax += (dx / den) * f; ay += (dy / den) * f; az += (dz / den) * f;
             }
         }
+        // a wave that leaves early (short last chunks only) reports the whole loop done: its partner, alone on the SIMD from here
+        // on, never reads it as lagging
+        if (nt < q && lane == 0) prog[w] = q;
     }
     __builtin_amdgcn_s_setprio(0);
     prof_event(pf, w, lane, EQUIV ? 121 : 120);       // (diagnostics builds) this wave left the loop; the barrier follows
     lds_barrier();                         // every wave left the loop: P (v.A), Q (v.B), v.W are dead -> partial sums
     if (lane == 0) reinterpret_cast<int*>(v.A - L_A + L_PROG)[w] = 0;      // progress slots: zero for the next pass (nobody reads them before its loop)
-    if (slot_ok) {
+    // the partial's place in LDS: row il g + c, receiver-major whatever the lane (pair_reduce_*).  Worked out again from the
+    // lane, so that nothing of the map lives in a register across the loop
+    int slot_w = 32 * w + c;
+    asm volatile("" : "+v"(slot_w));
+    const SlotLane sw = slot_lane(so, nb, slot_w);
+    const int prow = sw.il * so.g + sw.c;
+    float* pb = v.A + prow * PB_STRIDE;
+    if (sw.ok) {
         if (!EQUIV) {
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt)
@@ -747,7 +751,7 @@ __device__ __forceinline__ void pair_phase(const Lds& v, int nb, int w, int lane
         } else if (hh == 0) {
             // compact [slot][4] triples inside the P region: H (v.C) must survive a coordinate pass (per-atom phases version 3:
             // behind the weight ring of stream_phase, whose loaders start as soon as the loop is over)
-            *reinterpret_cast<float4*>(v.A + (v.misc[CX_V3] != 0 ? L_TRIP3 - L_A : 0) + 4 * slot) = make_float4(ax, ay, az, 0.0f);
+            *reinterpret_cast<float4*>(v.A + (v.misc[CX_V3] != 0 ? L_TRIP3 - L_A : 0) + 4 * prow) = make_float4(ax, ay, az, 0.0f);
         }
     }
 }
@@ -3008,6 +3012,16 @@ int32_t dl_last_hip_error(void) { return g_last_hip; }
 int32_t dl_max_atoms(void) { return NMAX; }
 #ifdef DL_TEST_HOOKS
 void dl_debug_team_fault(int32_t launches) { g_team_fault.store(launches < 0 ? 0 : launches); }
+// receiver_major != 0: the pair loops of every later launch number their slots il g + c again (no gathering of the short last
+// chunks); 0: the product's order.  Returns DL_OK, or DL_ERR_HIP with the HIP error kept for dl_last_hip_error
+int32_t dl_debug_slot_order(int32_t receiver_major) {
+    const int value = receiver_major != 0;
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(g_slots_receiver_major), &value, sizeof(value));
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) g_last_hip = int(e);
+    return e == hipSuccess ? DL_OK : DL_ERR_HIP;
+}
 #endif
 
 const char* dl_error_string(int32_t s) {

@@ -363,6 +363,10 @@ int32_t dl_team_max_atoms(int32_t team);
  * team launches gives up at its first exchange (exercises the fail-together path above); the count runs down by itself - the
  * switch cannot stay on by accident - and 0 clears it */
 void dl_debug_team_fault(int32_t launches);
+/* receiver_major != 0: the pair loops of every later launch number their slots receiver by receiver again, as they did before the
+ * short last chunks were gathered into the last waves (csrc/slot_order.h) - the order the tests compare the product's bit for
+ * bit with; 0 restores the product's order.  Synchronises the device; stays as set until it is called again */
+int32_t dl_debug_slot_order(int32_t receiver_major);
 #endif
 /* dl_egnn_forward_fc with a team per molecule (team = 1: identical to dl_egnn_forward_fc) */
 int32_t dl_egnn_forward_fc_team(const dl_model* m, int32_t B, int32_t N, const float* xh, const float* t,
