@@ -238,6 +238,25 @@ class DLFragmentMultiArgs(ctypes.Structure):
     ]
 
 
+DL_AROM_MAX_ATOMS, DL_AROM_MAX_RINGS, DL_AROM_MAX_SYSTEM = 256, 64, 32        # dl_aromatic_args: kept atoms, planar rings, system atoms
+DL_AROM_TOO_LARGE, DL_AROM_BAD_BOND = 4, 8            # dl_aromatic_args.status bits, beside the DL_BONDS_* bits carried forward
+DL_AROM_MANY_RINGS, DL_AROM_BIG_SYSTEM = 16, 32
+
+
+class DLAromaticArgs(ctypes.Structure):
+    _fields_ = [
+        ('B', ctypes.c_int32), ('N', ctypes.c_int32), ('nf', ctypes.c_int32),
+        ('x', ctypes.c_void_p), ('one_hot', ctypes.c_void_p), ('node_mask', ctypes.c_void_p),
+        ('drop_mask', ctypes.c_void_p), ('mark_mask', ctypes.c_void_p), ('ring_class', ctypes.c_void_p),
+        ('capacity', ctypes.c_int32),
+        ('n_bonds_in', ctypes.c_void_p), ('bonds', ctypes.c_void_p), ('status_in', ctypes.c_void_p),
+        ('tol2_ring', ctypes.c_double), ('tol2_sub', ctypes.c_double),
+        ('order_out', ctypes.c_void_p), ('bond_aromatic', ctypes.c_void_p), ('atom_aromatic', ctypes.c_void_p),
+        ('valence_out', ctypes.c_void_p), ('n_planar_rings', ctypes.c_void_p), ('n_aromatic_rings', ctypes.c_void_p),
+        ('n_aromatic_marked', ctypes.c_void_p), ('status', ctypes.c_void_p),
+    ]
+
+
 DL_POCKET_MAX_LIGAND, DL_POCKET_MAX_GROUPS = 256, 32768                     # dl_pocket_args: ligand atoms per pair; groups per protein
 DL_POCKET_NONFINITE, DL_POCKET_TOO_LARGE, DL_POCKET_TOO_MANY_GROUPS = 1, 2, 4  # dl_pocket_args.status bits
 DL_POCKET_BAD_PROTEIN, DL_POCKET_TRUNCATED = 8, 32
@@ -266,7 +285,7 @@ EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_stri
            'dl_size_train_num_params', 'dl_size_train_workspace_bytes', 'dl_size_train_forward', 'dl_size_train_backward',
            'dl_join_workspace_bytes', 'dl_sample_chain_fc_join', 'dl_bonds_workspace_bytes', 'dl_perceive_bonds',
            'dl_molecule_keys', 'dl_clash_scores', 'dl_shape_scores', 'dl_ring_scores', 'dl_fragment_cuts',
-           'dl_pocket_select', 'dl_fragment_multicuts', 'dl_best_rmsd')
+           'dl_pocket_select', 'dl_fragment_multicuts', 'dl_aromatic_rings', 'dl_best_rmsd')
 TEST_HOOK_EXPORTS = ('dl_debug_team_fault', 'dl_debug_slot_order')       # declared under #ifdef DL_TEST_HOOKS: the test-hooks build only
 
 _lib = None
@@ -398,6 +417,8 @@ def _open(path):
     lib.dl_fragment_cuts.argtypes = [ctypes.POINTER(DLFragmentArgs), vp]
     lib.dl_fragment_multicuts.restype = i32
     lib.dl_fragment_multicuts.argtypes = [ctypes.POINTER(DLFragmentMultiArgs), vp]
+    lib.dl_aromatic_rings.restype = i32
+    lib.dl_aromatic_rings.argtypes = [ctypes.POINTER(DLAromaticArgs), vp]
     lib.dl_pocket_select.restype = i32
     lib.dl_pocket_select.argtypes = [ctypes.POINTER(DLPocketArgs), vp]
     lib.dl_best_rmsd.restype = i32

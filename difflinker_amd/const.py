@@ -105,6 +105,15 @@ def max_valence_table(is_geom):
     return torch.tensor([max(v) if isinstance(v, (list, tuple)) else v for v in limits], dtype=torch.int32)
 
 
+def ring_class_table(is_geom):
+    """int32 ``[n_types]``: the class ``dl_aromatic_rings`` gives every element of the vocabulary, in index order: 1 for
+    carbon, 2 for nitrogen, 3 for oxygen and sulphur, 0 for everything else (halogens and phosphorus are never ring atoms of
+    an aromatic ring here)."""
+    idx2atom = GEOM_IDX2ATOM if is_geom else IDX2ATOM
+    classes = {'C': 1, 'N': 2, 'O': 3, 'S': 3}
+    return torch.tensor([classes.get(idx2atom[k], 0) for k in range(len(idx2atom))], dtype=torch.int32)
+
+
 # Bondi's van der Waals radii in Angstrom (J. Phys. Chem. 68, 441 (1964)) by GEOM atom index (C O N F S Cl Br I P; the ZINC
 # vocabulary is the leading 8): what the clash rule of ``metrics.analyze_clashes`` is built from
 VDW_RADII = (1.70, 1.52, 1.55, 1.47, 1.80, 1.75, 1.85, 1.98, 1.80)

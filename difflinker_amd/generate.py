@@ -22,7 +22,7 @@ from .datasets import MOADDataset, collate_with_fragment_edges, collate_with_fra
 from .io import get_pocket, get_protein_atoms, parse_molecule, pocket_arrays, read_molecule, read_pocket, save_sdf_file, save_xyz_file
 from .lightning import DDPM
 from .linker_size import SizeClassifier
-from .molecule_builder import perceive_all_bonds, summary
+from .molecule_builder import perceive_all_bonds, refine_bond_orders, summary
 from .utils import FoundNaNException
 
 
@@ -76,13 +76,17 @@ def _batches(dataset, batch_size, collate_fn):
 
 
 OUTPUT_FORMATS = ('xyz', 'sdf', 'both')
+BOND_ORDERS = ('distance', 'geometric')
 
 
 def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_dir, name, com_key, hide_pocket,
-                     output_format='xyz', metrics=False, clashes=False, protein=None, rings=False):
+                     output_format='xyz', metrics=False, clashes=False, protein=None, rings=False, bond_orders='distance',
+                     aromatic=False):
     if output_format not in OUTPUT_FORMATS:
         raise ValueError(f'output_format must be one of {OUTPUT_FORMATS}, got {output_format!r}')
-    written, found, scored, clash_records, ring_records = [], [], [], [], []
+    if bond_orders not in BOND_ORDERS:
+        raise ValueError(f'bond_orders must be one of {BOND_ORDERS}, got {bond_orders!r}')
+    written, found, scored, clash_records, ring_records, aromatic_records = [], [], [], [], [], []
     for batch_i, data in enumerate(_batches(dataset, batch_size, collate_fn)):
         n = len(data['positions'])
         chain = None
@@ -122,7 +126,10 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
             written += [os.path.join(output_dir, f'{nm}_.xyz') for nm in names]
         if output_format != 'xyz':                            # on the chain's output, before it leaves the device
             found.append(perceive_all_bonds(h, x, node_mask, ddpm.is_geom))
-            save_sdf_file(output_dir, h, x, node_mask, found[-1].bonds, found[-1].n_bonds, names=names,
+            shown = found[-1]
+            if bond_orders == 'geometric':                    # Kekule orders for the planar rings, from the same geometry
+                shown = refine_bond_orders(shown, h[:, :, :ddpm.num_classes], x, node_mask, ddpm.is_geom)[0]
+            save_sdf_file(output_dir, h, x, node_mask, shown.bonds, shown.n_bonds, names=names,
                           is_geom=ddpm.is_geom, suffix='')
             written += [os.path.join(output_dir, f'{nm}_.sdf') for nm in names]
         if metrics:                                           # the molecules as written: without the pocket
@@ -132,9 +139,13 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
             pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, x.shape[1] - m.shape[1]))     # noqa: E731
             ring_records += mol_metrics.rings_to_host(*mol_metrics.analyze_rings(
                 h[:, :, :ddpm.num_classes], x, node_mask, ddpm.is_geom, node_mask * (1 - pad(data['fragment_mask']))))
+        if aromatic:                                          # likewise
+            pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, x.shape[1] - m.shape[1]))     # noqa: E731
+            aromatic_records += mol_metrics.aromatic_to_host(mol_metrics.analyze_aromatic(
+                h[:, :, :ddpm.num_classes], x, node_mask, ddpm.is_geom, node_mask * (1 - pad(data['fragment_mask']))))
     if found:
         print(json.dumps(summary(found)))
-    if metrics or clashes or rings:
+    if metrics or clashes or rings or aromatic:
         scores = {}
         if metrics:                                           # no true molecule here: no novelty, no recovery
             scores = dict(mol_metrics.compute_metrics(scored), molecules=len(scored))
@@ -142,6 +153,8 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
             scores.update(mol_metrics.compute_clashes(clash_records))
         if rings:                                             # no true molecule here either
             scores.update(mol_metrics.compute_rings(ring_records))
+        if aromatic:
+            scores.update(mol_metrics.compute_aromatic(aromatic_records))
         with open(os.path.join(output_dir, 'metrics.json'), 'w') as f:
             json.dump(scores, f, indent=1)
     if clashes:                                               # one record per written file, by its name
@@ -155,13 +168,17 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
 
 
 def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anchors=None, device=None, output_format='xyz',
-             metrics=False, clashes=False, rings=False):
+             metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False):
     """``generate.py`` main(): fragments file -> ``n_samples`` molecules with a sampled linker, as ``.xyz`` files
     (``output_format='sdf'``: ``.sdf`` files with perceived bonds instead, ``'both'``: both; one JSON line with the number of
     molecules, the share in one piece and the mean bond count is printed then).  ``metrics=True`` also writes
     ``metrics.json`` to ``output_dir``: valence rule, connectivity and uniqueness of the samples (``metrics.compute_metrics``).
     ``rings=True`` adds the ring scores of the samples to ``metrics.json`` (``metrics.analyze_rings`` / ``compute_rings``: the
-    linker's ring count, small rings, macrocycles; the pocket variants take it as well)."""
+    linker's ring count, small rings, macrocycles; the pocket variants take it as well).  ``bond_orders='geometric'`` writes
+    the ``.sdf`` files with the Kekule orders of ``molecule_builder.refine_bond_orders`` (planar five- and six-rings
+    alternate; 1, 2 or 3, never 4) and ``aromatic=True`` adds ``aromatic_rings_n``, ``ring_filter`` and
+    ``valence_validity_geometric`` to ``metrics.json`` (``metrics.analyze_aromatic`` / ``compute_aromatic``); both rest on a
+    geometric rule of this project's own, not on OpenBabel's or RDKit's, and the pocket variants take them as well."""
     if clashes:
         raise ValueError('clashes are scored against a protein: pass a pocket or a protein file (--pocket / --protein)')
     device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
@@ -184,11 +201,12 @@ def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anc
     }] * n_samples
     return _sample_and_save(ddpm, dataset, collate_with_fragment_edges, sample_fn, min(n_samples, 64), output_dir, name,
                             com_key='fragment_mask', hide_pocket=False, output_format=output_format, metrics=metrics,
-                            rings=rings)
+                            rings=rings, bond_orders=bond_orders, aromatic=aromatic)
 
 
 def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size, device,
-                            output_format, metrics=False, clashes=False, protein=None, rings=False):
+                            output_format, metrics=False, clashes=False, protein=None, rings=False, bond_orders='distance',
+                            aromatic=False):
     frag_pos, frag_one_hot, frag_charges = frag
     pocket_pos, pocket_one_hot, pocket_charges = pocket
     positions = np.concatenate([frag_pos, pocket_pos], axis=0)
@@ -209,12 +227,12 @@ def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_s
     return _sample_and_save(ddpm, dataset, collate_with_fragment_without_pocket_edges, sample_fn,
                             min(n_samples, max_batch_size), output_dir, name, com_key='fragment_only_mask',
                             hide_pocket=True, output_format=output_format, metrics=metrics, clashes=clashes, protein=protein,
-                            rings=rings)
+                            rings=rings, bond_orders=bond_orders, aromatic=aromatic)
 
 
 def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, output_dir, n_samples, n_steps, linker_size,
                          anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz',
-                         metrics=False, clashes=False, rings=False):
+                         metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False):
     """``generate_with_pocket.py`` main(): the pocket is given as its own PDB file.  ``clashes=True`` scores every sample's
     generated atoms against the pocket atoms (``metrics.analyze_clashes``), adds the ``metrics.compute_clashes`` keys to
     ``metrics.json`` and writes ``clashes.json``: ``n_clashes``, ``n_clash_atoms`` and ``min_distance`` per written file."""
@@ -236,12 +254,13 @@ def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, ou
     frag = parse_molecule(molecule, is_geom=ddpm.is_geom)
     pocket = pocket_arrays(read_pocket(pocket_path), backbone_atoms_only)
     return _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size,
-                                   device, output_format, metrics, clashes, rings=rings)
+                                   device, output_format, metrics, clashes, rings=rings, bond_orders=bond_orders,
+                                   aromatic=aromatic)
 
 
 def generate_with_protein(input_path, protein_path, backbone_atoms_only, model, output_dir, n_samples, n_steps,
                           linker_size, anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz',
-                          metrics=False, clashes=False, rings=False):
+                          metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False):
     """``generate_with_protein.py`` main(): the pocket = residues of the protein within 6 A of the fragments.
     ``clashes=True`` as in ``generate_with_pocket``, but against ALL protein atoms whose element is in the vocabulary
     (``io.get_protein_atoms``), residues outside the pocket the model saw included; the pocket rows of the batch are then not
@@ -265,7 +284,8 @@ def generate_with_protein(input_path, protein_path, backbone_atoms_only, model, 
         protein = (torch.tensor(positions, dtype=const.TORCH_FLOAT, device=device),
                    torch.tensor(types, dtype=torch.int32, device=device))
     return _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size,
-                                   device, output_format, metrics, clashes, protein, rings=rings)
+                                   device, output_format, metrics, clashes, protein, rings=rings, bond_orders=bond_orders,
+                                   aromatic=aromatic)
 
 
 def main(argv=None):
@@ -296,11 +316,22 @@ def main(argv=None):
     p.add_argument('--rings', action='store_true',
                    help='perceive the rings of the generated molecules on the GPU (ring count of the linker, small rings, '
                         'macrocycles; the cyclomatic number, no aromaticity) and add the scores to metrics.json')
+    p.add_argument('--bond_orders', choices=BOND_ORDERS, default='distance',
+                   help='bond orders of the .sdf files: distance (the distance table of the reference\'s molecule_builder) or '
+                        'geometric (planar five- and six-rings get Kekule orders 1 / 2 from the 3D geometry, so aromatic rings '
+                        'alternate; a rule of this project, not OpenBabel\'s bond typing)')
+    p.add_argument('--aromatic', action='store_true',
+                   help='perceive aromatic rings from the geometry on the GPU (a rule of this project, not RDKit\'s) and add '
+                        'aromatic_rings_n, ring_filter and valence_validity_geometric to metrics.json')
     a = p.parse_args(argv)
     if a.clashes and a.pocket is None and a.protein is None:
         raise ValueError('--clashes scores the generated atoms against a protein: pass --pocket or --protein')
     extra = {'clashes': True} if a.clashes else {}
     more = {'rings': True} if a.rings else {}
+    if a.bond_orders != 'distance':
+        more['bond_orders'] = a.bond_orders
+    if a.aromatic:
+        more['aromatic'] = True
     if a.pocket is not None:
         files = generate_with_pocket(a.fragments, a.pocket, a.backbone_atoms_only, a.model, a.output, a.n_samples,
                                      a.n_steps, a.linker_size, a.anchors, a.max_batch_size, a.random_seed,

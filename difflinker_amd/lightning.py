@@ -102,6 +102,7 @@ class DDPM(_Base):
         self.geometry_metrics = False           # sample_and_analyze adds metrics.compute_geometry's RMSD keys (train --geometry)
         self.clash_metrics = False              # pocket models: it adds metrics.compute_clashes' keys as well (train --clashes)
         self.shape_metrics = False              # it adds metrics.compute_shapes' keys: every sample against its true molecule (train --shape)
+        self.aromatic_metrics = False           # it adds metrics.compute_aromatic's keys: aromatic rings of the linker, ring filter, valence rule on geometric orders (train --aromatic)
         self.ring_metrics = False               # it adds metrics.compute_rings' keys: ring count of the linker, small rings, macrocycles (train --rings)
         if _Base is nn.Module:
             self.current_epoch = 0              # Lightning's Trainer keeps this; here the training loop sets it
@@ -321,8 +322,11 @@ class DDPM(_Base):
         frame the two share (``metrics.compute_shapes``; pocket rows left out, once over all ligand rows and once over the
         linker rows).  With ``self.ring_metrics`` the rings of every sample and of its true molecule are perceived
         (``metrics.analyze_rings`` / ``compute_rings``; pocket rows dropped): the linker's ring count, small rings,
-        macrocycles.  No animation, no WandB."""
+        macrocycles.  With ``self.aromatic_metrics`` aromatic rings are perceived from the geometry and the ring bonds get
+        Kekule orders (``metrics.analyze_aromatic`` / ``compute_aromatic``, a rule of this project's own, not RDKit's):
+        ``aromatic_rings_n``, ``ring_filter``, ``valence_validity_geometric``.  No animation, no WandB."""
         pred, true, input_index = [], [], []
+        pred_aromatic, true_aromatic = [], []
         pred_rings, true_rings = [], []
         shapes, linker_shapes = [], []
         pred_x, true_x, n_linker = [], [], []
@@ -340,6 +344,10 @@ class DDPM(_Base):
                     data['one_hot'][:, :, :self.num_classes], data['positions'], data['linker_mask'], drop, is_geom=self.is_geom))
             if self.ring_metrics:
                 true_ring_batch = mol_metrics.rings_to_host(*mol_metrics.analyze_rings(
+                    data['one_hot'][:, :, :self.num_classes], data['positions'], data['atom_mask'], self.is_geom,
+                    data['linker_mask'], drop_mask=drop))
+            if self.aromatic_metrics:
+                true_aromatic_batch = mol_metrics.aromatic_to_host(mol_metrics.analyze_aromatic(
                     data['one_hot'][:, :, :self.num_classes], data['positions'], data['atom_mask'], self.is_geom,
                     data['linker_mask'], drop_mask=drop))
             if self.geometry_metrics:
@@ -378,6 +386,11 @@ class DDPM(_Base):
                     pred_rings += mol_metrics.rings_to_host(*mol_metrics.analyze_rings(
                         one_hot, x, node_mask, self.is_geom, node_mask * (1 - frag), drop_mask=out_drop))
                     true_rings += true_ring_batch
+                if self.aromatic_metrics:                                          # the template's linker rows marked
+                    frag = torch.nn.functional.pad(data['fragment_mask'], (0, 0, 0, node_mask.shape[1] - data['fragment_mask'].shape[1]))
+                    pred_aromatic += mol_metrics.aromatic_to_host(mol_metrics.analyze_aromatic(
+                        one_hot, x, node_mask, self.is_geom, node_mask * (1 - frag), drop_mask=out_drop))
+                    true_aromatic += true_aromatic_batch
                 if self.geometry_metrics:
                     pred_x += list(mol_metrics.kept_positions(x, node_mask, out_drop)[0])
                     true_x += true_x_batch
@@ -392,6 +405,8 @@ class DDPM(_Base):
             scores.update(mol_metrics.compute_shapes(shapes, linker_shapes, pred))
         if self.ring_metrics:
             scores.update(mol_metrics.compute_rings(pred_rings, true_rings))
+        if self.aromatic_metrics:
+            scores.update(mol_metrics.compute_aromatic(pred_aromatic, true_aromatic))
         return scores
 
     def _shape_records(self, data, one_hot, x, node_mask, drop, out_drop, linker):

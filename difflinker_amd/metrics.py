@@ -25,8 +25,13 @@ half of SC-RDKit; the grid rule is this project's own after RDKit's defaults, no
 
 ``analyze_rings`` / ``compute_rings`` score ring topology, which none of the above sees: the number of rings of the linker
 (the reference's ``rings_n``, compute_metrics.py:128-145), three- and four-membered rings, and macrocycles closed through a
-fragment (``dl_ring_scores``, ``csrc/rings.hip``).  The ring count is the cyclomatic number, not RDKit's symmetrised count;
-there is no aromaticity, so the reference's ring filter is not reproduced.
+fragment (``dl_ring_scores``, ``csrc/rings.hip``).  The ring count is the cyclomatic number, not RDKit's symmetrised count.
+
+``analyze_aromatic`` / ``compute_aromatic`` score what needs aromaticity: the aromatic rings of the linker, the reference's
+ring filter ("no double bond inside a non-aromatic ring", compute_metrics.py:269-277) and the valence rule on bond orders
+that treat aromatic rings properly (``dl_aromatic_rings``, ``csrc/aromatic.hip``).  Aromaticity is perceived from the 3D
+geometry by a rule of this project's own - not RDKit's model, not OpenBabel's bond typing; see
+``molecule_builder.refine_bond_orders``.
 """
 import ctypes
 import math
@@ -36,7 +41,7 @@ import numpy as np
 import torch
 
 from . import _lib, const
-from .molecule_builder import perceive_all_bonds
+from .molecule_builder import perceive_all_bonds, refine_bond_orders
 
 Analysis = namedtuple('Analysis', 'n_atoms n_over n_components n_bonds key colour status bonds')
 Graph = namedtuple('Graph', 'types bonds colours')
@@ -811,4 +816,80 @@ def compute_rings(pred, true=None):
         both = [(p, t) for p, t in zip(pred, true) if _ring_scored(p) and _ring_scored(t)]
         out['true_rings_n'] = mean([t.n_rings for _, t in both])
         out['rings_n_match'] = mean([p.n_rings == t.n_rings for p, t in both])
+    return out
+
+
+AromaticScores = namedtuple('AromaticScores', 'n_aromatic_linker n_aromatic n_planar n_filtered_bonds n_over status refined '
+                                              'aromatic')
+AromaticRecord = namedtuple('AromaticRecord', 'n_aromatic_linker n_aromatic n_planar n_filtered_bonds n_over status')
+AROMATIC_NAMES = ('aromatic_molecules', 'aromatic_flagged', 'aromatic_rings_n', 'ring_filter', 'valence_validity_geometric')
+
+
+def analyze_aromatic(one_hot, x, node_mask, is_geom, linker_mask, drop_mask=None, margins=const.MARGINS_EDM, planarity=0.1,
+                     substituent=0.5):
+    """Aromatic rings and geometric bond orders of every molecule of a batch on the HIP device: ONE bond perception
+    (``perceive_all_bonds``, which synchronises), then three launches that do not - ``refine_bond_orders`` with the
+    ``linker_mask`` rows marked, ``ring_scores`` on the same list and ``molecule_keys`` on the refined one - and device tensor
+    operations that combine them.  ``drop_mask`` rows (the pocket of a pocket model) are left out of all three.
+
+    Returns an ``AromaticScores`` of device tensors ``[B]``: ``n_aromatic_linker`` (aromatic rings all of whose atoms are
+    linker rows), ``n_aromatic``, ``n_planar``; ``n_filtered_bonds``, the bonds of new order 2 that lie in a ring
+    (``bond_ring > 0``) and are not aromatic - what the reference's ring filter rejects; ``n_over``, the atoms over their
+    valence limit with the new orders; ``status``, the bits of all three launches; and ``refined`` / ``aromatic`` as
+    ``refine_bond_orders`` returns them.  Aromaticity is this project's own geometric rule, not RDKit's or OpenBabel's."""
+    if not (one_hot.is_cuda and x.is_cuda and node_mask.is_cuda and linker_mask.is_cuda):
+        raise _lib.HipLibraryError('analyze_aromatic runs on the HIP device only (no CPU fallback): '
+                                   f'got tensors on {one_hot.device}, {x.device}, {node_mask.device}, {linker_mask.device}')
+    B, N = one_hot.shape[:2]
+    if linker_mask.numel() != B * N:
+        raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, linker_mask {tuple(linker_mask.shape)}')
+    found = perceive_all_bonds(one_hot, x, node_mask, is_geom, margins)
+    linker = linker_mask.reshape(B, N).to(torch.float32)
+    refined, aromatic = refine_bond_orders(found, one_hot, x, node_mask, is_geom, drop_mask, linker, planarity, substituent)
+    rings = ring_scores(node_mask, found, drop_mask)
+    keys = molecule_keys(one_hot, node_mask, refined, is_geom, drop_mask)
+    filtered = (refined.bonds[:, :, 2] == 2) & (rings.bond_ring > 0) & (aromatic.bond_aromatic == 0)
+    return AromaticScores(aromatic.n_aromatic_marked, aromatic.n_aromatic_rings, aromatic.n_planar_rings,
+                          filtered.sum(dim=1).to(torch.int32), keys.n_over, aromatic.status | rings.status | keys.status,
+                          refined, aromatic)
+
+
+def aromatic_to_host(result):
+    """One ``AromaticRecord`` of plain values per molecule of an ``AromaticScores``."""
+    columns = [getattr(result, name).cpu().tolist() for name in AromaticRecord._fields]
+    return [AromaticRecord(*row) for row in zip(*columns)]
+
+
+def _aromatic_scored(record):
+    return not record.status & ~_lib.DL_BONDS_NONFINITE
+
+
+def compute_aromatic(pred, true=None):
+    """Scores of the ``AromaticRecord`` values ``pred`` (``aromatic_to_host``), in fp64:
+
+    ``aromatic_molecules``          records scored; those with any status bit other than ``DL_BONDS_NONFINITE`` (a cut list, an
+                                    entry that is no bond, more than 256 atoms, more than 64 planar rings, a ring system of
+                                    more than 32 atoms) are left out of everything below
+    ``aromatic_flagged``            how many were left out
+    ``aromatic_rings_n``            mean number of aromatic rings that lie wholly in the linker
+    ``ring_filter``                 share of the scored records with no double bond inside a ring that is not aromatic - the
+                                    reference's 2D ring filter (compute_metrics.py:269-277) on this project's aromaticity
+    ``valence_validity_geometric``  share with no atom over its valence limit under the geometric bond orders
+
+    With ``true`` - one record per prediction, the data set's own molecule - over the positions where both are scored:
+    ``true_aromatic_rings_n``, ``true_ring_filter`` and ``true_valence_validity_geometric``.  A mean or a share over nothing
+    is ``None``, as in ``compute_rings``.  Aromaticity here is a geometric rule of this project's own, not RDKit's."""
+    if true is not None and len(true) != len(pred):
+        raise ValueError(f'{len(pred)} predictions, {len(true)} true records')
+    mean = lambda values: float(sum(values) / len(values)) if values else None      # noqa: E731
+    good = [m for m in pred if _aromatic_scored(m)]
+    out = {'aromatic_molecules': len(good), 'aromatic_flagged': len(pred) - len(good),
+           'aromatic_rings_n': mean([m.n_aromatic_linker for m in good]),
+           'ring_filter': mean([m.n_filtered_bonds == 0 for m in good]),
+           'valence_validity_geometric': mean([m.n_over == 0 for m in good])}
+    if true is not None:
+        both = [t for p, t in zip(pred, true) if _aromatic_scored(p) and _aromatic_scored(t)]
+        out['true_aromatic_rings_n'] = mean([t.n_aromatic_linker for t in both])
+        out['true_ring_filter'] = mean([t.n_filtered_bonds == 0 for t in both])
+        out['true_valence_validity_geometric'] = mean([t.n_over == 0 for t in both])
     return out

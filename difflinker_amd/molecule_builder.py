@@ -15,8 +15,10 @@ import torch
 from . import _lib, const
 
 Bonds = namedtuple('Bonds', 'n_bonds bonds valence n_components component status')
+Aromatic = namedtuple('Aromatic', 'bond_aromatic atom_aromatic n_planar_rings n_aromatic_rings n_aromatic_marked status')
 
 _TABLES = {}
+_RING_CLASSES = {}
 
 
 def _table(device, is_geom, margins):
@@ -71,6 +73,74 @@ def perceive_all_bonds(one_hot, x, node_mask, is_geom, margins=const.MARGINS_EDM
     if most > found.bonds.shape[1]:
         found = perceive_bonds(one_hot, x, node_mask, is_geom, margins, capacity=most)
     return found
+
+
+def _ring_classes(device, is_geom):
+    key = (device, bool(is_geom))
+    if key not in _RING_CLASSES:
+        _RING_CLASSES[key] = const.ring_class_table(is_geom).to(device).contiguous()
+    return _RING_CLASSES[key]
+
+
+def refine_bond_orders(found, one_hot, x, node_mask, is_geom, drop_mask=None, mark_mask=None, planarity=0.1,
+                       substituent=0.5):
+    """Kekule bond orders for the planar five- and six-rings of every molecule, from the 3D geometry, and the aromatic rings
+    among them (``dl_aromatic_rings``, ``csrc/aromatic.hip``): ONE launch on the result ``found`` of ``perceive_bonds`` for
+    the same ``one_hot``, ``x`` and ``node_mask``, without a host synchronisation.  The distance table of ``perceive_bonds``
+    turns an aromatic ring into an arbitrary mix of single and double bonds; this replaces the orders inside such rings and
+    leaves every other order alone.
+
+    THE RULE is this project's own (``include/difflinker_hip.h`` states it in full; ``tests/aromatic_ref.py`` restates it): it
+    is NOT RDKit's aromaticity model and NOT OpenBabel's bond typing.  Ring atoms are C and N of degree 2 or 3 and O and S of
+    degree 2; a chordless 5- or 6-cycle of them is planar when its atoms lie within ``planarity`` (A) and their other
+    neighbours within ``substituent`` (A) of the plane through its centroid whose normal is the ring's area vector; connected
+    planar rings form a system; O, S and three-bonded N give two electrons and take no ring double bond, an atom with a
+    double bond out of the rings gives none, and a matching that covers the most carbons, then the most two-bonded N, then is
+    lexicographically smallest, places the double bonds; a ring with six electrons and every carbon covered is aromatic.
+    No hydrogens (N-H and =N- are told apart only by the matching), no charges, rings of 5 and 6 atoms only; a planar
+    saturated ring is misread as conjugated.
+
+    ``drop_mask`` (the pocket) removes atoms together with their bonds, ``mark_mask`` (the linker) marks atoms, both
+    ``[B,N]`` or ``[B,N,1]`` by row.  Returns ``(refined, aromatic)``: ``refined`` is a ``Bonds`` whose list carries the new
+    orders (1, 2 or 3, never 4; 0 for an entry that is no bond) and whose ``valence`` is their sum per atom - whatever takes a
+    ``Bonds`` takes it; ``aromatic`` holds ``bond_aromatic [B,capacity]``, ``atom_aromatic [B,N]``, ``n_planar_rings``,
+    ``n_aromatic_rings``, ``n_aromatic_marked`` (aromatic rings all of whose atoms are marked) and ``status`` ``[B]``: the bits
+    of ``found.status`` plus ``_lib.DL_AROM_*`` (more than 256 kept atoms or 64 planar rings: the orders pass through; a
+    system of more than 32 atoms keeps its orders)."""
+    masks = (node_mask,) + tuple(m for m in (drop_mask, mark_mask) if m is not None)
+    if not (one_hot.is_cuda and x.is_cuda and found.bonds.is_cuda and all(m.is_cuda for m in masks)):
+        raise _lib.HipLibraryError('refine_bond_orders runs on the HIP device only (no CPU fallback): '
+                                   f'got tensors on {one_hot.device}, {x.device}, {found.bonds.device}')
+    B, N, nf = one_hot.shape
+    if x.shape != (B, N, 3) or any(m.numel() != B * N for m in masks) or found.bonds.dim() != 3 or found.bonds.shape[0] != B:
+        raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, x {tuple(x.shape)}, masks '
+                         f'{[tuple(m.shape) for m in masks]}, bonds {tuple(found.bonds.shape)}')
+    dev = one_hot.device
+    f32 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()     # noqa: E731
+    one_hot, x, node_mask, drop_mask, mark_mask = f32(one_hot), f32(x), f32(node_mask), f32(drop_mask), f32(mark_mask)
+    classes = _ring_classes(dev, is_geom)
+    if classes.numel() < nf:
+        raise ValueError(f'one_hot has {nf} types, the vocabulary {classes.numel()}')
+    capacity = found.bonds.shape[1]
+    bonds = found.bonds.contiguous()
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    order, valence = i32(B, capacity), i32(B, N)
+    out = Aromatic(i32(B, capacity), i32(B, N), i32(B), i32(B), i32(B), i32(B))
+    opt = lambda t: None if t is None else t.data_ptr()                     # noqa: E731
+    args = _lib.DLAromaticArgs(
+        B=B, N=N, nf=nf, x=x.data_ptr(), one_hot=one_hot.data_ptr(), node_mask=node_mask.data_ptr(), drop_mask=opt(drop_mask),
+        mark_mask=opt(mark_mask), ring_class=classes.data_ptr(), capacity=capacity, n_bonds_in=found.n_bonds.data_ptr(),
+        bonds=bonds.data_ptr() if capacity else None, status_in=found.status.data_ptr(),
+        tol2_ring=float(planarity) ** 2, tol2_sub=float(substituent) ** 2,
+        order_out=order.data_ptr() if capacity else None, bond_aromatic=out.bond_aromatic.data_ptr() if capacity else None,
+        atom_aromatic=out.atom_aromatic.data_ptr(), valence_out=valence.data_ptr(),
+        n_planar_rings=out.n_planar_rings.data_ptr(), n_aromatic_rings=out.n_aromatic_rings.data_ptr(),
+        n_aromatic_marked=out.n_aromatic_marked.data_ptr(), status=out.status.data_ptr())
+    with torch.cuda.device(dev):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.load().dl_aromatic_rings(ctypes.byref(args), stream), 'dl_aromatic_rings')
+    refined = found._replace(bonds=torch.cat([bonds[:, :, :2], order[:, :, None]], dim=2), valence=valence)
+    return refined, out
 
 
 def build_xae_molecules(one_hot, x, node_mask, is_geom, margins=const.MARGINS_EDM):

@@ -16,11 +16,11 @@ import torch
 from . import metrics as mol_metrics
 from . import utils
 from .datasets import MOADDataset, collate, collate_with_fragment_edges, get_dataloader
-from .generate import OUTPUT_FORMATS
+from .generate import BOND_ORDERS, OUTPUT_FORMATS
 from .io import save_sdf_file, save_xyz_file
 from .lightning import DDPM
 from .linker_size import SizeClassifier
-from .molecule_builder import perceive_all_bonds, summary
+from .molecule_builder import perceive_all_bonds, refine_bond_orders, summary
 
 
 def check_if_generated(_output_dir, _uuids, n_samples):
@@ -56,7 +56,8 @@ def _prepare(checkpoint, prefix, data, n_steps, device):
 
 
 def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=None, linker_size_model=None,
-           output_format='xyz', metrics=False, geometry=False, clashes=False, shape=False, rings=False):
+           output_format='xyz', metrics=False, geometry=False, clashes=False, shape=False, rings=False,
+           bond_orders='distance', aromatic=False):
     """``sample.py``.  Returns the output directory.  ``metrics=True`` scores the molecules sampled in this call against
     the data set's own (``metrics.compute_metrics``: valence rule, connectivity, uniqueness, novelty, recovery) and writes
     the result to ``metrics.json`` in the output directory; with ``geometry=True`` as well, the symmetry-aware RMSD of the
@@ -71,9 +72,16 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
     ``compute_shapes``: once over the ligand rows, once over the linker rows alone); its keys go into ``metrics.json`` in the
     same way, with ``shape_tanimoto_valid`` when ``metrics`` is asked for as well.  ``rings=True`` perceives the rings of
     every sample and of its true molecule, pocket rows left out (``metrics.analyze_rings`` / ``compute_rings``: the linker's
-    ring count ``rings_n``, small rings, macrocycles), and writes those keys in the same way."""
+    ring count ``rings_n``, small rings, macrocycles), and writes those keys in the same way.  ``bond_orders='geometric'``
+    writes the ``.sdf`` files with the Kekule orders of ``molecule_builder.refine_bond_orders`` (planar five- and six-rings
+    alternate; 1, 2 or 3, never 4); ``aromatic=True`` adds ``aromatic_rings_n``, ``ring_filter`` and
+    ``valence_validity_geometric`` of the samples and of their true molecules (``metrics.analyze_aromatic`` /
+    ``compute_aromatic``).  Both rest on a geometric rule of this project's own, not on OpenBabel's or RDKit's."""
     if output_format not in OUTPUT_FORMATS:
         raise ValueError(f'output_format must be one of {OUTPUT_FORMATS}, got {output_format!r}')
+    if bond_orders not in BOND_ORDERS:
+        raise ValueError(f'bond_orders must be one of {BOND_ORDERS}, got {bond_orders!r}')
+    pred_aromatic, true_aromatic = [], []
     found, pred, true, input_index = [], [], [], []
     pred_x, true_x, n_linker = [], [], []
     pred_clashes, true_clashes = [], []
@@ -136,6 +144,9 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
         if rings:                                              # the data set's own molecule, without the pocket
             true_ring_batch = mol_metrics.rings_to_host(*mol_metrics.analyze_rings(
                 h[:, :, :model.num_classes], x, node_mask, model.is_geom, batch['linker_mask']))
+        if aromatic:
+            true_aromatic_batch = mol_metrics.aromatic_to_host(mol_metrics.analyze_aromatic(
+                h[:, :, :model.num_classes], x, node_mask, model.is_geom, batch['linker_mask']))
         if geometry:
             true_x_batch = list(mol_metrics.kept_positions(x, node_mask)[0])
             n_linker_batch = batch['linker_mask'].reshape(len(uuids), -1).sum(1).long().tolist()
@@ -166,11 +177,19 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 pred_rings += mol_metrics.rings_to_host(*mol_metrics.analyze_rings(
                     hs[:, :, :model.num_classes], xs, out_mask, model.is_geom, out_mask * (1 - pad(batch['fragment_mask']))))
                 true_rings += true_ring_batch
+            if aromatic:                                       # likewise
+                pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, out_mask.shape[1] - m.shape[1]))      # noqa: E731
+                pred_aromatic += mol_metrics.aromatic_to_host(mol_metrics.analyze_aromatic(
+                    hs[:, :, :model.num_classes], xs, out_mask, model.is_geom, out_mask * (1 - pad(batch['fragment_mask']))))
+                true_aromatic += true_aromatic_batch
             if output_format != 'sdf':
                 save_xyz_file(output_dir, hs, xs, out_mask, [f'{u}/{i}' for u in uuids], is_geom=model.is_geom)
             if output_format != 'xyz':
                 found.append(perceive_all_bonds(hs, xs, out_mask, model.is_geom))
-                save_sdf_file(output_dir, hs, xs, out_mask, found[-1].bonds, found[-1].n_bonds, [f'{u}/{i}' for u in uuids],
+                shown = found[-1]
+                if bond_orders == 'geometric':                 # Kekule orders for the planar rings, from the same geometry
+                    shown = refine_bond_orders(shown, hs[:, :, :model.num_classes], xs, out_mask, model.is_geom)[0]
+                save_sdf_file(output_dir, hs, xs, out_mask, shown.bonds, shown.n_bonds, [f'{u}/{i}' for u in uuids],
                               is_geom=model.is_geom)
             if metrics:
                 types = hs[:, :, :model.num_classes]
@@ -183,7 +202,7 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 n_linker += n_linker_batch
     if found:
         print(json.dumps(summary(found)))
-    if metrics or clashes or shape or rings:
+    if metrics or clashes or shape or rings or aromatic:
         with open(os.path.join(output_dir, 'metrics.json'), 'w') as f:
             scores = {}
             if metrics:
@@ -196,6 +215,8 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 scores.update(mol_metrics.compute_shapes(shapes, linker_shapes, pred if metrics else None))
             if rings:
                 scores.update(mol_metrics.compute_rings(pred_rings, true_rings))
+            if aromatic:
+                scores.update(mol_metrics.compute_aromatic(pred_aromatic, true_aromatic))
             json.dump(scores, f, indent=1)
     return output_dir
 
@@ -258,6 +279,14 @@ def main(argv=None):
     p.add_argument('--rings', action='store_true',
                    help='perceive the rings of every sample and of its true molecule on the GPU (ring count of the linker, '
                         'small rings, macrocycles; the cyclomatic number, no aromaticity) and write the scores to metrics.json')
+    p.add_argument('--bond_orders', choices=BOND_ORDERS, default='distance',
+                   help='bond orders of the .sdf files: distance (the distance table of the reference\'s molecule_builder) or '
+                        'geometric (planar five- and six-rings get Kekule orders 1 / 2 from the 3D geometry; a rule of this '
+                        'project, not OpenBabel\'s bond typing)')
+    p.add_argument('--aromatic', action='store_true',
+                   help='perceive aromatic rings of every sample and of its true molecule from the geometry on the GPU (a rule '
+                        'of this project, not RDKit\'s) and write aromatic_rings_n, ring_filter and '
+                        'valence_validity_geometric to metrics.json')
     a = p.parse_args(argv)
     if a.keep_frames is not None:
         print(sample_trajectories(a.checkpoint, a.samples, a.prefix, a.keep_frames, a.device, a.data, a.n_steps))
@@ -265,7 +294,9 @@ def main(argv=None):
         print(sample(a.checkpoint, a.samples, a.prefix, a.n_samples, a.device, a.data, a.n_steps, a.linker_size_model,
                      a.output_format, a.metrics, **({'geometry': True} if a.geometry else {}),
                      **({'clashes': True} if a.clashes else {}), **({'shape': True} if a.shape else {}),
-                     **({'rings': True} if a.rings else {})))
+                     **({'rings': True} if a.rings else {}),
+                     **({'bond_orders': a.bond_orders} if a.bond_orders != 'distance' else {}),
+                     **({'aromatic': True} if a.aromatic else {})))
 
 
 if __name__ == '__main__':

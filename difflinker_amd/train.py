@@ -101,6 +101,10 @@ def main(argv=None):
     p.add_argument('--rings', action='store_true',
                    help='with --sample_every_epochs: add the ring scores of the samples (ring count of the linker, small rings, '
                         'macrocycles) to the epoch scores')
+    p.add_argument('--aromatic', action='store_true',
+                   help='with --sample_every_epochs: perceive aromatic rings from the geometry (a rule of this project, not '
+                        'RDKit\'s or OpenBabel\'s) and add aromatic_rings_n, ring_filter and valence_validity_geometric to the '
+                        'epoch scores')
     a = p.parse_args(argv)
     cfg = dict(DEFAULTS)
     if a.config is not None:
@@ -137,6 +141,7 @@ def main(argv=None):
     model.clash_metrics = bool(a.clashes)
     model.shape_metrics = bool(a.shape)
     model.ring_metrics = bool(a.rings)
+    model.aromatic_metrics = bool(a.aromatic)
     kept = lambda: {'best_validity_and_connectivity': best} if a.sample_every_epochs else {}   # noqa: E731
     step, epoch = start_step, start_epoch
     n_epochs = int(cfg['n_epochs'])

@@ -51,8 +51,13 @@
  *                                           below is this project's own after RDKit's defaults, NOT RDKit's grid
  *   dl_ring_scores                       <- rings_n of compute_metrics.py:128-145 (CalcNumRings of the linker) and the ring
  *                                           perception under its ring filter (:269-298), asked of the bond graph: the
- *                                           cyclomatic number and the smallest ring through every bond.  No aromaticity,
- *                                           so the filter itself is not reproduced
+ *                                           cyclomatic number and the smallest ring through every bond.  Aromaticity, which
+ *                                           the filter needs, is dl_aromatic_rings
+ *   dl_aromatic_rings                    <- (no reference counterpart in its own code: the reference hands every .xyz to
+ *                                           `obabel`, and check_ring_filter of compute_metrics.py:269-277 asks RDKit) planar
+ *                                           five- and six-rings from the geometry, Kekule orders for them and the aromatic
+ *                                           ones, under a rule stated below that is this project's own, NOT OpenBabel's or
+ *                                           RDKit's
  *   dl_fragment_cuts                     <- FragmentMol(minCuts = maxCuts = 2) with DeLinker's pattern
  *                                           (data/geom/generate_geom_multifrag.py:199-206) and the re-assembly of
  *                                           data/zinc/prepare_dataset.py, src/datasets.py:56-100
@@ -899,7 +904,8 @@ int32_t dl_shape_scores(const dl_shape_args* args, void* stream);
  * B < 0, N < 1, N > 1024 or capacity < 0 return DL_ERR_BAD_ARG; then B == 0 returns DL_OK without a launch; then a null
  * pointer (other than drop_mask, mark_mask, and `bonds` / `bond_ring` when capacity is 0) returns DL_ERR_BAD_ARG, all before
  * any device work.
- * Not here: aromaticity, enumerating the rings or counting them by size, fused / spiro / bridged classes. */
+ * Not here: enumerating the rings or counting them by size, fused / spiro / bridged classes.  Aromaticity: dl_aromatic_rings
+ * below. */
 #define DL_RINGS_MAX_ATOMS 256      /* kept atoms per molecule */
 #define DL_RING_BINS 7              /* 0: in no ring; 1..5: smallest ring of 3..7 atoms; 6: of 8 or more */
 #define DL_RINGS_TOO_LARGE 4        /* status bit, same value as DL_KEYS_TOO_LARGE */
@@ -1068,6 +1074,107 @@ typedef struct dl_fragment_multi_args {
     uint8_t* labels;                /* device uint8 [B,R,N] out (may be NULL when R is 0) */
 } dl_fragment_multi_args;
 int32_t dl_fragment_multicuts(const dl_fragment_multi_args* args, void* stream);
+
+/* ---- aromatic rings from 3D geometry, and Kekule bond orders for them (aromatic.hip) ---------------------------
+ * The distance table of dl_perceive_bonds calls a C-C bond double below 1.39 A and single from there on, so an aromatic ring
+ * (1.36 - 1.45 A) gets an arbitrary mix of orders.  This entry point finds the planar five- and six-rings of every molecule of
+ * a batch, gives their bonds alternating orders and says which rings are aromatic: one workgroup per molecule, ONE launch per
+ * batch, no host round trip.  THE RULE BELOW IS THIS PROJECT'S OWN.  It is NOT RDKit's aromaticity model and NOT OpenBabel's
+ * bond typing (the reference hands its .xyz files to `obabel`); tests/aromatic_ref.py restates it in plain Python and the
+ * kernel agrees with that bit for bit.
+ *
+ * CONVENTIONS, those of dl_ring_scores.  Atom k is the k-th row with node_mask != 0; its type is the FIRST largest entry of
+ * its one_hot row (finite values expected) and its class is ring_class[type]: 1 carbon, 2 nitrogen, 3 oxygen and sulphur,
+ * anything else counts as 0.  `drop_mask` (may be NULL) removes atoms AFTER that numbering, together with their bonds.  An
+ * entry (i, j, order) is a bond when 0 <= i, j < atoms, i != j and 1 <= order <= 3, in either orientation; any other entry is
+ * skipped and sets DL_AROM_BAD_BOND.  A repeated pair sets DL_AROM_BAD_BOND, and the order of its FIRST entry is the pair's
+ * input order.  Entries from min(n_bonds_in, capacity) on are not read.  "Kept" means: not dropped, both ends for a bond.
+ *
+ * 1. ELIGIBLE.  Degree is counted over the simple graph of the kept atoms.  Class 1 and class 2 atoms are eligible with
+ *    degree 2 or 3, class 3 atoms with degree exactly 2, class 0 atoms never.
+ * 2. CANDIDATE RINGS.  Every chordless simple cycle of 5 or 6 kept atoms, all eligible, once, in canonical order: from its
+ *    smallest atom number, in the direction whose second atom is smaller than its last.
+ * 3. PLANAR RINGS.  fp64, contraction off, every operation rounded on its own in the order written.  p_k = (double) x of the
+ *    cycle's atoms in canonical order; c = (((p_0 + p_1) + ...) + p_{n-1}) / (double) n by component; q_k = p_k - c;
+ *    m = ((q_0 x q_1) + (q_1 x q_2)) + ... + (q_{n-1} x q_0), a cross product being (a_y*b_z - a_z*b_y, a_z*b_x - a_x*b_z,
+ *    a_x*b_y - a_y*b_x); mm = (m_x*m_x + m_y*m_y) + m_z*m_z; a dot product v . m is (v_x*m_x + v_y*m_y) + v_z*m_z.
+ *    The ring is planar iff mm > 0, and d*d <= tol2_ring * mm with d = q_k . m for every ring atom, and d*d <= tol2_sub * mm
+ *    with d = (p_s - c) . m for every kept neighbour s of a ring atom that is not in the ring.  A NaN or inf coordinate
+ *    makes a comparison false: the ring is not planar.  tol2_ring and tol2_sub are squares of lengths in A; 0.1^2 and 0.5^2
+ *    sit between the aromatic rings of crystal ligands (ring atoms within 0.025 A, substituents within 0.15 A of this plane)
+ *    and saturated rings (chair cyclohexane: 0.25 A; a substituent on a tetrahedral ring carbon: about 1.26 A).
+ * 4. RING BONDS AND SYSTEMS.  A ring bond joins cyclically consecutive atoms of a planar ring; a system is a connected
+ *    component of the graph of ring bonds.
+ * 5. ROLES of system atoms, by the first rule that applies.  D (donor of two electrons, takes no ring double bond): class 3,
+ *    and class 2 of degree 3.  X (no electron): any other atom with a bond of input order 2 or 3 that is not a ring bond.
+ *    P: class 1.  F (flexible): class 2 of degree 2.
+ * 6. KEKULE ASSIGNMENT per system.  M is a set of ring bonds whose ends all have role P or F, no atom in two of them.  Among
+ *    all such sets M covers the most P atoms; among those, the most F atoms; among those, its sorted list of
+ *    (min(u,v), max(u,v)) pairs is lexicographically smallest.  A definition: the result does not depend on the list's order.
+ * 7. NEW ORDERS.  A ring bond gets order 2 if it is in M, else 1 (every entry of its pair); every other entry keeps its own
+ *    input order.
+ * 8. AROMATIC RINGS.  A planar ring is aromatic iff every P atom of it is covered by M and its contributions sum to exactly
+ *    6: 2 for D, 0 for X, 1 for a covered P or F, 2 for an uncovered F.  A bond is aromatic when it is a ring bond of an
+ *    aromatic ring, an atom when it lies in one.
+ *
+ *   order_out          [B,capacity], written in full: the new order of every entry that is a bond (an entry with a dropped
+ *                      end keeps its input order); 0 for skipped entries and from min(n_bonds_in, capacity) on.  Always 0..3
+ *   bond_aromatic      [B,capacity]: 1 for the entries of aromatic bonds, else 0
+ *   atom_aromatic      [B,N] by atom number: 1 for aromatic atoms; 0 for dropped atoms and from the atom count on
+ *   valence_out        [B,N] by atom number: the sum of the new orders over the distinct kept pairs of the atom (a pair
+ *                      outside the rings counts with its input order); 0 for dropped atoms and from the atom count on
+ *   n_planar_rings     planar rings
+ *   n_aromatic_rings   aromatic rings
+ *   n_aromatic_marked  aromatic rings whose atoms are all marked by `mark_mask` ([B,N] by row); 0 when mark_mask is NULL
+ *   status             the bits of `status_in`, plus DL_BONDS_OVERFLOW when n_bonds_in > capacity (a negative n_bonds_in
+ *                      counts as 0), DL_AROM_BAD_BOND, and the limits.  None disturbs the other molecules of the launch.
+ *                      DL_AROM_TOO_LARGE: more than DL_AROM_MAX_ATOMS KEPT atoms (N itself may be 1024): order_out holds
+ *                        the input orders, everything else is 0, and the list is not searched for repeated pairs.
+ *                      DL_AROM_MANY_RINGS: more than DL_AROM_MAX_RINGS planar rings: order_out holds the input orders,
+ *                        valence_out their sums, the flags and the three counts are 0.
+ *                      DL_AROM_BIG_SYSTEM: a system of more than DL_AROM_MAX_SYSTEM atoms: its bonds keep their input
+ *                        orders and its rings count as planar but not aromatic; the other systems are treated as usual.
+ *
+ * Integer work apart from step 3, which is exact in the order given: the same bits on every run and under every order of the
+ * list (order_out and bond_aromatic permuted with it).  Global memory is written with plain stores only, every output
+ * element is written, the callee allocates nothing.  A null `args`, B < 0, N < 1, N > 1024, nf < 1, capacity < 0, or a
+ * tolerance that is negative or NaN return DL_ERR_BAD_ARG; then B == 0 returns DL_OK without a launch; then a null pointer
+ * (other than drop_mask, mark_mask, and `bonds` / `order_out` / `bond_aromatic` when capacity is 0) returns DL_ERR_BAD_ARG,
+ * all before any device work.
+ * Limits of the rule: there are no hydrogens, so N-H and =N- are told apart only by the matching; no formal charges; only
+ * rings of 5 and 6 atoms; a planar saturated ring is misread as conjugated; orders outside planar rings stay the distance
+ * table's.  Not here: aromatic order 4 in the output, rings of other sizes, the cutting rules of dl_fragment_cuts. */
+#define DL_AROM_MAX_ATOMS 256       /* kept atoms per molecule */
+#define DL_AROM_MAX_RINGS 64        /* planar rings per molecule */
+#define DL_AROM_MAX_SYSTEM 32       /* atoms per ring system */
+#define DL_AROM_TOO_LARGE 4         /* status bit, same value as DL_KEYS_TOO_LARGE */
+#define DL_AROM_BAD_BOND 8          /* status bit, same value as DL_KEYS_BAD_BOND */
+#define DL_AROM_MANY_RINGS 16       /* status bit: more than DL_AROM_MAX_RINGS planar rings; orders pass through */
+#define DL_AROM_BIG_SYSTEM 32       /* status bit: a system of more than DL_AROM_MAX_SYSTEM atoms kept its input orders */
+typedef struct dl_aromatic_args {
+    int32_t B, N, nf;
+    const float* x;                 /* device f32 [B,N,3], Angstrom */
+    const float* one_hot;           /* device f32 [B,N,nf] */
+    const float* node_mask;         /* device f32 [B,N] */
+    const float* drop_mask;         /* device f32 [B,N] or NULL */
+    const float* mark_mask;         /* device f32 [B,N] or NULL */
+    const int32_t* ring_class;      /* device int32 [nf]: 1 C, 2 N, 3 O and S, 0 anything else */
+    int32_t capacity;               /* bonds the list holds per molecule */
+    const int32_t* n_bonds_in;      /* device int32 [B]: dl_bonds_args.n_bonds */
+    const int32_t* bonds;           /* device int32 [B,capacity,3]: dl_bonds_args.bonds (may be NULL when capacity is 0) */
+    const int32_t* status_in;       /* device int32 [B]: dl_bonds_args.status */
+    double tol2_ring;               /* square of the ring atoms' distance from the plane, A^2 (0.1 * 0.1) */
+    double tol2_sub;                /* square of the substituents' distance from the plane, A^2 (0.5 * 0.5) */
+    int32_t* order_out;             /* device int32 [B,capacity] out (may be NULL when capacity is 0) */
+    int32_t* bond_aromatic;         /* device int32 [B,capacity] out (may be NULL when capacity is 0) */
+    int32_t* atom_aromatic;         /* device int32 [B,N] out */
+    int32_t* valence_out;           /* device int32 [B,N] out */
+    int32_t* n_planar_rings;        /* device int32 [B] out */
+    int32_t* n_aromatic_rings;      /* device int32 [B] out */
+    int32_t* n_aromatic_marked;     /* device int32 [B] out */
+    int32_t* status;                /* device int32 [B] out */
+} dl_aromatic_args;
+int32_t dl_aromatic_rings(const dl_aromatic_args* args, void* stream);
 
 /* ---- pockets: the protein atoms around every ligand of a batch (pocket.hip) -----------------------------------
  * For every (ligand, protein) pair the protein atoms whose GROUP holds an atom within `cutoff` of some ligand atom: one
