@@ -77,10 +77,23 @@ def forward_cost(n, n_linker, n_layers, sublayers, team=1):
     return n_layers * (sublayers * (_pass_steps(own, n) + a_gcl) + _pass_steps(own_l, n) + a_eq)
 
 
-# The plan cache, and per device the side stream and the workspace of the launch on it, are shared by every EDM of the process;
-# _CACHE_LOCK guards the three dicts (lookup and insertion), not the tensors or streams in them.  One side workspace per device
-# is safe for any number of EDMs and caller streams because only the team launch beside the main one (_sample_chain_fused)
-# uses it, and that launch always runs on the device's one side stream, which serializes every use of the workspace.
+# The plan cache, and per device the side stream and the cached workspaces of the fused chain, are shared by every EDM of the
+# process; _CACHE_LOCK guards the three dicts (lookup and insertion), not the tensors or streams in them.  EVERY CACHED WORKSPACE
+# IS TIED TO THE ONE STREAM THAT SERIALISES ITS USES, which is what makes it safe for any number of EDMs, caller streams and threads:
+#   (device, 'teams')          the team launch beside the main one (side_launch of _sample_chain_fused).  It always runs on the
+#                              device's one side stream, whichever stream or thread the caller is on.
+#   (device, 'join', stream)   the exchange rows, arrival words and join words of dl_sample_chain_fc_join.  That launch, and the
+#                              hipMemsetAsync that clears its words, run on the CALLER's stream, so the buffer is keyed by that
+#                              stream: two chains on two streams never share handshake words.  (torch hands out streams from a
+#                              fixed pool, so the number of keys is bounded.)
+# A buffer that has to grow is replaced, and the old tensor may still be in use by a launch another thread queued: 'teams' buffers
+# are therefore marked as used by the side stream when they are made (record_stream: the allocator hands the block out again
+# only after the side stream's work queued up to the release has completed); a 'join' buffer is allocated on, used on and
+# released to the pool of the same stream, whose order covers it.
+# The stream and thread contract of the Python layer ("Streams and threads"; tests/test_gpu_streams.py):
+# DISTINCT Dynamics / EDM / SizeClassifier objects may run on any streams and threads at once.  ONE object caches one workspace
+# each (_fc_ws, _large_ws, _bwd_ws, _workspaces), so it is used on one stream at a time and may move to another stream once
+# that stream waits on the first.  This is narrower than the C ABI, where one dl_model may be shared by any number of streams.
 _CACHE_LOCK = threading.Lock()
 _PLAN_CACHE = {}
 _SIDE_STREAMS = {}
@@ -240,13 +253,17 @@ class EDM(torch.nn.Module):
             return _SIDE_STREAMS[key]
 
     @staticmethod
-    def _side_workspace(key, need, dev):
-        """scratch of the team launch beside the main one, one buffer per key (device, 'teams'): grown, never shrunk, reused by
-        every chain (see _CACHE_LOCK)"""
+    def _side_workspace(key, need, dev, used_on=None):
+        """A cached workspace of the fused chain, one buffer per key - (device, 'teams') or (device, 'join', caller's stream):
+        grown, never shrunk, reused by every chain on the stream that serialises its uses (see _CACHE_LOCK).  ``used_on``: the
+        stream of the launches when it is not the one the buffer is allocated on; a buffer replaced by a bigger one is then
+        kept from the allocator until what that stream holds at the release has run."""
         with _CACHE_LOCK:
             ws = _SIDE_WORKSPACE.get(key)
             if ws is None or ws.numel() < need:
                 ws = _SIDE_WORKSPACE[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+                if used_on is not None:
+                    ws.record_stream(used_on)
             return ws
 
     # ---- loss / VLB of held-out data (edm.py:41-124) -------------------------------------------------------
@@ -844,7 +861,7 @@ class EDM(torch.nn.Module):
             flags2 = torch.empty(bs, dtype=torch.int32, device=dev)
             steps2 = torch.empty(bs, dtype=torch.int32, device=dev)
             need = int(lib.dl_workspace_bytes(count, team_))
-            ws2 = self._side_workspace((dev.index, 'teams'), need, dev)
+            ws2 = self._side_workspace((dev.index, 'teams'), need, dev, used_on=side)
             skip = flags if q_begin is not None else None
             args2 = chain_args(flags2, steps2, team_, ws2, need, order_, first, count, q_begin=q_begin, skip=skip)
             side.wait_event(after)
@@ -875,7 +892,7 @@ class EDM(torch.nn.Module):
                     team_of[o_] = team_of[hp_] = j_
                 maps = torch.tensor(team_of + owners, dtype=torch.int32, device=dev)
                 need = int(lib.dl_join_workspace_bytes(len(owners)))
-                jws = self._side_workspace((dev.index, 'join'), need, dev)
+                jws = self._side_workspace((dev.index, 'join', cur.cuda_stream), need, dev)
                 jargs = _lib.DLJoinArgs(teams=len(owners), team_of=maps.data_ptr(), team_mol=maps.data_ptr() + 4 * bs,
                                         workspace=jws.data_ptr(), workspace_bytes=need, wait_ticks=None)
                 _lib.check(lib.dl_sample_chain_fc_join(handle, ctypes.byref(args), ctypes.byref(jargs),

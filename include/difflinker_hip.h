@@ -79,6 +79,12 @@
  *     dl_*_workspace_bytes query, 16-byte aligned, free to reuse once the launch has completed on `stream`.  Two
  *     launches that run concurrently need two workspaces; a dl_model itself is immutable after creation and may be
  *     shared by any number of streams.
+ *   - STREAMS AND THREADS: an entry point reads its inputs and writes its outputs and workspace in the order of `stream`
+ *     alone (the memsets that clear arrival, join and flag words included), from whichever thread it is called.  Calls with
+ *     distinct workspaces and outputs may be issued on any streams and threads at once, on one dl_model or several.  The
+ *     Python layer is narrower: one Dynamics / EDM / SizeClassifier object caches one workspace of each kind and is used on
+ *     one stream at a time (it may move to a stream that waits on the previous one); distinct objects are independent
+ *     (tests/test_gpu_streams.py).
  *   - THE WORKSPACE CONTRACT (every entry point that takes `workspace`): the contents of the workspace on entry are
  *     unspecified - stale bytes of any earlier use, NaN, inf and huge integers included; the library initialises what it
  *     needs (arrival words, counters, flag words) on `stream` before the kernels that read it; the contents on return are

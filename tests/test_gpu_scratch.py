@@ -139,17 +139,32 @@ FWD_SIZES = {'5': ([5], [2]),                                    # one partial t
              'lds-limit': ([55, 32, 31, 2, 40], [6, 3, 4, 1, 12])}   # the LDS limit; 9, 32, 33, 62 and 24 padding columns
 
 
+def forward_closure(make, sizes, linkers, nf, team, large=False, seed=11):
+    """Make the closure of a forward case (shared with tests/test_gpu_streams.py): ``build()`` makes a fresh denoiser and returns
+    it with ``launch(place)``, which puts the inputs on the device through ``place`` and enqueues the launch - no host read
+    before it - returning ``(eps_hat, nan_flags)``.  Also returns the host inputs."""
+    inp, z, t = P.ragged_inputs(sizes, linkers, nf, seed=seed)
+
+    def build():
+        dyn = make()
+        dyn.team = team
+
+        def launch(place=on):
+            return dyn._launch_forward(place(t), place(z), place(inp['node_mask']), place(inp['linker_mask']), place(inp['edge_mask']),
+                                       place(inp['context']), large=large)
+        return dyn, launch
+    return build, inp, z, t
+
+
 def forward_case(monkeypatch, make, sizes, linkers, nf, team, large=False, seed=11):
     from difflinker_amd import _lib
-    inp, z, t = P.ragged_inputs(sizes, linkers, nf, seed=seed)
+    build, inp, z, t = forward_closure(make, sizes, linkers, nf, team, large, seed)
     B, N = z.shape[:2]
     lib = _lib.load()
 
     def run():
-        dyn = make()
-        dyn.team = team
-        out, flags = dyn._launch_forward(on(t), on(z), on(inp['node_mask']), on(inp['linker_mask']), on(inp['edge_mask']),
-                                         on(inp['context']), large=large)
+        dyn, launch = build()
+        out, flags = launch()
         torch.cuda.synchronize()
         if large:
             ws, need = dyn._large_ws, int(lib.dl_pocket_workspace_bytes(B, N))
@@ -383,10 +398,11 @@ def test_backward_twice_on_one_model(monkeypatch, case):
 CHAIN_T, KEEP = 20, 2          # T = 20: the smallest at which EDM considers the hand-over plan
 
 
-def chain_case(monkeypatch, make, sizes, linkers, nf, route, split=None, inpainting=False, expect=(), T=CHAIN_T):
-    """``EDM.sample_chain`` from a fixed noise bank and once more with Philox draws; ``expect(edm)`` names the workspaces the
-    route must have used as ``[(key of product_workspaces, least bytes)]``.  Outputs: both chains and the flag / step arrays
-    the fused launches reported (none on the host-driven loops, where no exception means no flag)."""
+def chain_closure(make, sizes, linkers, nf, route, split=None, inpainting=False, T=CHAIN_T):
+    """Make the closure of a chain case (shared with tests/test_gpu_streams.py): ``build()`` makes a fresh EDM and returns it with
+    ``sample(place, place_bank)``: ``EDM.sample_chain`` from a fixed noise bank and once more with Philox draws, the inputs put on
+    the device through ``place`` (the bank through ``place_bank``; None: handed over on the host).  Returns both chains and the
+    flag / step arrays the fused launches reported (none on the host-driven loops, where no exception means no flag)."""
     inp, _, _ = P.ragged_inputs(sizes, linkers, nf, seed=172)
     B, N = inp['x'].shape[:2]
     if inpainting:
@@ -394,31 +410,47 @@ def chain_case(monkeypatch, make, sizes, linkers, nf, route, split=None, inpaint
         bank = (torch.randn(1 + 2 * T + 2, B, N, 3, generator=g0), torch.randn(1 + 2 * T + 2, B, N, nf, generator=g0))
     else:
         bank = edm_oracle.NoiseBank.generate(T, B, N, 3, nf, seed=173).stacked()
-    g = {k: on(v) for k, v in inp.items()}
-    if inpainting:
-        args = (g['x'], g['h'], g['node_mask'], g['edge_mask'], g['fragment_mask'], g['linker_mask'], g['context'])
-    else:
-        args = (g['x'], g['h'], g['node_mask'], g['fragment_mask'], g['linker_mask'], g['edge_mask'], g['context'])
 
-    def run():
+    def build():
         edm = make(T)
         if split is not None:
             edm.split_chain = split
-        reported = []
-        raise_on = edm._raise_on_chain_flags
-        edm._raise_on_chain_flags = lambda f, s: (reported.append((f.clone(), s.clone())), raise_on(f, s))[1]
-        out = {}
-        for source in ('bank', 'philox'):
-            edm.last_route = None
-            if source == 'philox':
-                edm.noise_source, edm.noise_seed = 'philox', 9
-            try:
-                out[f'chain.{source}'] = edm.sample_chain(*args, keep_frames=KEEP, noise_bank=bank if source == 'bank' else None)
-                torch.cuda.synchronize()
-            finally:
-                assert edm.last_route == route, (edm.last_route, route)
-        for k, (f, s) in enumerate(reported):
-            out[f'nan_flags.{k}'], out[f'nan_step.{k}'] = f, s
+
+        def sample(place=on, place_bank=None):
+            g = {k: place(v) for k, v in inp.items()}
+            if inpainting:
+                args = (g['x'], g['h'], g['node_mask'], g['edge_mask'], g['fragment_mask'], g['linker_mask'], g['context'])
+            else:
+                args = (g['x'], g['h'], g['node_mask'], g['fragment_mask'], g['linker_mask'], g['edge_mask'], g['context'])
+            noise = bank if place_bank is None else tuple(place_bank(v) for v in bank)
+            reported = []
+            raise_on = edm._raise_on_chain_flags
+            edm._raise_on_chain_flags = lambda f, s: (reported.append((f.clone(), s.clone())), raise_on(f, s))[1]
+            out = {}
+            for source in ('bank', 'philox'):
+                edm.last_route = None
+                if source == 'philox':
+                    edm.noise_source, edm.noise_seed = 'philox', 9
+                try:
+                    out[f'chain.{source}'] = edm.sample_chain(*args, keep_frames=KEEP, noise_bank=noise if source == 'bank' else None)
+                    torch.cuda.synchronize()
+                finally:
+                    assert edm.last_route == route, (edm.last_route, route)
+            for k, (f, s) in enumerate(reported):
+                out[f'nan_flags.{k}'], out[f'nan_step.{k}'] = f, s
+            return out
+        return edm, sample
+    return build
+
+
+def chain_case(monkeypatch, make, sizes, linkers, nf, route, split=None, inpainting=False, expect=(), T=CHAIN_T):
+    """Check a chain case: ``expect(edm)`` names the workspaces the route must have used as ``[(key of product_workspaces, least
+    bytes)]``."""
+    build = chain_closure(make, sizes, linkers, nf, route, split, inpainting, T)
+
+    def run():
+        edm, sample = build()
+        out = sample()
         held = product_workspaces(edm.dynamics)
         want = list(expect(edm)) if callable(expect) else list(expect)
         assert held and want
@@ -560,7 +592,8 @@ def test_chain_with_the_join_hand_over(monkeypatch, variant):
     need = int(_lib.load().dl_join_workspace_bytes(len(plan[1])))
     make = _fc_edm(2, 361, flags=ALL_FLAGS) if variant == 'attention-tanh-mean' else _fc_edm(2, 301, precision=variant)
     chain_case(monkeypatch, make, J.SIZES, J.LINKERS, J.NF, 'join', split=True,
-               expect=[('0._fc_ws', _ws_bytes(len(J.SIZES), 1)), (f"side{(P.dev().index, 'join')}", need)])
+               expect=[('0._fc_ws', _ws_bytes(len(J.SIZES), 1)),
+                       (f"side{(P.dev().index, 'join', torch.cuda.current_stream(P.dev()).cuda_stream)}", need)])
 
 
 def test_chain_split_by_size(monkeypatch):
@@ -574,18 +607,19 @@ def test_chain_split_by_size(monkeypatch):
                expect=[('0._fc_ws', 1), ('0._large_ws', 1)])
 
 
+def _inpainting_edm(T):
+    from difflinker_amd import Dynamics, InpaintingEDM
+    nf, L = J.NF, 1
+    dyn = Dynamics(n_dims=3, in_node_nf=nf, context_node_nf=1, hidden_nf=128, n_layers=L, norm_constant=1e-6,
+                   normalization='batch_norm', centering=True)
+    dyn.load_state_dict(seeded_state_dict(nf + 2, 128, L, 81), strict=True)
+    edm = InpaintingEDM(dyn.to(P.dev()), in_node_nf=nf, n_dims=3, timesteps=500, noise_schedule='polynomial_2',
+                        noise_precision=1e-5, loss_type='l2', norm_values=[1, 4, 10]).to(P.dev())
+    edm.T = T
+    return edm
+
+
 def test_inpainting_chain(monkeypatch):
     """d. ``InpaintingEDM.sample_chain``: the host-driven loop (denoiser on teams + the fused tail per step); it launches no
     fused chain, so ``last_route`` stays None."""
-    from difflinker_amd import Dynamics, InpaintingEDM
-    nf, L = J.NF, 1
-
-    def make(T):
-        dyn = Dynamics(n_dims=3, in_node_nf=nf, context_node_nf=1, hidden_nf=128, n_layers=L, norm_constant=1e-6,
-                       normalization='batch_norm', centering=True)
-        dyn.load_state_dict(seeded_state_dict(nf + 2, 128, L, 81), strict=True)
-        edm = InpaintingEDM(dyn.to(P.dev()), in_node_nf=nf, n_dims=3, timesteps=500, noise_schedule='polynomial_2',
-                            noise_precision=1e-5, loss_type='l2', norm_values=[1, 4, 10]).to(P.dev())
-        edm.T = T
-        return edm
-    chain_case(monkeypatch, make, [12, 33, 10], [4, 6, 3], nf, None, inpainting=True, expect=[('0._fc_ws', 1)])
+    chain_case(monkeypatch, _inpainting_edm, [12, 33, 10], [4, 6, 3], J.NF, None, inpainting=True, expect=[('0._fc_ws', 1)])
