@@ -273,6 +273,34 @@ class DLPocketArgs(ctypes.Structure):
     ]
 
 
+DL_FP_MAX_ATOMS, DL_FP_MAX_RADIUS = 256, 4              # dl_fingerprint_args: kept atoms per molecule; rounds of refinement
+DL_FP_TOO_LARGE, DL_FP_BAD_BOND = 4, 8                # dl_fingerprint_args.status bits, beside the DL_BONDS_* bits carried forward
+DL_FP_BITS = (512, 1024, 2048)                        # n_bits dl_fingerprints takes
+DL_TANIMOTO_TILE = 128                                # rows of B a workgroup of dl_tanimoto_nearest stages at a time
+
+
+class DLFingerprintArgs(ctypes.Structure):            # the stream is the last FIELD: the entry point takes the struct alone
+    _fields_ = [
+        ('B', ctypes.c_int32), ('N', ctypes.c_int32), ('nf', ctypes.c_int32),
+        ('one_hot', ctypes.c_void_p), ('node_mask', ctypes.c_void_p), ('drop_mask', ctypes.c_void_p),
+        ('centre_mask', ctypes.c_void_p), ('capacity', ctypes.c_int32),
+        ('n_bonds_in', ctypes.c_void_p), ('bonds', ctypes.c_void_p), ('status_in', ctypes.c_void_p),
+        ('radius', ctypes.c_int32), ('n_bits', ctypes.c_int32),
+        ('bits', ctypes.c_void_p), ('n_on', ctypes.c_void_p), ('n_atoms', ctypes.c_void_p), ('n_centres', ctypes.c_void_p),
+        ('status', ctypes.c_void_p), ('stream', ctypes.c_void_p),
+    ]
+
+
+class DLTanimotoArgs(ctypes.Structure):               # likewise
+    _fields_ = [
+        ('Ma', ctypes.c_int32), ('Mb', ctypes.c_int32), ('W', ctypes.c_int32), ('G', ctypes.c_int32),
+        ('a_bits', ctypes.c_void_p), ('b_bits', ctypes.c_void_p), ('a_offsets', ctypes.c_void_p), ('b_offsets', ctypes.c_void_p),
+        ('exclude_diagonal', ctypes.c_int32),
+        ('nn_index', ctypes.c_void_p), ('nn_common', ctypes.c_void_p), ('nn_union', ctypes.c_void_p), ('n_pairs', ctypes.c_void_p),
+        ('sum_q20', ctypes.c_void_p), ('stream', ctypes.c_void_p),
+    ]
+
+
 EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_string', 'dl_model_num_tensors',
            'dl_model_create', 'dl_model_destroy', 'dl_egnn_forward_fc', 'dl_sampler_step', 'dl_sample_chain_fc',
            'dl_set_profile_buffer', 'dl_profile_max_events', 'dl_pocket_workspace_bytes', 'dl_egnn_forward_pocket',
@@ -285,7 +313,8 @@ EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_stri
            'dl_size_train_num_params', 'dl_size_train_workspace_bytes', 'dl_size_train_forward', 'dl_size_train_backward',
            'dl_join_workspace_bytes', 'dl_sample_chain_fc_join', 'dl_bonds_workspace_bytes', 'dl_perceive_bonds',
            'dl_molecule_keys', 'dl_clash_scores', 'dl_shape_scores', 'dl_ring_scores', 'dl_fragment_cuts',
-           'dl_pocket_select', 'dl_fragment_multicuts', 'dl_aromatic_rings', 'dl_best_rmsd')
+           'dl_pocket_select', 'dl_fragment_multicuts', 'dl_aromatic_rings', 'dl_fingerprints',
+           'dl_tanimoto_nearest', 'dl_best_rmsd')
 TEST_HOOK_EXPORTS = ('dl_debug_team_fault', 'dl_debug_slot_order')       # declared under #ifdef DL_TEST_HOOKS: the test-hooks build only
 
 _lib = None
@@ -419,6 +448,10 @@ def _open(path):
     lib.dl_fragment_multicuts.argtypes = [ctypes.POINTER(DLFragmentMultiArgs), vp]
     lib.dl_aromatic_rings.restype = i32
     lib.dl_aromatic_rings.argtypes = [ctypes.POINTER(DLAromaticArgs), vp]
+    lib.dl_fingerprints.restype = i32
+    lib.dl_fingerprints.argtypes = [ctypes.POINTER(DLFingerprintArgs)]
+    lib.dl_tanimoto_nearest.restype = i32
+    lib.dl_tanimoto_nearest.argtypes = [ctypes.POINTER(DLTanimotoArgs)]
     lib.dl_pocket_select.restype = i32
     lib.dl_pocket_select.argtypes = [ctypes.POINTER(DLPocketArgs), vp]
     lib.dl_best_rmsd.restype = i32

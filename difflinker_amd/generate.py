@@ -81,12 +81,13 @@ BOND_ORDERS = ('distance', 'geometric')
 
 def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_dir, name, com_key, hide_pocket,
                      output_format='xyz', metrics=False, clashes=False, protein=None, rings=False, bond_orders='distance',
-                     aromatic=False):
+                     aromatic=False, diversity=False):
     if output_format not in OUTPUT_FORMATS:
         raise ValueError(f'output_format must be one of {OUTPUT_FORMATS}, got {output_format!r}')
     if bond_orders not in BOND_ORDERS:
         raise ValueError(f'bond_orders must be one of {BOND_ORDERS}, got {bond_orders!r}')
     written, found, scored, clash_records, ring_records, aromatic_records = [], [], [], [], [], []
+    prints = []
     for batch_i, data in enumerate(_batches(dataset, batch_size, collate_fn)):
         n = len(data['positions'])
         chain = None
@@ -143,9 +144,13 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
             pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, x.shape[1] - m.shape[1]))     # noqa: E731
             aromatic_records += mol_metrics.aromatic_to_host(mol_metrics.analyze_aromatic(
                 h[:, :, :ddpm.num_classes], x, node_mask, ddpm.is_geom, node_mask * (1 - pad(data['fragment_mask']))))
+        if diversity:                                         # likewise; the bits stay on the device
+            pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, x.shape[1] - m.shape[1]))     # noqa: E731
+            prints.append(mol_metrics.analyze_fingerprints(
+                h[:, :, :ddpm.num_classes], x, node_mask, ddpm.is_geom, node_mask * (1 - pad(data['fragment_mask']))))
     if found:
         print(json.dumps(summary(found)))
-    if metrics or clashes or rings or aromatic:
+    if metrics or clashes or rings or aromatic or diversity:
         scores = {}
         if metrics:                                           # no true molecule here: no novelty, no recovery
             scores = dict(mol_metrics.compute_metrics(scored), molecules=len(scored))
@@ -155,6 +160,10 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
             scores.update(mol_metrics.compute_rings(ring_records))
         if aromatic:
             scores.update(mol_metrics.compute_aromatic(aromatic_records))
+        if diversity:                                         # one input: every sample against every other
+            whole, linker = (mol_metrics.cat_fingerprints([p[k] for p in prints]) for k in range(2))
+            records = mol_metrics.diversity_records(whole, linker, [0] * whole.bits.shape[0])
+            scores.update(mol_metrics.compute_diversity(records, with_true=False, with_reference=False))
         with open(os.path.join(output_dir, 'metrics.json'), 'w') as f:
             json.dump(scores, f, indent=1)
     if clashes:                                               # one record per written file, by its name
@@ -168,7 +177,7 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
 
 
 def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anchors=None, device=None, output_format='xyz',
-             metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False):
+             metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False, diversity=False):
     """``generate.py`` main(): fragments file -> ``n_samples`` molecules with a sampled linker, as ``.xyz`` files
     (``output_format='sdf'``: ``.sdf`` files with perceived bonds instead, ``'both'``: both; one JSON line with the number of
     molecules, the share in one piece and the mean bond count is printed then).  ``metrics=True`` also writes
@@ -178,7 +187,10 @@ def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anc
     the ``.sdf`` files with the Kekule orders of ``molecule_builder.refine_bond_orders`` (planar five- and six-rings
     alternate; 1, 2 or 3, never 4) and ``aromatic=True`` adds ``aromatic_rings_n``, ``ring_filter`` and
     ``valence_validity_geometric`` to ``metrics.json`` (``metrics.analyze_aromatic`` / ``compute_aromatic``); both rest on a
-    geometric rule of this project's own, not on OpenBabel's or RDKit's, and the pocket variants take them as well."""
+    geometric rule of this project's own, not on OpenBabel's or RDKit's, and the pocket variants take them as well.
+    ``diversity=True`` adds ``internal_diversity`` and ``internal_diversity_linker`` of the samples of this one input
+    (``metrics.analyze_fingerprints`` / ``compute_diversity``): one minus the mean pairwise Tanimoto similarity on this
+    project's own circular fingerprint, not RDKit's Morgan fingerprint."""
     if clashes:
         raise ValueError('clashes are scored against a protein: pass a pocket or a protein file (--pocket / --protein)')
     device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
@@ -201,7 +213,7 @@ def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anc
     }] * n_samples
     return _sample_and_save(ddpm, dataset, collate_with_fragment_edges, sample_fn, min(n_samples, 64), output_dir, name,
                             com_key='fragment_mask', hide_pocket=False, output_format=output_format, metrics=metrics,
-                            rings=rings, bond_orders=bond_orders, aromatic=aromatic)
+                            rings=rings, bond_orders=bond_orders, aromatic=aromatic, diversity=diversity)
 
 
 def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size, device,
@@ -323,6 +335,10 @@ def main(argv=None):
     p.add_argument('--aromatic', action='store_true',
                    help='perceive aromatic rings from the geometry on the GPU (a rule of this project, not RDKit\'s) and add '
                         'aromatic_rings_n, ring_filter and valence_validity_geometric to metrics.json')
+    p.add_argument('--diversity', action='store_true',
+                   help='without --pocket / --protein: fingerprint the generated molecules on the GPU (this project\'s '
+                        'circular fingerprint, not RDKit\'s Morgan) and add internal_diversity and internal_diversity_linker '
+                        'to metrics.json')
     a = p.parse_args(argv)
     if a.clashes and a.pocket is None and a.protein is None:
         raise ValueError('--clashes scores the generated atoms against a protein: pass --pocket or --protein')
@@ -342,7 +358,8 @@ def main(argv=None):
                                       output_format=a.output_format, metrics=a.metrics, **extra, **more)
     else:
         files = generate(a.fragments, a.model, a.output, a.n_samples, a.n_steps, a.linker_size, a.anchors,
-                         output_format=a.output_format, metrics=a.metrics, **more)
+                         output_format=a.output_format, metrics=a.metrics, **more,
+                         **({'diversity': True} if a.diversity else {}))
     if a.output_format == 'xyz':
         print(f'Saved {len(files)} generated molecules in .xyz format in directory {a.output}')
     else:

@@ -103,6 +103,7 @@ class DDPM(_Base):
         self.clash_metrics = False              # pocket models: it adds metrics.compute_clashes' keys as well (train --clashes)
         self.shape_metrics = False              # it adds metrics.compute_shapes' keys: every sample against its true molecule (train --shape)
         self.aromatic_metrics = False           # it adds metrics.compute_aromatic's keys: aromatic rings of the linker, ring filter, valence rule on geometric orders (train --aromatic)
+        self.diversity_metrics = False          # it adds metrics.compute_diversity's keys: internal diversity of each input's samples, similarity to the true molecule (train --diversity)
         self.ring_metrics = False               # it adds metrics.compute_rings' keys: ring count of the linker, small rings, macrocycles (train --rings)
         if _Base is nn.Module:
             self.current_epoch = 0              # Lightning's Trainer keeps this; here the training loop sets it
@@ -324,10 +325,15 @@ class DDPM(_Base):
         (``metrics.analyze_rings`` / ``compute_rings``; pocket rows dropped): the linker's ring count, small rings,
         macrocycles.  With ``self.aromatic_metrics`` aromatic rings are perceived from the geometry and the ring bonds get
         Kekule orders (``metrics.analyze_aromatic`` / ``compute_aromatic``, a rule of this project's own, not RDKit's):
-        ``aromatic_rings_n``, ``ring_filter``, ``valence_validity_geometric``.  No animation, no WandB."""
+        ``aromatic_rings_n``, ``ring_filter``, ``valence_validity_geometric``.  With ``self.diversity_metrics`` every sample
+        and every true molecule is fingerprinted (``metrics.analyze_fingerprints`` / ``compute_diversity``; this project's own
+        circular fingerprint, not RDKit's Morgan; pocket rows dropped): ``internal_diversity`` and
+        ``internal_diversity_linker`` among each input's samples, ``similarity_to_true`` and ``similarity_to_true_linker``.
+        No animation, no WandB."""
         pred, true, input_index = [], [], []
         pred_aromatic, true_aromatic = [], []
         pred_rings, true_rings = [], []
+        pred_prints, true_prints, print_input = [], [], []
         shapes, linker_shapes = [], []
         pred_x, true_x, n_linker = [], [], []
         clashes = self.clash_metrics and self.pockets
@@ -350,6 +356,11 @@ class DDPM(_Base):
                 true_aromatic_batch = mol_metrics.aromatic_to_host(mol_metrics.analyze_aromatic(
                     data['one_hot'][:, :, :self.num_classes], data['positions'], data['atom_mask'], self.is_geom,
                     data['linker_mask'], drop_mask=drop))
+            if self.diversity_metrics:                                             # one row per input, kept on the device
+                true_prints.append(mol_metrics.analyze_fingerprints(
+                    data['one_hot'][:, :, :self.num_classes], data['positions'], data['atom_mask'], self.is_geom,
+                    data['linker_mask'], drop_mask=drop))
+                sampled = len(print_input)
             if self.geometry_metrics:
                 true_x_batch = list(mol_metrics.kept_positions(data['positions'], data['atom_mask'], drop)[0])
                 n_linker_batch = data['linker_mask'].reshape(n, -1).sum(1).long().tolist()
@@ -391,10 +402,17 @@ class DDPM(_Base):
                     pred_aromatic += mol_metrics.aromatic_to_host(mol_metrics.analyze_aromatic(
                         one_hot, x, node_mask, self.is_geom, node_mask * (1 - frag), drop_mask=out_drop))
                     true_aromatic += true_aromatic_batch
+                if self.diversity_metrics:                                         # the template's linker rows the centres
+                    frag = torch.nn.functional.pad(data['fragment_mask'], (0, 0, 0, node_mask.shape[1] - data['fragment_mask'].shape[1]))
+                    pred_prints.append(mol_metrics.analyze_fingerprints(
+                        one_hot, x, node_mask, self.is_geom, node_mask * (1 - frag), drop_mask=out_drop))
+                    print_input += range(first, first + n)
                 if self.geometry_metrics:
                     pred_x += list(mol_metrics.kept_positions(x, node_mask, out_drop)[0])
                     true_x += true_x_batch
                     n_linker += n_linker_batch
+            if self.diversity_metrics and len(print_input) == sampled:             # every chain of the batch failed: its true
+                true_prints.pop()                                                  # molecules would have no samples to go with
             first += n
         scores = mol_metrics.compute_metrics(pred, true, input_index)
         if self.geometry_metrics:
@@ -407,6 +425,13 @@ class DDPM(_Base):
             scores.update(mol_metrics.compute_rings(pred_rings, true_rings))
         if self.aromatic_metrics:
             scores.update(mol_metrics.compute_aromatic(pred_aromatic, true_aromatic))
+        if self.diversity_metrics:
+            records = []
+            if pred_prints:
+                whole, linker, true_whole, true_linker = (mol_metrics.cat_fingerprints([p[k] for p in parts])
+                                                          for parts in (pred_prints, true_prints) for k in range(2))
+                records = mol_metrics.diversity_records(whole, linker, print_input, true_whole, true_linker)
+            scores.update(mol_metrics.compute_diversity(records, with_true=True, with_reference=False))
         return scores
 
     def _shape_records(self, data, one_hot, x, node_mask, drop, out_drop, linker):

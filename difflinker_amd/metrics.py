@@ -32,6 +32,11 @@ ring filter ("no double bond inside a non-aromatic ring", compute_metrics.py:269
 that treat aromatic rings properly (``dl_aromatic_rings``, ``csrc/aromatic.hip``).  Aromaticity is perceived from the 3D
 geometry by a rule of this project's own - not RDKit's model, not OpenBabel's bond typing; see
 ``molecule_builder.refine_bond_orders``.
+
+``analyze_fingerprints`` / ``tanimoto_nearest`` / ``compute_diversity`` answer the set-level questions exact identity cannot:
+are the samples of one input different from each other, how close does a sample come to its true molecule, how close is the
+nearest molecule of a reference set (``dl_fingerprints`` and ``dl_tanimoto_nearest``, ``csrc/fingerprint.hip``).  The circular
+fingerprint is this project's own, built on the colours of ``molecule_keys`` - not RDKit's Morgan fingerprint.
 """
 import ctypes
 import math
@@ -892,4 +897,239 @@ def compute_aromatic(pred, true=None):
         out['true_aromatic_rings_n'] = mean([t.n_aromatic_linker for t in both])
         out['true_ring_filter'] = mean([t.n_filtered_bonds == 0 for t in both])
         out['true_valence_validity_geometric'] = mean([t.n_over == 0 for t in both])
+    return out
+
+
+Fingerprints = namedtuple('Fingerprints', 'bits n_on n_atoms n_centres status')
+Nearest = namedtuple('Nearest', 'index common union sum_q20 n_pairs')
+DiversityRecord = namedtuple('DiversityRecord', 'input status sum_q20 n_pairs sum_q20_linker n_pairs_linker true_common '
+                                                'true_union true_common_linker true_union_linker ref_common ref_union')
+DIVERSITY_NAMES = ('diversity_molecules', 'internal_diversity', 'internal_diversity_linker')
+DIVERSITY_TRUE_NAMES = ('similarity_to_true', 'similarity_to_true_linker')
+DIVERSITY_REFERENCE_NAMES = ('nearest_reference_similarity', 'nearest_reference_identical')
+Q20 = 1 << 20                                    # the fixed point of dl_tanimoto_args.sum_q20
+
+
+def fingerprints(one_hot, node_mask, found, drop_mask=None, centre_mask=None, radius=2, n_bits=2048):
+    """``dl_fingerprints`` on the result ``found`` of ``perceive_bonds`` (or ``refine_bond_orders``) for the same ``one_hot``
+    and ``node_mask``: device tensors in, a ``Fingerprints`` of device tensors out, on torch's current stream, no host
+    synchronisation.  It mirrors ``molecule_keys``.
+
+    THE RULE (this project's own; NOT RDKit's Morgan fingerprint: the invariants are the element and the bond orders alone,
+    the hash is the one of ``molecule_keys``, duplicate environments are not removed and nothing is counted).  With the
+    colours ``c_r`` of ``molecule_keys``' refinement after ``r`` rounds, the on-bits of a molecule are ``c_r[i] mod n_bits``
+    for ``0 <= r <= radius`` and every kept atom ``i`` that is a centre; ``centre_mask`` (``[B,N]`` or ``[B,N,1]`` by row,
+    like ``drop_mask``) chooses the centres, every kept atom without it.  The environments always see the whole kept molecule.
+
+    ``bits`` int32 ``[B, n_bits / 32]`` (the 32 bits of each word; bit ``k`` of a fingerprint is bit ``k % 32`` of word
+    ``k // 32``), ``n_on``, ``n_atoms`` (kept), ``n_centres`` and ``status`` int32 ``[B]``: the ``_lib.DL_BONDS_*`` bits of
+    ``found`` plus ``DL_FP_BAD_BOND`` and ``DL_FP_TOO_LARGE`` (more than 256 kept atoms: no bits)."""
+    masks = (node_mask,) + tuple(m for m in (drop_mask, centre_mask) if m is not None)
+    if not (one_hot.is_cuda and all(m.is_cuda for m in masks) and found.n_bonds.is_cuda):
+        raise _lib.HipLibraryError('fingerprints runs on the HIP device only (no CPU fallback): '
+                                   f'got tensors on {one_hot.device}, {", ".join(str(m.device) for m in masks)}')
+    if radius not in range(_lib.DL_FP_MAX_RADIUS + 1) or n_bits not in _lib.DL_FP_BITS:
+        raise ValueError(f'radius must be 0..{_lib.DL_FP_MAX_RADIUS} and n_bits one of {_lib.DL_FP_BITS}: got {radius}, {n_bits}')
+    B, N, nf = one_hot.shape
+    if any(m.numel() != B * N for m in masks) or found.bonds.dim() != 3 or found.bonds.shape[0] != B:
+        raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, masks {[tuple(m.shape) for m in masks]}, bonds '
+                         f'{tuple(found.bonds.shape)}')
+    dev = one_hot.device
+    f32 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()     # noqa: E731
+    one_hot, node_mask, drop_mask, centre_mask = f32(one_hot), f32(node_mask), f32(drop_mask), f32(centre_mask)
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    out = Fingerprints(i32(B, n_bits // 32), i32(B), i32(B), i32(B), i32(B))
+    capacity = found.bonds.shape[1]
+    opt = lambda t: None if t is None else t.data_ptr()                     # noqa: E731
+    with torch.cuda.device(dev):
+        args = _lib.DLFingerprintArgs(
+            B=B, N=N, nf=nf, one_hot=one_hot.data_ptr(), node_mask=node_mask.data_ptr(), drop_mask=opt(drop_mask),
+            centre_mask=opt(centre_mask), capacity=capacity, n_bonds_in=found.n_bonds.data_ptr(),
+            bonds=found.bonds.data_ptr() if capacity else None, status_in=found.status.data_ptr(), radius=int(radius),
+            n_bits=int(n_bits), bits=out.bits.data_ptr(), n_on=out.n_on.data_ptr(), n_atoms=out.n_atoms.data_ptr(),
+            n_centres=out.n_centres.data_ptr(), status=out.status.data_ptr(),
+            stream=torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.load().dl_fingerprints(ctypes.byref(args)), 'dl_fingerprints')
+    return out
+
+
+def analyze_fingerprints(one_hot, x, node_mask, is_geom, linker_mask, drop_mask=None, margins=const.MARGINS_EDM, radius=2,
+                         n_bits=2048):
+    """Fingerprints of every molecule of a batch on the HIP device, in two views of ONE bond perception
+    (``perceive_all_bonds``, which synchronises; the two ``dl_fingerprints`` launches do not): ``(whole, linker)``, both
+    ``Fingerprints``.  ``whole`` has every kept atom as a centre; ``linker`` only the ``linker_mask`` rows, whose
+    environments still reach into the fragments.  ``drop_mask`` rows (the pocket of a pocket model) are left out of both.
+    All samples of one input share their fragments, so ``whole`` mostly measures the fragments; ``linker`` is the one that
+    tells the samples of an input apart."""
+    if not (one_hot.is_cuda and x.is_cuda and node_mask.is_cuda and linker_mask.is_cuda):
+        raise _lib.HipLibraryError('analyze_fingerprints runs on the HIP device only (no CPU fallback): '
+                                   f'got tensors on {one_hot.device}, {x.device}, {node_mask.device}, {linker_mask.device}')
+    B, N = one_hot.shape[:2]
+    if linker_mask.numel() != B * N:
+        raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, linker_mask {tuple(linker_mask.shape)}')
+    found = perceive_all_bonds(one_hot, x, node_mask, is_geom, margins)
+    whole = fingerprints(one_hot, node_mask, found, drop_mask, None, radius, n_bits)
+    return whole, fingerprints(one_hot, node_mask, found, drop_mask, linker_mask.reshape(B, N), radius, n_bits)
+
+
+def tanimoto_nearest(a_bits, b_bits, a_offsets=None, b_offsets=None, exclude_diagonal=False, want_sum=True):
+    """``dl_tanimoto_nearest``: for every row of ``a_bits [Ma,W]`` its nearest neighbour and its summed similarity among the
+    candidate rows of ``b_bits [Mb,W]`` (``Fingerprints.bits``; the two may be the same tensor), on torch's current stream
+    with no host synchronisation.  ``a_offsets`` and ``b_offsets`` (int32 ``[G+1]``, both or neither; ``a_offsets`` must not
+    decrease) split the rows into ``G`` groups: row ``i`` with ``a_offsets[g] <= i < a_offsets[g+1]`` has the candidates
+    ``b_offsets[g] <= j < b_offsets[g+1]``, without ``j == i`` when ``exclude_diagonal``.  Without offsets: one group over
+    everything.
+
+    The similarity of a pair is Tanimoto on THIS PROJECT'S fingerprint (not RDKit's): ``c / u`` with ``c = popcount(a & b)``
+    and ``u = popcount(a | b)``, and 1 when both are empty.  Returns a ``Nearest`` of device tensors ``[Ma]``: ``index`` (the
+    candidate of the greatest similarity, compared exactly; of equal ones the lowest; -1 without candidates), ``common`` and
+    ``union`` (that pair's ``c`` and ``u``), ``sum_q20`` (int64: the sum over the candidates of ``floor(c * 2**20 / u)``, or
+    ``None`` without ``want_sum``) and ``n_pairs`` (candidates).  All integers: the same bits on every run."""
+    given = (a_bits, b_bits) + tuple(t for t in (a_offsets, b_offsets) if t is not None)
+    if not all(t.is_cuda for t in given):
+        raise _lib.HipLibraryError('tanimoto_nearest runs on the HIP device only (no CPU fallback): '
+                                   f'got tensors on {", ".join(str(t.device) for t in given)}')
+    if a_bits.dim() != 2 or b_bits.dim() != 2 or a_bits.shape[1] != b_bits.shape[1] or a_bits.shape[1] * 32 not in _lib.DL_FP_BITS:
+        raise ValueError(f'shapes disagree: a_bits {tuple(a_bits.shape)}, b_bits {tuple(b_bits.shape)}')
+    if a_bits.dtype != torch.int32 or b_bits.dtype != torch.int32:
+        raise ValueError(f'fingerprint rows are int32 words, got {a_bits.dtype} and {b_bits.dtype}')
+    if (a_offsets is None) != (b_offsets is None) or (a_offsets is not None and a_offsets.numel() != b_offsets.numel()):
+        raise ValueError('a_offsets and b_offsets come together and have the same length')
+    dev = a_bits.device
+    Ma, W = a_bits.shape
+    Mb = b_bits.shape[0]
+    a_bits, b_bits = a_bits.contiguous(), b_bits.contiguous()
+    if a_offsets is None:
+        a_offsets, b_offsets = (torch.full((2,), m, dtype=torch.int32, device=dev) for m in (Ma, Mb))     # [0, M], filled on
+        a_offsets[0], b_offsets[0] = 0, 0                                                                  # the device
+    a_offsets, b_offsets = (t.to(device=dev, dtype=torch.int32).contiguous() for t in (a_offsets, b_offsets))
+    G = max(a_offsets.numel() - 1, 0)
+    i32 = lambda: torch.empty(Ma, dtype=torch.int32, device=dev)            # noqa: E731
+    out = Nearest(i32(), i32(), i32(), torch.empty(Ma, dtype=torch.int64, device=dev) if want_sum else None, i32())
+    with torch.cuda.device(dev):
+        args = _lib.DLTanimotoArgs(
+            Ma=Ma, Mb=Mb, W=W, G=G, a_bits=a_bits.data_ptr() if Ma else None, b_bits=b_bits.data_ptr() if Mb else None,
+            a_offsets=a_offsets.data_ptr() if G else None, b_offsets=b_offsets.data_ptr() if G else None,
+            exclude_diagonal=int(bool(exclude_diagonal)), nn_index=out.index.data_ptr(), nn_common=out.common.data_ptr(),
+            nn_union=out.union.data_ptr(), n_pairs=out.n_pairs.data_ptr(),
+            sum_q20=out.sum_q20.data_ptr() if want_sum else None, stream=torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.load().dl_tanimoto_nearest(ctypes.byref(args)), 'dl_tanimoto_nearest')
+    return out
+
+
+def _grouped(rows, groups, n_groups):
+    """``rows`` (int64 positions) sorted by their group, and the int32 offsets ``[n_groups + 1]`` of the groups."""
+    order = torch.argsort(groups[rows], stable=True)
+    counts = torch.bincount(groups[rows], minlength=n_groups)
+    offsets = torch.zeros(n_groups + 1, dtype=torch.int64, device=rows.device)
+    offsets[1:] = torch.cumsum(counts, 0)
+    return rows[order], offsets.to(torch.int32)
+
+
+def diversity_records(whole, linker, input_index, true_whole=None, true_linker=None, reference=None):
+    """The ``DiversityRecord`` values ``compute_diversity`` reads, one per sample, from fingerprints kept on the device.
+
+    ``whole`` and ``linker`` are the two ``Fingerprints`` of ``analyze_fingerprints`` for ALL samples (batches concatenated
+    with ``cat_fingerprints``); ``input_index[k]`` names the input sample ``k`` came from.  With ``true_whole`` /
+    ``true_linker`` (the same for the true molecules, one row per DISTINCT input, in order of first appearance in
+    ``input_index``) every sample is also compared with its own true molecule; with ``reference`` (int32 bits ``[R,W]`` of
+    a reference set, clean rows only) with its nearest row there.  A sample or true molecule with a status bit in either
+    view takes part in no comparison.  Launches: two for the pairs among the samples of each input (groups = inputs,
+    diagonal excluded), two against the true molecules (B groups of one row), one against the reference (one group)."""
+    n = whole.bits.shape[0]
+    if not (linker.bits.shape[0] == n == len(input_index)):
+        raise ValueError(f'{n} and {linker.bits.shape[0]} fingerprints, {len(input_index)} input indices')
+    dev = whole.bits.device
+    dense = {}
+    groups_host = [dense.setdefault(v, len(dense)) for v in input_index]
+    G = len(dense)
+    status = (whole.status | linker.status)
+    zeros = lambda: torch.zeros(n, dtype=torch.int64, device=dev)           # noqa: E731
+    cols = {name: zeros() for name in DiversityRecord._fields[2:]}
+    if n:
+        groups = torch.tensor(groups_host, dtype=torch.int64, device=dev)
+        rows, offsets = _grouped(torch.nonzero(status == 0).reshape(-1), groups, G)
+        for view, tail in ((whole, ''), (linker, '_linker')):
+            bits = view.bits[rows].contiguous()
+            near = tanimoto_nearest(bits, bits, offsets, offsets, exclude_diagonal=True)
+            cols['sum_q20' + tail][rows], cols['n_pairs' + tail][rows] = near.sum_q20, near.n_pairs.long()
+        if true_whole is not None:
+            if true_whole.bits.shape[0] != G or true_linker.bits.shape[0] != G:
+                raise ValueError(f'{G} inputs, {true_whole.bits.shape[0]} and {true_linker.bits.shape[0]} true fingerprints')
+            clean = (true_whole.status | true_linker.status) == 0
+            b_offsets = torch.zeros(G + 1, dtype=torch.int64, device=dev)
+            b_offsets[1:] = torch.cumsum(clean.long(), 0)                   # a flagged true molecule: an empty range
+            b_offsets = b_offsets.to(torch.int32)
+            for view, true_view, tail in ((whole, true_whole, ''), (linker, true_linker, '_linker')):
+                near = tanimoto_nearest(view.bits[rows].contiguous(), true_view.bits[clean].contiguous(), offsets, b_offsets,
+                                        want_sum=False)
+                has = near.index >= 0
+                cols['true_common' + tail][rows] = torch.where(has, near.common, -1).long()
+                cols['true_union' + tail][rows] = near.union.long()
+        if reference is not None:
+            near = tanimoto_nearest(whole.bits[rows].contiguous(), reference, want_sum=False)
+            cols['ref_common'][rows] = torch.where(near.index >= 0, near.common, -1).long()
+            cols['ref_union'][rows] = near.union.long()
+    status = status.cpu().tolist()
+    host = {name: t.cpu().tolist() for name, t in cols.items()}
+    absent = [name for name in cols if (name.startswith('true_') and true_whole is None)
+              or (name.startswith('ref_') and reference is None)]
+    out = []
+    for k in range(n):
+        values = {name: (None if name in absent else host[name][k]) for name in cols}
+        for c, u in (('true_common', 'true_union'), ('true_common_linker', 'true_union_linker'), ('ref_common', 'ref_union')):
+            if values[c] is not None and (values[c] < 0 or status[k] != 0):  # nothing to compare with
+                values[c] = values[u] = None
+        out.append(DiversityRecord(input=input_index[k], status=status[k], **values))
+    return out
+
+
+def cat_fingerprints(parts):
+    """One ``Fingerprints`` from the ``Fingerprints`` of several batches, rows concatenated on the device."""
+    return Fingerprints(*(torch.cat([getattr(p, name) for p in parts]) for name in Fingerprints._fields))
+
+
+def _similarity(common, union):
+    return 1.0 if union == 0 else common / union
+
+
+def compute_diversity(records, with_true=None, with_reference=None):
+    """Set-level scores of the ``DiversityRecord`` values ``records`` (``diversity_records``), on the host, in fp64.  Every
+    similarity here is Tanimoto on THIS PROJECT'S circular fingerprint (``fingerprints``), NOT on RDKit's Morgan
+    fingerprint: the numbers compare runs of this project with each other and nothing else.
+
+    ``diversity_molecules``           records scored: those with status 0; the others are left out of everything below
+    ``internal_diversity``            the mean, over the inputs with at least two scored samples, of ``1 - `` the mean
+                                      pairwise similarity among that input's samples (from ``sum_q20 / n_pairs / 2**20``:
+                                      every ordered pair once, each similarity rounded down to a multiple of ``2**-20``)
+    ``internal_diversity_linker``     the same on the fingerprints whose centres are the linker atoms: the one that tells the
+                                      samples of an input apart, since they share their fragments
+    ``similarity_to_true``, ``similarity_to_true_linker``
+                                      when the records carry them: the mean similarity of every scored sample to its own
+                                      true molecule
+    ``nearest_reference_similarity``  when the records carry them: the mean of every scored sample's greatest similarity to
+                                      the reference set, and
+    ``nearest_reference_identical``   the share of those samples with a reference fingerprint equal to their own
+
+    ``with_true`` / ``with_reference`` say whether those keys are wanted; ``None`` (the default): when some record carries
+    such a value.  A mean over nothing is ``None``, as in ``compute_rings``."""
+    mean = lambda values: float(sum(values) / len(values)) if values else None      # noqa: E731
+    good = [m for m in records if m.status == 0]
+    out = {'diversity_molecules': len(good)}
+    for tail in ('', '_linker'):
+        sums = {}
+        for m in good:
+            total, pairs = sums.get(m.input, (0, 0))
+            sums[m.input] = (total + getattr(m, 'sum_q20' + tail), pairs + getattr(m, 'n_pairs' + tail))
+        out['internal_diversity' + tail] = mean([1.0 - total / pairs / Q20 for total, pairs in sums.values() if pairs > 0])
+    carried = lambda u: any(getattr(m, u) is not None for m in records)      # noqa: E731
+    for name, c, u, wanted in (('similarity_to_true', 'true_common', 'true_union', with_true),
+                               ('similarity_to_true_linker', 'true_common_linker', 'true_union_linker', with_true),
+                               ('nearest_reference_similarity', 'ref_common', 'ref_union', with_reference)):
+        if not (carried(u) if wanted is None else wanted):
+            continue
+        scored = [(getattr(m, c), getattr(m, u)) for m in good if getattr(m, u) is not None]
+        out[name] = mean([_similarity(cc, uu) for cc, uu in scored])
+        if name == 'nearest_reference_similarity':
+            out['nearest_reference_identical'] = mean([cc == uu for cc, uu in scored])
     return out

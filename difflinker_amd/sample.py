@@ -57,7 +57,7 @@ def _prepare(checkpoint, prefix, data, n_steps, device):
 
 def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=None, linker_size_model=None,
            output_format='xyz', metrics=False, geometry=False, clashes=False, shape=False, rings=False,
-           bond_orders='distance', aromatic=False):
+           bond_orders='distance', aromatic=False, diversity=False, diversity_reference=None):
     """``sample.py``.  Returns the output directory.  ``metrics=True`` scores the molecules sampled in this call against
     the data set's own (``metrics.compute_metrics``: valence rule, connectivity, uniqueness, novelty, recovery) and writes
     the result to ``metrics.json`` in the output directory; with ``geometry=True`` as well, the symmetry-aware RMSD of the
@@ -76,7 +76,14 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
     writes the ``.sdf`` files with the Kekule orders of ``molecule_builder.refine_bond_orders`` (planar five- and six-rings
     alternate; 1, 2 or 3, never 4); ``aromatic=True`` adds ``aromatic_rings_n``, ``ring_filter`` and
     ``valence_validity_geometric`` of the samples and of their true molecules (``metrics.analyze_aromatic`` /
-    ``compute_aromatic``).  Both rest on a geometric rule of this project's own, not on OpenBabel's or RDKit's."""
+    ``compute_aromatic``).  Both rest on a geometric rule of this project's own, not on OpenBabel's or RDKit's.
+    ``diversity=True`` fingerprints every sample and every true molecule, pocket rows left out
+    (``metrics.analyze_fingerprints``: once with every atom as a centre, once with the linker atoms), keeps the bits on the
+    device across the batches and writes ``metrics.compute_diversity``'s keys in the same way: ``internal_diversity`` and
+    ``internal_diversity_linker`` among the samples of each input, ``similarity_to_true`` and ``similarity_to_true_linker``.
+    ``diversity_reference`` names another data set under ``data`` (typically the training set); it is fingerprinted once,
+    in batches, and ``nearest_reference_similarity`` / ``nearest_reference_identical`` join the keys.  All of these are
+    Tanimoto similarities on this project's own circular fingerprint, not on RDKit's Morgan fingerprint."""
     if output_format not in OUTPUT_FORMATS:
         raise ValueError(f'output_format must be one of {OUTPUT_FORMATS}, got {output_format!r}')
     if bond_orders not in BOND_ORDERS:
@@ -87,6 +94,8 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
     pred_clashes, true_clashes = [], []
     shapes, linker_shapes = [], []
     pred_rings, true_rings = [], []
+    pred_prints, true_prints, print_input = [], [], []
+    diversity = diversity or diversity_reference is not None
     geometry = geometry and metrics
     exp = 'model' if isinstance(checkpoint, DDPM) else checkpoint.split('/')[-1].replace('.ckpt', '')
     collate_fn, sample_fn = collate, None
@@ -147,6 +156,9 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
         if aromatic:
             true_aromatic_batch = mol_metrics.aromatic_to_host(mol_metrics.analyze_aromatic(
                 h[:, :, :model.num_classes], x, node_mask, model.is_geom, batch['linker_mask']))
+        if diversity:                                          # likewise; one row per input, kept on the device
+            true_prints.append(mol_metrics.analyze_fingerprints(
+                h[:, :, :model.num_classes], x, node_mask, model.is_geom, batch['linker_mask']))
         if geometry:
             true_x_batch = list(mol_metrics.kept_positions(x, node_mask)[0])
             n_linker_batch = batch['linker_mask'].reshape(len(uuids), -1).sum(1).long().tolist()
@@ -182,6 +194,11 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 pred_aromatic += mol_metrics.aromatic_to_host(mol_metrics.analyze_aromatic(
                     hs[:, :, :model.num_classes], xs, out_mask, model.is_geom, out_mask * (1 - pad(batch['fragment_mask']))))
                 true_aromatic += true_aromatic_batch
+            if diversity:                                      # likewise
+                pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, out_mask.shape[1] - m.shape[1]))      # noqa: E731
+                pred_prints.append(mol_metrics.analyze_fingerprints(
+                    hs[:, :, :model.num_classes], xs, out_mask, model.is_geom, out_mask * (1 - pad(batch['fragment_mask']))))
+                print_input += [(batch_idx, k) for k in range(len(uuids))]
             if output_format != 'sdf':
                 save_xyz_file(output_dir, hs, xs, out_mask, [f'{u}/{i}' for u in uuids], is_geom=model.is_geom)
             if output_format != 'xyz':
@@ -202,7 +219,7 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 n_linker += n_linker_batch
     if found:
         print(json.dumps(summary(found)))
-    if metrics or clashes or shape or rings or aromatic:
+    if metrics or clashes or shape or rings or aromatic or diversity:
         with open(os.path.join(output_dir, 'metrics.json'), 'w') as f:
             scores = {}
             if metrics:
@@ -217,8 +234,40 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 scores.update(mol_metrics.compute_rings(pred_rings, true_rings))
             if aromatic:
                 scores.update(mol_metrics.compute_aromatic(pred_aromatic, true_aromatic))
+            if diversity:
+                reference = None if diversity_reference is None else reference_fingerprints(model, diversity_reference)
+                scores.update(_diversity_scores(pred_prints, true_prints, print_input, reference))
             json.dump(scores, f, indent=1)
     return output_dir
+
+
+def reference_fingerprints(model, prefix, radius=2, n_bits=2048):
+    """The whole-molecule fingerprints (``metrics.fingerprints``, every atom a centre, pocket rows left out) of the data set
+    ``prefix`` under the model's data path, computed once, batch by batch, and kept on the device: int32 ``[R, n_bits / 32]``,
+    the molecules with a status bit left out."""
+    from .datasets import ZincDataset
+    dataset_type = MOADDataset if '.' in prefix else ZincDataset
+    dataset = dataset_type(data_path=model.data_path, prefix=prefix, device=model.torch_device)
+    rows = []
+    for batch in get_dataloader(dataset, model.batch_size, collate_fn=collate):
+        node_mask = batch['atom_mask'] - batch['pocket_mask'] if 'pocket_mask' in batch else batch['atom_mask']
+        types = batch['one_hot'][:, :, :model.num_classes]
+        found = perceive_all_bonds(types, batch['positions'], node_mask, model.is_geom)
+        prints = mol_metrics.fingerprints(types, node_mask, found, radius=radius, n_bits=n_bits)
+        rows.append(prints.bits[prints.status == 0])
+    if not rows:
+        return torch.zeros(0, n_bits // 32, dtype=torch.int32, device=model.torch_device)
+    return torch.cat(rows).contiguous()
+
+
+def _diversity_scores(pred_prints, true_prints, input_index, reference=None):
+    """``metrics.compute_diversity`` of the per-batch ``(whole, linker)`` fingerprint pairs gathered while sampling."""
+    if not pred_prints:
+        return mol_metrics.compute_diversity([], with_true=bool(true_prints) or None, with_reference=reference is not None)
+    whole, linker = (mol_metrics.cat_fingerprints([p[k] for p in pred_prints]) for k in range(2))
+    true = [None, None] if not true_prints else [mol_metrics.cat_fingerprints([p[k] for p in true_prints]) for k in range(2)]
+    records = mol_metrics.diversity_records(whole, linker, input_index, true[0], true[1], reference)
+    return mol_metrics.compute_diversity(records, with_true=bool(true_prints), with_reference=reference is not None)
 
 
 def sample_trajectories(checkpoint, chains, prefix, keep_frames, device, data=None, n_steps=None, batch_size=32):
@@ -287,6 +336,13 @@ def main(argv=None):
                    help='perceive aromatic rings of every sample and of its true molecule from the geometry on the GPU (a rule '
                         'of this project, not RDKit\'s) and write aromatic_rings_n, ring_filter and '
                         'valence_validity_geometric to metrics.json')
+    p.add_argument('--diversity', action='store_true',
+                   help='fingerprint every sample and every true molecule on the GPU (this project\'s circular fingerprint, '
+                        'not RDKit\'s Morgan) and write internal_diversity, internal_diversity_linker, similarity_to_true and '
+                        'similarity_to_true_linker to metrics.json')
+    p.add_argument('--diversity_reference', default=None, metavar='PREFIX',
+                   help='with --diversity: another data set under --data (typically the training set); every sample\'s '
+                        'greatest similarity to it is written as nearest_reference_similarity / nearest_reference_identical')
     a = p.parse_args(argv)
     if a.keep_frames is not None:
         print(sample_trajectories(a.checkpoint, a.samples, a.prefix, a.keep_frames, a.device, a.data, a.n_steps))
@@ -296,7 +352,8 @@ def main(argv=None):
                      **({'clashes': True} if a.clashes else {}), **({'shape': True} if a.shape else {}),
                      **({'rings': True} if a.rings else {}),
                      **({'bond_orders': a.bond_orders} if a.bond_orders != 'distance' else {}),
-                     **({'aromatic': True} if a.aromatic else {})))
+                     **({'aromatic': True} if a.aromatic else {}), **({'diversity': True} if a.diversity else {}),
+                     **({'diversity_reference': a.diversity_reference} if a.diversity_reference else {})))
 
 
 if __name__ == '__main__':

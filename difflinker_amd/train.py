@@ -105,6 +105,9 @@ def main(argv=None):
                    help='with --sample_every_epochs: perceive aromatic rings from the geometry (a rule of this project, not '
                         'RDKit\'s or OpenBabel\'s) and add aromatic_rings_n, ring_filter and valence_validity_geometric to the '
                         'epoch scores')
+    p.add_argument('--diversity', action='store_true',
+                   help='with --sample_every_epochs: add internal_diversity(_linker) and similarity_to_true(_linker) of the '
+                        'samples to the epoch scores (Tanimoto on this project\'s circular fingerprint, not RDKit\'s Morgan)')
     a = p.parse_args(argv)
     cfg = dict(DEFAULTS)
     if a.config is not None:
@@ -142,6 +145,7 @@ def main(argv=None):
     model.shape_metrics = bool(a.shape)
     model.ring_metrics = bool(a.rings)
     model.aromatic_metrics = bool(a.aromatic)
+    model.diversity_metrics = bool(a.diversity)
     kept = lambda: {'best_validity_and_connectivity': best} if a.sample_every_epochs else {}   # noqa: E731
     step, epoch = start_step, start_epoch
     n_epochs = int(cfg['n_epochs'])

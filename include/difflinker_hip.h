@@ -58,6 +58,12 @@
  *                                           five- and six-rings from the geometry, Kekule orders for them and the aromatic
  *                                           ones, under a rule stated below that is this project's own, NOT OpenBabel's or
  *                                           RDKit's
+ *   dl_fingerprints                      <- (no reference counterpart: the field reports internal diversity and similarity
+ *                                           to the training set over RDKit's Morgan fingerprints; the reference computes
+ *                                           neither) circular fingerprints from the colour refinement of dl_molecule_keys.
+ *                                           This project's own fingerprint, NOT RDKit's: stated below
+ *   dl_tanimoto_nearest                  <- (no reference counterpart) for every row of one fingerprint set the most similar
+ *                                           row and the summed Tanimoto similarity among a segment of another set
  *   dl_fragment_cuts                     <- FragmentMol(minCuts = maxCuts = 2) with DeLinker's pattern
  *                                           (data/geom/generate_geom_multifrag.py:199-206) and the re-assembly of
  *                                           data/zinc/prepare_dataset.py, src/datasets.py:56-100
@@ -1247,6 +1253,112 @@ typedef struct dl_pocket_args {
     int32_t* index;                 /* device int32 [B,capacity] out (may be NULL when capacity is 0) */
 } dl_pocket_args;
 int32_t dl_pocket_select(const dl_pocket_args* args, void* stream);
+
+/* ---- circular fingerprints and their Tanimoto similarity (fingerprint.hip) -------------------------------------
+ * THE CALLING FORM.  These two entry points take their args struct ALONE, and the stream is the LAST FIELD of the struct
+ * (`stream`: a hipStream_t as void*, NULL = the default stream).  The contract is that of every other entry point: inputs
+ * are read and outputs written in the order of that stream and of no other (tests/test_gpu_fingerprint.py holds both to
+ * it).  Moving the two into the (args, stream) form of the rest of this header, together with their cases in the stream
+ * table of tests/test_gpu_streams.py, is a follow-up for whoever next edits that table.
+ *
+ * FINGERPRINTS.  One workgroup per molecule, ONE launch per batch, on the list dl_perceive_bonds (or dl_aromatic_rings'
+ * order_out spliced into it) left on the device.  The list is read with the conventions of dl_molecule_keys: atom k is the
+ * k-th row with node_mask != 0; `drop_mask` (may be NULL) removes atoms AFTER that numbering, together with every bond that
+ * touches them; an entry (i, j, order) is a bond when 0 <= i, j < atoms, i != j and 1 <= order <= 3, in either orientation;
+ * any other entry is skipped and sets DL_FP_BAD_BOND; entries from min(n_bonds_in, capacity) on are never read (a negative
+ * n_bonds_in counts as 0).  `centre_mask` (may be NULL; [B,N] by row like drop_mask) chooses the CENTRES: with it only
+ * environments centred on a marked kept atom set bits, while the environments themselves still see the whole kept molecule.
+ * The callers pass the linker mask: all samples of one input share their fragments.
+ *
+ * With mix64 and mix2 as stated at dl_molecule_keys, all arithmetic modulo 2^64:
+ *     c_0[i]   = mix2(0x243F6A8885A308D3, type_i + 1)            type: the first largest entry of the one-hot row
+ *     c_r+1[i] = mix2(c_r[i], sum over the kept bonds (i, j, order) of mix2(c_r[j], order))
+ *     on-bits  = { c_r[i] mod n_bits : 0 <= r <= radius, i kept and a centre }
+ * radius is 0 .. DL_FP_MAX_RADIUS (2 is the neighbourhood of ECFP4), n_bits 512, 1024 or 2048, W = n_bits / 32.
+ *
+ *   bits        uint32 [B,W]: bit k of a fingerprint is bit k % 32 of word k / 32
+ *   n_on        bits set
+ *   n_atoms     kept atoms
+ *   n_centres   kept atoms that are centres
+ *   status      the bits of `status_in`, plus DL_BONDS_OVERFLOW when n_bonds_in > capacity, DL_FP_BAD_BOND, and
+ *               DL_FP_TOO_LARGE for more than DL_FP_MAX_ATOMS KEPT atoms: bits, n_on and n_centres of that molecule are
+ *               then 0 (its list is not looked at) and the other molecules of the launch are untouched.  N itself may be up
+ *               to 1024: pockets are dropped, not counted.  The list may be of any length.
+ *
+ * Integer work only: the same bits on every run, under every order of the list and every renumbering of the atoms.  Global
+ * memory is written with plain stores only, every output element is written, the callee allocates nothing.  A null `args`,
+ * B < 0, N < 1, N > 1024, nf < 1 or > 16, capacity < 0, a radius outside 0 .. DL_FP_MAX_RADIUS or another n_bits return
+ * DL_ERR_BAD_ARG; then B == 0 returns DL_OK without a launch; then a null pointer (other than drop_mask, centre_mask, and
+ * `bonds` when capacity is 0) returns DL_ERR_BAD_ARG, all before any device work.
+ * What this is NOT: RDKit's Morgan / ECFP fingerprint.  Other invariants (the element and the bond orders only: no charge,
+ * hydrogen count, ring membership or isotope), another hash, no removal of duplicate environments, no counts.  Numbers are
+ * comparable within this project only. */
+#define DL_FP_MAX_ATOMS 256         /* kept atoms per molecule */
+#define DL_FP_MAX_RADIUS 4
+#define DL_FP_TOO_LARGE 4           /* status bit, same value as DL_KEYS_TOO_LARGE */
+#define DL_FP_BAD_BOND 8            /* status bit, same value as DL_KEYS_BAD_BOND */
+typedef struct dl_fingerprint_args {
+    int32_t B, N, nf;
+    const float* one_hot;           /* device f32 [B,N,nf] */
+    const float* node_mask;         /* device f32 [B,N] */
+    const float* drop_mask;         /* device f32 [B,N] or NULL */
+    const float* centre_mask;       /* device f32 [B,N] or NULL */
+    int32_t capacity;               /* bonds the list holds per molecule */
+    const int32_t* n_bonds_in;      /* device int32 [B]: dl_bonds_args.n_bonds */
+    const int32_t* bonds;           /* device int32 [B,capacity,3]: dl_bonds_args.bonds (may be NULL when capacity is 0) */
+    const int32_t* status_in;       /* device int32 [B]: dl_bonds_args.status */
+    int32_t radius;                 /* 0 .. DL_FP_MAX_RADIUS */
+    int32_t n_bits;                 /* 512, 1024 or 2048 */
+    uint32_t* bits;                 /* device uint32 [B,n_bits/32] out */
+    int32_t* n_on;                  /* device int32 [B] out */
+    int32_t* n_atoms;               /* device int32 [B] out */
+    int32_t* n_centres;             /* device int32 [B] out */
+    int32_t* status;                /* device int32 [B] out */
+    void* stream;                   /* hipStream_t; NULL: the default stream */
+} dl_fingerprint_args;
+int32_t dl_fingerprints(const dl_fingerprint_args* args);
+
+/* TANIMOTO.  Segmented all-pairs similarity of two fingerprint sets, reduced per row of the first: a_bits uint32 [Ma,W]
+ * and b_bits uint32 [Mb,W] (W = 16, 32 or 64; 16-byte aligned; they may be the same buffer), G groups given by the device
+ * arrays a_offsets[G+1] and b_offsets[G+1].  Row i of A belongs to the group g with a_offsets[g] <= i < a_offsets[g+1];
+ * a_offsets must not decrease (the kernel finds g by bisection), and a row in no group has no candidates.  Row i's
+ * CANDIDATES are the rows b_offsets[g] <= j < b_offsets[g+1] of B, without j == i when `exclude_diagonal` is set.  Every
+ * offset is clamped to [0, M] first, so no offset can make the kernel read outside the two sets; an empty or inverted B
+ * range has no candidates.  G = 1 with the whole ranges is plain all-pairs.
+ *
+ * For a pair c = popcount(a & b) and u = popcount(a) + popcount(b) - c; the similarity is the exact fraction c / u, and
+ * 1 / 1 when u is 0 (two empty fingerprints are equal).
+ *
+ *   nn_index    the candidate of the greatest similarity, fractions compared exactly by cross-multiplication in integers;
+ *               of equal ones the lowest j; -1 without candidates
+ *   nn_common, nn_union   that pair's c and u (u == 0 is reported as it is); 0 and 0 without candidates
+ *   n_pairs     candidates
+ *   sum_q20     (may be NULL: then nothing is summed and no division is issued) the sum over the candidates of
+ *               u == 0 ? 2^20 : (c << 20) / u, in unsigned integer division
+ *
+ * Integers throughout: the same bits on every run and for every tiling.  Plain stores only, every output element is
+ * written, the callee allocates nothing; the B range of a row is never split, so nothing is combined across workgroups.  A
+ * null `args`, a negative Ma, Mb or G, another W, a null or misaligned a_bits (unless Ma is 0) or b_bits (unless Mb is 0),
+ * or null offsets (unless G is 0) return DL_ERR_BAD_ARG; then Ma == 0 returns DL_OK without a launch; then a null output
+ * other than sum_q20 returns DL_ERR_BAD_ARG, all before any device work.  G == 0 or Mb == 0 still write every row's "no
+ * candidates" values.
+ * Not here: the dense similarity matrix, clustering, picking diverse subsets. */
+#define DL_TANIMOTO_TILE 128        /* rows of B a workgroup stages in LDS at a time */
+typedef struct dl_tanimoto_args {
+    int32_t Ma, Mb, W, G;
+    const uint32_t* a_bits;         /* device uint32 [Ma,W] (may be NULL when Ma is 0) */
+    const uint32_t* b_bits;         /* device uint32 [Mb,W] (may be NULL when Mb is 0) */
+    const int32_t* a_offsets;       /* device int32 [G+1], not decreasing (may be NULL when G is 0) */
+    const int32_t* b_offsets;       /* device int32 [G+1] (may be NULL when G is 0) */
+    int32_t exclude_diagonal;
+    int32_t* nn_index;              /* device int32 [Ma] out */
+    int32_t* nn_common;             /* device int32 [Ma] out */
+    int32_t* nn_union;              /* device int32 [Ma] out */
+    int32_t* n_pairs;               /* device int32 [Ma] out */
+    uint64_t* sum_q20;              /* device 64-bit [Ma] out, or NULL */
+    void* stream;                   /* hipStream_t; NULL: the default stream */
+} dl_tanimoto_args;
+int32_t dl_tanimoto_nearest(const dl_tanimoto_args* args);
 
 const char* dl_error_string(int32_t status);
 int32_t dl_last_hip_error(void);
