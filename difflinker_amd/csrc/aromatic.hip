@@ -3,11 +3,11 @@
 // is this project's own, stated in full in include/difflinker_hip.h and restated in tests/aromatic_ref.py; it is NOT RDKit's
 // aromaticity model and NOT OpenBabel's bond typing, which the reference reaches through `obabel`.
 //
-// One 256-thread workgroup per molecule, one launch per batch, with the conventions of rings.hip: atom k is the k-th row with
+// One 256-thread workgroup per molecule, one launch per batch, with the conventions of mol_graph.h: atom k is the k-th row with
 // node_mask != 0; drop_mask removes atoms after that numbering together with their bonds; an entry (i, j, order) is a bond
 // when 0 <= i, j < atoms, i != j and 1 <= order <= 3; anything else is skipped and sets DL_AROM_BAD_BOND.
 //
-//   stage    rows ranked as in rings.hip; the kept atoms' coordinates, classes and marks go to LDS by kept index
+//   stage    rows ranked by number_rows of mol_graph.h; the kept atoms' coordinates, classes and marks go to LDS by kept index
 //   build    the 256 x 256 bit matrix of the kept pairs (LDS atomicOr; the old value tells a repeated pair)
 //   cycles   thread s owns kept atom s: a depth-first walk over eligible atoms larger than s, at most six deep and at most
 //            3 * 2^4 leaves, that closes chordless cycles of 5 and 6 atoms in canonical order.  The thread that closes a
@@ -26,74 +26,22 @@
 // LDS: 3 x 8 KiB matrices + 4 KiB map + 3 KiB coordinates + 6 KiB solver workspaces + per-atom and per-ring arrays: about
 // 45 KiB, static.
 // Global memory is written with plain vector stores only; no global atomics of any kind; every output element is written.
-#include "pack_layout.h"
+#include "mol_graph.h"
 #include "kekule.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-using u64 = unsigned long long;
-
-constexpr int AT = 256;                          // threads per molecule
-constexpr int AW = AT / 64;                      // waves
 constexpr int MAX_ROWS = 1024;                   // N, as for dl_perceive_bonds
-constexpr int MAX_KEPT = DL_AROM_MAX_ATOMS;
-constexpr int WORDS = MAX_KEPT / 64;
+constexpr int MAX_KEPT = MATRIX_ATOMS;           // DL_AROM_MAX_ATOMS
+constexpr int WORDS = MATRIX_WORDS;
 constexpr int MAX_RINGS = DL_AROM_MAX_RINGS;
 constexpr int MAX_SYSTEM = DL_AROM_MAX_SYSTEM;
 constexpr int SLOTS = 8;                         // systems solved at a time
 constexpr int MARK = 1 << 16;                    // s_map: kept index | MARK
-constexpr int BONDS_OVERFLOW = 1;                // DL_BONDS_OVERFLOW of dl_bonds_args.status
 enum : int { ROLE_NONE = 0, ROLE_D, ROLE_X, ROLE_P, ROLE_F };
-static_assert(MAX_KEPT == AT && WORDS == 4, "one thread per kept atom, four words per row");
-static_assert(MAX_RINGS <= AT && MAX_SYSTEM == kekule::MAXV, "one thread per ring; kekule.h holds a system");
-
-__device__ __forceinline__ int block_exclusive_scan(int v, int* lds /* [AW] */, int& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int up = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += up;
-    }
-    if (lane == 63) lds[w] = incl;
-    __syncthreads();
-    int base = 0, sum = 0;
-#pragma unroll
-    for (int k = 0; k < AW; ++k) {
-        if (k < w) base += lds[k];
-        sum += lds[k];
-    }
-    __syncthreads();
-    total = sum;
-    return base + incl - v;
-}
-
-// entry e of the list: a bond of this molecule (0 <= i, j < n, i != j, order 1..3)?
-__device__ __forceinline__ bool load_bond(const int* list, int e, int n, int& i, int& j, int& order) {
-    i = list[e * 3];
-    j = list[e * 3 + 1];
-    order = list[e * 3 + 2];
-    return i >= 0 && j >= 0 && i < n && j < n && i != j && order >= 1 && order <= 3;
-}
-
-// no entry before e is a bond of the same pair
-__device__ __forceinline__ bool first_of_pair(const int* list, int e, int n, int i, int j) {
-    const int lo = min(i, j), hi = max(i, j);
-    for (int f = 0; f < e; ++f) {
-        int fi, fj, fo;
-        if (load_bond(list, f, n, fi, fj, fo) && min(fi, fj) == lo && max(fi, fj) == hi) return false;
-    }
-    return true;
-}
-
-__device__ __forceinline__ bool bit(const u64* m, int u, int v) { return (m[u * WORDS + (v >> 6)] >> (v & 63)) & 1; }
-
-__device__ __forceinline__ void set_pair(u64* m, int u, int v) {
-    atomicOr(&m[u * WORDS + (v >> 6)], 1ull << (v & 63));
-    atomicOr(&m[v * WORDS + (u >> 6)], 1ull << (u & 63));
-}
+static_assert(MAX_RINGS <= WG && MAX_SYSTEM == kekule::MAXV, "one thread per ring; kekule.h holds a system");
 
 // the first `limit` neighbours of atom a in ascending order; returns how many were written
 __device__ __forceinline__ int neighbours(const u64* m, int a, int* out, int limit) {
@@ -153,7 +101,7 @@ __device__ bool ring_is_planar(const u64* adj, const float* xs, const int* path,
     return true;
 }
 
-__global__ __launch_bounds__(AT) void aromatic_rings_kernel(dl_aromatic_args a) {
+__global__ __launch_bounds__(WG) void aromatic_rings_kernel(dl_aromatic_args a) {
     __shared__ __align__(16) u64 s_adj[MAX_KEPT * WORDS];         // kept pairs
     __shared__ __align__(16) u64 s_rb[MAX_KEPT * WORDS];          // ring bonds
     __shared__ __align__(16) u64 s_ab[MAX_KEPT * WORDS];          // aromatic bonds
@@ -170,30 +118,22 @@ __global__ __launch_bounds__(AT) void aromatic_rings_kernel(dl_aromatic_args a) 
     __shared__ unsigned char s_ring[MAX_RINGS * 6], s_ring_len[MAX_RINGS];
     __shared__ int s_count[4];                                    // planar rings, aromatic rings, aromatic marked rings, systems
     __shared__ int s_work[SLOTS * kekule::WORDS];
-    __shared__ int s_scan[AW];
+    __shared__ int s_scan[WG_WAVES];
 
     const int b = blockIdx.x, tid = threadIdx.x;
     const int N = a.N, nf = a.nf, capacity = a.capacity;
 
-    // ---- stage: rank the real rows, and the kept rows among themselves (thread t owns the rows [t * per, t * per + per))
-    const int per = (N + AT - 1) / AT;
-    const int r0 = min(tid * per, N), r1 = min(r0 + per, N);
+    // ---- stage: rank the real rows, and the kept rows among themselves
+    const Rows rows = own_rows(N);
     const float* mask = a.node_mask + size_t(b) * N;
     const float* drop = a.drop_mask ? a.drop_mask + size_t(b) * N : nullptr;
     const float* mark = a.mark_mask ? a.mark_mask + size_t(b) * N : nullptr;
-    int mine = 0, mine_kept = 0;
-    for (int r = r0; r < r1; ++r) {
-        if (mask[r] == 0.0f) continue;
-        ++mine;
-        mine_kept += !(drop && drop[r] != 0.0f);
-    }
-    int n = 0, n_kept = 0;
-    int k = block_exclusive_scan(mine, s_scan, n);
-    int kk = block_exclusive_scan(mine_kept, s_scan, n_kept);
+    const RowNumbers rn = number_rows(rows, mask, drop, s_scan);
+    const int n = rn.n, n_kept = rn.n_kept;
 
     const int given = a.n_bonds_in[b];
     const int nb = min(max(given, 0), capacity);
-    const int status_in = a.status_in[b] | (given > capacity ? BONDS_OVERFLOW : 0);
+    const int status_in = a.status_in[b] | (given > capacity ? DL_BONDS_OVERFLOW : 0);
     const int* list = a.bonds + size_t(b) * capacity * 3;        // never read when nb == 0
     int* order_out = a.order_out + size_t(b) * capacity;
     int* bond_aromatic = a.bond_aromatic + size_t(b) * capacity;
@@ -202,13 +142,13 @@ __global__ __launch_bounds__(AT) void aromatic_rings_kernel(dl_aromatic_args a) 
 
     if (n_kept > MAX_KEPT) {                     // uniform over the workgroup: the matrices do not hold this molecule
         int bad = 0;
-        for (int e = tid; e < capacity; e += AT) {
+        for (int e = tid; e < capacity; e += WG) {
             int i, j, order = 0;
-            if (e < nb && !load_bond(list, e, n, i, j, order)) { bad = 1; order = 0; }
+            if (e < nb && !load_bond<3>(list, e, n, i, j, order)) { bad = 1; order = 0; }
             order_out[e] = e < nb ? order : 0;
             bond_aromatic[e] = 0;
         }
-        for (int i = tid; i < N; i += AT) { atom_aromatic[i] = 0; valence_out[i] = 0; }
+        for (int i = tid; i < N; i += WG) { atom_aromatic[i] = 0; valence_out[i] = 0; }
         bad = __syncthreads_or(bad);
         if (tid == 0) {
             a.n_planar_rings[b] = 0;
@@ -221,19 +161,17 @@ __global__ __launch_bounds__(AT) void aromatic_rings_kernel(dl_aromatic_args a) 
 
     const float* xs = a.x + size_t(b) * N * 3;
     const float* hot = a.one_hot + size_t(b) * N * nf;
-    for (int r = r0; r < r1; ++r) {
+    // the numbering loop and, below, the list's length and the pair build stand here in their own text and not as
+    // for_each_real_row, bonds_in and add_pair of mol_graph.h: with those refine_bond_orders measured 0.3 % slower than before
+    // the helpers were shared, and this kernel is the one the time goes to (profiles/mol_graph/README.md)
+    int k = rn.k, kk = rn.kk;
+    for (int r = rows.r0; r < rows.r1; ++r) {
         if (mask[r] == 0.0f) continue;
         const bool kept = !(drop && drop[r] != 0.0f);
         const bool marked = mark && mark[r] != 0.0f;
         s_map[k++] = kept ? (kk | (marked ? MARK : 0)) : -1;
         if (!kept) continue;
-        int type = 0;
-        float top = hot[size_t(r) * nf];
-        for (int t = 1; t < nf; ++t) {
-            const float v = hot[size_t(r) * nf + t];
-            if (v > top) { top = v; type = t; }
-        }
-        const int cls = a.ring_class[type];
+        const int cls = a.ring_class[first_maximum(hot + size_t(r) * nf, nf)];
         s_cls[kk] = cls >= 1 && cls <= 3 ? cls : 0;
         s_mark[kk] = marked;
         s_x[kk * 3] = xs[r * 3];
@@ -254,9 +192,9 @@ __global__ __launch_bounds__(AT) void aromatic_rings_kernel(dl_aromatic_args a) 
 
     // ---- build: the bit matrix over the kept atoms
     int bad = 0, repeated = 0;
-    for (int e = tid; e < nb; e += AT) {
+    for (int e = tid; e < nb; e += WG) {
         int i, j, order;
-        if (!load_bond(list, e, n, i, j, order)) { bad = 1; continue; }
+        if (!load_bond<3>(list, e, n, i, j, order)) { bad = 1; continue; }
         const int mi = s_map[i], mj = s_map[j];
         if ((mi | mj) < 0) continue;                             // an end is dropped: no bond of this graph, and no error
         const int u = mi & 0xFFFF, v = mj & 0xFFFF;
@@ -354,13 +292,13 @@ __global__ __launch_bounds__(AT) void aromatic_rings_kernel(dl_aromatic_args a) 
     if (in_system) atomicAdd(&s_size[s_label[tid]], 1);
 
     // ---- roles
-    for (int e = tid; e < nb; e += AT) {
+    for (int e = tid; e < nb; e += WG) {
         int i, j, order;
-        if (!load_bond(list, e, n, i, j, order) || order < 2) continue;
+        if (!load_bond<3>(list, e, n, i, j, order) || order < 2) continue;
         const int mi = s_map[i], mj = s_map[j];
         if ((mi | mj) < 0) continue;
         const int u = mi & 0xFFFF, v = mj & 0xFFFF;
-        if (bit(s_rb, u, v) || (repeated && !first_of_pair(list, e, n, i, j))) continue;
+        if (bit(s_rb, u, v) || (repeated && seen_before<3>(list, e, n, i, j))) continue;
         atomicOr(&s_exo[u], 1);
         atomicOr(&s_exo[v], 1);
     }
@@ -444,9 +382,9 @@ __global__ __launch_bounds__(AT) void aromatic_rings_kernel(dl_aromatic_args a) 
     __syncthreads();
 
     // ---- write
-    for (int e = tid; e < capacity; e += AT) {
+    for (int e = tid; e < capacity; e += WG) {
         int order = 0, aromatic = 0, i, j;
-        if (e < nb && load_bond(list, e, n, i, j, order)) {
+        if (e < nb && load_bond<3>(list, e, n, i, j, order)) {
             const int mi = s_map[i], mj = s_map[j];
             if ((mi | mj) >= 0) {
                 const int u = mi & 0xFFFF, v = mj & 0xFFFF;
@@ -454,7 +392,7 @@ __global__ __launch_bounds__(AT) void aromatic_rings_kernel(dl_aromatic_args a) 
                     order = s_mate[u] == v ? 2 : 1;
                     aromatic = bit(s_ab, u, v);
                 }
-                if (!repeated || first_of_pair(list, e, n, i, j)) {
+                if (!(repeated && seen_before<3>(list, e, n, i, j))) {
                     atomicAdd(&s_val[u], order);
                     atomicAdd(&s_val[v], order);
                 }
@@ -466,7 +404,7 @@ __global__ __launch_bounds__(AT) void aromatic_rings_kernel(dl_aromatic_args a) 
         bond_aromatic[e] = aromatic;
     }
     __syncthreads();
-    for (int i = tid; i < N; i += AT) {
+    for (int i = tid; i < N; i += WG) {
         int valence = 0, aromatic = 0;
         if (i < n && s_map[i] >= 0) {
             valence = s_val[s_map[i] & 0xFFFF];
@@ -496,7 +434,7 @@ int32_t dl_aromatic_rings(const dl_aromatic_args* a, void* stream) {
         !a->valence_out || !a->n_planar_rings || !a->n_aromatic_rings || !a->n_aromatic_marked || !a->status ||
         (a->capacity > 0 && (!a->bonds || !a->order_out || !a->bond_aromatic)))
         return DL_ERR_BAD_ARG;
-    hipLaunchKernelGGL(aromatic_rings_kernel, dim3(a->B), dim3(AT), 0, static_cast<hipStream_t>(stream), *a);
+    hipLaunchKernelGGL(aromatic_rings_kernel, dim3(a->B), dim3(WG), 0, static_cast<hipStream_t>(stream), *a);
     return hipGetLastError() == hipSuccess ? DL_OK : DL_ERR_HIP;
 }
 

@@ -24,36 +24,12 @@
 //           component whatever the order of the updates: the outputs have the same bits on every run.
 //
 // Global memory is written with plain vector stores only; no global atomics of any kind.
-#include "pack_layout.h"
+#include "workgroup.h"
 
 namespace {
 
-constexpr int BT = 256;                          // threads per molecule
-constexpr int BW = BT / 64;                      // waves
 constexpr int MAX_ATOMS = 1024;
 constexpr int MAX_TYPES = 16;                    // widest one-hot row / table edge
-
-// exclusive prefix sum of one int per thread over the workgroup; returns the total through `total`
-__device__ __forceinline__ int block_exclusive_scan(int v, int* lds /* [BW] */, int& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int up = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += up;
-    }
-    if (lane == 63) lds[w] = incl;
-    __syncthreads();
-    int base = 0, sum = 0;
-#pragma unroll
-    for (int k = 0; k < BW; ++k) {
-        if (k < w) base += lds[k];
-        sum += lds[k];
-    }
-    __syncthreads();
-    total = sum;
-    return base + incl - v;
-}
 
 struct Mol {
     const float *x, *y, *z;
@@ -77,10 +53,10 @@ __device__ __forceinline__ int pair_order(const Mol& m, int i, int j) {
     return order;
 }
 
-__global__ __launch_bounds__(BT) void perceive_bonds_kernel(dl_bonds_args a) {
+__global__ __launch_bounds__(WG) void perceive_bonds_kernel(dl_bonds_args a) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     __shared__ float s_table[MAX_TYPES * MAX_TYPES * 3];
-    __shared__ int s_scan[BW];
+    __shared__ int s_scan[WG_WAVES];
 
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int N = a.N, nf = a.nf;
@@ -92,40 +68,31 @@ __global__ __launch_bounds__(BT) void perceive_bonds_kernel(dl_bonds_args a) {
     int* s_val = s_first + N;
     int* s_label = s_val + N;
 
-    for (int k = tid; k < nf * nf * 3; k += BT) s_table[k] = a.table[k];
+    for (int k = tid; k < nf * nf * 3; k += WG) s_table[k] = a.table[k];
 
-    // ---- stage: compact the real rows (thread t owns the contiguous rows [t * per, t * per + per))
-    const int per = (N + BT - 1) / BT;
-    const int r0 = tid * per, r1 = min(r0 + per, N);
+    // ---- stage: compact the real rows
+    const Rows own = own_rows(N);
+    const int per = own.per, r0 = own.r0;        // the scan below deals the atoms out the same way
     const float* mask = a.node_mask + size_t(b) * N;
-    int mine = 0;
-    for (int r = r0; r < r1; ++r) mine += mask[r] != 0.0f;
     int n = 0;
-    int k = block_exclusive_scan(mine, s_scan, n);
+    int k = block_exclusive_scan(count_rows(own, mask), s_scan, n);
     int bad = 0;
-    for (int r = r0; r < r1; ++r) {
+    for (int r = own.r0; r < own.r1; ++r) {
         if (mask[r] == 0.0f) continue;
         const float* xr = a.x + (size_t(b) * N + r) * 3;
-        const float* hr = a.one_hot + (size_t(b) * N + r) * nf;
         const float px = xr[0], py = xr[1], pz = xr[2];
         bad |= !(isfinite(px) && isfinite(py) && isfinite(pz));
-        int best = 0;
-        float vmax = hr[0];
-        for (int c = 1; c < nf; ++c) {
-            const float v = hr[c];
-            if (v > vmax) { vmax = v; best = c; }
-        }
         s_x[k] = px; s_y[k] = py; s_z[k] = pz;
-        s_type[k] = best;
+        s_type[k] = first_maximum(a.one_hot + (size_t(b) * N + r) * nf, nf);
         ++k;
     }
-    for (int i = tid; i < N; i += BT) { s_first[i] = 0; s_val[i] = 0; s_label[i] = i; }
+    for (int i = tid; i < N; i += WG) { s_first[i] = 0; s_val[i] = 0; s_label[i] = i; }
     bad = __syncthreads_or(bad);
 
     const Mol m{s_x, s_y, s_z, s_type, s_table, nf};
 
     // ---- count: bonds of row i (j < i) and valences
-    for (int i = w; i < n; i += BW) {
+    for (int i = w; i < n; i += WG_WAVES) {
         int cnt = 0, vi = 0;
         for (int j0 = 0; j0 < i; j0 += 64) {
             const int j = j0 + lane;
@@ -144,10 +111,10 @@ __global__ __launch_bounds__(BT) void perceive_bonds_kernel(dl_bonds_args a) {
     __syncthreads();
 
     // ---- scan: first slot of every row
-    int rows[(MAX_ATOMS + BT - 1) / BT];
+    int rows[(MAX_ATOMS + WG - 1) / WG];
     int sum = 0;
 #pragma unroll
-    for (int q = 0; q < (MAX_ATOMS + BT - 1) / BT; ++q) {
+    for (int q = 0; q < (MAX_ATOMS + WG - 1) / WG; ++q) {
         const int r = r0 + q;
         rows[q] = (q < per && r < n) ? s_first[r] : 0;
         sum += rows[q];
@@ -155,7 +122,7 @@ __global__ __launch_bounds__(BT) void perceive_bonds_kernel(dl_bonds_args a) {
     int n_bonds = 0;
     int slot = block_exclusive_scan(sum, s_scan, n_bonds);
 #pragma unroll
-    for (int q = 0; q < (MAX_ATOMS + BT - 1) / BT; ++q) {
+    for (int q = 0; q < (MAX_ATOMS + WG - 1) / WG; ++q) {
         const int r = r0 + q;
         if (q < per && r < n) { s_first[r] = slot; slot += rows[q]; }
     }
@@ -163,7 +130,7 @@ __global__ __launch_bounds__(BT) void perceive_bonds_kernel(dl_bonds_args a) {
 
     // ---- fill: (i, j, order) in row-major order
     int* out = a.bonds + size_t(b) * a.capacity * 3;
-    for (int i = w; i < n; i += BW) {
+    for (int i = w; i < n; i += WG_WAVES) {
         int at = s_first[i];
         for (int j0 = 0; j0 < i; j0 += 64) {
             const int j = j0 + lane;
@@ -178,7 +145,7 @@ __global__ __launch_bounds__(BT) void perceive_bonds_kernel(dl_bonds_args a) {
     // ---- label: smallest atom index of every component
     for (;;) {
         int changed = 0;
-        for (int i = w; i < n; i += BW) {
+        for (int i = w; i < n; i += WG_WAVES) {
             for (int j0 = 0; j0 < i; j0 += 64) {
                 const int j = j0 + lane;
                 if (j < i && pair_order(m, i, j) > 0) {
@@ -191,7 +158,7 @@ __global__ __launch_bounds__(BT) void perceive_bonds_kernel(dl_bonds_args a) {
             }
         }
         __syncthreads();
-        for (int i = tid; i < n; i += BT) {
+        for (int i = tid; i < n; i += WG) {
             const int l = s_label[i], ll = s_label[l];
             if (ll != l) { s_label[i] = ll; changed = 1; }      // ll <= l: concurrent jumps only lower labels further
         }
@@ -199,14 +166,13 @@ __global__ __launch_bounds__(BT) void perceive_bonds_kernel(dl_bonds_args a) {
     }
 
     int roots = 0;
-    for (int i = tid; i < N; i += BT) {
+    for (int i = tid; i < N; i += WG) {
         const bool real = i < n;
         a.valence[size_t(b) * N + i] = real ? s_val[i] : 0;
         a.component[size_t(b) * N + i] = real ? s_label[i] : -1;
         roots += real && s_label[i] == i;
     }
-    int n_comp = 0;
-    block_exclusive_scan(roots, s_scan, n_comp);
+    const int n_comp = block_sum(roots, s_scan);
     if (tid == 0) {
         a.n_bonds[b] = n_bonds;
         a.n_components[b] = n_comp;
@@ -233,7 +199,7 @@ int32_t dl_perceive_bonds(const dl_bonds_args* a, void* stream) {
         !a->status || (a->capacity > 0 && !a->bonds))
         return DL_ERR_BAD_ARG;
     if (a->workspace_bytes < dl_bonds_workspace_bytes(a->B, a->N)) return DL_ERR_BAD_ARG;
-    hipLaunchKernelGGL(perceive_bonds_kernel, dim3(a->B), dim3(BT), lds_bytes(a->N), static_cast<hipStream_t>(stream), *a);
+    hipLaunchKernelGGL(perceive_bonds_kernel, dim3(a->B), dim3(WG), lds_bytes(a->N), static_cast<hipStream_t>(stream), *a);
     return hipGetLastError() == hipSuccess ? DL_OK : DL_ERR_HIP;
 }
 

@@ -32,80 +32,16 @@
 //   write    the thread that owns a row writes its two per-atom outputs, query row or not: every output is written in full.
 //
 // Global memory is written with plain vector stores only; no atomics of any kind, in LDS or in global memory.
-#include <hip/hip_runtime.h>
-#include <cstdint>
-#include "../../include/difflinker_hip.h"
+#include "workgroup.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int CT = 256;                          // threads per molecule
-constexpr int CW = CT / 64;                      // waves
 constexpr int CLASH_MAX_QUERY = 1024;            // four queries per thread at most
-constexpr int QPT_MAX = CLASH_MAX_QUERY / CT;
+constexpr int QPT_MAX = CLASH_MAX_QUERY / WG;
 constexpr int MAX_TYPES = 16;
-constexpr int TILE = CT;                         // targets per LDS tile: one candidate per thread
-
-// exclusive scan of one int per thread over the workgroup; `total` is the sum, the same in every thread
-__device__ __forceinline__ int block_exclusive_scan(int v, int* s_scan /* [CW] */, int& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    if (lane == 63) s_scan[w] = inc;
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int k = 0; k < CW; ++k) {
-        const int s = s_scan[k];
-        if (k < w) before += s;
-        total += s;
-    }
-    __syncthreads();
-    return before + inc - v;
-}
-
-__device__ __forceinline__ int block_sum(int v, int* s_scan /* [CW] */) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if ((threadIdx.x & 63) == 0) s_scan[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int s = 0;
-#pragma unroll
-    for (int k = 0; k < CW; ++k) s += s_scan[k];
-    __syncthreads();
-    return s;
-}
-
-__device__ __forceinline__ float block_min(float v, float* s_min /* [CW] */) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float o = __shfl_xor(v, off, 64);
-        v = o < v ? o : v;
-    }
-    if ((threadIdx.x & 63) == 0) s_min[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float m = s_min[0];
-#pragma unroll
-    for (int k = 1; k < CW; ++k) m = s_min[k] < m ? s_min[k] : m;
-    __syncthreads();
-    return m;
-}
-
-__device__ __forceinline__ int first_maximum(const float* row, int nf) {
-    int best = 0;
-    float vmax = row[0];
-    for (int c = 1; c < nf; ++c) {
-        const float v = row[c];
-        if (v > vmax) { vmax = v; best = c; }
-    }
-    return best;
-}
+constexpr int TILE = WG;                         // targets per LDS tile: one candidate per thread
 
 __device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 
@@ -130,12 +66,12 @@ __device__ __forceinline__ void score_tile(const float4* s_tile, const float* s_
     }
 }
 
-__global__ __launch_bounds__(CT) void clash_scores_kernel(dl_clash_args a) {
+__global__ __launch_bounds__(WG) void clash_scores_kernel(dl_clash_args a) {
     __shared__ float4 s_tile[TILE];
     __shared__ float s_t2[MAX_TYPES * MAX_TYPES];
     __shared__ float4 s_q[CLASH_MAX_QUERY];      // staged queries (x, y, z, type), then the partials: x = clashes, y = contacts, z = minimum
-    __shared__ int s_scan[CW];
-    __shared__ float s_min[CW];
+    __shared__ int s_scan[WG_WAVES];
+    __shared__ float s_min[WG_WAVES];
 
     const int b = blockIdx.x, tid = threadIdx.x;
     const int N = a.N, nf = a.nf;
@@ -146,17 +82,15 @@ __global__ __launch_bounds__(CT) void clash_scores_kernel(dl_clash_args a) {
     const float inf = __builtin_inff(), nan = __builtin_nanf("");
 
     // ---- count and compact the query rows: thread t owns rows [r0, r1)
-    const int per = (N + CT - 1) / CT;
-    const int r0 = min(tid * per, N), r1 = min(r0 + per, N);
-    int mine = 0;
-    for (int r = r0; r < r1; ++r) mine += qmask[r] != 0.0f;
+    const Rows rows = own_rows(N);
+    const int r0 = rows.r0, r1 = rows.r1;
     int nq = 0;
-    const int k0 = block_exclusive_scan(mine, s_scan, nq);
+    const int k0 = block_exclusive_scan(count_rows(rows, qmask), s_scan, nq);
     int status = nq > CLASH_MAX_QUERY ? DL_CLASH_TOO_LARGE : 0;          // uniform over the workgroup
     int n_target = 0;
 
     if (!status) {
-        for (int k = tid; k < MAX_TYPES * MAX_TYPES; k += CT) {          // t2[b * 16 + a] = threshold[a][b]^2, 0 = never
+        for (int k = tid; k < MAX_TYPES * MAX_TYPES; k += WG) {          // t2[b * 16 + a] = threshold[a][b]^2, 0 = never
             const int tb = k / MAX_TYPES, qa = k % MAX_TYPES;
             const float t = (tb < nf && qa < nf) ? a.threshold[qa * nf + tb] : 0.0f;
             s_t2[k] = t > 0.0f ? t * t : 0.0f;                           // d2 >= +0, so `d2 < 0` never holds
@@ -173,14 +107,14 @@ __global__ __launch_bounds__(CT) void clash_scores_kernel(dl_clash_args a) {
 
         // ---- this thread's queries: group g of G, lane ql of Qpad
         int Qpad = 1;
-        while (Qpad < nq && Qpad < CT) Qpad <<= 1;
-        const int G = CT / Qpad, ql = tid & (Qpad - 1), g = tid / Qpad;
-        const bool many = nq > CT;
+        while (Qpad < nq && Qpad < WG) Qpad <<= 1;
+        const int G = WG / Qpad, ql = tid & (Qpad - 1), g = tid / Qpad;
+        const bool many = nq > WG;
         float qx[QPT_MAX], qy[QPT_MAX], qz[QPT_MAX], mn[QPT_MAX];
         int qa[QPT_MAX], cnt[QPT_MAX], con[QPT_MAX];
 #pragma unroll
         for (int q = 0; q < QPT_MAX; ++q) {
-            const int kq = ql + q * CT;
+            const int kq = ql + q * WG;
             const bool have = kq < nq && (q == 0 || many);
             const float4 v = have ? s_q[kq] : make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
             qx[q] = v.x; qy[q] = v.y; qz[q] = v.z; qa[q] = __float_as_int(v.w);
@@ -224,9 +158,9 @@ __global__ __launch_bounds__(CT) void clash_scores_kernel(dl_clash_args a) {
         // ---- the groups' partials of every query meet: slot q * 256 + tid is this thread's own
 #pragma unroll
         for (int q = 0; q < QPT_MAX; ++q)
-            s_q[q * CT + tid] = make_float4(__int_as_float(cnt[q]), __int_as_float(con[q]), mn[q], 0.0f);
+            s_q[q * WG + tid] = make_float4(__int_as_float(cnt[q]), __int_as_float(con[q]), mn[q], 0.0f);
         __syncthreads();
-        for (int kq = tid; kq < nq; kq += CT) {                          // with G > 1, nq <= Qpad: column kq is this thread's alone
+        for (int kq = tid; kq < nq; kq += WG) {                          // with G > 1, nq <= Qpad: column kq is this thread's alone
             float4 sum = s_q[kq];
             int c = __float_as_int(sum.x), n = __float_as_int(sum.y);
             for (int gg = 1; gg < G; ++gg) {
@@ -291,7 +225,7 @@ int32_t dl_clash_scores(const dl_clash_args* a, void* stream) {
         !a->n_clash_atoms || !a->n_contacts || !a->min_dist2 || !a->status || !a->atom_clashes || !a->atom_min_dist2 ||
         (a->M > 0 && (!a->target_x || !a->target_type)))
         return DL_ERR_BAD_ARG;
-    hipLaunchKernelGGL(clash_scores_kernel, dim3(a->B), dim3(CT), 0, static_cast<hipStream_t>(stream), *a);
+    hipLaunchKernelGGL(clash_scores_kernel, dim3(a->B), dim3(WG), 0, static_cast<hipStream_t>(stream), *a);
     return hipGetLastError() == hipSuccess ? DL_OK : DL_ERR_HIP;
 }
 

@@ -30,40 +30,29 @@ constexpr int FP_MAX_TYPES = 16;
 constexpr int FP_MAX_WORDS = 64;                 // 2048 bits
 constexpr int FP_KEEP = 1 << 8, FP_CENTRE = 1 << 9;              // s_tk: type | flags
 
-__global__ __launch_bounds__(KT) void fingerprints_kernel(dl_fingerprint_args a) {
+__global__ __launch_bounds__(WG) void fingerprints_kernel(dl_fingerprint_args a) {
     __shared__ u64 s_col[FP_ROWS];
     __shared__ u64 s_sum[FP_ROWS];
     __shared__ int s_tk[FP_ROWS];
     __shared__ unsigned s_bits[FP_MAX_WORDS];
-    __shared__ int s_scan[KW];
+    __shared__ int s_scan[WG_WAVES];
 
     const int b = blockIdx.x, tid = threadIdx.x;
     const int N = a.N, nf = a.nf, W = a.n_bits / 32;
 
-    // ---- stage: number the real rows (thread t owns the contiguous rows [t * per, t * per + per))
-    const int per = (N + KT - 1) / KT;
-    const int r0 = min(tid * per, N), r1 = min(r0 + per, N);
+    // ---- stage: number the real rows
+    const Rows rows = own_rows(N);
     const float* mask = a.node_mask + size_t(b) * N;
     const float* drop = a.drop_mask ? a.drop_mask + size_t(b) * N : nullptr;
     const float* centre = a.centre_mask ? a.centre_mask + size_t(b) * N : nullptr;
-    int mine = 0, mine_kept = 0, mine_centres = 0;
-    for (int r = r0; r < r1; ++r) {
-        if (mask[r] == 0.0f) continue;
-        ++mine;
-        const bool kept = !(drop && drop[r] != 0.0f);
-        mine_kept += kept;
-        mine_centres += kept && !(centre && centre[r] == 0.0f);
-    }
-    int n = 0;
-    int k = block_exclusive_scan(mine, s_scan, n);
-    const int n_kept = block_sum(mine_kept, s_scan);
-    const int n_centres = block_sum(mine_centres, s_scan);
-    const int n_in = a.n_bonds_in[b];
-    const int status_in = a.status_in[b] | (n_in > a.capacity ? DL_BONDS_OVERFLOW : 0);
+    const RowNumbers rn = number_rows(rows, mask, drop, s_scan);
+    const int n = rn.n, n_kept = rn.n_kept;
+    const BondsIn in = bonds_in(a.n_bonds_in, a.status_in, b, a.capacity);
+    const int status_in = in.status, nb = in.nb;
     uint32_t* bits = a.bits + size_t(b) * W;
 
     if (n_kept > DL_FP_MAX_ATOMS) {              // uniform over the workgroup; the list is not looked at
-        for (int w = tid; w < W; w += KT) bits[w] = 0;
+        for (int w = tid; w < W; w += WG) bits[w] = 0;
         if (tid == 0) {
             a.n_on[b] = 0;
             a.n_atoms[b] = n_kept;
@@ -73,58 +62,50 @@ __global__ __launch_bounds__(KT) void fingerprints_kernel(dl_fingerprint_args a)
         return;
     }
 
-    for (int r = r0; r < r1; ++r) {
-        if (mask[r] == 0.0f) continue;
-        const float* hr = a.one_hot + (size_t(b) * N + r) * nf;
-        int best = 0;
-        float vmax = hr[0];
-        for (int c = 1; c < nf; ++c) {
-            const float v = hr[c];
-            if (v > vmax) { vmax = v; best = c; }
-        }
-        const bool kept = !(drop && drop[r] != 0.0f);
-        s_tk[k] = best | (kept ? FP_KEEP : 0) | (kept && !(centre && centre[r] == 0.0f) ? FP_CENTRE : 0);
-        ++k;
-    }
+    int mine_centres = 0;
+    for_each_real_row(rows, mask, drop, rn, [&](int r, int k, bool kept, int) {
+        const bool is_centre = kept && !(centre && centre[r] == 0.0f);
+        s_tk[k] = first_maximum(a.one_hot + (size_t(b) * N + r) * nf, nf) | (kept ? FP_KEEP : 0) | (is_centre ? FP_CENTRE : 0);
+        mine_centres += is_centre;
+    });
     if (tid < FP_MAX_WORDS) s_bits[tid] = 0;
-    __syncthreads();
-    for (int i = tid; i < n; i += KT) {
+    const int n_centres = block_sum(mine_centres, s_scan);       // its barriers also publish s_tk and the cleared bit row
+    for (int i = tid; i < n; i += WG) {
         s_col[i] = (s_tk[i] & FP_KEEP) ? mix2(SEED_COLOUR, u64((s_tk[i] & 0xFF) + 1)) : 0;
         s_sum[i] = 0;
     }
     __syncthreads();
 
-    const int nb = min(max(n_in, 0), a.capacity);
     const int* list = a.bonds + size_t(b) * a.capacity * 3;      // never dereferenced when nb is 0
     const unsigned bit_mask = unsigned(a.n_bits) - 1;            // n_bits is a power of two
     int bad = 0;
     Bond bd;
     for (int r = 0;; ++r) {
-        for (int i = tid; i < n; i += KT)
+        for (int i = tid; i < n; i += WG)
             if (s_tk[i] & FP_CENTRE) {
                 const unsigned bit = unsigned(s_col[i]) & bit_mask;
                 atomicOr(&s_bits[bit >> 5], 1u << (bit & 31));
             }
         if (r == a.radius) break;
-        for (int e = tid; e < nb; e += KT) {
+        for (int e = tid; e < nb; e += WG) {
             if (!load_bond(list, e, n, bd, bad) || !(s_tk[bd.i] & s_tk[bd.j] & FP_KEEP)) continue;
-            atomicAdd(reinterpret_cast<unsigned long long*>(&s_sum[bd.i]), (unsigned long long)mix2(s_col[bd.j], u64(bd.order)));
-            atomicAdd(reinterpret_cast<unsigned long long*>(&s_sum[bd.j]), (unsigned long long)mix2(s_col[bd.i], u64(bd.order)));
+            atomicAdd(&s_sum[bd.i], mix2(s_col[bd.j], u64(bd.order)));
+            atomicAdd(&s_sum[bd.j], mix2(s_col[bd.i], u64(bd.order)));
         }
         __syncthreads();
-        for (int i = tid; i < n; i += KT) {
+        for (int i = tid; i < n; i += WG) {
             if (s_tk[i] & FP_KEEP) s_col[i] = mix2(s_col[i], s_sum[i]);
             s_sum[i] = 0;
         }
         __syncthreads();
     }
     if (a.radius == 0) {                         // no round has looked at the list: one pass for the status bit alone
-        for (int e = tid; e < nb; e += KT) load_bond(list, e, n, bd, bad);
+        for (int e = tid; e < nb; e += WG) load_bond(list, e, n, bd, bad);
     }
     bad = __syncthreads_or(bad);                 // also orders the ORs of the last round before the reads below
 
     int on = 0;
-    for (int w = tid; w < W; w += KT) {
+    for (int w = tid; w < W; w += WG) {
         const unsigned v = s_bits[w];
         bits[w] = v;
         on += __popc(v);
@@ -272,7 +253,7 @@ int32_t dl_fingerprints(const dl_fingerprint_args* a) {
     if (!a->one_hot || !a->node_mask || !a->n_bonds_in || !a->status_in || !a->bits || !a->n_on || !a->n_atoms || !a->n_centres ||
         !a->status || (a->capacity > 0 && !a->bonds))
         return DL_ERR_BAD_ARG;
-    hipLaunchKernelGGL(fingerprints_kernel, dim3(a->B), dim3(KT), 0, static_cast<hipStream_t>(a->stream), *a);
+    hipLaunchKernelGGL(fingerprints_kernel, dim3(a->B), dim3(WG), 0, static_cast<hipStream_t>(a->stream), *a);
     return hipGetLastError() == hipSuccess ? DL_OK : DL_ERR_HIP;
 }
 

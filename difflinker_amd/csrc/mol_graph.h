@@ -1,15 +1,17 @@
 // mol_graph.h — what the kernels that read a perceived bond list with 256 threads per molecule share (mol_keys.hip,
-// fingerprint.hip): the 64-bit mixing function of the colour refinement, the workgroup scan that numbers the real rows, and
-// the test that says whether a list entry is a bond.  The definitions are quoted in include/difflinker_hip.h.
+// fingerprint.hip, rings.hip, aromatic.hip), on top of workgroup.h: the 64-bit mixing function of the colour
+// refinement, the test that says whether a list entry is a bond, the list's length and overflow bit, the numbering of the real
+// and of the kept rows, and the 256 x 256 bit matrix in LDS with its breadth-first search.  Small functions that each kernel
+// calls in its own order; what a kernel counts and flags around them is its own and is specified in include/difflinker_hip.h.
+// fragment.hip is to use them too and still carries its own copies of the scan, load_bond, seen_before, bit_in_word, has and
+// search: with the shared ones its star enumeration measured 3 to 7 % slower although its text is the same, so it waits
+// until that is understood (profiles/mol_graph/README.md).
 #pragma once
-#include "pack_layout.h"
+#include "workgroup.h"
 
 namespace {
 
-using u64 = uint64_t;
-
-constexpr int KT = 256;                          // threads per molecule
-constexpr int KW = KT / 64;                      // waves
+using u64 = unsigned long long;                  // the 64-bit type the LDS atomics take; uint64_t outputs convert by value
 
 constexpr u64 SEED_COLOUR = 0x243F6A8885A308D3ull, SEED_KEY = 0x13198A2E03707344ull, MIX_B = 0xD6E8FEB86659FD93ull;
 
@@ -21,46 +23,156 @@ __device__ __forceinline__ u64 mix64(u64 z) {
 }
 __device__ __forceinline__ u64 mix2(u64 a, u64 b) { return mix64(a + b * MIX_B); }
 
-// exclusive prefix sum of one int per thread over the workgroup; returns the total through `total`
-__device__ __forceinline__ int block_exclusive_scan(int v, int* lds /* [KW] */, int& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int up = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += up;
-    }
-    if (lane == 63) lds[w] = incl;
-    __syncthreads();
-    int base = 0, sum = 0;
-#pragma unroll
-    for (int k = 0; k < KW; ++k) {
-        if (k < w) base += lds[k];
-        sum += lds[k];
-    }
-    __syncthreads();
-    total = sum;
-    return base + incl - v;
-}
-
-__device__ __forceinline__ int block_sum(int v, int* lds) {
-    int total = 0;
-    block_exclusive_scan(v, lds, total);
-    return total;
+// ---- the bond list ------------------------------------------------------------------------------------------------------------
+// entry e of the list: a bond of this molecule (0 <= i, j < n, i != j, 1 <= order <= MAX_ORDER)?  MAX_ORDER is 3 wherever the
+// list is what dl_perceive_bonds wrote, whose orders are 1..3.  fragment.hip's rule is 4 (its own copy today): it cuts the
+// molecules of a data set, read from files in which 4 marks an aromatic bond - a bond of the graph, never cuttable, no bad entry
+template <int MAX_ORDER>
+__device__ __forceinline__ bool load_bond(const int* list, int e, int n, int& i, int& j, int& order) {
+    i = list[e * 3];
+    j = list[e * 3 + 1];
+    order = list[e * 3 + 2];
+    return i >= 0 && j >= 0 && i < n && j < n && i != j && order >= 1 && order <= MAX_ORDER;
 }
 
 struct Bond {
     int i, j, order;
 };
 
-// entry e of the list: a bond of this molecule (0 <= i, j < n, i != j, order 1..3)?  `bad` collects the entries that are not.
+// the same for a list of dl_perceive_bonds; `bad` collects the entries that are no bond
 __device__ __forceinline__ bool load_bond(const int* list, int e, int n, Bond& bd, int& bad) {
-    bd.i = list[e * 3];
-    bd.j = list[e * 3 + 1];
-    bd.order = list[e * 3 + 2];
-    const bool ok = bd.i >= 0 && bd.j >= 0 && bd.i < n && bd.j < n && bd.i != bd.j && bd.order >= 1 && bd.order <= 3;
+    const bool ok = load_bond<3>(list, e, n, bd.i, bd.j, bd.order);
     bad |= !ok;
     return ok;
+}
+
+// does an entry before e hold the pair (i, j), in either orientation?  "The first entry of a repeated pair" needs list order,
+// which the bit matrix does not keep; this walks the list, so ask only when the build saw a repeated pair somewhere
+template <int MAX_ORDER>
+__device__ __forceinline__ bool seen_before(const int* list, int e, int n, int i, int j) {
+    for (int f = 0; f < e; ++f) {
+        int fi, fj, forder;
+        if (load_bond<MAX_ORDER>(list, f, n, fi, fj, forder) && ((fi == i && fj == j) || (fi == j && fj == i))) return true;
+    }
+    return false;
+}
+
+// How much of molecule b's list is read: n_bonds_in clamped to [0, capacity] (a negative count is 0).  `status` is the
+// incoming status (status_in may be null: none) with DL_BONDS_OVERFLOW when the list was cut short at its capacity
+struct BondsIn {
+    int nb, status;
+};
+
+__device__ __forceinline__ BondsIn bonds_in(const int* n_bonds_in, const int* status_in, int b, int capacity) {
+    const int given = n_bonds_in[b];
+    return {min(max(given, 0), capacity), (status_in ? status_in[b] : 0) | (given > capacity ? DL_BONDS_OVERFLOW : 0)};
+}
+
+// ---- atoms ----------------------------------------------------------------------------------------------------------------------
+// Atom k is the k-th row with node_mask != 0 (as bonds.hip numbers them); drop_mask (may be null) removes atoms after that
+// numbering, and the kept atoms are numbered among themselves.  number_rows counts this thread's rows and scans the counts:
+// n and n_kept are the molecule's, k and kk the numbers of this thread's first real and first kept row.  for_each_real_row
+// then calls f(r, k, kept, kk) for every real row r of the thread, where each kernel stages its own payload
+struct RowNumbers {
+    int n, n_kept, k, kk;
+};
+
+__device__ __forceinline__ RowNumbers number_rows(const Rows& rows, const float* mask, const float* drop, int* lds /* [WG_WAVES] */) {
+    int mine = 0, mine_kept = 0;
+    for (int r = rows.r0; r < rows.r1; ++r) {
+        if (mask[r] == 0.0f) continue;
+        ++mine;
+        mine_kept += !(drop && drop[r] != 0.0f);
+    }
+    RowNumbers s;
+    s.k = block_exclusive_scan(mine, lds, s.n);
+    s.kk = block_exclusive_scan(mine_kept, lds, s.n_kept);
+    return s;
+}
+
+template <class F>
+__device__ __forceinline__ void for_each_real_row(const Rows& rows, const float* mask, const float* drop, const RowNumbers& s, F&& f) {
+    int k = s.k, kk = s.kk;
+    for (int r = rows.r0; r < rows.r1; ++r) {
+        if (mask[r] == 0.0f) continue;
+        const bool kept = !(drop && drop[r] != 0.0f);
+        f(r, k, kept, kk);
+        ++k;
+        kk += kept;
+    }
+}
+
+// ---- the bit matrix -------------------------------------------------------------------------------------------------------------
+// A graph of at most MATRIX_ATOMS atoms as MATRIX_ATOMS rows of MATRIX_WORDS 64-bit words in LDS: bit v of row u is the pair
+// (u, v).  One thread per atom clears or reads a row, hence MATRIX_ATOMS == WG
+constexpr int MATRIX_ATOMS = 256, MATRIX_WORDS = MATRIX_ATOMS / 64;
+static_assert(MATRIX_ATOMS == WG && MATRIX_WORDS == 4, "one thread per atom, four words per row");
+static_assert(DL_RINGS_MAX_ATOMS == MATRIX_ATOMS && DL_AROM_MAX_ATOMS == MATRIX_ATOMS && DL_FRAG_MAX_ATOMS == MATRIX_ATOMS,
+              "the limits the header promises are the matrix's");
+
+__device__ __forceinline__ u64 bit_in_word(int atom, int w) { return (atom >> 6) == w ? 1ull << (atom & 63) : 0ull; }
+
+// is `atom` in the set (one row of a matrix, or any MATRIX_WORDS words)?
+__device__ __forceinline__ bool has(const u64* set, int atom) { return (set[atom >> 6] >> (atom & 63)) & 1ull; }
+
+__device__ __forceinline__ bool bit(const u64* m, int u, int v) { return has(m + u * MATRIX_WORDS, v); }
+
+__device__ __forceinline__ void set_pair(u64* m, int u, int v) {
+    atomicOr(&m[u * MATRIX_WORDS + (v >> 6)], 1ull << (v & 63));
+    atomicOr(&m[v * MATRIX_WORDS + (u >> 6)], 1ull << (u & 63));
+}
+
+// set_pair for the build from a list: returns whether the pair was not there yet.  atomicOr returns the old value, so exactly
+// one entry of each distinct pair sees it unset, whatever the order the atomics land in and whichever orientation an entry has
+// (the bit that decides is always the one in the smaller atom's row)
+__device__ __forceinline__ bool add_pair(u64* adj, int u, int v) {
+    const int lo = min(u, v), hi = max(u, v);
+    const u64 one = 1ull << (hi & 63);
+    const u64 old = atomicOr(&adj[lo * MATRIX_WORDS + (hi >> 6)], one);
+    atomicOr(&adj[hi * MATRIX_WORDS + (lo >> 6)], 1ull << (lo & 63));
+    return !(old & one);
+}
+
+// Breadth-first search from u over the matrix, level-synchronous, frontier and visited set in registers.  `masked` (or -1)
+// is taken out of u's row at level 0 only: the bond (u, masked) can be walked nowhere else, because u is visited from the
+// start.  Ends when a level contains `target` (returns its distance in bonds from u) or is empty (returns -1: visited[] is
+// then everything that can be reached).  target must not be u: u is in no frontier, so the search would never meet it
+// (rings.hip passes the two ends of a bond, which differ).  Reads the matrix only: no other lane matters
+__device__ __forceinline__ int search(const u64* adj, int u, int masked, int target, u64 (&visited)[MATRIX_WORDS]) {
+    u64 frontier[MATRIX_WORDS], goal[MATRIX_WORDS];
+#pragma unroll
+    for (int w = 0; w < MATRIX_WORDS; ++w) {
+        goal[w] = bit_in_word(target, w);
+        frontier[w] = adj[u * MATRIX_WORDS + w] & ~bit_in_word(masked, w);
+        visited[w] = frontier[w] | bit_in_word(u, w);
+    }
+    for (int level = 1; level <= MATRIX_ATOMS; ++level) {        // frontier = the atoms `level` bonds from u
+        u64 hit = 0, any = 0;
+#pragma unroll
+        for (int w = 0; w < MATRIX_WORDS; ++w) {
+            hit |= frontier[w] & goal[w];
+            any |= frontier[w];
+        }
+        if (hit) return level;
+        if (!any) return -1;
+        u64 next[MATRIX_WORDS] = {0, 0, 0, 0};
+#pragma unroll
+        for (int w = 0; w < MATRIX_WORDS; ++w) {
+            u64 f = frontier[w];
+            while (f) {
+                const u64* row = adj + (w * 64 + __builtin_ctzll(f)) * MATRIX_WORDS;
+                f &= f - 1;
+#pragma unroll
+                for (int q = 0; q < MATRIX_WORDS; ++q) next[q] |= row[q];
+            }
+        }
+#pragma unroll
+        for (int w = 0; w < MATRIX_WORDS; ++w) {
+            frontier[w] = next[w] & ~visited[w];
+            visited[w] |= frontier[w];
+        }
+    }
+    return -1;                                                   // not reached: every level adds an atom or ends the search
 }
 
 }  // namespace

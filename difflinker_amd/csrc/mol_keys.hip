@@ -23,7 +23,7 @@
 // is left of 60 KiB (1024 atoms: 7168 entries, 3.5 bonds per atom; 292 atoms: 12 per atom).  A molecule beyond either limit
 // gets DL_KEYS_TOO_LARGE and a zero key.
 //
-//   stage   real rows compacted in row order (the scan of bonds.hip); type = first maximum of the one-hot row
+//   stage   real rows compacted in row order (number_rows of mol_graph.h); type = first maximum of the one-hot row
 //   count   one thread per list entry: degree and valence of both atoms by integer LDS adds (one packed word)
 //   label   with drop_mask only: min-label propagation and pointer jumping as in bonds.hip, over the list instead of over
 //           all pairs; without it n_components is taken as given
@@ -42,11 +42,11 @@ constexpr size_t LDS_BUDGET = 60 * 1024;         // dynamic LDS; the static arra
 
 constexpr int KEEP = 1 << 8;                     // s_tk: type | KEEP
 
-__global__ __launch_bounds__(KT) void molecule_keys_kernel(dl_mol_keys_args a, int atoms_lds, int adj_cap) {
+__global__ __launch_bounds__(WG) void molecule_keys_kernel(dl_mol_keys_args a, int atoms_lds, int adj_cap) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
-    __shared__ int s_scan[KW];
+    __shared__ int s_scan[WG_WAVES];
     __shared__ int s_maxval[MAX_TYPES];
-    __shared__ u64 s_part[KT];
+    __shared__ u64 s_part[WG];
 
     const int b = blockIdx.x, tid = threadIdx.x;
     const int N = a.N, nf = a.nf;
@@ -60,25 +60,17 @@ __global__ __launch_bounds__(KT) void molecule_keys_kernel(dl_mol_keys_args a, i
 
     if (tid < nf) s_maxval[tid] = a.max_valence[tid];
 
-    // ---- stage: compact the real rows (thread t owns the contiguous rows [t * per, t * per + per))
-    const int per = (N + KT - 1) / KT;
-    const int r0 = min(tid * per, N), r1 = min(r0 + per, N);
+    // ---- stage: compact the real rows
+    const Rows rows = own_rows(N);
     const float* mask = a.node_mask + size_t(b) * N;
     const float* drop = a.drop_mask ? a.drop_mask + size_t(b) * N : nullptr;
-    int mine = 0, mine_kept = 0;
-    for (int r = r0; r < r1; ++r) {
-        if (mask[r] == 0.0f) continue;
-        ++mine;
-        mine_kept += !(drop && drop[r] != 0.0f);
-    }
-    int n = 0;
-    int k = block_exclusive_scan(mine, s_scan, n);
-    const int n_kept = block_sum(mine_kept, s_scan);
+    const RowNumbers rn = number_rows(rows, mask, drop, s_scan);
+    const int n = rn.n, n_kept = rn.n_kept;
     const int status_in = a.status_in[b];
     uint64_t* colour = a.colour + size_t(b) * N;
 
     if (n > MAX_ATOMS) {                         // uniform over the workgroup: nothing below fits
-        for (int i = tid; i < N; i += KT) colour[i] = 0;
+        for (int i = tid; i < N; i += WG) colour[i] = 0;
         if (tid == 0) {
             a.n_atoms[b] = n_kept;
             a.n_over[b] = 0;
@@ -90,27 +82,18 @@ __global__ __launch_bounds__(KT) void molecule_keys_kernel(dl_mol_keys_args a, i
         return;
     }
 
-    for (int r = r0; r < r1; ++r) {
-        if (mask[r] == 0.0f) continue;
-        const float* hr = a.one_hot + (size_t(b) * N + r) * nf;
-        int best = 0;
-        float vmax = hr[0];
-        for (int c = 1; c < nf; ++c) {
-            const float v = hr[c];
-            if (v > vmax) { vmax = v; best = c; }
-        }
-        s_tk[k] = best | ((drop && drop[r] != 0.0f) ? 0 : KEEP);
-        ++k;
-    }
-    for (int i = tid; i < n; i += KT) { s_dv[i] = 0; s_label[i] = i; }
+    for_each_real_row(rows, mask, drop, rn, [&](int r, int k, bool kept, int) {
+        s_tk[k] = first_maximum(a.one_hot + (size_t(b) * N + r) * nf, nf) | (kept ? KEEP : 0);
+    });
+    for (int i = tid; i < n; i += WG) { s_dv[i] = 0; s_label[i] = i; }
     __syncthreads();
 
     // ---- count: degree and valence over the kept bonds
-    const int nb = min(max(a.n_bonds_in[b], 0), a.capacity);
+    const int nb = bonds_in(a.n_bonds_in, nullptr, b, a.capacity).nb;   // status_in passes through as it is: no overflow bit here
     const int* list = a.bonds + size_t(b) * a.capacity * 3;
     int bad = 0, mine_bonds = 0;
     Bond bd;
-    for (int e = tid; e < nb; e += KT) {
+    for (int e = tid; e < nb; e += WG) {
         if (!load_bond(list, e, n, bd, bad) || !(s_tk[bd.i] & s_tk[bd.j] & KEEP)) continue;
         atomicAdd(&s_dv[bd.i], 1 | (bd.order << 16));
         atomicAdd(&s_dv[bd.j], 1 | (bd.order << 16));
@@ -124,7 +107,7 @@ __global__ __launch_bounds__(KT) void molecule_keys_kernel(dl_mol_keys_args a, i
     if (drop) {
         for (;;) {
             int changed = 0, unused = 0;
-            for (int e = tid; e < nb; e += KT) {
+            for (int e = tid; e < nb; e += WG) {
                 if (!load_bond(list, e, n, bd, unused) || !(s_tk[bd.i] & s_tk[bd.j] & KEEP)) continue;
                 const int li = s_label[bd.i], lj = s_label[bd.j];
                 if (li != lj) {
@@ -133,14 +116,14 @@ __global__ __launch_bounds__(KT) void molecule_keys_kernel(dl_mol_keys_args a, i
                 }
             }
             __syncthreads();
-            for (int i = tid; i < n; i += KT) {
+            for (int i = tid; i < n; i += WG) {
                 const int l = s_label[i], ll = s_label[l];
                 if (ll != l) { s_label[i] = ll; changed = 1; }      // ll <= l: concurrent jumps only lower labels further
             }
             if (!__syncthreads_or(changed)) break;
         }
         int roots = 0;
-        for (int i = tid; i < n; i += KT) roots += (s_tk[i] & KEEP) && s_label[i] == i;
+        for (int i = tid; i < n; i += WG) roots += (s_tk[i] & KEEP) && s_label[i] == i;
         n_comp = block_sum(roots, s_scan);
     } else {
         n_comp = a.n_components_in[b];
@@ -148,7 +131,7 @@ __global__ __launch_bounds__(KT) void molecule_keys_kernel(dl_mol_keys_args a, i
 
     // ---- valence rule: with every atom kept the valence of bonds.hip holds (also for a list its capacity cut short)
     int over = 0;
-    for (int i = tid; i < n; i += KT) {
+    for (int i = tid; i < n; i += WG) {
         if (!(s_tk[i] & KEEP)) continue;
         const int v = drop ? (s_dv[i] >> 16) : a.valence_in[size_t(b) * N + i];
         over += v > s_maxval[s_tk[i] & 0xFF];
@@ -156,7 +139,7 @@ __global__ __launch_bounds__(KT) void molecule_keys_kernel(dl_mol_keys_args a, i
     const int n_over = block_sum(over, s_scan);
 
     // ---- scan: CSR row starts (thread t owns the contiguous atoms [t * pa, t * pa + pa))
-    const int pa = (n + KT - 1) / KT;
+    const int pa = (n + WG - 1) / WG;
     const int a0 = tid * pa;
     int sum = 0;
     for (int q = 0; q < pa; ++q)
@@ -174,13 +157,13 @@ __global__ __launch_bounds__(KT) void molecule_keys_kernel(dl_mol_keys_args a, i
     if (!too_large) {
         // ---- fill: the slot of an entry is the row's cursor; the order inside a row is free, the rounds only sum over it
         int unused = 0;
-        for (int e = tid; e < nb; e += KT) {
+        for (int e = tid; e < nb; e += WG) {
             if (!load_bond(list, e, n, bd, unused) || !(s_tk[bd.i] & s_tk[bd.j] & KEEP)) continue;
             const int pi = atomicAdd(&s_end[bd.i], 1), pj = atomicAdd(&s_end[bd.j], 1);
             if (pi < n_adj) s_adj[pi] = bd.j | (bd.order << 10);
             if (pj < n_adj) s_adj[pj] = bd.i | (bd.order << 10);
         }
-        for (int i = tid; i < n; i += KT) {
+        for (int i = tid; i < n; i += WG) {
             cur[i] = (s_tk[i] & KEEP) ? mix2(SEED_COLOUR, u64((s_tk[i] & 0xFF) + 1)) : 0;
             nxt[i] = 0;
         }
@@ -188,7 +171,7 @@ __global__ __launch_bounds__(KT) void molecule_keys_kernel(dl_mol_keys_args a, i
 
         // ---- rounds: n_kept of them, one gather per atom
         for (int r = 0; r < n_kept; ++r) {
-            for (int i = tid; i < n; i += KT) {
+            for (int i = tid; i < n; i += WG) {
                 if (!(s_tk[i] & KEEP)) continue;
                 const int lo = i ? s_end[i - 1] : 0, hi = min(s_end[i], n_adj);
                 u64 s = 0;
@@ -203,18 +186,18 @@ __global__ __launch_bounds__(KT) void molecule_keys_kernel(dl_mol_keys_args a, i
         }
 
         u64 part = 0;
-        for (int i = tid; i < n; i += KT)
+        for (int i = tid; i < n; i += WG)
             if (s_tk[i] & KEEP) part += mix64(cur[i]);
         s_part[tid] = part;
         __syncthreads();
         if (tid == 0) {
             u64 total = 0;
-            for (int t = 0; t < KT; ++t) total += s_part[t];
+            for (int t = 0; t < WG; ++t) total += s_part[t];
             key = mix2(mix2(mix2(SEED_KEY, u64(n_kept)), u64(n_bonds)), total);
         }
     }
 
-    for (int i = tid; i < N; i += KT) colour[i] = (i < n && !too_large) ? cur[i] : 0;
+    for (int i = tid; i < N; i += WG) colour[i] = (i < n && !too_large) ? cur[i] : 0;
     if (tid == 0) {
         a.n_atoms[b] = n_kept;
         a.n_over[b] = n_over;
@@ -243,7 +226,7 @@ int32_t dl_molecule_keys(const dl_mol_keys_args* a, void* stream) {
     const long long want = 2 * (a->capacity < pairs ? (long long)a->capacity : pairs);
     const long long room = (long long)((LDS_BUDGET - atom_bytes) / 4);
     const int adj_cap = int(want < room ? want : room);
-    hipLaunchKernelGGL(molecule_keys_kernel, dim3(a->B), dim3(KT), atom_bytes + size_t(adj_cap) * 4, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(molecule_keys_kernel, dim3(a->B), dim3(WG), atom_bytes + size_t(adj_cap) * 4, static_cast<hipStream_t>(stream),
                        *a, atoms_lds, adj_cap);
     return hipGetLastError() == hipSuccess ? DL_OK : DL_ERR_HIP;
 }

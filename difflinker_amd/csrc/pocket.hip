@@ -29,54 +29,21 @@
 //
 // LDS: 6 KiB ligand + 4 KiB bitset, static.  Global memory is written with plain vector stores only; no global atomics; every
 // output element is written on every launch.
-#include <hip/hip_runtime.h>
-#include <cstdint>
-#include "../../include/difflinker_hip.h"
+#include "workgroup.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int PT = 256;                          // threads per pair
-constexpr int PW = PT / 64;                      // waves
 constexpr int MAX_LIGAND = DL_POCKET_MAX_LIGAND;
 constexpr int MAX_GROUPS = DL_POCKET_MAX_GROUPS;
 constexpr int SET_WORDS = MAX_GROUPS / 32;
-static_assert(MAX_LIGAND == PT && SET_WORDS % PT == 0, "one staged ligand atom per thread, whole words of the set per thread");
+static_assert(MAX_LIGAND == WG && SET_WORDS % WG == 0, "one staged ligand atom per thread, whole words of the set per thread");
 
-// exclusive prefix sum of one int per thread over the workgroup; `total` is the sum, the same in every thread
-__device__ __forceinline__ int block_exclusive_scan(int v, int* s_scan /* [PW] */, int& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    if (lane == 63) s_scan[w] = inc;
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int k = 0; k < PW; ++k) {
-        const int s = s_scan[k];
-        if (k < w) before += s;
-        total += s;
-    }
-    __syncthreads();
-    return before + inc - v;
-}
-
-__device__ __forceinline__ int block_sum(int v, int* s_scan /* [PW] */) {
-    int total = 0;
-    block_exclusive_scan(v, s_scan, total);
-    return total;
-}
-
-__global__ __launch_bounds__(PT) void pocket_select_kernel(dl_pocket_args a) {
+__global__ __launch_bounds__(WG) void pocket_select_kernel(dl_pocket_args a) {
     __shared__ double s_lig[MAX_LIGAND * 3];
     __shared__ unsigned int s_set[SET_WORDS];
-    __shared__ int s_scan[PW];
+    __shared__ int s_scan[WG_WAVES];
 
     const int b = blockIdx.x, tid = threadIdx.x;
     const int L = a.L, Mmax = a.Mmax, R = a.capacity;
@@ -84,13 +51,11 @@ __global__ __launch_bounds__(PT) void pocket_select_kernel(dl_pocket_args a) {
     int* index = a.index + size_t(b) * R;                       // never written when R == 0
 
     // ---- stage: count the real ligand rows (thread t owns the rows [r0, r1))
-    const int per = (L + PT - 1) / PT;
-    const int r0 = min(tid * per, L), r1 = min(r0 + per, L);
+    const Rows rows = own_rows(L);
+    const int r0 = rows.r0, r1 = rows.r1;
     const float* mask = a.ligand_mask + size_t(b) * L;          // never read when L == 0
-    int mine = 0;
-    for (int r = r0; r < r1; ++r) mine += mask[r] != 0.0f;
     int n_ligand = 0;
-    int k = block_exclusive_scan(mine, s_scan, n_ligand);
+    int k = block_exclusive_scan(count_rows(rows, mask), s_scan, n_ligand);
 
     // which atoms are this pair's: every access below stays inside [0, M_total) and inside the row of `member`
     const int p = a.pair_protein[b];
@@ -121,14 +86,14 @@ __global__ __launch_bounds__(PT) void pocket_select_kernel(dl_pocket_args a) {
             ++k;
         }
 #pragma unroll
-        for (int w = 0; w < SET_WORDS / PT; ++w) s_set[w * PT + tid] = 0u;
+        for (int w = 0; w < SET_WORDS / WG; ++w) s_set[w * WG + tid] = 0u;
         __syncthreads();
 
         // ---- pass 1: contact atoms and the groups they select
         const double c2 = a.cutoff * a.cutoff;
         const float* px = a.protein_x + size_t(first) * 3;
         const int* group = a.protein_group + first;
-        for (int j = tid; j < M; j += PT) {
+        for (int j = tid; j < M; j += WG) {
             const float fx = px[3 * size_t(j)], fy = px[3 * size_t(j) + 1], fz = px[3 * size_t(j) + 2];
             const int g = group[j];
             const bool finite = isfinite(fx) && isfinite(fy) && isfinite(fz), known = g >= 0 && g < MAX_GROUPS;
@@ -152,18 +117,18 @@ __global__ __launch_bounds__(PT) void pocket_select_kernel(dl_pocket_args a) {
     }
 
     if (status) {                                // ---- dead outputs
-        for (int j = tid; j < Mmax; j += PT) member[j] = 0;
-        for (int q = tid; q < R; q += PT) index[q] = -1;
+        for (int j = tid; j < Mmax; j += WG) member[j] = 0;
+        for (int q = tid; q < R; q += WG) index[q] = -1;
         n_contact = 0;
     } else {
         n_contact = block_sum(n_contact, s_scan);
 #pragma unroll
-        for (int w = 0; w < SET_WORDS / PT; ++w) n_groups += __popc(s_set[w * PT + tid]);
+        for (int w = 0; w < SET_WORDS / WG; ++w) n_groups += __popc(s_set[w * WG + tid]);
         n_groups = block_sum(n_groups, s_scan);
 
         // ---- pass 2: pocket atoms, numbered in file order (uniform trip count: the scan has barriers)
         const int* group = a.protein_group + first;
-        for (int j0 = 0; j0 < M; j0 += PT) {
+        for (int j0 = 0; j0 < M; j0 += WG) {
             const int j = j0 + tid;
             int pocket = 0;
             if (j < M) {
@@ -176,8 +141,8 @@ __global__ __launch_bounds__(PT) void pocket_select_kernel(dl_pocket_args a) {
             if (pocket && slot < R) index[slot] = j;
             n_pocket += tile;
         }
-        for (int j = M + tid; j < Mmax; j += PT) member[j] = 0;
-        for (int q = min(n_pocket, R) + tid; q < R; q += PT) index[q] = -1;
+        for (int j = M + tid; j < Mmax; j += WG) member[j] = 0;
+        for (int q = min(n_pocket, R) + tid; q < R; q += WG) index[q] = -1;
         if (n_pocket > R) status |= DL_POCKET_TRUNCATED;
     }
     if (tid == 0) {
@@ -201,7 +166,7 @@ int32_t dl_pocket_select(const dl_pocket_args* a, void* stream) {
         !a->status || (a->M_total > 0 && (!a->protein_x || !a->protein_group)) || (a->L > 0 && (!a->ligand_x || !a->ligand_mask)) ||
         (a->Mmax > 0 && !a->member) || (a->capacity > 0 && !a->index))
         return DL_ERR_BAD_ARG;
-    hipLaunchKernelGGL(pocket_select_kernel, dim3(a->B), dim3(PT), 0, static_cast<hipStream_t>(stream), *a);
+    hipLaunchKernelGGL(pocket_select_kernel, dim3(a->B), dim3(WG), 0, static_cast<hipStream_t>(stream), *a);
     return hipGetLastError() == hipSuccess ? DL_OK : DL_ERR_HIP;
 }
 

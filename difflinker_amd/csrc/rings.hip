@@ -3,7 +3,7 @@
 // reference asks of RDKit's ring perception (compute_metrics.py:128-145, CalcNumRings of the linker) asked of the graph.
 //
 // One 256-thread workgroup per molecule, one launch per batch, reading what dl_perceive_bonds wrote for the same batch, with
-// the conventions of mol_keys.hip: atom k is the k-th row with node_mask != 0; drop_mask removes atoms after that numbering
+// the conventions of mol_graph.h: atom k is the k-th row with node_mask != 0; drop_mask removes atoms after that numbering
 // together with every bond that touches them; an entry (i, j, order) is a bond when 0 <= i, j < atoms, i != j and
 // 1 <= order <= 3, in either orientation; anything else is skipped and sets DL_RINGS_BAD_BOND.  mark_mask marks atoms (the
 // callers pass the linker): the second histogram row counts the bonds with a marked end.
@@ -11,7 +11,7 @@
 // At most DL_RINGS_MAX_ATOMS = 256 KEPT atoms (N itself may be 1024: pocket rows are dropped, not counted).  The graph over
 // the kept atoms is a 256 x 256 bit matrix in LDS, four 64-bit words per row.
 //
-//   stage   real rows ranked in row order (the scan of mol_keys.hip), kept rows ranked among themselves; s_map[atom] is the
+//   stage   real rows ranked in row order (number_rows of mol_graph.h), kept rows ranked among themselves; s_map[atom] is the
 //           kept index | MARK, or -1 for a dropped atom
 //   build   one thread per list entry: LDS atomicOr of bit (lo, hi) and bit (hi, lo).  The old value of the first says
 //           whether the pair was there already: exactly one entry of each distinct pair sees it unset, whatever the order, so
@@ -28,136 +28,47 @@
 // LDS: 8 KiB matrix + 4 KiB map + 2 KiB labels and per-atom minima + the histograms: 14.4 KiB, static.  Rows are 32 bytes, so
 // lanes that read different rows of one 256-byte bank row at once conflict; nothing here pads against it.
 // Global memory is written with plain vector stores only; no global atomics of any kind; every output element is written.
-#include "pack_layout.h"
+#include "mol_graph.h"
 
 namespace {
 
-using u64 = unsigned long long;
-
-constexpr int RT = 256;                          // threads per molecule
-constexpr int RW = RT / 64;                      // waves
 constexpr int MAX_ROWS = 1024;                   // N, as for dl_perceive_bonds
-constexpr int MAX_KEPT = DL_RINGS_MAX_ATOMS;
-constexpr int WORDS = MAX_KEPT / 64;             // 64-bit words per row of the matrix
+constexpr int MAX_KEPT = MATRIX_ATOMS;           // DL_RINGS_MAX_ATOMS
+constexpr int WORDS = MATRIX_WORDS;              // 64-bit words per row of the matrix
 constexpr int BINS = DL_RING_BINS;
 constexpr int MARK = 1 << 16;                    // s_map: kept index | MARK
 constexpr int NO_RING = 0x7fffffff;
-constexpr int BONDS_OVERFLOW = 1;                // DL_BONDS_OVERFLOW of dl_bonds_args.status
-static_assert(MAX_KEPT == RT && WORDS == 4, "one thread per kept atom, four words per row");
-
-// exclusive prefix sum of one int per thread over the workgroup; returns the total through `total`
-__device__ __forceinline__ int block_exclusive_scan(int v, int* lds /* [RW] */, int& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int up = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += up;
-    }
-    if (lane == 63) lds[w] = incl;
-    __syncthreads();
-    int base = 0, sum = 0;
-#pragma unroll
-    for (int k = 0; k < RW; ++k) {
-        if (k < w) base += lds[k];
-        sum += lds[k];
-    }
-    __syncthreads();
-    total = sum;
-    return base + incl - v;
-}
-
-__device__ __forceinline__ int block_sum(int v, int* lds) {
-    int total = 0;
-    block_exclusive_scan(v, lds, total);
-    return total;
-}
-
-// entry e of the list: a bond of this molecule (0 <= i, j < n, i != j, order 1..3)?
-__device__ __forceinline__ bool load_bond(const int* list, int e, int n, int& i, int& j) {
-    i = list[e * 3];
-    j = list[e * 3 + 1];
-    const int order = list[e * 3 + 2];
-    return i >= 0 && j >= 0 && i < n && j < n && i != j && order >= 1 && order <= 3;
-}
-
-__device__ __forceinline__ u64 bit_in_word(int atom, int w) { return (atom >> 6) == w ? 1ull << (atom & 63) : 0ull; }
-
-// atoms of the smallest cycle through the bond (u, v) of the matrix, 0 when the bond is a bridge
-__device__ __forceinline__ int smallest_ring(const u64* adj, int u, int v) {
-    u64 frontier[WORDS], visited[WORDS], target[WORDS];
-#pragma unroll
-    for (int w = 0; w < WORDS; ++w) {
-        target[w] = bit_in_word(v, w);
-        frontier[w] = adj[u * WORDS + w] & ~target[w];          // level 1 without the bond itself
-        visited[w] = frontier[w] | bit_in_word(u, w);
-    }
-    for (int level = 1; level < MAX_KEPT; ++level) {             // frontier = the atoms `level` bonds from u
-        u64 next[WORDS] = {0, 0, 0, 0};
-#pragma unroll
-        for (int w = 0; w < WORDS; ++w) {
-            u64 f = frontier[w];
-            while (f) {
-                const u64* row = adj + (w * 64 + __builtin_ctzll(f)) * WORDS;
-                f &= f - 1;
-#pragma unroll
-                for (int q = 0; q < WORDS; ++q) next[q] |= row[q];
-            }
-        }
-        u64 hit = 0, any = 0;
-#pragma unroll
-        for (int w = 0; w < WORDS; ++w) {
-            next[w] &= ~visited[w];
-            hit |= next[w] & target[w];
-            any |= next[w];
-            visited[w] |= next[w];
-            frontier[w] = next[w];
-        }
-        if (hit) return level + 2;                               // v is level + 1 bonds from u: that path and the bond
-        if (!any) return 0;
-    }
-    return 0;                                                    // not reached: every level adds an atom or ends the search
-}
 
 __device__ __forceinline__ int ring_bin(int ring) { return ring == 0 ? 0 : (ring <= 7 ? ring - 2 : BINS - 1); }
 
-__global__ __launch_bounds__(RT) void ring_scores_kernel(dl_rings_args a) {
+__global__ __launch_bounds__(WG) void ring_scores_kernel(dl_rings_args a) {
     __shared__ __align__(16) u64 s_adj[MAX_KEPT * WORDS];
     __shared__ int s_map[MAX_ROWS];
     __shared__ int s_label[MAX_KEPT];
     __shared__ int s_min[MAX_KEPT];
     __shared__ int s_hist[2 * BINS];
-    __shared__ int s_scan[RW];
+    __shared__ int s_scan[WG_WAVES];
 
     const int b = blockIdx.x, tid = threadIdx.x;
     const int N = a.N, capacity = a.capacity;
 
-    // ---- stage: rank the real rows, and the kept rows among themselves (thread t owns the rows [t * per, t * per + per))
-    const int per = (N + RT - 1) / RT;
-    const int r0 = min(tid * per, N), r1 = min(r0 + per, N);
+    // ---- stage: rank the real rows, and the kept rows among themselves
+    const Rows rows = own_rows(N);
     const float* mask = a.node_mask + size_t(b) * N;
     const float* drop = a.drop_mask ? a.drop_mask + size_t(b) * N : nullptr;
     const float* mark = a.mark_mask ? a.mark_mask + size_t(b) * N : nullptr;
-    int mine = 0, mine_kept = 0;
-    for (int r = r0; r < r1; ++r) {
-        if (mask[r] == 0.0f) continue;
-        ++mine;
-        mine_kept += !(drop && drop[r] != 0.0f);
-    }
-    int n = 0, n_kept = 0;
-    int k = block_exclusive_scan(mine, s_scan, n);
-    int kk = block_exclusive_scan(mine_kept, s_scan, n_kept);
+    const RowNumbers rn = number_rows(rows, mask, drop, s_scan);
+    const int n = rn.n, n_kept = rn.n_kept;
 
-    const int given = a.n_bonds_in[b];
-    const int nb = min(max(given, 0), capacity);
-    const int status_in = a.status_in[b] | (given > capacity ? BONDS_OVERFLOW : 0);
+    const BondsIn in = bonds_in(a.n_bonds_in, a.status_in, b, capacity);
+    const int nb = in.nb, status_in = in.status;
     int* bond_ring = a.bond_ring + size_t(b) * capacity;
     int* atom_ring = a.atom_ring + size_t(b) * N;
     int* hist = a.ring_hist + size_t(b) * 2 * BINS;
 
     if (n_kept > MAX_KEPT) {                     // uniform over the workgroup: the matrix does not hold this molecule
-        for (int e = tid; e < capacity; e += RT) bond_ring[e] = 0;
-        for (int i = tid; i < N; i += RT) atom_ring[i] = 0;
+        for (int e = tid; e < capacity; e += WG) bond_ring[e] = 0;
+        for (int i = tid; i < N; i += WG) atom_ring[i] = 0;
         if (tid < 2 * BINS) hist[tid] = 0;
         if (tid == 0) {
             a.n_atoms[b] = n_kept;
@@ -169,12 +80,9 @@ __global__ __launch_bounds__(RT) void ring_scores_kernel(dl_rings_args a) {
         return;
     }
 
-    for (int r = r0; r < r1; ++r) {
-        if (mask[r] == 0.0f) continue;
-        const bool kept = !(drop && drop[r] != 0.0f);
-        s_map[k++] = kept ? (kk | ((mark && mark[r] != 0.0f) ? MARK : 0)) : -1;
-        kk += kept;
-    }
+    for_each_real_row(rows, mask, drop, rn, [&](int r, int k, bool kept, int kk) {
+        s_map[k] = kept ? (kk | ((mark && mark[r] != 0.0f) ? MARK : 0)) : -1;
+    });
 #pragma unroll
     for (int w = 0; w < WORDS; ++w) s_adj[tid * WORDS + w] = 0;
     s_label[tid] = tid;
@@ -185,18 +93,13 @@ __global__ __launch_bounds__(RT) void ring_scores_kernel(dl_rings_args a) {
     // ---- build: the bit matrix over the kept atoms
     const int* list = a.bonds + size_t(b) * capacity * 3;       // never read when nb == 0
     int bad = 0, mine_bonds = 0;
-    for (int e = tid; e < nb; e += RT) {
-        int i, j;
-        if (!load_bond(list, e, n, i, j)) { bad = 1; continue; }
+    for (int e = tid; e < nb; e += WG) {
+        int i, j, order;
+        if (!load_bond<3>(list, e, n, i, j, order)) { bad = 1; continue; }
         const int mi = s_map[i], mj = s_map[j];
         if ((mi | mj) < 0) continue;                             // an end is dropped: no bond of this graph, and no error
-        const int u = mi & 0xFFFF, v = mj & 0xFFFF;
-        const int lo = min(u, v), hi = max(u, v);
-        const u64 bit = 1ull << (hi & 63);
-        const u64 old = atomicOr(&s_adj[lo * WORDS + (hi >> 6)], bit);
-        atomicOr(&s_adj[hi * WORDS + (lo >> 6)], 1ull << (lo & 63));
-        if (old & bit) bad = 1;                                  // the pair a second time
-        else ++mine_bonds;
+        if (add_pair(s_adj, mi & 0xFFFF, mj & 0xFFFF)) ++mine_bonds;
+        else bad = 1;                                            // the pair a second time
     }
     bad = __syncthreads_or(bad);
     const int n_bonds = block_sum(mine_bonds, s_scan);
@@ -227,13 +130,15 @@ __global__ __launch_bounds__(RT) void ring_scores_kernel(dl_rings_args a) {
     const int n_comp = block_sum(atom && s_label[tid] == tid, s_scan);
 
     // ---- search: the smallest ring through every bond of the list
-    for (int e = tid; e < capacity; e += RT) {
-        int ring = 0, i, j;
-        if (e < nb && load_bond(list, e, n, i, j)) {
+    for (int e = tid; e < capacity; e += WG) {
+        int ring = 0, i, j, order;
+        if (e < nb && load_bond<3>(list, e, n, i, j, order)) {
             const int mi = s_map[i], mj = s_map[j];
             if ((mi | mj) >= 0) {
                 const int u = mi & 0xFFFF, v = mj & 0xFFFF;
-                ring = smallest_ring(s_adj, u, v);
+                u64 visited[WORDS];
+                const int d = search(s_adj, u, v, v, visited);   // v is d bonds from u without the bond itself
+                ring = d < 0 ? 0 : d + 1;                        // that path and the bond; a bridge: 0
                 const int bin = ring_bin(ring);
                 atomicAdd(&s_hist[bin], 1);
                 if ((mi | mj) & MARK) atomicAdd(&s_hist[BINS + bin], 1);
@@ -247,7 +152,7 @@ __global__ __launch_bounds__(RT) void ring_scores_kernel(dl_rings_args a) {
     }
     __syncthreads();
 
-    for (int i = tid; i < N; i += RT) {
+    for (int i = tid; i < N; i += WG) {
         int ring = 0;
         if (i < n && s_map[i] >= 0) {
             const int least = s_min[s_map[i] & 0xFFFF];
@@ -275,7 +180,7 @@ int32_t dl_ring_scores(const dl_rings_args* a, void* stream) {
     if (!a->node_mask || !a->n_bonds_in || !a->status_in || !a->n_atoms || !a->n_bonds || !a->n_components || !a->n_rings ||
         !a->atom_ring || !a->ring_hist || !a->status || (a->capacity > 0 && (!a->bonds || !a->bond_ring)))
         return DL_ERR_BAD_ARG;
-    hipLaunchKernelGGL(ring_scores_kernel, dim3(a->B), dim3(RT), 0, static_cast<hipStream_t>(stream), *a);
+    hipLaunchKernelGGL(ring_scores_kernel, dim3(a->B), dim3(WG), 0, static_cast<hipStream_t>(stream), *a);
     return hipGetLastError() == hipSuccess ? DL_OK : DL_ERR_HIP;
 }
 

@@ -30,12 +30,10 @@
 //
 // Global memory is written with plain vector stores only; no global atomics of any kind.
 #include <climits>
-#include "pack_layout.h"
+#include "workgroup.h"
 
 namespace {
 
-constexpr int RT = 256;                          // threads per pair
-constexpr int RW = RT / 64;                      // waves
 constexpr int RMSD_MAX_ATOMS = 1024;             // 2 x 16 bytes of LDS per atom: 32 KiB
 constexpr int RED_DOUBLES = 16;                  // LDS scratch behind the coordinates: 4 wave partials, 4 wave indices, 9 of R
 constexpr int MAX_SWEEPS = 16;                   // cyclic Jacobi on a symmetric 4x4 settles in 5 to 7
@@ -47,13 +45,13 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 
 // sum of one double per thread over the workgroup, the same value in every thread; the order of the additions is fixed
-__device__ __forceinline__ double block_sum(double v, double* red /* [RW] */) {
+__device__ __forceinline__ double block_sum(double v, double* red /* [WG_WAVES] */) {
     v = wave_sum(v);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
     double s = 0.0;
 #pragma unroll
-    for (int w = 0; w < RW; ++w) s += red[w];
+    for (int w = 0; w < WG_WAVES; ++w) s += red[w];
     __syncthreads();
     return s;
 }
@@ -132,13 +130,13 @@ __device__ __forceinline__ int jacobi4(double A[4][4], double V[4][4], double& l
     return top;
 }
 
-__global__ __launch_bounds__(RT) void best_rmsd_kernel(dl_rmsd_args a, int atoms_lds) {
+__global__ __launch_bounds__(WG) void best_rmsd_kernel(dl_rmsd_args a, int atoms_lds) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     float4* s_a = reinterpret_cast<float4*>(lds_raw);
     float4* s_b = s_a + atoms_lds;
-    double* s_red = reinterpret_cast<double*>(s_b + atoms_lds);      // [RW]
-    int* s_idx = reinterpret_cast<int*>(s_red + RW);                 // [RW] (two doubles' room)
-    double* s_rot = s_red + RW + 2;                                  // [9]
+    double* s_red = reinterpret_cast<double*>(s_b + atoms_lds);      // [WG_WAVES]
+    int* s_idx = reinterpret_cast<int*>(s_red + WG_WAVES);           // [WG_WAVES] (two doubles' room)
+    double* s_rot = s_red + WG_WAVES + 2;                            // [9]
 
     const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int n = a.n_atoms[p];
@@ -161,7 +159,7 @@ __global__ __launch_bounds__(RT) void best_rmsd_kernel(dl_rmsd_args a, int atoms
     const float* xb = a.xb + size_t(p) * a.n_max * 3;
     double sum[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     int bad = 0;
-    for (int k = tid; k < n; k += RT) {
+    for (int k = tid; k < n; k += WG) {
         const float4 va = make_float4(xa[3 * k], xa[3 * k + 1], xa[3 * k + 2], 0.0f);
         const float4 vb = make_float4(xb[3 * k], xb[3 * k + 1], xb[3 * k + 2], 0.0f);
         bad |= !(isfinite(va.x) && isfinite(va.y) && isfinite(va.z) && isfinite(vb.x) && isfinite(vb.y) && isfinite(vb.z));
@@ -184,7 +182,7 @@ __global__ __launch_bounds__(RT) void best_rmsd_kernel(dl_rmsd_args a, int atoms
 
     // ---- centre (each thread its own atoms again), Ga + Gb of the values as stored
     double g = 0.0;
-    for (int k = tid; k < n; k += RT) {
+    for (int k = tid; k < n; k += WG) {
         float4 va = s_a[k], vb = s_b[k];
         va.x = float(double(va.x) - centre[0]); va.y = float(double(va.y) - centre[1]); va.z = float(double(va.z) - centre[2]);
         vb.x = float(double(vb.x) - centre[3]); vb.y = float(double(vb.y) - centre[4]); vb.z = float(double(vb.z) - centre[5]);
@@ -199,7 +197,7 @@ __global__ __launch_bounds__(RT) void best_rmsd_kernel(dl_rmsd_args a, int atoms
     const uint16_t* tab = a.maps + size_t(first) * a.n_max;
     double best = __builtin_inf(), best_S[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     int best_j = INT_MAX;
-    for (int j = tid; j < m; j += RT) {
+    for (int j = tid; j < m; j += WG) {
         double S[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         const uint16_t* col = tab + j;
 #pragma unroll 4
@@ -238,7 +236,7 @@ __global__ __launch_bounds__(RT) void best_rmsd_kernel(dl_rmsd_args a, int atoms
     rv = s_red[0];
     rj = s_idx[0];
 #pragma unroll
-    for (int k = 1; k < RW; ++k) {
+    for (int k = 1; k < WG_WAVES; ++k) {
         const double ov = s_red[k];
         const int oj = s_idx[k];
         if (ov < rv || (ov == rv && oj < rj)) { rv = ov; rj = oj; }
@@ -254,7 +252,7 @@ __global__ __launch_bounds__(RT) void best_rmsd_kernel(dl_rmsd_args a, int atoms
     }
 
     // ---- winner: the rotation from the eigenvector, then the residual itself
-    if (tid == rj % RT) {
+    if (tid == rj % WG) {
         double N[4][4], V[4][4];
         horn_matrix(best_S, N);
         double lambda;
@@ -281,7 +279,7 @@ __global__ __launch_bounds__(RT) void best_rmsd_kernel(dl_rmsd_args a, int atoms
     for (int c = 0; c < 9; ++c) R[c] = s_rot[c];
     const uint16_t* col = tab + rj;
     double res = 0.0;
-    for (int k = tid; k < n; k += RT) {
+    for (int k = tid; k < n; k += WG) {
         const int image = min(int(col[size_t(k) * m]), n - 1);
         const float4 va = s_a[k], vb = s_b[image];
         const double ax = va.x, ay = va.y, az = va.z;
@@ -310,7 +308,7 @@ int32_t dl_best_rmsd(const dl_rmsd_args* a, void* stream) {
         return DL_ERR_BAD_ARG;
     const int atoms_lds = a->n_max < RMSD_MAX_ATOMS ? a->n_max : RMSD_MAX_ATOMS;
     const size_t lds = size_t(atoms_lds) * 2 * sizeof(float4) + RED_DOUBLES * sizeof(double);
-    hipLaunchKernelGGL(best_rmsd_kernel, dim3(a->P), dim3(RT), lds, static_cast<hipStream_t>(stream), *a, atoms_lds);
+    hipLaunchKernelGGL(best_rmsd_kernel, dim3(a->P), dim3(WG), lds, static_cast<hipStream_t>(stream), *a, atoms_lds);
     return hipGetLastError() == hipSuccess ? DL_OK : DL_ERR_HIP;
 }
 

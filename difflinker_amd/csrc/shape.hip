@@ -34,16 +34,12 @@
 // before LDS is touched: a table outside what the host wrapper admits (r2 not finite or above 400) can give wrong sums, never
 // a write outside the planes.  Global memory is written with plain vector stores only, no global atomics; every output
 // element is written; nothing is allocated.
-#include <hip/hip_runtime.h>
-#include <cstdint>
-#include "../../include/difflinker_hip.h"
+#include "workgroup.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int ST = 256;                          // threads per pair
-constexpr int SW = ST / 64;                      // waves
 constexpr int MAX_TYPES = 16;
 constexpr int BR = 32;                           // points per brick edge: one word of a plane holds a row along x
 constexpr int PLANE = BR * BR;                   // words per plane
@@ -51,66 +47,10 @@ constexpr int E_MAX = 41;                        // reach of an atom in lattice 
 constexpr float COORD_MAX = 4096.0f;
 constexpr int EXTENT_MAX = 240;
 
-__device__ __forceinline__ int block_exclusive_scan(int v, int* s_scan /* [SW] */, int& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    if (lane == 63) s_scan[w] = inc;
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int k = 0; k < SW; ++k) {
-        const int s = s_scan[k];
-        if (k < w) before += s;
-        total += s;
-    }
-    __syncthreads();
-    return before + inc - v;
-}
-
-__device__ __forceinline__ int block_sum(int v, int* s_scan /* [SW] */) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if ((threadIdx.x & 63) == 0) s_scan[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int s = 0;
-#pragma unroll
-    for (int k = 0; k < SW; ++k) s += s_scan[k];
-    __syncthreads();
-    return s;
-}
-
-__device__ __forceinline__ int block_min(int v, int* s_scan) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, 64));
-    if ((threadIdx.x & 63) == 0) s_scan[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int s = s_scan[0];
-#pragma unroll
-    for (int k = 1; k < SW; ++k) s = min(s, s_scan[k]);
-    __syncthreads();
-    return s;
-}
-
-__device__ __forceinline__ int first_maximum(const float* row, int nf) {
-    int best = 0;
-    float vmax = row[0];
-    for (int c = 1; c < nf; ++c) {
-        const float v = row[c];
-        if (v > vmax) { vmax = v; best = c; }
-    }
-    return best;
-}
-
 // the participating rows of one molecule: counts them, ORs the two coordinate flags, widens the lattice extent
 __device__ __forceinline__ void look(const float* x, const float* mask, int n_rows, int& count, int& nonfinite, int& far,
                                      int (&lo)[3], int (&hi)[3]) {
-    for (int r = threadIdx.x; r < n_rows; r += ST) {
+    for (int r = threadIdx.x; r < n_rows; r += WG) {
         if (mask[r] == 0.0f) continue;
         ++count;
 #pragma unroll
@@ -125,11 +65,11 @@ __device__ __forceinline__ void look(const float* x, const float* mask, int n_ro
     }
 }
 
-__global__ __launch_bounds__(ST) void shape_scores_kernel(dl_shape_args a) {
+__global__ __launch_bounds__(WG) void shape_scores_kernel(dl_shape_args a) {
     __shared__ uint32_t s_plane[6 * PLANE];      // [molecule * 3 + (level - 1)][z][y], bit x
-    __shared__ float4 s_atom[ST];                // the chunk's atoms that reach the brick: x, y, z, type
+    __shared__ float4 s_atom[WG];                // the chunk's atoms that reach the brick: x, y, z, type
     __shared__ float s_r2[MAX_TYPES * 4];        // r2[t][0..2], and their largest
-    __shared__ int s_scan[SW];
+    __shared__ int s_scan[WG_WAVES];
 
     const int b = blockIdx.x, tid = threadIdx.x;
     const int nf = a.nf;
@@ -142,7 +82,7 @@ __global__ __launch_bounds__(ST) void shape_scores_kernel(dl_shape_args a) {
     int lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {-INT32_MAX, -INT32_MAX, -INT32_MAX};
     look(xa, ma, a.Na, n_a, nonfinite, far, lo, hi);
     look(xb, mb, a.Nb, n_b, nonfinite, far, lo, hi);
-    for (int k = tid; k < MAX_TYPES * 4; k += ST) {
+    for (int k = tid; k < MAX_TYPES * 4; k += WG) {
         const int t = k >> 2, c = k & 3;
         float v = 0.0f;
         if (t < nf) {
@@ -177,7 +117,7 @@ __global__ __launch_bounds__(ST) void shape_scores_kernel(dl_shape_args a) {
 #pragma unroll
         for (int d = 0; d < 3; ++d) nb[d] = (hi[d] + 2 + E - o[d]) / BR + 1;
 
-        for (int k = tid; k < 6 * PLANE; k += ST) s_plane[k] = 0u;
+        for (int k = tid; k < 6 * PLANE; k += WG) s_plane[k] = 0u;
         __syncthreads();
 
         for (int bz = 0; bz < nb[2]; ++bz)
@@ -189,7 +129,7 @@ __global__ __launch_bounds__(ST) void shape_scores_kernel(dl_shape_args a) {
                 uint32_t* plane = s_plane + m * 3 * PLANE;
                 const float* xm = m ? xb : xa, * hm = m ? hb : ha, * mm = m ? mb : ma;
                 const int n_rows = m ? a.Nb : a.Na;
-                for (int r0 = 0; r0 < n_rows; r0 += ST) {
+                for (int r0 = 0; r0 < n_rows; r0 += WG) {
                     // ---- this chunk's rows that take part and reach the brick, compacted
                     const int r = r0 + tid;
                     float4 atom = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -212,7 +152,7 @@ __global__ __launch_bounds__(ST) void shape_scores_kernel(dl_shape_args a) {
 
                     // ---- the columns of these atoms' cubes: item = (atom, z, y), y fastest
                     const int items = n_here * D * D;
-                    for (int w = tid; w < items; w += ST) {
+                    for (int w = tid; w < items; w += WG) {
                         const int at = w / (D * D), rem = w - at * (D * D);
                         const int kk = rem / D, jj = rem - kk * D;
                         const float4 q = s_atom[at];
@@ -245,7 +185,7 @@ __global__ __launch_bounds__(ST) void shape_scores_kernel(dl_shape_args a) {
             __syncthreads();                                             // every OR of this brick has landed
             if (!touched) continue;                                      // uniform; the planes are still clear
             // ---- count the brick and clear it for the next
-            for (int w = tid; w < PLANE; w += ST) {
+            for (int w = tid; w < PLANE; w += WG) {
                 const uint32_t a1 = s_plane[w], a2 = s_plane[PLANE + w], a3 = s_plane[2 * PLANE + w];
                 const uint32_t b1 = s_plane[3 * PLANE + w], b2 = s_plane[4 * PLANE + w], b3 = s_plane[5 * PLANE + w];
                 vol_a += __popc(a1) + __popc(a2) + __popc(a3);
@@ -290,7 +230,7 @@ int32_t dl_shape_scores(const dl_shape_args* a, void* stream) {
     if (!a->x_a || !a->one_hot_a || !a->mask_a || !a->x_b || !a->one_hot_b || !a->mask_b || !a->r2 || !a->vol_a || !a->vol_b ||
         !a->vol_min || !a->core_a || !a->core_b || !a->core_both || !a->n_a || !a->n_b || !a->status)
         return DL_ERR_BAD_ARG;
-    hipLaunchKernelGGL(shape_scores_kernel, dim3(a->B), dim3(ST), 0, static_cast<hipStream_t>(stream), *a);
+    hipLaunchKernelGGL(shape_scores_kernel, dim3(a->B), dim3(WG), 0, static_cast<hipStream_t>(stream), *a);
     return hipGetLastError() == hipSuccess ? DL_OK : DL_ERR_HIP;
 }
 

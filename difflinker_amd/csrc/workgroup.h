@@ -1,0 +1,114 @@
+// workgroup.h — what every analysis kernel with one 256-thread workgroup per molecule (or pair) needs: the workgroup size, the
+// scan and the reductions over one value per thread, the atom type of a one-hot row, and the rule that says which rows of a
+// molecule a thread owns.  mol_graph.h adds what the kernels that read a bond list share.
+//
+// THE WORKGROUP FUNCTIONS (block_*) take `lds`, one word per wave (WG_WAVES words) of LDS that they alone use while they
+// run; each has two barriers, the second after its last read of `lds`, so the same words can serve the next call at once;
+// and each may only be called from uniform control flow: every thread of the workgroup calls it, or none.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include "../../include/difflinker_hip.h"
+
+namespace {
+
+constexpr int WG = 256;                          // threads per workgroup
+constexpr int WG_WAVES = WG / 64;                // waves
+
+// exclusive prefix sum of one int per thread over the workgroup; `total` is the sum, the same in every thread
+__device__ __forceinline__ int block_exclusive_scan(int v, int* lds /* [WG_WAVES] */, int& total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int incl = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int up = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += up;
+    }
+    if (lane == 63) lds[w] = incl;
+    __syncthreads();
+    int base = 0, sum = 0;
+#pragma unroll
+    for (int k = 0; k < WG_WAVES; ++k) {
+        if (k < w) base += lds[k];
+        sum += lds[k];
+    }
+    __syncthreads();
+    total = sum;
+    return base + incl - v;
+}
+
+// sum of one int per thread over the workgroup, the same in every thread (a butterfly: fewer shuffles than the scan)
+__device__ __forceinline__ int block_sum(int v, int* lds /* [WG_WAVES] */) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int s = 0;
+#pragma unroll
+    for (int k = 0; k < WG_WAVES; ++k) s += lds[k];
+    __syncthreads();
+    return s;
+}
+
+// minimum of one int per thread over the workgroup, the same in every thread
+__device__ __forceinline__ int block_min(int v, int* lds /* [WG_WAVES] */) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, 64));
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int s = lds[0];
+#pragma unroll
+    for (int k = 1; k < WG_WAVES; ++k) s = min(s, lds[k]);
+    __syncthreads();
+    return s;
+}
+
+// the same for floats.  `o < v ? o : v` and no fminf: the comparison decides what a NaN does (it never wins against the
+// value a thread holds), and clash.hip's contract for non-finite coordinates is written against exactly this
+__device__ __forceinline__ float block_min(float v, float* lds /* [WG_WAVES] */) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float o = __shfl_xor(v, off, 64);
+        v = o < v ? o : v;
+    }
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float m = lds[0];
+#pragma unroll
+    for (int k = 1; k < WG_WAVES; ++k) m = lds[k] < m ? lds[k] : m;
+    __syncthreads();
+    return m;
+}
+
+// the atom type of a one-hot row: the index of its FIRST largest entry (include/difflinker_hip.h quotes this rule for every
+// entry point that reads one_hot)
+__device__ __forceinline__ int first_maximum(const float* row, int nf) {
+    int best = 0;
+    float vmax = row[0];
+    for (int c = 1; c < nf; ++c) {
+        const float v = row[c];
+        if (v > vmax) { vmax = v; best = c; }
+    }
+    return best;
+}
+
+// Thread t owns the contiguous rows [t * per, t * per + per) of a molecule's n_rows, per = ceil(n_rows / WG), cut off at
+// n_rows: rows in row order fall to threads in thread order, so a scan over the threads' counts numbers them in row order
+struct Rows {
+    int per, r0, r1;
+};
+
+__device__ __forceinline__ Rows own_rows(int n_rows) {
+    const int per = (n_rows + WG - 1) / WG;
+    const int r0 = min(int(threadIdx.x) * per, n_rows);
+    return {per, r0, min(r0 + per, n_rows)};
+}
+
+// how many of this thread's rows have mask != 0
+__device__ __forceinline__ int count_rows(const Rows& rows, const float* mask) {
+    int mine = 0;
+    for (int r = rows.r0; r < rows.r1; ++r) mine += mask[r] != 0.0f;
+    return mine;
+}
+
+}  // namespace

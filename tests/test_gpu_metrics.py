@@ -196,6 +196,34 @@ def test_cut_list_and_foreign_entries_set_their_bits():
     assert nan.status.tolist() == [0, _lib.DL_BONDS_NONFINITE] and nan.n_components.tolist() == [1, 3]
 
 
+def test_negative_count_too_many_rows_and_an_empty_batch():
+    """What ``dl_molecule_keys`` shares with the other list kernels and no test above reaches: ``n_bonds_in`` below zero reads
+    no entry, more than 1024 real rows give DL_KEYS_TOO_LARGE and zeros, and an empty batch launches nothing.  N = 1100 is no
+    multiple of 256 and molecule 1 sits in the last rows, in the last threads' ranges."""
+    from difflinker_amd import _lib
+    from difflinker_amd.metrics import molecule_keys
+    from difflinker_amd.molecule_builder import Bonds
+    B, N, nf = 2, 1100, 8
+    one_hot = torch.zeros(B, N, nf, device=DEV)
+    one_hot[0, :, 0] = 1
+    one_hot[1, :, 2] = 1
+    mask = torch.zeros(B, N, 1, device=DEV)
+    mask[0, :1025] = 1
+    mask[1, 1093:] = 1                                                  # seven atoms
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=DEV)     # noqa: E731
+    chain = [(0, 1, 1), (1, 2, 1), (2, 3, 1), (3, 4, 2)]
+    found = Bonds(i32([4, -7]), i32([chain, chain]), torch.zeros(B, N, dtype=torch.int32, device=DEV), i32([1022, 7]), None,
+                  i32([0, 2]))
+    got = molecule_keys(one_hot, mask, found, False)
+    colours, key, n_atoms, n_bonds = ref.colours_and_key([2] * 7, [])
+    assert got.status.tolist() == [_lib.DL_KEYS_TOO_LARGE, 2]
+    assert got.n_atoms.tolist() == [1025, n_atoms] and got.n_bonds.tolist() == [0, n_bonds] and got.n_over.tolist() == [0, 0]
+    assert got.n_components.tolist() == [0, 7] and got.key.tolist() == [0, ref.signed(key)]
+    assert not got.colour[0].any() and got.colour[1].tolist() == [ref.signed(c) for c in colours] + [0] * (N - 7)
+    none = molecule_keys(one_hot[:0], mask[:0], Bonds(i32([]), found.bonds[:0], found.valence[:0], i32([]), None, i32([])), False)
+    assert none.key.shape == (0,) and none.colour.shape == (0, N) and none.status.shape == (0,)
+
+
 # ---- DDPM.sample_and_analyze and the training loop ---------------------------------------------------------------------
 
 def zigzag(n, shift=0.0):
