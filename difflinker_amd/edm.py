@@ -308,8 +308,9 @@ class EDM(torch.nn.Module):
         bs, n = x.size(0), x.size(1)
         nf, T = self.in_node_nf, int(self.T)
         f32 = lambda t_, shape: t_.reshape(shape).to(dev, torch.float32).contiguous()      # noqa: E731
-        xn, hn = self.normalize(x, h)
-        xh = torch.cat([xn, hn], dim=2).to(torch.float32).contiguous()
+        # (fp32 first, then normalised: the arithmetic is fp32 whatever dtype the caller's tensors have)
+        xn, hn = self.normalize(x.to(torch.float32), h.to(torch.float32))
+        xh = torch.cat([xn, hn], dim=2).contiguous()
         nm = f32(node_mask, (bs, n))
         fm = f32(fragment_mask, (bs, n)) if fragment_mask is not None else None
         lm = f32(linker_mask, (bs, n)) if linker_mask is not None else None
@@ -961,6 +962,8 @@ class EDM(torch.nn.Module):
         ``mol_index`` (device int32 ``[B]``): the rows of these molecules of a larger batch, and nothing else."""
         nx = torch.empty((1, n_samples, n_nodes, self.n_dims), device=device)
         nh = torch.empty((1, n_samples, n_nodes, self.in_node_nf), device=device)
+        if mol_index is not None:
+            mol_index = mol_index.to(device=device, dtype=torch.int32).contiguous()
         with torch.cuda.device(device):
             stream = torch.cuda.current_stream(device).cuda_stream
             _lib.check(_lib.load().dl_philox_fill(seed, mol_offset, _lib.ptr(mol_index), n_samples, n_nodes, self.in_node_nf, k, 1,
@@ -989,7 +992,7 @@ class EDM(torch.nn.Module):
             return torch.cat([torch.randn((n_samples, n_nodes, self.n_dims), device=dev),
                               torch.randn((n_samples, n_nodes, self.in_node_nf), device=dev)], dim=2)
 
-        x, h = self.normalize(x, h)
+        x, h = self.normalize(x.to(torch.float32), h.to(torch.float32))          # (fp32 first, as in _loss_rows)
         xh = torch.cat([x, h], dim=2)
         z = xh * fragment_mask + (draw() * linker_mask) * linker_mask
         chain = torch.zeros((keep_frames,) + z.size(), device=dev)
@@ -1195,8 +1198,8 @@ class InpaintingEDM(EDM):
         nf, T = self.in_node_nf, self.T
         f32 = lambda t_, shape: t_.reshape(shape).to(torch.float32).contiguous()      # noqa: E731
         nm, fm, lm = f32(node_mask, (bs, n)), f32(fragment_mask, (bs, n)), f32(linker_mask, (bs, n))
-        xn, hn = self.normalize(x, h)
-        xh = torch.cat([xn, hn], dim=2).float()
+        xn, hn = self.normalize(x.to(torch.float32), h.to(torch.float32))        # (fp32 first, as in _loss_rows)
+        xh = torch.cat([xn, hn], dim=2)
         xh_frag = (xh * fm.unsqueeze(-1)).contiguous()
         # initial z: centre-of-gravity-free position noise + feature noise on the node mask (edm.py:559, :715-727)
         nm3 = nm.unsqueeze(-1)

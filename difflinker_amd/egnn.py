@@ -531,8 +531,9 @@ class Dynamics(nn.Module):
 
     def forward(self, t, xh, node_mask, linker_mask, edge_mask, context):
         """
-        - t: (B, 1) or a single value     - xh: (B, N, 3 + nf)       - node_mask: (B, N, 1)
-        - linker_mask: (B, N, 1) or None  - edge_mask: (B*N*N, 1) int8 {0,-1,-2}   - context: (B, N, C)
+        - t: (B, 1), (B) or a single value  - xh: (B, N, 3 + nf)     - node_mask: (B, N, 1) or (B, N)
+        - linker_mask: (B, N, 1), (B, N) or None  - edge_mask: (B*N*N, 1) or (B, N, N), int8 {0,-1,-2}  - context: (B, N, C)
+        Any strides, storage offset and real or bool dtype whose values are exact in fp32 / int8.
         Returns eps_hat (B, N, 3 + nf) = cat[vel, h_final]; raises ``utils.FoundNaNException``.
         """
         assert self.graph_type == 'FC'

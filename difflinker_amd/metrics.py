@@ -46,7 +46,7 @@ import numpy as np
 import torch
 
 from . import _lib, const
-from .molecule_builder import perceive_all_bonds, refine_bond_orders
+from .molecule_builder import normalize_bonds, perceive_all_bonds, refine_bond_orders
 
 Analysis = namedtuple('Analysis', 'n_atoms n_over n_components n_bonds key colour status bonds')
 Graph = namedtuple('Graph', 'types bonds colours')
@@ -80,6 +80,7 @@ def molecule_keys(one_hot, node_mask, found, is_geom, drop_mask=None):
     i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
     i64 = lambda *shape: torch.empty(shape, dtype=torch.int64, device=dev)  # noqa: E731
     out = Analysis(i32(B), i32(B), i32(B), i32(B), i64(B), i64(B, N), i32(B), found)
+    found = normalize_bonds(found, B, dev, 'molecule_keys')          # (what the kernel reads; the result keeps the caller's object)
     capacity = found.bonds.shape[1]
     args = _lib.DLMolKeysArgs(
         B=B, N=N, nf=nf, one_hot=one_hot.data_ptr(), node_mask=node_mask.data_ptr(),
@@ -736,6 +737,7 @@ def ring_scores(node_mask, found, drop_mask=None, mark_mask=None):
     capacity = found.bonds.shape[1]
     i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
     out = Rings(i32(B), i32(B), i32(B), i32(B), i32(B, capacity), i32(B, N), i32(B, 2, _lib.DL_RING_BINS), i32(B), found)
+    found = normalize_bonds(found, B, dev, 'ring_scores')
     opt = lambda t: None if t is None else t.data_ptr()                     # noqa: E731
     args = _lib.DLRingsArgs(
         B=B, N=N, node_mask=node_mask.data_ptr(), drop_mask=opt(drop_mask), mark_mask=opt(mark_mask), capacity=capacity,
@@ -939,6 +941,7 @@ def fingerprints(one_hot, node_mask, found, drop_mask=None, centre_mask=None, ra
     one_hot, node_mask, drop_mask, centre_mask = f32(one_hot), f32(node_mask), f32(drop_mask), f32(centre_mask)
     i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
     out = Fingerprints(i32(B, n_bits // 32), i32(B), i32(B), i32(B), i32(B))
+    found = normalize_bonds(found, B, dev, 'fingerprints')
     capacity = found.bonds.shape[1]
     opt = lambda t: None if t is None else t.data_ptr()                     # noqa: E731
     with torch.cuda.device(dev):
@@ -972,9 +975,14 @@ def analyze_fingerprints(one_hot, x, node_mask, is_geom, linker_mask, drop_mask=
     return whole, fingerprints(one_hot, node_mask, found, drop_mask, linker_mask.reshape(B, N), radius, n_bits)
 
 
+def _aligned_rows(rows):
+    return rows.clone() if rows.data_ptr() % 16 else rows
+
+
 def tanimoto_nearest(a_bits, b_bits, a_offsets=None, b_offsets=None, exclude_diagonal=False, want_sum=True):
     """``dl_tanimoto_nearest``: for every row of ``a_bits [Ma,W]`` its nearest neighbour and its summed similarity among the
-    candidate rows of ``b_bits [Mb,W]`` (``Fingerprints.bits``; the two may be the same tensor), on torch's current stream
+    candidate rows of ``b_bits [Mb,W]`` (``Fingerprints.bits``: int32 words, any other dtype is refused with a ``ValueError``; any
+    strides and offset; the two may be the same tensor), on torch's current stream
     with no host synchronisation.  ``a_offsets`` and ``b_offsets`` (int32 ``[G+1]``, both or neither; ``a_offsets`` must not
     decrease) split the rows into ``G`` groups: row ``i`` with ``a_offsets[g] <= i < a_offsets[g+1]`` has the candidates
     ``b_offsets[g] <= j < b_offsets[g+1]``, without ``j == i`` when ``exclude_diagonal``.  Without offsets: one group over
@@ -998,7 +1006,11 @@ def tanimoto_nearest(a_bits, b_bits, a_offsets=None, b_offsets=None, exclude_dia
     dev = a_bits.device
     Ma, W = a_bits.shape
     Mb = b_bits.shape[0]
-    a_bits, b_bits = a_bits.contiguous(), b_bits.contiguous()
+    # the kernel reads the rows 16 bytes at a time and the C entry point refuses a pointer that is not aligned to that (a row
+    # slice of a larger set is aligned to 4): such rows are handed over as an aligned copy
+    same = b_bits is a_bits
+    a_bits = _aligned_rows(a_bits.contiguous())
+    b_bits = a_bits if same else _aligned_rows(b_bits.contiguous())
     if a_offsets is None:
         a_offsets, b_offsets = (torch.full((2,), m, dtype=torch.int32, device=dev) for m in (Ma, Mb))     # [0, M], filled on
         a_offsets[0], b_offsets[0] = 0, 0                                                                  # the device

@@ -75,6 +75,41 @@ def perceive_all_bonds(one_hot, x, node_mask, is_geom, margins=const.MARGINS_EDM
     return found
 
 
+_KERNEL_READS = ('n_bonds', 'bonds', 'valence', 'n_components', 'status')    # ``component`` goes to no kernel: left as it is
+
+
+def _canonical_members(found, B, device):
+    """``found`` with every member a kernel reads (``_KERNEL_READS``) that is not ``None`` as a dense int32 tensor on ``device``
+    - the layout the kernels read at a member's ``data_ptr()``.  A member that is one already is passed on as it is (no copy).
+    ``bonds`` must be ``[B,capacity,3]`` and every other such member must have ``B`` rows; ``ValueError`` names the member that
+    is not."""
+    if not torch.is_tensor(found.bonds) or found.bonds.dim() != 3 or found.bonds.shape[0] != B or found.bonds.shape[2] != 3:
+        shape = tuple(found.bonds.shape) if torch.is_tensor(found.bonds) else None
+        raise ValueError(f'shapes disagree: bonds {shape} of a Bonds for {B} molecules must be [{B},capacity,3]')
+    new = {}
+    for name in _KERNEL_READS:
+        t = getattr(found, name)
+        if t is None:
+            continue
+        if t.dim() < 1 or t.shape[0] != B:
+            raise ValueError(f'shapes disagree: {name} {tuple(t.shape)} of a Bonds for {B} molecules')
+        new[name] = t.to(device=device, dtype=torch.int32).contiguous()
+    return found._replace(**new)
+
+
+def normalize_bonds(found, B, device, who):
+    """The ``Bonds`` a wrapper hands to a kernel: ``found`` may be the caller's own - the list int64 (``torch.tensor(rows)``) or a
+    capacity slice ``wider[:, :capacity]`` of a longer one, the counts any integer dtype, strided or sliced - and every member
+    the kernel reads becomes dense int32 (``_canonical_members``; a ``Bonds`` of ``perceive_bonds`` is not copied).  Members on
+    the host raise ``HipLibraryError``: there is no CPU fallback."""
+    where = [(name, getattr(found, name).device) for name in _KERNEL_READS
+             if getattr(found, name) is not None and not getattr(found, name).is_cuda]
+    if where:
+        raise _lib.HipLibraryError(f'{who} runs on the HIP device only (no CPU fallback): got the Bonds members '
+                                   + ', '.join(f'{name} on {d}' for name, d in where))
+    return _canonical_members(found, B, device)
+
+
 def _ring_classes(device, is_geom):
     key = (device, bool(is_geom))
     if key not in _RING_CLASSES:
@@ -116,21 +151,22 @@ def refine_bond_orders(found, one_hot, x, node_mask, is_geom, drop_mask=None, ma
         raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, x {tuple(x.shape)}, masks '
                          f'{[tuple(m.shape) for m in masks]}, bonds {tuple(found.bonds.shape)}')
     dev = one_hot.device
+    given = normalize_bonds(found, B, dev, 'refine_bond_orders')
     f32 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()     # noqa: E731
     one_hot, x, node_mask, drop_mask, mark_mask = f32(one_hot), f32(x), f32(node_mask), f32(drop_mask), f32(mark_mask)
     classes = _ring_classes(dev, is_geom)
     if classes.numel() < nf:
         raise ValueError(f'one_hot has {nf} types, the vocabulary {classes.numel()}')
-    capacity = found.bonds.shape[1]
-    bonds = found.bonds.contiguous()
+    capacity = given.bonds.shape[1]
+    bonds = given.bonds
     i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
     order, valence = i32(B, capacity), i32(B, N)
     out = Aromatic(i32(B, capacity), i32(B, N), i32(B), i32(B), i32(B), i32(B))
     opt = lambda t: None if t is None else t.data_ptr()                     # noqa: E731
     args = _lib.DLAromaticArgs(
         B=B, N=N, nf=nf, x=x.data_ptr(), one_hot=one_hot.data_ptr(), node_mask=node_mask.data_ptr(), drop_mask=opt(drop_mask),
-        mark_mask=opt(mark_mask), ring_class=classes.data_ptr(), capacity=capacity, n_bonds_in=found.n_bonds.data_ptr(),
-        bonds=bonds.data_ptr() if capacity else None, status_in=found.status.data_ptr(),
+        mark_mask=opt(mark_mask), ring_class=classes.data_ptr(), capacity=capacity, n_bonds_in=given.n_bonds.data_ptr(),
+        bonds=bonds.data_ptr() if capacity else None, status_in=given.status.data_ptr(),
         tol2_ring=float(planarity) ** 2, tol2_sub=float(substituent) ** 2,
         order_out=order.data_ptr() if capacity else None, bond_aromatic=out.bond_aromatic.data_ptr() if capacity else None,
         atom_aromatic=out.atom_aromatic.data_ptr(), valence_out=valence.data_ptr(),
