@@ -79,7 +79,8 @@ def pocket_molecules(batch, n_frag, n_pocket, linker, nf, seed, min_gap=1e-4):
     uniform in a 5 A ball, ``n_pocket`` pocket atoms uniform in a 10 A ball, then the linker
     rows.  ``fragment_mask`` covers fragment+pocket atoms like the MOAD data
     (lightning.py:431-433).  Pairs closer than ``min_gap`` to the 4 A / 10 A cut-offs are
-    re-drawn so edge membership does not flip between implementations."""
+    re-drawn so edge membership does not flip between implementations.
+    Pairs exactly ON a cut-off are tested on the lattice molecules of tests/lattice_cases.py instead."""
     g = torch.Generator().manual_seed(seed)
     mols = []
     for b in range(batch):

@@ -47,7 +47,8 @@ def pocket_batch(batch, n_frag, n_pocket, linker, nf, seed, anchors=False, far_a
 
 def assert_clear_of_cutoffs(z, inp, graph_type):
     """The precondition of every comparison: in fp64 no same-molecule pair of real atoms lies within ``GAP`` of a cut-off that
-    applies to it, so the fp32 edge set of the kernels is the fp64 edge set of the oracle."""
+    applies to it, so the fp32 edge set of the kernels is the fp64 edge set of the oracle.  The comparison itself - a pair
+    exactly on a cut-off - is tested on the lattice molecules of tests/lattice_cases.py (tests/test_gpu_cutoff_ties.py)."""
     x = (z[..., :3] * inp['node_mask']).double()
     real = inp['node_mask'][..., 0] != 0
     pock = (inp['context'][..., -1] != 0) & real
