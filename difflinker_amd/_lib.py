@@ -301,6 +301,38 @@ class DLTanimotoArgs(ctypes.Structure):               # likewise
     ]
 
 
+DL_PHARM_MAX_ATOMS, DL_PHARM_MAX_RINGS, DL_PHARM_FAMILIES = 256, 64, 7    # dl_pharm_args: kept atoms, aromatic rings; families
+DL_PHARM_TOO_LARGE, DL_PHARM_BAD_BOND = 4, 8          # dl_pharm_args.status bits, beside the DL_BONDS_* bits carried forward
+DL_PHARM_MANY_RINGS, DL_PHARM_OVERFLOW, DL_PHARM_NONFINITE = 16, 32, 64
+
+
+class DLPharmArgs(ctypes.Structure):                  # the stream is the last FIELD, as for dl_fingerprints
+    _fields_ = [
+        ('B', ctypes.c_int32), ('N', ctypes.c_int32), ('nf', ctypes.c_int32),
+        ('x', ctypes.c_void_p), ('one_hot', ctypes.c_void_p), ('node_mask', ctypes.c_void_p),
+        ('drop_mask', ctypes.c_void_p), ('mark_mask', ctypes.c_void_p), ('feature_class', ctypes.c_void_p),
+        ('default_valence', ctypes.c_void_p), ('capacity', ctypes.c_int32),
+        ('n_bonds_in', ctypes.c_void_p), ('bonds', ctypes.c_void_p), ('bond_aromatic', ctypes.c_void_p),
+        ('status_in', ctypes.c_void_p), ('Fcap', ctypes.c_int32),
+        ('family', ctypes.c_void_p), ('anchor', ctypes.c_void_p), ('position', ctypes.c_void_p), ('marked', ctypes.c_void_p),
+        ('n_features', ctypes.c_void_p), ('family_count', ctypes.c_void_p), ('status', ctypes.c_void_p),
+        ('stream', ctypes.c_void_p),
+    ]
+
+
+class DLFeatureMatchArgs(ctypes.Structure):           # likewise
+    _fields_ = [
+        ('B', ctypes.c_int32), ('Fa', ctypes.c_int32), ('Fb', ctypes.c_int32),
+        ('family_a', ctypes.c_void_p), ('position_a', ctypes.c_void_p), ('marked_a', ctypes.c_void_p),
+        ('n_features_a', ctypes.c_void_p),
+        ('family_b', ctypes.c_void_p), ('position_b', ctypes.c_void_p), ('marked_b', ctypes.c_void_p),
+        ('n_features_b', ctypes.c_void_p),
+        ('radius2', ctypes.c_float), ('marked_only', ctypes.c_int32),
+        ('best_index', ctypes.c_void_p), ('best_d2', ctypes.c_void_p), ('n_a', ctypes.c_void_p), ('n_b', ctypes.c_void_p),
+        ('n_matched', ctypes.c_void_p), ('stream', ctypes.c_void_p),
+    ]
+
+
 EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_string', 'dl_model_num_tensors',
            'dl_model_create', 'dl_model_destroy', 'dl_egnn_forward_fc', 'dl_sampler_step', 'dl_sample_chain_fc',
            'dl_set_profile_buffer', 'dl_profile_max_events', 'dl_pocket_workspace_bytes', 'dl_egnn_forward_pocket',
@@ -314,7 +346,7 @@ EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_stri
            'dl_join_workspace_bytes', 'dl_sample_chain_fc_join', 'dl_bonds_workspace_bytes', 'dl_perceive_bonds',
            'dl_molecule_keys', 'dl_clash_scores', 'dl_shape_scores', 'dl_ring_scores', 'dl_fragment_cuts',
            'dl_pocket_select', 'dl_fragment_multicuts', 'dl_aromatic_rings', 'dl_fingerprints',
-           'dl_tanimoto_nearest', 'dl_best_rmsd')
+           'dl_tanimoto_nearest', 'dl_pharmacophore_features', 'dl_feature_match', 'dl_best_rmsd')
 TEST_HOOK_EXPORTS = ('dl_debug_team_fault', 'dl_debug_slot_order')       # declared under #ifdef DL_TEST_HOOKS: the test-hooks build only
 
 _lib = None
@@ -452,6 +484,10 @@ def _open(path):
     lib.dl_fingerprints.argtypes = [ctypes.POINTER(DLFingerprintArgs)]
     lib.dl_tanimoto_nearest.restype = i32
     lib.dl_tanimoto_nearest.argtypes = [ctypes.POINTER(DLTanimotoArgs)]
+    lib.dl_pharmacophore_features.restype = i32
+    lib.dl_pharmacophore_features.argtypes = [ctypes.POINTER(DLPharmArgs)]
+    lib.dl_feature_match.restype = i32
+    lib.dl_feature_match.argtypes = [ctypes.POINTER(DLFeatureMatchArgs)]
     lib.dl_pocket_select.restype = i32
     lib.dl_pocket_select.argtypes = [ctypes.POINTER(DLPocketArgs), vp]
     lib.dl_best_rmsd.restype = i32

@@ -114,6 +114,24 @@ def ring_class_table(is_geom):
     return torch.tensor([classes.get(idx2atom[k], 0) for k in range(len(idx2atom))], dtype=torch.int32)
 
 
+# what ``dl_pharmacophore_features`` needs to know of an element: its class (1 C, 2 N, 3 O, 4 S, 5 P, 6 F, 7 Cl / Br / I) and
+# the number of bonds it carries when neutral, from which the open valences (implicit hydrogens) are counted
+FEATURE_CLASSES = {'C': 1, 'N': 2, 'O': 3, 'S': 4, 'P': 5, 'F': 6, 'Cl': 7, 'Br': 7, 'I': 7}
+DEFAULT_VALENCE = {'C': 4, 'N': 3, 'O': 2, 'F': 1, 'S': 2, 'Cl': 1, 'Br': 1, 'I': 1, 'P': 3}
+
+
+def feature_class_table(is_geom):
+    """int32 ``[n_types]``: the class ``dl_pharmacophore_features`` gives every element of the vocabulary, in index order."""
+    idx2atom = GEOM_IDX2ATOM if is_geom else IDX2ATOM
+    return torch.tensor([FEATURE_CLASSES.get(idx2atom[k], 0) for k in range(len(idx2atom))], dtype=torch.int32)
+
+
+def default_valence_table(is_geom):
+    """int32 ``[n_types]``: the default valence of every element of the vocabulary, in index order (``DEFAULT_VALENCE``)."""
+    idx2atom = GEOM_IDX2ATOM if is_geom else IDX2ATOM
+    return torch.tensor([DEFAULT_VALENCE[idx2atom[k]] for k in range(len(idx2atom))], dtype=torch.int32)
+
+
 # Bondi's van der Waals radii in Angstrom (J. Phys. Chem. 68, 441 (1964)) by GEOM atom index (C O N F S Cl Br I P; the ZINC
 # vocabulary is the leading 8): what the clash rule of ``metrics.analyze_clashes`` is built from
 VDW_RADII = (1.70, 1.52, 1.55, 1.47, 1.80, 1.75, 1.85, 1.98, 1.80)

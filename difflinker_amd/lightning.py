@@ -102,6 +102,7 @@ class DDPM(_Base):
         self.geometry_metrics = False           # sample_and_analyze adds metrics.compute_geometry's RMSD keys (train --geometry)
         self.clash_metrics = False              # pocket models: it adds metrics.compute_clashes' keys as well (train --clashes)
         self.shape_metrics = False              # it adds metrics.compute_shapes' keys: every sample against its true molecule (train --shape)
+        self.pharmacophore_metrics = False      # it adds metrics.compute_pharmacophores' keys: feature-map score of every sample against its true molecule, sc_similarity with shape_metrics (train --pharmacophore)
         self.aromatic_metrics = False           # it adds metrics.compute_aromatic's keys: aromatic rings of the linker, ring filter, valence rule on geometric orders (train --aromatic)
         self.diversity_metrics = False          # it adds metrics.compute_diversity's keys: internal diversity of each input's samples, similarity to the true molecule (train --diversity)
         self.ring_metrics = False               # it adds metrics.compute_rings' keys: ring count of the linker, small rings, macrocycles (train --rings)
@@ -323,7 +324,10 @@ class DDPM(_Base):
         frame the two share (``metrics.compute_shapes``; pocket rows left out, once over all ligand rows and once over the
         linker rows).  With ``self.ring_metrics`` the rings of every sample and of its true molecule are perceived
         (``metrics.analyze_rings`` / ``compute_rings``; pocket rows dropped): the linker's ring count, small rings,
-        macrocycles.  With ``self.aromatic_metrics`` aromatic rings are perceived from the geometry and the ring bonds get
+        macrocycles.  With ``self.pharmacophore_metrics`` the pharmacophore features of every sample are matched against its true
+        molecule's (``metrics.analyze_pharmacophores`` / ``compute_pharmacophores``, this project's rule after RDKit's
+        ``BaseFeatures.fdef``, not RDKit's numbers): ``feature_similarity(_linker)``, and ``sc_similarity`` when
+        ``self.shape_metrics`` is set too.  With ``self.aromatic_metrics`` aromatic rings are perceived from the geometry and the ring bonds get
         Kekule orders (``metrics.analyze_aromatic`` / ``compute_aromatic``, a rule of this project's own, not RDKit's):
         ``aromatic_rings_n``, ``ring_filter``, ``valence_validity_geometric``.  With ``self.diversity_metrics`` every sample
         and every true molecule is fingerprinted (``metrics.analyze_fingerprints`` / ``compute_diversity``; this project's own
@@ -335,6 +339,7 @@ class DDPM(_Base):
         pred_rings, true_rings = [], []
         pred_prints, true_prints, print_input = [], [], []
         shapes, linker_shapes = [], []
+        pharm, linker_pharm = [], []
         pred_x, true_x, n_linker = [], [], []
         clashes = self.clash_metrics and self.pockets
         pred_clashes, true_clashes = [], []
@@ -392,6 +397,10 @@ class DDPM(_Base):
                 if self.shape_metrics:
                     shapes += self._shape_records(data, one_hot, x, node_mask, drop, out_drop, linker=False)
                     linker_shapes += self._shape_records(data, one_hot, x, node_mask, drop, out_drop, linker=True)
+                if self.pharmacophore_metrics:
+                    whole, linker = self._pharmacophore_records(data, one_hot, x, node_mask, drop, out_drop)
+                    pharm += whole
+                    linker_pharm += linker
                 if self.ring_metrics:                                              # the template's linker rows marked
                     frag = torch.nn.functional.pad(data['fragment_mask'], (0, 0, 0, node_mask.shape[1] - data['fragment_mask'].shape[1]))
                     pred_rings += mol_metrics.rings_to_host(*mol_metrics.analyze_rings(
@@ -421,6 +430,8 @@ class DDPM(_Base):
             scores.update(mol_metrics.compute_clashes(pred_clashes, true_clashes))
         if self.shape_metrics:
             scores.update(mol_metrics.compute_shapes(shapes, linker_shapes, pred))
+        if self.pharmacophore_metrics:
+            scores.update(mol_metrics.compute_pharmacophores(pharm, linker_pharm, shapes if self.shape_metrics else None))
         if self.ring_metrics:
             scores.update(mol_metrics.compute_rings(pred_rings, true_rings))
         if self.aromatic_metrics:
@@ -434,10 +445,9 @@ class DDPM(_Base):
             scores.update(mol_metrics.compute_diversity(records, with_true=True, with_reference=False))
         return scores
 
-    def _shape_records(self, data, one_hot, x, node_mask, drop, out_drop, linker):
-        """``metrics.ShapeRecord`` per molecule of a sampled batch against the data set's molecule.  ``sample_chain`` centres
-        its input on ``center_of_mass`` and the data set's positions are not centred, so the true molecule is moved the same
-        way first: the two then share the fragments' coordinates.  Pocket rows take part on neither side."""
+    def _true_positions(self, data):
+        """The data set's positions moved as ``sample_chain`` moves its input (centred on ``center_of_mass``), so that a sample
+        and its true molecule share the fragments' coordinates."""
         if self.inpainting:                                                        # the conditions of ``sample_chain``
             com_mask = data['atom_mask']
         elif isinstance(self.val_dataset, MOADDataset) and self.center_of_mass == 'fragments':
@@ -448,7 +458,21 @@ class DDPM(_Base):
             com_mask = data['anchors']
         else:
             raise NotImplementedError(self.center_of_mass)
-        true_x = utils.remove_partial_mean_with_mask(data['positions'], data['atom_mask'], com_mask)
+        return utils.remove_partial_mean_with_mask(data['positions'], data['atom_mask'], com_mask)
+
+    def _pharmacophore_records(self, data, one_hot, x, node_mask, drop, out_drop):
+        """``metrics.pharmacophores_to_host`` of a sampled batch against the data set's molecules, in the frame of
+        ``_shape_records``: the linker rows marked, the pocket rows dropped on both sides."""
+        pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, node_mask.shape[1] - m.shape[1]))      # noqa: E731
+        return mol_metrics.pharmacophores_to_host(mol_metrics.analyze_pharmacophores(
+            one_hot, x, node_mask, node_mask * (1 - pad(data['fragment_mask'])), data['one_hot'][:, :, :self.num_classes],
+            self._true_positions(data), data['atom_mask'], data['linker_mask'], is_geom=self.is_geom, drop_a=out_drop, drop_b=drop))
+
+    def _shape_records(self, data, one_hot, x, node_mask, drop, out_drop, linker):
+        """``metrics.ShapeRecord`` per molecule of a sampled batch against the data set's molecule.  ``sample_chain`` centres
+        its input on ``center_of_mass`` and the data set's positions are not centred, so the true molecule is moved the same
+        way first: the two then share the fragments' coordinates.  Pocket rows take part on neither side."""
+        true_x = self._true_positions(data)
         pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, node_mask.shape[1] - m.shape[1]))      # noqa: E731
         if linker:
             mask, true_mask = node_mask * (1 - pad(data['fragment_mask'])), data['linker_mask']

@@ -37,6 +37,11 @@ geometry by a rule of this project's own - not RDKit's model, not OpenBabel's bo
 are the samples of one input different from each other, how close does a sample come to its true molecule, how close is the
 nearest molecule of a reference set (``dl_fingerprints`` and ``dl_tanimoto_nearest``, ``csrc/fingerprint.hip``).  The circular
 fingerprint is this project's own, built on the colours of ``molecule_keys`` - not RDKit's Morgan fingerprint.
+
+``analyze_pharmacophores`` / ``compute_pharmacophores`` give the other half of SC-RDKit: pharmacophore features perceived from
+the refined bond graph and their Best-mode feature-map match against the true molecule's (``dl_pharmacophore_features`` and
+``dl_feature_match``, ``csrc/pharmacophore.hip``), and with the shape records ``sc_similarity``.  The feature rule is this
+project's own, after RDKit's ``BaseFeatures.fdef`` and ``FeatMapParams`` defaults - not RDKit's numbers.
 """
 import ctypes
 import math
@@ -46,7 +51,7 @@ import numpy as np
 import torch
 
 from . import _lib, const
-from .molecule_builder import normalize_bonds, perceive_all_bonds, refine_bond_orders
+from .molecule_builder import normalize_bonds, perceive_all_bonds, perceive_bonds, refine_bond_orders
 
 Analysis = namedtuple('Analysis', 'n_atoms n_over n_components n_bonds key colour status bonds')
 Graph = namedtuple('Graph', 'types bonds colours')
@@ -623,7 +628,7 @@ def analyze_shapes(one_hot_a, x_a, mask_a, one_hot_b, x_b, mask_b, is_geom=True,
     order; a flagged pair has every other output 0.  No host synchronisation.
 
     What this is NOT: no alignment (the molecules are compared where they are), no pharmacophore features (the other half
-    of SC-RDKit), no hydrogens, not RDKit's numbers.  The lattice is fixed in space: a common shift of both molecules by
+    of SC-RDKit is ``analyze_pharmacophores``), no hydrogens, not RDKit's numbers.  The lattice is fixed in space: a common shift of both molecules by
     less than the spacing moves the counts a little."""
     tensors = (one_hot_a, x_a, mask_a, one_hot_b, x_b, mask_b)
     if not all(t.is_cuda for t in tensors):
@@ -1144,4 +1149,221 @@ def compute_diversity(records, with_true=None, with_reference=None):
         out[name] = mean([_similarity(cc, uu) for cc, uu in scored])
         if name == 'nearest_reference_similarity':
             out['nearest_reference_identical'] = mean([cc == uu for cc, uu in scored])
+    return out
+
+
+Features = namedtuple('Features', 'family anchor position marked n_features family_count status')
+FeatureMatch = namedtuple('FeatureMatch', 'best_index best_d2 n_a n_b n_matched')
+Pharmacophores = namedtuple('Pharmacophores', 'features_a features_b whole linker status')
+PharmRecord = namedtuple('PharmRecord', 'n_a n_b n_matched score status')
+PHARM_NAMES = ('feature_molecules', 'feature_flagged', 'feature_similarity', 'feature_similarity_linker')
+PHARM_SC_NAMES = ('sc_similarity', 'sc_similarity_7', 'sc_similarity_8', 'sc_similarity_9')
+_PHARM_TABLES = {}
+
+
+def _pharm_tables(device, is_geom):
+    key = (device, bool(is_geom))
+    if key not in _PHARM_TABLES:
+        _PHARM_TABLES[key] = (const.feature_class_table(is_geom).to(device).contiguous(),
+                              const.default_valence_table(is_geom).to(device).contiguous())
+    return _PHARM_TABLES[key]
+
+
+def pharmacophore_features(one_hot, x, node_mask, found, bond_aromatic, is_geom, drop_mask=None, mark_mask=None, capacity=None):
+    """``dl_pharmacophore_features`` (``csrc/pharmacophore.hip``) on the results ``(found, aromatic)`` of
+    ``refine_bond_orders`` for the same ``one_hot``, ``x`` and ``node_mask``: ``found`` is the refined ``Bonds`` (any ``Bonds``
+    does) and ``bond_aromatic`` is ``aromatic.bond_aromatic`` ``[B,capacity of the list]``.  Device tensors in, a ``Features``
+    of device tensors out, on torch's current stream, no host synchronisation.
+
+    THE RULE is this project's own, after RDKit's ``BaseFeatures.fdef``; it is NOT RDKit's feature factory and these are NOT
+    RDKit's numbers (``include/difflinker_hip.h`` states it in full; ``tests/pharmacophore_ref.py`` restates it).  Families:
+    0 Donor (N, O with an open valence), 1 Acceptor (O outside aromatic rings; N without an open valence that has a multiple
+    bond or is a tertiary amine away from conjugation), 2 PosIonizable (aliphatic amines; amidine and guanidine carbons),
+    3 NegIonizable (carboxylic, phosphoric and sulfonic acid centres), 4 Hydrophobe (C among C; Cl, Br, I; thioether S),
+    5 Aromatic (the centroid of every five- and six-ring of aromatic bonds), 6 LumpedHydrophobe (such a ring of carbons).  No
+    hydrogens and no charges; no ZnBinder and no alkyl lumps.
+
+    ``drop_mask`` (the pocket) removes atoms together with their bonds, ``mark_mask`` (the linker) marks atoms, both ``[B,N]``
+    or ``[B,N,1]`` by row.  ``capacity`` is the length of the feature list per molecule, ``max(3 * N, 16)`` by default.
+    ``family`` / ``anchor`` / ``marked`` ``[B,capacity]`` int32 (family -1 from the count on), ``position [B,capacity,3]``
+    fp32, ``n_features [B]`` (the true count), ``family_count [B,7]``, ``status [B]``: the bits of ``found.status`` plus
+    ``_lib.DL_PHARM_*`` (more than 256 kept atoms: nothing is listed; more than 64 rings: no ring features; the list too short;
+    a NaN coordinate)."""
+    masks = (node_mask,) + tuple(m for m in (drop_mask, mark_mask) if m is not None)
+    if not (one_hot.is_cuda and x.is_cuda and bond_aromatic.is_cuda and found.bonds.is_cuda and all(m.is_cuda for m in masks)):
+        raise _lib.HipLibraryError('pharmacophore_features runs on the HIP device only (no CPU fallback): '
+                                   f'got tensors on {one_hot.device}, {x.device}, {bond_aromatic.device}, {found.bonds.device}')
+    B, N, nf = one_hot.shape
+    if x.shape != (B, N, 3) or any(m.numel() != B * N for m in masks) or found.bonds.dim() != 3 or found.bonds.shape[0] != B \
+            or bond_aromatic.shape != found.bonds.shape[:2]:
+        raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, x {tuple(x.shape)}, masks '
+                         f'{[tuple(m.shape) for m in masks]}, bonds {tuple(found.bonds.shape)}, bond_aromatic '
+                         f'{tuple(bond_aromatic.shape)}')
+    dev = one_hot.device
+    found = normalize_bonds(found, B, dev, 'pharmacophore_features')
+    f32 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()     # noqa: E731
+    one_hot, x, node_mask, drop_mask, mark_mask = f32(one_hot), f32(x), f32(node_mask), f32(drop_mask), f32(mark_mask)
+    bond_aromatic = bond_aromatic.to(device=dev, dtype=torch.int32).contiguous()
+    classes, valences = _pharm_tables(dev, is_geom)
+    if classes.numel() < nf:
+        raise ValueError(f'one_hot has {nf} types, the vocabulary {classes.numel()}')
+    bond_capacity = found.bonds.shape[1]
+    Fcap = max(3 * N, 16) if capacity is None else int(capacity)
+    if Fcap < 0:
+        raise ValueError(f'capacity must not be negative, got {capacity}')
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    out = Features(i32(B, Fcap), i32(B, Fcap), torch.empty((B, Fcap, 3), dtype=torch.float32, device=dev), i32(B, Fcap), i32(B),
+                   i32(B, _lib.DL_PHARM_FAMILIES), i32(B))
+    opt = lambda t: None if t is None else t.data_ptr()                     # noqa: E731
+    with torch.cuda.device(dev):
+        args = _lib.DLPharmArgs(
+            B=B, N=N, nf=nf, x=x.data_ptr(), one_hot=one_hot.data_ptr(), node_mask=node_mask.data_ptr(), drop_mask=opt(drop_mask),
+            mark_mask=opt(mark_mask), feature_class=classes.data_ptr(), default_valence=valences.data_ptr(),
+            capacity=bond_capacity, n_bonds_in=found.n_bonds.data_ptr(), bonds=found.bonds.data_ptr() if bond_capacity else None,
+            bond_aromatic=bond_aromatic.data_ptr() if bond_capacity else None, status_in=found.status.data_ptr(), Fcap=Fcap,
+            family=out.family.data_ptr() if Fcap else None, anchor=out.anchor.data_ptr() if Fcap else None,
+            position=out.position.data_ptr() if Fcap else None, marked=out.marked.data_ptr() if Fcap else None,
+            n_features=out.n_features.data_ptr(), family_count=out.family_count.data_ptr(), status=out.status.data_ptr(),
+            stream=torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.load().dl_pharmacophore_features(ctypes.byref(args)), 'dl_pharmacophore_features')
+    return out
+
+
+def feature_match(a, b, radius=2.5, marked_only=False):
+    """``dl_feature_match``: the Best-mode feature-map match of every pair of two ``Features`` (``a`` the samples, ``b`` their
+    true molecules; any namedtuple with ``family``, ``position``, ``marked`` and ``n_features`` does, and the two lists may have
+    different capacities), on torch's current stream with no host synchronisation.
+
+    A feature takes part when its family is 0..6 and, with ``marked_only``, it is marked.  For every feature of ``b`` that takes
+    part the nearest feature of ``a`` of the same family that takes part and lies strictly within ``radius``:
+    ``d2 = ((dx*dx) + (dy*dy)) + (dz*dz)`` in fp32 without fused multiply-adds against ``radius * radius`` rounded to fp32 once;
+    of equal distances the lowest index.  Returns a ``FeatureMatch``: ``best_index`` int32 and ``best_d2`` fp32 ``[B,Fb]``
+    (-1 and +inf for none), ``n_a``, ``n_b`` (features taking part) and ``n_matched`` ``[B]``.  ``feature_score`` turns a row
+    into the score.  This is RDKit's ``FeatMapScoreMode.Best`` with its default radius - on this project's features, NOT RDKit's."""
+    tensors = (a.family, a.position, a.marked, a.n_features, b.family, b.position, b.marked, b.n_features)
+    if not all(t.is_cuda for t in tensors):
+        raise _lib.HipLibraryError('feature_match runs on the HIP device only (no CPU fallback): '
+                                   f'got tensors on {", ".join(str(t.device) for t in tensors)}')
+    radius2 = float(radius) * float(radius)
+    if not radius2 >= 0.0:
+        raise ValueError(f'radius must be a number, got {radius}')
+    B = a.n_features.shape[0]
+    if a.family.dim() != 2 or b.family.dim() != 2:
+        raise ValueError(f'shapes disagree: family {tuple(a.family.shape)} and {tuple(b.family.shape)}')
+    Fa, Fb = a.family.shape[1], b.family.shape[1]
+    for name, t, shape in (('a.n_features', a.n_features, (B,)), ('a.family', a.family, (B, Fa)), ('a.position', a.position, (B, Fa, 3)), ('a.marked', a.marked, (B, Fa)),
+                           ('b.family', b.family, (B, Fb)), ('b.position', b.position, (B, Fb, 3)), ('b.marked', b.marked, (B, Fb)),
+                           ('b.n_features', b.n_features, (B,))):
+        if tuple(t.shape) != shape:
+            raise ValueError(f'shapes disagree: {name} {tuple(t.shape)}, expected {shape}')
+    dev = a.family.device
+    i32 = lambda t: t.to(device=dev, dtype=torch.int32).contiguous()        # noqa: E731
+    f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()      # noqa: E731
+    fam_a, mk_a, n_a, pos_a = i32(a.family), i32(a.marked), i32(a.n_features), f32(a.position)
+    fam_b, mk_b, n_b, pos_b = i32(b.family), i32(b.marked), i32(b.n_features), f32(b.position)
+    new = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    out = FeatureMatch(new(B, Fb), torch.empty((B, Fb), dtype=torch.float32, device=dev), new(B), new(B), new(B))
+    with torch.cuda.device(dev):
+        args = _lib.DLFeatureMatchArgs(
+            B=B, Fa=Fa, Fb=Fb, family_a=fam_a.data_ptr() if Fa else None, position_a=pos_a.data_ptr() if Fa else None,
+            marked_a=mk_a.data_ptr() if Fa else None, n_features_a=n_a.data_ptr(),
+            family_b=fam_b.data_ptr() if Fb else None, position_b=pos_b.data_ptr() if Fb else None,
+            marked_b=mk_b.data_ptr() if Fb else None, n_features_b=n_b.data_ptr(), radius2=radius2,
+            marked_only=int(bool(marked_only)), best_index=out.best_index.data_ptr() if Fb else None,
+            best_d2=out.best_d2.data_ptr() if Fb else None, n_a=out.n_a.data_ptr(), n_b=out.n_b.data_ptr(),
+            n_matched=out.n_matched.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.load().dl_feature_match(ctypes.byref(args)), 'dl_feature_match')
+    return out
+
+
+def feature_score(best_d2, n_a, n_b):
+    """The feature-map score of one pair on the host, in fp64 with ``math.exp``: ``sum_j exp(-best_d2[j]) / min(n_a, n_b)``
+    over the matched features (finite ``best_d2``) in index order - RDKit's Gaussian profile of width 1 in Best mode, divided
+    as the reference's ``get_FeatureMapScore`` divides.  ``None`` when ``min(n_a, n_b)`` is 0.  ``best_d2`` is a row of
+    ``FeatureMatch.best_d2`` as plain floats."""
+    if min(n_a, n_b) == 0:
+        return None
+    return sum(math.exp(-d) for d in best_d2 if d != math.inf) / min(n_a, n_b)
+
+
+def analyze_pharmacophores(one_hot_a, x_a, mask_a, linker_a, one_hot_b, x_b, mask_b, linker_b, is_geom=True, drop_a=None,
+                           drop_b=None, margins=const.MARGINS_EDM, radius=2.5):
+    """Pharmacophore features of molecule A (the sample) and molecule B (its true molecule) of every pair of a batch, and
+    their feature-map match, on the HIP device without a host synchronisation: on both sides ``perceive_bonds``, then
+    ``refine_bond_orders``, then ``pharmacophore_features`` with the linker rows (``linker_a`` / ``linker_b``, ``[B,N]`` or
+    ``[B,N,1]``) marked and the ``drop_a`` / ``drop_b`` rows (the pocket) left out; then ``feature_match`` twice: over all
+    features (``whole``) and over the marked ones alone (``linker``).  ``Na`` and ``Nb`` may differ; the two molecules are
+    compared where they are, no alignment.
+
+    Returns a ``Pharmacophores``: ``features_a``, ``features_b`` (``Features``), ``whole``, ``linker`` (``FeatureMatch``) and
+    ``status [B]``, the bits of both sides.  ``perceive_bonds`` is used with its default capacity, so a molecule whose atoms
+    are piled on one another carries ``DL_BONDS_OVERFLOW`` and is left out of the scores.  The features are this project's
+    own, after RDKit's ``BaseFeatures.fdef``, NOT RDKit's."""
+    tensors = (one_hot_a, x_a, mask_a, linker_a, one_hot_b, x_b, mask_b, linker_b)
+    if not all(t.is_cuda for t in tensors):
+        raise _lib.HipLibraryError('analyze_pharmacophores runs on the HIP device only (no CPU fallback): '
+                                   f'got tensors on {", ".join(str(t.device) for t in tensors)}')
+    sides = []
+    for one_hot, x, mask, linker, drop in ((one_hot_a, x_a, mask_a, linker_a, drop_a), (one_hot_b, x_b, mask_b, linker_b, drop_b)):
+        B, N = one_hot.shape[:2]
+        if linker.numel() != B * N or mask.numel() != B * N:
+            raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, mask {tuple(mask.shape)}, linker '
+                             f'{tuple(linker.shape)}')
+        found = perceive_bonds(one_hot, x, mask, is_geom, margins)
+        refined, aromatic = refine_bond_orders(found, one_hot, x, mask, is_geom, drop, linker)
+        sides.append(pharmacophore_features(one_hot, x, mask, refined, aromatic.bond_aromatic, is_geom, drop, linker))
+    fa, fb = sides
+    return Pharmacophores(fa, fb, feature_match(fa, fb, radius), feature_match(fa, fb, radius, marked_only=True),
+                          fa.status | fb.status)
+
+
+def pharmacophores_to_host(result):
+    """``(records, linker_records)`` of a ``Pharmacophores``: one ``PharmRecord`` of plain values per pair for the match over
+    all features and one for the match over the linker's, the score by ``feature_score``."""
+    status = result.status.cpu().tolist()
+    out = []
+    for match in (result.whole, result.linker):
+        d2 = match.best_d2.cpu().tolist()
+        columns = zip(match.n_a.cpu().tolist(), match.n_b.cpu().tolist(), match.n_matched.cpu().tolist(), d2, status)
+        out.append([PharmRecord(n_a, n_b, n_matched, feature_score(row, n_a, n_b), s) for n_a, n_b, n_matched, row, s in columns])
+    return tuple(out)
+
+
+def _pharm_scored(record):
+    return not record.status & ~(_lib.DL_BONDS_NONFINITE | _lib.DL_PHARM_NONFINITE) and record.score is not None
+
+
+def compute_pharmacophores(records, linker_records=None, shape_records=None):
+    """Scores of the ``PharmRecord`` values ``records`` (``pharmacophores_to_host``; A the sample, B its true molecule), in fp64.
+    The features are this project's own, after RDKit's ``BaseFeatures.fdef`` and ``FeatMapParams`` defaults, NOT RDKit's: the
+    numbers compare runs of this project with each other and nothing else.
+
+    ``feature_molecules``          pairs scored: no status bit but a NaN coordinate's, and features on both sides; the others
+                                   are left out of everything below
+    ``feature_flagged``            pairs with any other status bit (a cut list of bonds or features, an entry that is no bond,
+                                   more than 256 atoms, more than 64 rings)
+    ``feature_similarity``         mean feature-map score over the whole ligand.  The sample and its true molecule SHARE THEIR
+                                   FRAGMENTS, whose features match at distance 0, so this number is inflated by them and
+                                   says little about the linker
+    ``feature_similarity_linker``  mean score of ``linker_records``, the match over the features that sit on linker atoms
+                                   alone: the informative one (``None`` without ``linker_records``)
+
+    With ``shape_records`` (``shapes_to_host`` of ``analyze_shapes`` for the same pairs), over the pairs both scored:
+    ``sc_similarity``, the mean of ``0.5 * feature score + 0.5 * (vol_min / vol_a)`` - where the reference has SC-RDKit - and
+    ``sc_similarity_7/8/9``, the percentage of those pairs above 0.7 / 0.8 / 0.9.  A mean or a percentage over nothing is
+    ``None``, as in ``compute_shapes``."""
+    if shape_records is not None and len(shape_records) != len(records):
+        raise ValueError(f'{len(records)} feature records, {len(shape_records)} shape records')
+    mean = lambda values: float(sum(values) / len(values)) if values else None      # noqa: E731
+    good = [m for m in records if _pharm_scored(m)]
+    flagged = ~(_lib.DL_BONDS_NONFINITE | _lib.DL_PHARM_NONFINITE)
+    out = {'feature_molecules': len(good), 'feature_flagged': sum(1 for m in records if m.status & flagged),
+           'feature_similarity': mean([m.score for m in good]),
+           'feature_similarity_linker': None if linker_records is None else mean([m.score for m in linker_records
+                                                                                  if _pharm_scored(m)])}
+    if shape_records is not None:
+        sc = [0.5 * m.score + 0.5 * (s.vol_min / s.vol_a) for m, s in zip(records, shape_records)
+              if _pharm_scored(m) and _shape_scored(s)]
+        above = lambda bar: 100.0 * sum(v > bar for v in sc) / len(sc) if sc else None   # noqa: E731
+        out.update(sc_similarity=mean(sc), sc_similarity_7=above(0.7), sc_similarity_8=above(0.8), sc_similarity_9=above(0.9))
     return out

@@ -57,7 +57,7 @@ def _prepare(checkpoint, prefix, data, n_steps, device):
 
 def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=None, linker_size_model=None,
            output_format='xyz', metrics=False, geometry=False, clashes=False, shape=False, rings=False,
-           bond_orders='distance', aromatic=False, diversity=False, diversity_reference=None):
+           bond_orders='distance', aromatic=False, diversity=False, diversity_reference=None, pharmacophore=False):
     """``sample.py``.  Returns the output directory.  ``metrics=True`` scores the molecules sampled in this call against
     the data set's own (``metrics.compute_metrics``: valence rule, connectivity, uniqueness, novelty, recovery) and writes
     the result to ``metrics.json`` in the output directory; with ``geometry=True`` as well, the symmetry-aware RMSD of the
@@ -83,7 +83,12 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
     ``internal_diversity_linker`` among the samples of each input, ``similarity_to_true`` and ``similarity_to_true_linker``.
     ``diversity_reference`` names another data set under ``data`` (typically the training set); it is fingerprinted once,
     in batches, and ``nearest_reference_similarity`` / ``nearest_reference_identical`` join the keys.  All of these are
-    Tanimoto similarities on this project's own circular fingerprint, not on RDKit's Morgan fingerprint."""
+    Tanimoto similarities on this project's own circular fingerprint, not on RDKit's Morgan fingerprint.
+    ``pharmacophore=True`` perceives the pharmacophore features of every sample and of its true molecule and matches them
+    (``metrics.analyze_pharmacophores`` / ``compute_pharmacophores``), on the pairs and rows of ``shape=True``: ligand rows
+    without the pocket, the linker marked.  ``feature_similarity`` and ``feature_similarity_linker`` go into ``metrics.json``,
+    and with ``shape=True`` as well ``sc_similarity`` and ``sc_similarity_7/8/9``, where the reference has SC-RDKit.  The
+    features are this project's own, after RDKit's ``BaseFeatures.fdef`` and ``FeatMapParams`` defaults, not RDKit's numbers."""
     if output_format not in OUTPUT_FORMATS:
         raise ValueError(f'output_format must be one of {OUTPUT_FORMATS}, got {output_format!r}')
     if bond_orders not in BOND_ORDERS:
@@ -93,6 +98,7 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
     pred_x, true_x, n_linker = [], [], []
     pred_clashes, true_clashes = [], []
     shapes, linker_shapes = [], []
+    pharm, linker_pharm = [], []
     pred_rings, true_rings = [], []
     pred_prints, true_prints, print_input = [], [], []
     diversity = diversity or diversity_reference is not None
@@ -184,6 +190,13 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 linker_shapes += mol_metrics.shapes_to_host(mol_metrics.analyze_shapes(
                     types, xs, out_mask * (1 - pad(batch['fragment_mask'])), true_types, x, batch['linker_mask'],
                     is_geom=model.is_geom))
+            if pharmacophore:                                  # the same pairs and rows; the linker rows marked
+                pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, out_mask.shape[1] - m.shape[1]))      # noqa: E731
+                whole, linker = mol_metrics.pharmacophores_to_host(mol_metrics.analyze_pharmacophores(
+                    hs[:, :, :model.num_classes], xs, out_mask, out_mask * (1 - pad(batch['fragment_mask'])),
+                    h[:, :, :model.num_classes], x, node_mask, batch['linker_mask'], is_geom=model.is_geom))
+                pharm += whole
+                linker_pharm += linker
             if rings:                                          # out_mask holds no pocket row here
                 pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, out_mask.shape[1] - m.shape[1]))      # noqa: E731
                 pred_rings += mol_metrics.rings_to_host(*mol_metrics.analyze_rings(
@@ -219,7 +232,7 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 n_linker += n_linker_batch
     if found:
         print(json.dumps(summary(found)))
-    if metrics or clashes or shape or rings or aromatic or diversity:
+    if metrics or clashes or shape or rings or aromatic or diversity or pharmacophore:
         with open(os.path.join(output_dir, 'metrics.json'), 'w') as f:
             scores = {}
             if metrics:
@@ -230,6 +243,8 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 scores.update(mol_metrics.compute_clashes(pred_clashes, true_clashes))
             if shape:
                 scores.update(mol_metrics.compute_shapes(shapes, linker_shapes, pred if metrics else None))
+            if pharmacophore:
+                scores.update(mol_metrics.compute_pharmacophores(pharm, linker_pharm, shapes if shape else None))
             if rings:
                 scores.update(mol_metrics.compute_rings(pred_rings, true_rings))
             if aromatic:
@@ -343,6 +358,11 @@ def main(argv=None):
     p.add_argument('--diversity_reference', default=None, metavar='PREFIX',
                    help='with --diversity: another data set under --data (typically the training set); every sample\'s '
                         'greatest similarity to it is written as nearest_reference_similarity / nearest_reference_identical')
+    p.add_argument('--pharmacophore', action='store_true',
+                   help='perceive the pharmacophore features of every sample and of its true molecule on the GPU and write their '
+                        'feature-map score to metrics.json (feature_similarity, feature_similarity_linker; with --shape also '
+                        'sc_similarity and sc_similarity_7/8/9 - this project\'s features after RDKit\'s BaseFeatures.fdef, not '
+                        'SC-RDKit\'s numbers)')
     a = p.parse_args(argv)
     if a.keep_frames is not None:
         print(sample_trajectories(a.checkpoint, a.samples, a.prefix, a.keep_frames, a.device, a.data, a.n_steps))
@@ -353,7 +373,8 @@ def main(argv=None):
                      **({'rings': True} if a.rings else {}),
                      **({'bond_orders': a.bond_orders} if a.bond_orders != 'distance' else {}),
                      **({'aromatic': True} if a.aromatic else {}), **({'diversity': True} if a.diversity else {}),
-                     **({'diversity_reference': a.diversity_reference} if a.diversity_reference else {})))
+                     **({'diversity_reference': a.diversity_reference} if a.diversity_reference else {}),
+                     **({'pharmacophore': True} if a.pharmacophore else {})))
 
 
 if __name__ == '__main__':

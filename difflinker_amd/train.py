@@ -108,6 +108,10 @@ def main(argv=None):
     p.add_argument('--diversity', action='store_true',
                    help='with --sample_every_epochs: add internal_diversity(_linker) and similarity_to_true(_linker) of the '
                         'samples to the epoch scores (Tanimoto on this project\'s circular fingerprint, not RDKit\'s Morgan)')
+    p.add_argument('--pharmacophore', action='store_true',
+                   help='with --sample_every_epochs: add the feature-map score of every sample\'s pharmacophore features '
+                        'against its true molecule\'s to the epoch scores (feature_similarity(_linker); with --shape also '
+                        'sc_similarity; this project\'s features after RDKit\'s BaseFeatures.fdef, not RDKit\'s numbers)')
     a = p.parse_args(argv)
     cfg = dict(DEFAULTS)
     if a.config is not None:
@@ -146,6 +150,7 @@ def main(argv=None):
     model.ring_metrics = bool(a.rings)
     model.aromatic_metrics = bool(a.aromatic)
     model.diversity_metrics = bool(a.diversity)
+    model.pharmacophore_metrics = bool(a.pharmacophore)
     kept = lambda: {'best_validity_and_connectivity': best} if a.sample_every_epochs else {}   # noqa: E731
     step, epoch = start_step, start_epoch
     n_epochs = int(cfg['n_epochs'])

@@ -64,6 +64,12 @@
  *                                           This project's own fingerprint, NOT RDKit's: stated below
  *   dl_tanimoto_nearest                  <- (no reference counterpart) for every row of one fingerprint set the most similar
  *                                           row and the summed Tanimoto similarity among a segment of another set
+ *   dl_pharmacophore_features            <- the feature half of SC-RDKit (src/delinker_utils/calc_SC_RDKit.py:7-25,
+ *                                           BuildFeatureFactory over BaseFeatures.fdef): donors, acceptors, ionizable
+ *                                           groups, hydrophobes and aromatic rings of every molecule, from the bond graph.
+ *                                           The rule stated below is this project's own after that file, NOT RDKit's
+ *   dl_feature_match                     <- get_FeatureMapScore of the same file (:20-30): the Best-mode feature-map match
+ *                                           of every sample's features with its true molecule's, the Gaussian left to the host
  *   dl_fragment_cuts                     <- FragmentMol(minCuts = maxCuts = 2) with DeLinker's pattern
  *                                           (data/geom/generate_geom_multifrag.py:199-206) and the re-assembly of
  *                                           data/zinc/prepare_dataset.py, src/datasets.py:56-100
@@ -1359,6 +1365,155 @@ typedef struct dl_tanimoto_args {
     void* stream;                   /* hipStream_t; NULL: the default stream */
 } dl_tanimoto_args;
 int32_t dl_tanimoto_nearest(const dl_tanimoto_args* args);
+
+/* ---- pharmacophore features and their feature-map match (pharmacophore.hip) ------------------------------------
+ * The reference scores every sample with SC-RDKit = 0.5 * feature-map score + 0.5 * (1 - ShapeProtrudeDist).
+ * dl_shape_scores gives the shape half; these two entry points give the feature half: the pharmacophore features of every
+ * molecule of a batch, and the Best-mode match of two feature lists.  Both take their arguments alone, the stream as the
+ * last field.  THE RULE BELOW IS THIS PROJECT'S OWN, after RDKit's BaseFeatures.fdef and the FeatMapParams defaults.  It is
+ * NOT RDKit's feature factory (no SMARTS is matched) and these are NOT RDKit's numbers; tests/pharmacophore_ref.py restates
+ * it in plain Python and the kernels agree with that bit for bit.
+ *
+ * FEATURES.  One workgroup per molecule, ONE launch per batch.  CONVENTIONS, those of dl_aromatic_rings.  Atom k is the k-th
+ * row with node_mask != 0; its type is the FIRST largest entry of its one_hot row, its class is feature_class[type]
+ * (1 C, 2 N, 3 O, 4 S, 5 P, 6 F, 7 Cl / Br / I, anything else counts as 0) and its default valence default_valence[type].
+ * `drop_mask` (may be NULL) removes atoms AFTER that numbering, together with their bonds; `mark_mask` (may be NULL) marks
+ * atoms by row.  An entry (i, j, order) is a bond when 0 <= i, j < atoms, i != j and 1 <= order <= 3, in either
+ * orientation; any other entry is skipped and sets DL_PHARM_BAD_BOND.  A repeated pair sets DL_PHARM_BAD_BOND, and its FIRST
+ * entry gives the pair its order and its aromatic flag (bond_aromatic[entry] != 0; the output of dl_aromatic_rings for the
+ * same list).  Entries from min(n_bonds_in, capacity) on are not read.  "Kept" means: not dropped, both ends for a bond.
+ *
+ * Per kept atom u, over the distinct kept pairs: deg; val, the sum of the orders; h = max(0, default_valence - val);
+ * arom, u ends an aromatic pair; multi, u has a pair of order 2 or 3.  "Neighbour" means the other end of a kept pair.
+ *
+ *   0 Donor            class N or O with h >= 1
+ *   1 Acceptor         class O with !arom and val <= 2; class N with h == 0, val <= 3 and either multi, or deg == 3, !arom
+ *                      and no neighbour w with arom(w) or multi(w) (no amide, aniline, sulfonamide, enamine, N-substituted
+ *                      pyrrole)
+ *   2 PosIonizable     class N with !arom, !multi, val <= 3, deg >= 1, every neighbour of class C and none of them arom or
+ *                      multi (an aliphatic amine); class C with !arom, exactly one pair of order 2, which goes to a class N
+ *                      atom, no pair of order 3, at least one more class N neighbour by a pair of order 1, and no neighbour
+ *                      of class O or S (amidine and guanidine, placed at the carbon)
+ *   3 NegIonizable     with T the neighbours of class O and degree 1: at least one of T is joined by a pair of order 2, and
+ *                      class C with |T| >= 2 (a carboxylate that the distance table reads as two C=O counts), class P with
+ *                      |T| >= 2, class S with |T| >= 3 (a sulfone or sulfonamide does not count)
+ *   4 Hydrophobe       class C with deg >= 1 and every neighbour of class C; class 7 with deg == 1; class S with deg == 2,
+ *                      !multi, !arom and both neighbours of class C
+ *   5 Aromatic         every chordless simple cycle of 5 or 6 kept atoms whose cyclically consecutive pairs are all aromatic
+ *                      (chordless: no kept pair, aromatic or not, between two atoms of the cycle that are not consecutive),
+ *                      once, in the canonical order of dl_aromatic_rings step 2: from its smallest atom, in the direction
+ *                      whose second atom is smaller than its last.  RING ATOMS have two or three aromatic pairs: an atom
+ *                      with one, or with more than three, lies in no ring here (dl_aromatic_rings never writes more than
+ *                      three; the limit bounds the search).  The position is the centroid
+ *                      (((p_0 + p_1) + ...) + p_{n-1}) / (double) n by component, p_k = (double) x in canonical order, fp64,
+ *                      contraction off, every operation rounded on its own, then rounded to fp32 once
+ *   6 LumpedHydrophobe an Aromatic ring whose atoms are all of class C, at the same position
+ *
+ * THE LIST.  Atom features first, sorted by (atom number, family): position is the atom's x as given (bit for bit), anchor
+ * the atom number.  Ring features follow, the rings sorted lexicographically by their canonical atom sequence, each giving
+ * Aromatic and then, if it applies, LumpedHydrophobe: anchor is the ring's smallest atom.  An atom feature is marked when its
+ * anchor's row is marked, a ring feature when every atom of the ring is.
+ *
+ *   family        [B,Fcap]: 0..6; -1 from min(n_features, Fcap) on
+ *   anchor        [B,Fcap]: atom number; -1 from there on
+ *   position      [B,Fcap,3] f32; 0 from there on
+ *   marked        [B,Fcap]: 0 or 1; 0 from there on
+ *   n_features    [B]: the true count, which may exceed Fcap
+ *   family_count  [B,DL_PHARM_FAMILIES]: the true count of every family
+ *   status        [B]: the bits of `status_in`, plus DL_BONDS_OVERFLOW when n_bonds_in > capacity (a negative n_bonds_in
+ *                 counts as 0), DL_PHARM_BAD_BOND, and the limits.  None disturbs the other molecules of the launch.
+ *                 DL_PHARM_TOO_LARGE: more than DL_PHARM_MAX_ATOMS KEPT atoms (N itself may be 1024): nothing is listed,
+ *                   every count is 0 and the list of bonds is not read.
+ *                 DL_PHARM_MANY_RINGS: more than DL_PHARM_MAX_RINGS rings: the ring features are left out and their two
+ *                   counts are 0; the atom features stay.
+ *                 DL_PHARM_OVERFLOW: n_features > Fcap; the list holds the first Fcap.
+ *                 DL_PHARM_NONFINITE: a kept atom has a NaN or inf coordinate; the features are listed as they are.
+ *
+ * Integer work apart from the centroid, which is exact in the order given: the same bits on every run and under every order
+ * of the list.  Global memory is written with plain stores only, every output element is written, the callee allocates
+ * nothing.  A null `args`, B < 0, N < 1, N > 1024, nf < 1, capacity < 0 or Fcap < 0 return DL_ERR_BAD_ARG; then B == 0
+ * returns DL_OK without a launch; then a null pointer (other than drop_mask, mark_mask, `bonds` / `bond_aromatic` when
+ * capacity is 0, and the four lists when Fcap is 0) returns DL_ERR_BAD_ARG, all before any device work.
+ * Limits of the rule: no hydrogens, so h is a count of open valences; no formal charges, so a quaternary N or an N-oxide is
+ * not told apart; no SMARTS.  Not here: RDKit's ZnBinder, its alkyl-group lumps (iPr, tBu, chains), feature directions. */
+#define DL_PHARM_MAX_ATOMS 256      /* kept atoms per molecule */
+#define DL_PHARM_MAX_RINGS 64       /* aromatic rings per molecule */
+#define DL_PHARM_FAMILIES 7         /* Donor, Acceptor, PosIonizable, NegIonizable, Hydrophobe, Aromatic, LumpedHydrophobe */
+#define DL_PHARM_AROMATIC 5         /* the family of a ring; DL_PHARM_AROMATIC + 1 is LumpedHydrophobe */
+#define DL_PHARM_TOO_LARGE 4        /* status bit, same value as DL_KEYS_TOO_LARGE */
+#define DL_PHARM_BAD_BOND 8         /* status bit, same value as DL_KEYS_BAD_BOND */
+#define DL_PHARM_MANY_RINGS 16      /* status bit, same value as DL_AROM_MANY_RINGS */
+#define DL_PHARM_OVERFLOW 32        /* status bit: n_features > Fcap */
+#define DL_PHARM_NONFINITE 64       /* status bit: a kept atom has a NaN / inf coordinate */
+typedef struct dl_pharm_args {
+    int32_t B, N, nf;
+    const float* x;                 /* device f32 [B,N,3], Angstrom */
+    const float* one_hot;           /* device f32 [B,N,nf] */
+    const float* node_mask;         /* device f32 [B,N] */
+    const float* drop_mask;         /* device f32 [B,N] or NULL */
+    const float* mark_mask;         /* device f32 [B,N] or NULL */
+    const int32_t* feature_class;   /* device int32 [nf]: 1 C, 2 N, 3 O, 4 S, 5 P, 6 F, 7 Cl / Br / I, 0 anything else */
+    const int32_t* default_valence; /* device int32 [nf]: C 4, N 3, O 2, F 1, S 2, Cl 1, Br 1, I 1, P 3 */
+    int32_t capacity;               /* bonds the list holds per molecule */
+    const int32_t* n_bonds_in;      /* device int32 [B]: dl_bonds_args.n_bonds */
+    const int32_t* bonds;           /* device int32 [B,capacity,3]: the list with dl_aromatic_args.order_out as orders (may be NULL when capacity is 0) */
+    const int32_t* bond_aromatic;   /* device int32 [B,capacity]: dl_aromatic_args.bond_aromatic (may be NULL when capacity is 0) */
+    const int32_t* status_in;       /* device int32 [B]: dl_aromatic_args.status */
+    int32_t Fcap;                   /* features the list holds per molecule */
+    int32_t* family;                /* device int32 [B,Fcap] out (may be NULL when Fcap is 0, as the next three) */
+    int32_t* anchor;                /* device int32 [B,Fcap] out */
+    float* position;                /* device f32 [B,Fcap,3] out */
+    int32_t* marked;                /* device int32 [B,Fcap] out */
+    int32_t* n_features;            /* device int32 [B] out */
+    int32_t* family_count;          /* device int32 [B,DL_PHARM_FAMILIES] out */
+    int32_t* status;                /* device int32 [B] out */
+    void* stream;                   /* hipStream_t; NULL: the default stream */
+} dl_pharm_args;
+int32_t dl_pharmacophore_features(const dl_pharm_args* args);
+
+/* FEATURE MATCH.  For every pair (A = the sample, B = the true molecule) of two feature lists of dl_pharmacophore_features
+ * the Best-mode match of RDKit's feature maps: one workgroup per pair.  The lists' capacities Fa and Fb may differ; the counts
+ * n_features_a and n_features_b are clamped to [0, Fa] and [0, Fb].  A feature TAKES PART when it lies below its clamped
+ * count, its family is 0 .. DL_PHARM_FAMILIES - 1 and, with `marked_only`, its `marked` is not 0.
+ *
+ * For every B feature j that takes part, over the A features i of the same family that take part:
+ * dx = a_x - b_x (dy, dz alike), d2 = ((dx*dx) + (dy*dy)) + (dz*dz), every operation a separate fp32 round-to-nearest
+ * operation in exactly this order (as dl_clash_scores computes it).  i is a candidate when d2 < radius2, STRICTLY; the best
+ * candidate has the smallest d2 and, of equal ones, the smallest i.  A NaN position is no candidate of anything.
+ *
+ *   best_index  [B,Fb]: the best candidate of feature j; -1 for none, for a feature that takes no part and from the count on
+ *   best_d2     [B,Fb] f32: its d2; +inf wherever best_index is -1
+ *   n_a, n_b    [B]: the features of A and of B that take part
+ *   n_matched   [B]: the features of B with a candidate
+ *
+ * The Gaussian is NOT taken on the device, so that the contract stays bit-exact: the caller computes
+ * sum_j exp(-best_d2_j) / min(n_a, n_b) in fp64, which is RDKit's width 1, radius 2.5 (radius2 = 6.25) and
+ * FeatMapScoreMode.Best divided as the reference's get_FeatureMapScore divides - on this project's features, NOT RDKit's.
+ * Plain stores only, every output element is written, the callee allocates nothing.  A null `args`, a negative B, Fa or Fb,
+ * or a radius2 that is negative or NaN return DL_ERR_BAD_ARG; then B == 0 returns DL_OK without a launch; then a null pointer
+ * (other than A's lists when Fa is 0, and B's lists and the two per-feature outputs when Fb is 0) returns DL_ERR_BAD_ARG,
+ * all before any device work.
+ * Not here: the other score modes (All, Closest), feature directions, any alignment of the two molecules. */
+typedef struct dl_feature_match_args {
+    int32_t B, Fa, Fb;
+    const int32_t* family_a;        /* device int32 [B,Fa] (may be NULL when Fa is 0, as the next two) */
+    const float* position_a;        /* device f32 [B,Fa,3] */
+    const int32_t* marked_a;        /* device int32 [B,Fa] */
+    const int32_t* n_features_a;    /* device int32 [B] */
+    const int32_t* family_b;        /* device int32 [B,Fb] (may be NULL when Fb is 0, as the next two) */
+    const float* position_b;        /* device f32 [B,Fb,3] */
+    const int32_t* marked_b;        /* device int32 [B,Fb] */
+    const int32_t* n_features_b;    /* device int32 [B] */
+    float radius2;                  /* square of the cut-off, A^2 (2.5 * 2.5) */
+    int32_t marked_only;
+    int32_t* best_index;            /* device int32 [B,Fb] out (may be NULL when Fb is 0) */
+    float* best_d2;                 /* device f32 [B,Fb] out (may be NULL when Fb is 0) */
+    int32_t* n_a;                   /* device int32 [B] out */
+    int32_t* n_b;                   /* device int32 [B] out */
+    int32_t* n_matched;             /* device int32 [B] out */
+    void* stream;                   /* hipStream_t; NULL: the default stream */
+} dl_feature_match_args;
+int32_t dl_feature_match(const dl_feature_match_args* args);
 
 const char* dl_error_string(int32_t status);
 int32_t dl_last_hip_error(void);
