@@ -4,7 +4,7 @@
 // Scope: egnn_dynamics, hidden_nf = 128, SiLU, sum aggregation, no attention / tanh / sin_embedding (the released FC
 // configurations); any n_layers, inv_sublayers 1..4, norm_constant, normalization_factor, context width, condition_time.
 // Parameters come as ONE flat fp32 buffer in Dynamics.parameters() order (egnn.py: egnn_tensor_order) and the gradient
-// leaves in the same layout.  fp32 throughout (plain FMA chains), no f16 split modes.
+// leaves in the same layout.  fp32 arithmetic (plain FMA chains, no f16 split modes); the long sums are split or run in fp64 (SUMC).
 //
 // Two launches:
 //   backward_mol_kernel   one 256-thread workgroup per molecule.  (1) a forward-with-save pass in fp32 writes the node state
@@ -30,6 +30,12 @@ constexpr int BT = 256;                        // threads per molecule
 constexpr int WLD = H + 1;                     // LDS row stride of a staged 128x128 weight block (odd: conflict-free both ways)
 constexpr int TP = 32;                         // pairs per tile (one receiver, 32 senders)
 constexpr int BWD_MAX_ATOMS = 1024;
+// No sum over the atoms or the pairs of a molecule is one chain of N or N^2 fp32 additions: the rounding error of such a chain
+// grows with its length (the GCL's edge_mlp gradients were 4e-6 off the fp64 gradient at N = 257, eight times fp32 eager
+// autograd's error).  Where a thread owns one number (a bias entry, S_i) it adds in fp64; where it owns 64 (a slice of a weight
+// gradient) it adds partial sums - a receiver's row in the pair passes, SUMC node rows in outer_w - and then the partials.
+// A padded row or pair adds an exact zero at every level, so padding changes no bit.
+constexpr int SUMC = 16;
 
 // per-molecule workspace (floats), each region rounded up to 16 floats
 struct Ws {
@@ -97,9 +103,12 @@ __device__ void node_mv(const Lds& L, float* out, const float* in, int N, const 
     const int c = threadIdx.x & (H - 1);
     for (int n = threadIdx.x >> 7; n < N; n += 2) {
         const float* x = in + long(n) * H;
-        float s = 0.0f;
-#pragma unroll 8
-        for (int k = 0; k < H; ++k) s += (TRANS ? L.w[k * WLD + c] : L.w[c * WLD + k]) * x[k];
+        float s4[4] = {0.0f, 0.0f, 0.0f, 0.0f};              // four interleaved chains of 32, not one of 128
+#pragma unroll 2
+        for (int k = 0; k < H; k += 4)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) s4[u] += (TRANS ? L.w[(k + u) * WLD + c] : L.w[c * WLD + k + u]) * x[k + u];
+        float s = (s4[0] + s4[1]) + (s4[2] + s4[3]);
         s *= scale;
         if (bias) s += bias[c];
         out[long(n) * H + c] = acc ? out[long(n) * H + c] + s : s;
@@ -113,11 +122,19 @@ __device__ void outer_w(float* gW, long ld, long col0, const float* G, const flo
     float acc[64];
 #pragma unroll
     for (int k = 0; k < 64; ++k) acc[k] = 0.0f;
-    for (int n = 0; n < N; ++n) {
-        const float g = G[long(n) * H + o];
-        const float* x = In + long(n) * H + k0;
+    for (int n0 = 0; n0 < N; n0 += SUMC) {                     // partial sums of SUMC rows, then the sum of the partials
+        float part[64];
 #pragma unroll
-        for (int k = 0; k < 64; ++k) acc[k] += g * x[k];
+        for (int k = 0; k < 64; ++k) part[k] = 0.0f;
+        const int n1 = n0 + SUMC < N ? n0 + SUMC : N;
+        for (int n = n0; n < n1; ++n) {
+            const float g = G[long(n) * H + o];
+            const float* x = In + long(n) * H + k0;
+#pragma unroll
+            for (int k = 0; k < 64; ++k) part[k] += g * x[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 64; ++k) acc[k] += part[k];
     }
 #pragma unroll
     for (int k = 0; k < 64; ++k) gW[o * ld + col0 + k0 + k] = acc[k];
@@ -126,9 +143,9 @@ __device__ void outer_w(float* gW, long ld, long col0, const float* G, const flo
 // gb[c] = sum_n G[n][c]
 __device__ void col_sum(float* gb, const float* G, int N) {
     if (threadIdx.x < H) {
-        float s = 0.0f;
+        double s = 0.0;
         for (int n = 0; n < N; ++n) s += G[long(n) * H + threadIdx.x];
-        gb[threadIdx.x] = s;
+        gb[threadIdx.x] = float(s);
     }
 }
 
@@ -174,13 +191,16 @@ __device__ void pair_pass(Lds& L, const Mol& m, const float* P, const float* h, 
     float gw2[64];                                               // dW2[o = tid >> 1][k0 + 0..63]
 #pragma unroll
     for (int k = 0; k < 64; ++k) gw2[k] = 0.0f;
-    float gb2 = 0.0f, gwr = 0.0f, gwd = 0.0f, gb1 = 0.0f, gw3 = 0.0f;
+    double gb2 = 0.0, gwr = 0.0, gwd = 0.0, gb1 = 0.0, gw3 = 0.0;   // one number per thread each: summed in fp64
     if (BWD && tid < H)
         for (int j = 0; j < N; ++j) tj[long(j) * H + tid] = 0.0f;
     __syncthreads();
     for (int i = 0; i < N; ++i) {
         float row_acc = 0.0f;                                     // GCL_FWD: aggregate channel c (half ph); COORD: x sum / dx_i
-        float row_si = 0.0f;                                      // BWD: S_i[c]
+        double row_si = 0.0;                                      // BWD: S_i[c]
+        float rw2[64];                                            // BWD: the row's part of gw2
+#pragma unroll
+        for (int k = 0; k < 64; ++k) rw2[k] = 0.0f;
         float upc[3] = {0.0f, 0.0f, 0.0f};
         if (MODE == COORD_BWD) {
             const float lmi = m.lm ? m.lm[i] : 1.0f;
@@ -295,7 +315,7 @@ __device__ void pair_pass(Lds& L, const Mol& m, const float* P, const float* h, 
 #pragma unroll
                         for (int k = 0; k < 64; k += 4) {
                             const float4 v = *reinterpret_cast<const float4*>(&L.m1[p * H + k0 + k]);
-                            gw2[k] += g * v.x; gw2[k + 1] += g * v.y; gw2[k + 2] += g * v.z; gw2[k + 3] += g * v.w;
+                            rw2[k] += g * v.x; rw2[k + 1] += g * v.y; rw2[k + 2] += g * v.z; rw2[k + 3] += g * v.w;
                         }
                         if ((tid & 1) == 0) gb2 += g;
                     }
@@ -303,10 +323,12 @@ __device__ void pair_pass(Lds& L, const Mol& m, const float* P, const float* h, 
                 // dm1 = W2^T dpre2, dpre1 = dm1 silu'(pre1)  (channel c = k of the first layer)
                 for (int q = 0; q < TP / 2; ++q) {
                     const int p = ph * (TP / 2) + q;
-                    float s = 0.0f;
-#pragma unroll 8
-                    for (int o = 0; o < H; ++o) s += L.w[o * WLD + c] * L.t3[p * H + o];
-                    L.pre1[p * H + c] = s * dsilu(L.pre1[p * H + c]);
+                    float s4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 2
+                    for (int o = 0; o < H; o += 4)
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) s4[u] += L.w[(o + u) * WLD + c] * L.t3[p * H + o + u];
+                    L.pre1[p * H + c] = ((s4[0] + s4[1]) + (s4[2] + s4[3])) * dsilu(L.pre1[p * H + c]);
                 }
                 __syncthreads();
                 if (tid < H) {
@@ -330,7 +352,9 @@ __device__ void pair_pass(Lds& L, const Mol& m, const float* P, const float* h, 
                 __syncthreads();
                 if (tid < TP * 3) {                                     // x gradient of the tile's senders
                     const int p = tid / 3, q = tid % 3, j = j0 + p;
-                    const float g = L.ddiff[p * 3 + q] + 2.0f * L.diff[p * 3 + q] * L.dr[p];
+                    // x_i - x_i is zero whatever x is: the self pair (live in collate's mask, with 1 / den = 1e4 at
+                    // norm_constant <= 1e-6) has no x gradient; added to dxi and taken off dxj it would cost them four digits
+                    const float g = j == i ? 0.0f : L.ddiff[p * 3 + q] + 2.0f * L.diff[p * 3 + q] * L.dr[p];
                     L.ddiff[p * 3 + q] = g;
                     if (j < N) dxj[long(j) * 4 + q] -= g;
                 }
@@ -352,8 +376,10 @@ __device__ void pair_pass(Lds& L, const Mol& m, const float* P, const float* h, 
                 out[long(i) * 4 + tid] = (x[long(i) * 4 + tid] + row_acc * m.inv_norm * lmi) * m.nm[i];
             }
         } else {
-            if (tid < H) { si[long(i) * H + tid] = row_si; gb1 += row_si; }
+            if (tid < H) { si[long(i) * H + tid] = float(row_si); gb1 += row_si; }
             if (tid < 3) dxi[long(i) * 4 + tid] += row_acc;
+#pragma unroll
+            for (int k = 0; k < 64; ++k) gw2[k] += rw2[k];
         }
     }
     __syncthreads();
@@ -367,15 +393,15 @@ __device__ void pair_pass(Lds& L, const Mol& m, const float* P, const float* h, 
         const int o = tid >> 1, k0 = (tid & 1) * 64;
 #pragma unroll
         for (int k = 0; k < 64; ++k) gW2[o * H + k0 + k] = gw2[k];
-        if ((tid & 1) == 0) gb2p[o] = gb2;
+        if ((tid & 1) == 0) gb2p[o] = float(gb2);
     }
     if (tid < H) {
-        gW1[tid * ld1 + 2 * H] = gwr;
-        gW1[tid * ld1 + 2 * H + 1] = gwd;
-        gb1p[tid] = gb1;
+        gW1[tid * ld1 + 2 * H] = float(gwr);
+        gW1[tid * ld1 + 2 * H + 1] = float(gwd);
+        gb1p[tid] = float(gb1);
     }
     if (COORD) {                                                       // combine the two pair halves of dw3
-        L.red[tid] = gw3;
+        L.red[tid] = float(gw3);
         __syncthreads();
         if (tid < H) gP[C_4W + tid] = L.red[tid] + L.red[tid + H];
     }
@@ -578,9 +604,9 @@ __global__ void __launch_bounds__(256) reduce_kernel(const float* __restrict__ w
                                                      float* __restrict__ grad) {
     const long p = long(blockIdx.x) * 256 + threadIdx.x;
     if (p >= P) return;
-    float s = 0.0f;
+    double s = 0.0;
     for (int b = 0; b < B; ++b) s += ws[long(b) * stride + goff + p];
-    grad[p] = s;
+    grad[p] = float(s);
 }
 
 bool scope_ok(const dl_backward_args* a) {

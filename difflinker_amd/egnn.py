@@ -634,6 +634,7 @@ class DynamicsWithPockets(Dynamics):
 
 # ---- training: the backward of the denoiser (csrc/egnn_backward.hip: fully connected; csrc/egnn_backward_sparse.hip: pockets) ----
 TRAINABLE_POCKET_GRAPHS = ('FC-4A', 'FC-10A-4A')
+MAX_STATE_WIDTH = 16                  # row width of the per-atom state [x(3), h(in_node_nf)] (csrc/pack_layout.h: DMAX)
 
 
 def check_trainable(dyn):
@@ -654,6 +655,8 @@ def check_trainable(dyn):
     if dyn.aggregation_method != 'sum': out.append(f'aggregation_method={dyn.aggregation_method!r}')
     if dyn.sin_embedding: out.append('sin_embedding=True')
     if dyn.dynamics.hidden_nf != HIDDEN_WIDTH: out.append(f'hidden_nf={dyn.dynamics.hidden_nf} (the backward is 128 wide)')
+    if 3 + dyn.in_node_nf > MAX_STATE_WIDTH:
+        out.append(f'in_node_nf={dyn.in_node_nf} (the kernels take 3 + in_node_nf <= {MAX_STATE_WIDTH})')
     if out:
         raise NotImplementedError('training (the HIP backward) covers fully-connected Dynamics and DynamicsWithPockets on the '
                                   'FC-4A / FC-10A-4A graphs, with the released hyper-parameters only; outside it: '

@@ -61,11 +61,13 @@ def assert_clear_of_cutoffs(z, inp, graph_type):
     assert not bool(near.any()), f'{int(near.sum())} pairs within {GAP} A of a cut-off: choose another seed'
 
 
-def make_dyn(nf, ctx, L, S, wseed, graph_type, trained=False, centering=False):
+def make_dyn(nf, ctx, L, S, wseed, graph_type, trained=False, centering=False, norm_constant=1e-6, normalization_factor=100,
+             coord_gain=0.02):
     from difflinker_amd import DynamicsWithPockets
     dyn = DynamicsWithPockets(n_dims=3, in_node_nf=nf, context_node_nf=ctx, hidden_nf=128, n_layers=L, inv_sublayers=S,
-                              norm_constant=1e-6, normalization_factor=100, centering=centering, graph_type=graph_type)
-    sd = seeded_state_dict(nf + ctx + 1, 128, L, wseed, coord_gain=0.02, inv_sublayers=S)
+                              norm_constant=norm_constant, normalization_factor=normalization_factor, centering=centering,
+                              graph_type=graph_type)
+    sd = seeded_state_dict(nf + ctx + 1, 128, L, wseed, coord_gain=coord_gain, inv_sublayers=S)
     if trained:
         sd = trained_like_state_dict(sd, wseed)
     dyn.load_state_dict({k: v.float() for k, v in sd.items()}, strict=True)
@@ -114,7 +116,12 @@ CASES = {   # (seeds: the first of seed, seed + 100, ... whose batch is clear of
     'centering': ((2, 12, 40, (3, 8), 9, 517), 'FC-10A-4A', 2, 1, 2, True, False, False),
     'trained_like': ((2, 12, 40, (3, 8), 9, 19), 'FC-10A-4A', 2, 2, 2, False, True, False),
     'c4_geometry': ((2, 30, 252, (8, 12), 9, 641321), 'FC-10A-4A', 2, 2, 2, False, False, False),    # N about 292
+    'nc1_norm1': ((3, 12, 70, (3, 8), 9, 233), 'FC-10A-4A', 2, 2, 2, False, False, False),       # the 'fc10_ragged' geometry
+    'nc0': ((3, 12, 70, (3, 8), 9, 233), 'FC-10A-4A', 2, 2, 2, False, False, False),
 }
+# norm_constant where it weighs in d coord_diff (every other case: 1e-6, which no power of the denominator can be told from):
+# the reference's EGNN default with a coordinate path that carries weight, and the default of Dynamics
+NORMS = {'nc1_norm1': dict(norm_constant=1.0, normalization_factor=1.0, coord_gain=1.0), 'nc0': dict(norm_constant=0.0)}
 
 
 def case_inputs(case):
@@ -122,7 +129,7 @@ def case_inputs(case):
     batch, n_frag, n_pocket, linker, nf, seed = mol
     inp, z, t, G = pocket_batch(batch, n_frag, n_pocket, linker, nf, seed, anchors=ctx == 3, far_atom=far)
     assert_clear_of_cutoffs(z, inp, graph)
-    dyn = make_dyn(nf, ctx, L, S, wseed=60 + L + S, graph_type=graph, trained=trained, centering=centering)
+    dyn = make_dyn(nf, ctx, L, S, wseed=60 + L + S, graph_type=graph, trained=trained, centering=centering, **NORMS.get(case, {}))
     return dyn, inp, z, t, G
 
 
