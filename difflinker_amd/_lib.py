@@ -169,6 +169,31 @@ class DLClashArgs(ctypes.Structure):
     ]
 
 
+DL_XS_HYDROPHOBIC, DL_XS_DONOR, DL_XS_ACCEPTOR = 16, 32, 64               # xs_type bits above the element index (bits 0-3)
+DL_INTERACT_TERMS = 5                                                     # gauss1, gauss2, repulsion, hydrophobic, hbond
+DL_INTERACT_NONFINITE, DL_INTERACT_TOO_LARGE, DL_INTERACT_BAD_TYPE, DL_INTERACT_UNTYPED = 1, 2, 4, 8   # status bits
+
+
+class DLInteractTypesArgs(ctypes.Structure):           # the stream is the last FIELD, as for dl_fingerprints
+    _fields_ = [
+        ('B', ctypes.c_int32), ('N', ctypes.c_int32), ('nf', ctypes.c_int32),
+        ('x', ctypes.c_void_p), ('one_hot', ctypes.c_void_p), ('group', ctypes.c_void_p), ('table', ctypes.c_void_p),
+        ('xs_type', ctypes.c_void_p), ('status', ctypes.c_void_p), ('stream', ctypes.c_void_p),
+    ]
+
+
+class DLInteractArgs(ctypes.Structure):                # likewise
+    _fields_ = [
+        ('B', ctypes.c_int32), ('N', ctypes.c_int32), ('nf', ctypes.c_int32),
+        ('x', ctypes.c_void_p), ('xs_type', ctypes.c_void_p), ('query_mask', ctypes.c_void_p),
+        ('target_mask', ctypes.c_void_p), ('M', ctypes.c_int32), ('target_x', ctypes.c_void_p),
+        ('target_xs', ctypes.c_void_p), ('radius', ctypes.c_void_p),
+        ('n_query', ctypes.c_void_p), ('n_target', ctypes.c_void_p), ('n_pairs', ctypes.c_void_p),
+        ('n_hbonds', ctypes.c_void_p), ('n_hydrophobic', ctypes.c_void_p), ('terms', ctypes.c_void_p),
+        ('status', ctypes.c_void_p), ('atom_terms', ctypes.c_void_p), ('stream', ctypes.c_void_p),
+    ]
+
+
 DL_SHAPE_NONFINITE, DL_SHAPE_OUT_OF_RANGE, DL_SHAPE_TOO_LARGE = 1, 2, 4  # dl_shape_args.status: one of these, or 0
 
 
@@ -344,6 +369,7 @@ EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_stri
            'dl_egnn_backward_pocket_workspace_bytes', 'dl_egnn_backward_pocket',
            'dl_size_train_num_params', 'dl_size_train_workspace_bytes', 'dl_size_train_forward', 'dl_size_train_backward',
            'dl_join_workspace_bytes', 'dl_sample_chain_fc_join', 'dl_bonds_workspace_bytes', 'dl_perceive_bonds',
+           'dl_interaction_types', 'dl_interaction_scores',
            'dl_molecule_keys', 'dl_clash_scores', 'dl_shape_scores', 'dl_ring_scores', 'dl_fragment_cuts',
            'dl_pocket_select', 'dl_fragment_multicuts', 'dl_aromatic_rings', 'dl_fingerprints',
            'dl_tanimoto_nearest', 'dl_pharmacophore_features', 'dl_feature_match', 'dl_best_rmsd')
@@ -470,6 +496,10 @@ def _open(path):
     lib.dl_molecule_keys.argtypes = [ctypes.POINTER(DLMolKeysArgs), vp]
     lib.dl_clash_scores.restype = i32
     lib.dl_clash_scores.argtypes = [ctypes.POINTER(DLClashArgs), vp]
+    lib.dl_interaction_types.restype = i32
+    lib.dl_interaction_types.argtypes = [ctypes.POINTER(DLInteractTypesArgs)]
+    lib.dl_interaction_scores.restype = i32
+    lib.dl_interaction_scores.argtypes = [ctypes.POINTER(DLInteractArgs)]
     lib.dl_shape_scores.restype = i32
     lib.dl_shape_scores.argtypes = [ctypes.POINTER(DLShapeArgs), vp]
     lib.dl_ring_scores.restype = i32

@@ -150,6 +150,19 @@ def clash_threshold_table(is_geom, scale=0.75, tolerance=0.0):
     return table.to(TORCH_FLOAT)
 
 
+# The atom radii of Trott & Olson's scoring function (AutoDock Vina, J. Comput. Chem. 31, 455 (2010)) in Angstrom by GEOM atom
+# index (C O N F S Cl Br I P), from which ``metrics.analyze_interactions`` forms surface distances, and the published weights
+# of its five intermolecular terms: gauss1, gauss2, repulsion, hydrophobic, hydrogen bond.  The rotor weight is not used
+XS_RADII = (1.9, 1.7, 1.8, 1.5, 2.0, 1.8, 2.0, 2.2, 2.1)
+INTERACTION_WEIGHTS = (-0.035579, -0.005156, 0.840245, -0.035069, -0.587439)
+
+
+def xs_radius_table(is_geom):
+    """fp64 ``[n_types]``: ``XS_RADII`` of the vocabulary, in index order."""
+    n = GEOM_NUMBER_OF_ATOM_TYPES if is_geom else NUMBER_OF_ATOM_TYPES
+    return torch.tensor(XS_RADII[:n], dtype=torch.float64)
+
+
 def shape_radius_table(is_geom, scale=0.8, step=0.25):
     """``[n_types][3]`` fp32 SQUARED radii in Angstrom^2 of the three levels of the shape rule (``metrics.analyze_shapes``):
     ``r_k = scale * VDW_RADII[type] + k * step`` for ``k = 0, 1, 2`` in fp64, rounded to fp32 once, then ``r_k * r_k`` as one

@@ -39,8 +39,7 @@ struct Mol {
 };
 
 __device__ __forceinline__ int pair_order(const Mol& m, int i, int j) {
-    const float dx = m.x[i] - m.x[j], dy = m.y[i] - m.y[j], dz = m.z[i] - m.z[j];
-    const float d = 100.0f * sqrtf(dx * dx + dy * dy + dz * dz);
+    const float d = bond_distance_pm(m.x[i] - m.x[j], m.y[i] - m.y[j], m.z[i] - m.z[j]);
     const float* t = m.table + (m.type[i] * m.nf + m.type[j]) * 3;
     int order = 0;
     if (d < t[0]) {

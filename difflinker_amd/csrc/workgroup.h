@@ -1,6 +1,6 @@
 // workgroup.h — what every analysis kernel with one 256-thread workgroup per molecule (or pair) needs: the workgroup size, the
-// scan and the reductions over one value per thread, the atom type of a one-hot row, and the rule that says which rows of a
-// molecule a thread owns.  mol_graph.h adds what the kernels that read a bond list share.
+// scan and the reductions over one value per thread, the atom type of a one-hot row, the pm distance of the bond rule, and the rule that
+// says which rows of a molecule a thread owns.  mol_graph.h adds what the kernels that read a bond list share.
 //
 // THE WORKGROUP FUNCTIONS (block_*) take `lds`, one word per wave (WG_WAVES words) of LDS that they alone use while they
 // run; each has two barriers, the second after its last read of `lds`, so the same words can serve the next call at once;
@@ -78,6 +78,25 @@ __device__ __forceinline__ float block_min(float v, float* lds /* [WG_WAVES] */)
     for (int k = 1; k < WG_WAVES; ++k) m = lds[k] < m ? lds[k] : m;
     __syncthreads();
     return m;
+}
+
+// sum of one 64-bit integer per thread over the workgroup, the same in every thread (the fixed-point sums of interaction.hip)
+__device__ __forceinline__ long long block_sum(long long v, long long* lds /* [WG_WAVES] */) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    long long s = 0;
+#pragma unroll
+    for (int k = 0; k < WG_WAVES; ++k) s += lds[k];
+    __syncthreads();
+    return s;
+}
+
+// the distance in pm that bond perception compares with its table (bonds.hip's rule `100 |x_i - x_j| < T`, strict): the one
+// place the arithmetic is written, so that every kernel that asks "are these two bonded?" rounds as bonds.hip does
+__device__ __forceinline__ float bond_distance_pm(float dx, float dy, float dz) {
+    return 100.0f * sqrtf(dx * dx + dy * dy + dz * dz);
 }
 
 // the atom type of a one-hot row: the index of its FIRST largest entry (include/difflinker_hip.h quotes this rule for every

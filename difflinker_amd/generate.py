@@ -81,13 +81,13 @@ BOND_ORDERS = ('distance', 'geometric')
 
 def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_dir, name, com_key, hide_pocket,
                      output_format='xyz', metrics=False, clashes=False, protein=None, rings=False, bond_orders='distance',
-                     aromatic=False, diversity=False):
+                     aromatic=False, diversity=False, interactions=False, typed_protein=None):
     if output_format not in OUTPUT_FORMATS:
         raise ValueError(f'output_format must be one of {OUTPUT_FORMATS}, got {output_format!r}')
     if bond_orders not in BOND_ORDERS:
         raise ValueError(f'bond_orders must be one of {BOND_ORDERS}, got {bond_orders!r}')
     written, found, scored, clash_records, ring_records, aromatic_records = [], [], [], [], [], []
-    prints = []
+    prints, contact_records = [], []
     for batch_i, data in enumerate(_batches(dataset, batch_size, collate_fn)):
         n = len(data['positions'])
         chain = None
@@ -118,6 +118,13 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
                 scored_x = torch.where(pocket_rows.bool(), pad(data['positions']), x)      # through the COM frame left them
             clash_records += mol_metrics.clashes_to_host(mol_metrics.analyze_clashes(
                 h[:, :, :ddpm.num_classes], scored_x, generated, pocket_rows, protein=protein, is_geom=ddpm.is_geom))
+        if interactions:                                      # the same rows and frame; the linker typed within the whole ligand
+            pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, x.shape[1] - m.shape[1]))     # noqa: E731
+            pocket_rows = pad(data['pocket_mask'])
+            scored_x = torch.where(pocket_rows.bool(), pad(data['positions']), x)
+            contact_records += mol_metrics.interactions_to_host(mol_metrics.analyze_interactions(
+                h[:, :, :ddpm.num_classes], scored_x, node_mask * (1 - pad(data['fragment_mask'])), node_mask * (1 - pocket_rows),
+                pocket_rows if typed_protein is None else None, protein=typed_protein, is_geom=ddpm.is_geom))
         if hide_pocket:                                       # generate_with_pocket.py:272
             node_mask = node_mask.clone()
             width = data['pocket_mask'].shape[1]
@@ -150,12 +157,14 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
                 h[:, :, :ddpm.num_classes], x, node_mask, ddpm.is_geom, node_mask * (1 - pad(data['fragment_mask']))))
     if found:
         print(json.dumps(summary(found)))
-    if metrics or clashes or rings or aromatic or diversity:
+    if metrics or clashes or rings or aromatic or diversity or interactions:
         scores = {}
         if metrics:                                           # no true molecule here: no novelty, no recovery
             scores = dict(mol_metrics.compute_metrics(scored), molecules=len(scored))
         if clashes:
             scores.update(mol_metrics.compute_clashes(clash_records))
+        if interactions:
+            scores.update(mol_metrics.compute_interactions(contact_records))
         if rings:                                             # no true molecule here either
             scores.update(mol_metrics.compute_rings(ring_records))
         if aromatic:
@@ -172,6 +181,13 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
         with open(os.path.join(output_dir, 'clashes.json'), 'w') as f:
             json.dump({os.path.basename(path): {'n_clashes': m.n_clashes, 'n_clash_atoms': m.n_clash_atoms,
                                                 'min_distance': finite(m.min_distance)}
+                       for path in written for m in [by_name[os.path.basename(path).rsplit('_.', 1)[0]]]}, f, indent=1)
+    if interactions:                                          # likewise
+        by_name = {f'output_{i}_{name}': m for i, m in enumerate(contact_records)}
+        with open(os.path.join(output_dir, 'interactions.json'), 'w') as f:
+            json.dump({os.path.basename(path): {'score': m.score, 'terms': dict(zip(mol_metrics.INTERACTION_TERMS, m.terms)),
+                                                'n_pairs': m.n_pairs, 'n_hbonds': m.n_hbonds,
+                                                'n_hydrophobic': m.n_hydrophobic, 'status': m.status}
                        for path in written for m in [by_name[os.path.basename(path).rsplit('_.', 1)[0]]]}, f, indent=1)
     return written
 
@@ -218,7 +234,7 @@ def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anc
 
 def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size, device,
                             output_format, metrics=False, clashes=False, protein=None, rings=False, bond_orders='distance',
-                            aromatic=False):
+                            aromatic=False, interactions=False, typed_protein=None):
     frag_pos, frag_one_hot, frag_charges = frag
     pocket_pos, pocket_one_hot, pocket_charges = pocket
     positions = np.concatenate([frag_pos, pocket_pos], axis=0)
@@ -239,15 +255,21 @@ def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_s
     return _sample_and_save(ddpm, dataset, collate_with_fragment_without_pocket_edges, sample_fn,
                             min(n_samples, max_batch_size), output_dir, name, com_key='fragment_only_mask',
                             hide_pocket=True, output_format=output_format, metrics=metrics, clashes=clashes, protein=protein,
-                            rings=rings, bond_orders=bond_orders, aromatic=aromatic)
+                            rings=rings, bond_orders=bond_orders, aromatic=aromatic, interactions=interactions,
+                            typed_protein=typed_protein)
 
 
 def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, output_dir, n_samples, n_steps, linker_size,
                          anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz',
-                         metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False):
+                         metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False, interactions=False):
     """``generate_with_pocket.py`` main(): the pocket is given as its own PDB file.  ``clashes=True`` scores every sample's
     generated atoms against the pocket atoms (``metrics.analyze_clashes``), adds the ``metrics.compute_clashes`` keys to
-    ``metrics.json`` and writes ``clashes.json``: ``n_clashes``, ``n_clash_atoms`` and ``min_distance`` per written file."""
+    ``metrics.json`` and writes ``clashes.json``: ``n_clashes``, ``n_clash_atoms`` and ``min_distance`` per written file.
+    ``interactions=True`` scores the contacts of the generated atoms, typed within the whole ligand, with the pocket atoms
+    (``metrics.analyze_interactions``: the intermolecular terms of Trott & Olson under this project's own typing, not
+    AutoDock Vina's numbers), adds the ``metrics.compute_interactions`` keys to ``metrics.json`` and writes
+    ``interactions.json``: ``score``, the five fixed-point ``terms`` (units of 2^-32), ``n_pairs``, ``n_hbonds``,
+    ``n_hydrophobic`` and ``status`` per written file."""
     device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
     os.makedirs(output_dir, exist_ok=True)
     if random_seed is not None:
@@ -267,16 +289,18 @@ def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, ou
     pocket = pocket_arrays(read_pocket(pocket_path), backbone_atoms_only)
     return _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size,
                                    device, output_format, metrics, clashes, rings=rings, bond_orders=bond_orders,
-                                   aromatic=aromatic)
+                                   aromatic=aromatic, interactions=interactions)
 
 
 def generate_with_protein(input_path, protein_path, backbone_atoms_only, model, output_dir, n_samples, n_steps,
                           linker_size, anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz',
-                          metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False):
+                          metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False,
+                          interactions=False):
     """``generate_with_protein.py`` main(): the pocket = residues of the protein within 6 A of the fragments.
     ``clashes=True`` as in ``generate_with_pocket``, but against ALL protein atoms whose element is in the vocabulary
     (``io.get_protein_atoms``), residues outside the pocket the model saw included; the pocket rows of the batch are then not
-    targets, so no atom counts twice."""
+    targets, so no atom counts twice.  ``interactions=True`` likewise scores against the whole protein, which is typed once
+    (``metrics.protein_types``), so no residue is cut at a pocket boundary."""
     device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
     os.makedirs(output_dir, exist_ok=True)
     if random_seed is not None:
@@ -290,14 +314,17 @@ def generate_with_protein(input_path, protein_path, backbone_atoms_only, model, 
     name = '.'.join(input_path.split('/')[-1].split('.')[:-1])
     frag = parse_molecule(molecule, is_geom=ddpm.is_geom)
     pocket = get_pocket(molecule, protein_path, backbone_atoms_only)
-    protein = None
-    if clashes:
+    protein, typed_protein = None, None
+    if clashes or interactions:
         positions, types = get_protein_atoms(protein_path, ddpm.is_geom)
         protein = (torch.tensor(positions, dtype=const.TORCH_FLOAT, device=device),
                    torch.tensor(types, dtype=torch.int32, device=device))
+    if interactions:
+        typed_protein = protein + (mol_metrics.protein_types(*protein, is_geom=ddpm.is_geom),)
     return _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size,
-                                   device, output_format, metrics, clashes, protein, rings=rings, bond_orders=bond_orders,
-                                   aromatic=aromatic)
+                                   device, output_format, metrics, clashes, protein if clashes else None, rings=rings,
+                                   bond_orders=bond_orders, aromatic=aromatic, interactions=interactions,
+                                   typed_protein=typed_protein)
 
 
 def main(argv=None):
@@ -325,6 +352,11 @@ def main(argv=None):
                    help='with --pocket / --protein: count the steric clashes of the generated atoms with the pocket atoms / '
                         'with all protein atoms on the GPU (0.75 x the sum of the van der Waals radii), add the scores to '
                         'metrics.json and write clashes.json with one record per written file')
+    p.add_argument('--interactions', action='store_true',
+                   help='with --pocket / --protein: score the contacts of the generated atoms with the pocket atoms / with all '
+                        'protein atoms on the GPU (the intermolecular terms of Trott & Olson under this project\'s heavy-atom '
+                        'typing, not AutoDock Vina\'s numbers), add the scores to metrics.json and write interactions.json with '
+                        'one record per written file')
     p.add_argument('--rings', action='store_true',
                    help='perceive the rings of the generated molecules on the GPU (ring count of the linker, small rings, '
                         'macrocycles; the cyclomatic number, no aromaticity) and add the scores to metrics.json')
@@ -342,7 +374,11 @@ def main(argv=None):
     a = p.parse_args(argv)
     if a.clashes and a.pocket is None and a.protein is None:
         raise ValueError('--clashes scores the generated atoms against a protein: pass --pocket or --protein')
+    if a.interactions and a.pocket is None and a.protein is None:
+        raise ValueError('--interactions scores the generated atoms against a protein: pass --pocket or --protein')
     extra = {'clashes': True} if a.clashes else {}
+    if a.interactions:
+        extra['interactions'] = True
     more = {'rings': True} if a.rings else {}
     if a.bond_orders != 'distance':
         more['bond_orders'] = a.bond_orders

@@ -101,6 +101,7 @@ class DDPM(_Base):
         self.metrics = {}                                                       # lightning.py:43: name -> value per epoch
         self.geometry_metrics = False           # sample_and_analyze adds metrics.compute_geometry's RMSD keys (train --geometry)
         self.clash_metrics = False              # pocket models: it adds metrics.compute_clashes' keys as well (train --clashes)
+        self.interaction_metrics = False        # pocket models: metrics.compute_interactions' keys (train --interactions)
         self.shape_metrics = False              # it adds metrics.compute_shapes' keys: every sample against its true molecule (train --shape)
         self.pharmacophore_metrics = False      # it adds metrics.compute_pharmacophores' keys: feature-map score of every sample against its true molecule, sc_similarity with shape_metrics (train --pharmacophore)
         self.aromatic_metrics = False           # it adds metrics.compute_aromatic's keys: aromatic rings of the linker, ring filter, valence rule on geometric orders (train --aromatic)
@@ -320,6 +321,9 @@ class DDPM(_Base):
         samples (``metrics.compute_geometry``) is added: ``rmsd`` (``None`` when nothing recovered), ``rmsd_molecules``,
         ``rmsd_truncated``.  With ``self.clash_metrics`` a pocket model also gets the ``metrics.compute_clashes`` keys: the
         samples' linker atoms against the pocket atoms, and the data set's own linkers in the same pockets as ``true``.
+        With ``self.interaction_metrics`` a pocket model likewise gets the ``metrics.compute_interactions`` keys: the contacts
+        of the same rows under the intermolecular terms of Trott & Olson and this project's own typing (not AutoDock Vina's
+        numbers), the linker typed within the whole ligand.
         With ``self.shape_metrics`` every sample's gridded van der Waals volume is compared with its true molecule's in the
         frame the two share (``metrics.compute_shapes``; pocket rows left out, once over all ligand rows and once over the
         linker rows).  With ``self.ring_metrics`` the rings of every sample and of its true molecule are perceived
@@ -343,6 +347,8 @@ class DDPM(_Base):
         pred_x, true_x, n_linker = [], [], []
         clashes = self.clash_metrics and self.pockets
         pred_clashes, true_clashes = [], []
+        contacts = self.interaction_metrics and self.pockets
+        pred_contacts, true_contacts = [], []
         first = 0
         for b, data in enumerate(dataloader):
             drop = data['pocket_mask'] if self.pockets else None                   # lightning.py:331-334
@@ -353,6 +359,10 @@ class DDPM(_Base):
             if clashes:
                 true_clash_batch = mol_metrics.clashes_to_host(mol_metrics.analyze_clashes(
                     data['one_hot'][:, :, :self.num_classes], data['positions'], data['linker_mask'], drop, is_geom=self.is_geom))
+            if contacts:
+                true_contact_batch = mol_metrics.interactions_to_host(mol_metrics.analyze_interactions(
+                    data['one_hot'][:, :, :self.num_classes], data['positions'], data['linker_mask'], data['atom_mask'] - drop,
+                    drop, is_geom=self.is_geom))
             if self.ring_metrics:
                 true_ring_batch = mol_metrics.rings_to_host(*mol_metrics.analyze_rings(
                     data['one_hot'][:, :, :self.num_classes], data['positions'], data['atom_mask'], self.is_geom,
@@ -394,6 +404,11 @@ class DDPM(_Base):
                     pred_clashes += mol_metrics.clashes_to_host(mol_metrics.analyze_clashes(
                         one_hot, x, node_mask * (1 - frag), out_drop, is_geom=self.is_geom))
                     true_clashes += true_clash_batch
+                if contacts:                                                       # the same rows; the ligand: all but the pocket
+                    frag = torch.nn.functional.pad(data['fragment_mask'], (0, 0, 0, node_mask.shape[1] - data['fragment_mask'].shape[1]))
+                    pred_contacts += mol_metrics.interactions_to_host(mol_metrics.analyze_interactions(
+                        one_hot, x, node_mask * (1 - frag), node_mask * (1 - out_drop), out_drop, is_geom=self.is_geom))
+                    true_contacts += true_contact_batch
                 if self.shape_metrics:
                     shapes += self._shape_records(data, one_hot, x, node_mask, drop, out_drop, linker=False)
                     linker_shapes += self._shape_records(data, one_hot, x, node_mask, drop, out_drop, linker=True)
@@ -428,6 +443,8 @@ class DDPM(_Base):
             scores.update(mol_metrics.compute_geometry(pred, true, pred_x, true_x, n_linker))
         if clashes:
             scores.update(mol_metrics.compute_clashes(pred_clashes, true_clashes))
+        if contacts:
+            scores.update(mol_metrics.compute_interactions(pred_contacts, true_contacts))
         if self.shape_metrics:
             scores.update(mol_metrics.compute_shapes(shapes, linker_shapes, pred))
         if self.pharmacophore_metrics:

@@ -42,6 +42,12 @@ fingerprint is this project's own, built on the colours of ``molecule_keys`` - n
 the refined bond graph and their Best-mode feature-map match against the true molecule's (``dl_pharmacophore_features`` and
 ``dl_feature_match``, ``csrc/pharmacophore.hip``), and with the shape records ``sc_similarity``.  The feature rule is this
 project's own, after RDKit's ``BaseFeatures.fdef`` and ``FeatMapParams`` defaults - not RDKit's numbers.
+
+``analyze_interactions`` / ``compute_interactions`` answer what the clash score cannot: does the linker make contacts with
+the protein, and more or fewer than the data set's own linker in the same pocket?  Heavy atoms typed as hydrophobic, donor or
+acceptor from elements and geometry, and the intermolecular terms of Trott & Olson (AutoDock Vina, 2010) over them
+(``dl_interaction_types`` and ``dl_interaction_scores``, ``csrc/interaction.hip``).  This project's own rule after that
+published form - NOT AutoDock Vina's numbers: no hydrogens, no PDBQT typing, no search, no intramolecular term.
 """
 import ctypes
 import math
@@ -598,6 +604,230 @@ def compute_clashes(pred, true=None):
         out['true_clashes_per_molecule'] = mean([t.n_clashes for _, t in both])
         out['true_clash_free'] = mean([t.n_clashes == 0 for _, t in both])
         out['clash_excess'] = mean([p.n_clashes - t.n_clashes for p, t in both])
+    return out
+
+
+XsTypes = namedtuple('XsTypes', 'xs_type status')
+Interactions = namedtuple('Interactions', 'n_query n_target n_pairs n_hbonds n_hydrophobic terms status atom_terms xs_type '
+                                          'type_status query_mask')
+InteractionRecord = namedtuple('InteractionRecord', 'n_query n_target n_pairs n_hbonds n_hydrophobic terms score status '
+                                                    'atom_scores')
+INTERACTION_TERMS = ('gauss1', 'gauss2', 'repulsion', 'hydrophobic', 'hbond')
+INTERACTION_NAMES = ('interaction_molecules', 'interaction_flagged', 'interaction_score') + \
+    tuple(f'interaction_{name}' for name in INTERACTION_TERMS) + \
+    ('hbonds_per_molecule', 'hydrophobic_contacts_per_molecule', 'interaction_score_per_atom')
+INTERACTION_TRUE_NAMES = ('true_interaction_score', 'true_hbonds_per_molecule', 'interaction_excess')
+FIXED_ONE = 4294967296.0            # 2^32: one unit of the fixed-point terms
+
+
+def _f32(t, dev):
+    return t.to(device=dev, dtype=torch.float32).contiguous()
+
+
+def interaction_types(one_hot, x, group, is_geom=True, margins=const.MARGINS_EDM):
+    """Heavy atoms typed as hydrophobic, hydrogen-bond donor or acceptor from elements and geometry alone, for every molecule
+    of a batch in one launch of ``dl_interaction_types`` (``csrc/interaction.hip``) on the HIP device.
+
+    ``one_hot [B,N,nf]`` (an atom's element is the first largest entry, in the project's order C O N F S Cl Br I P),
+    ``x [B,N,3]``, ``group [B,N]`` or ``[B,N,1]`` of integers: 0 = the row is not typed and never read; rows of one molecule
+    with the same non-zero id are typed among themselves.  Two rows of a group are NEIGHBOURS when ``perceive_bonds`` would
+    bond them (the single-bond bound of ``const.bond_threshold_table(is_geom, margins)``, the same fp32 arithmetic, strict);
+    ``deg`` counts them, ``hetero`` says one is not carbon.  C is HYDROPHOBIC when not hetero; F, Cl, Br, I are HYDROPHOBIC;
+    N is a DONOR when ``deg < 3`` and never an acceptor; O is always an ACCEPTOR and a DONOR too when ``deg == 0`` (a water)
+    or when ``deg == 1`` and that neighbour lies at ``d2 >= 1.6875`` A^2 (a hydroxyl, not a carbonyl); S and P carry no flag.
+
+    KNOWN MISREADINGS: a pyridine or nitrile N is typed a donor; a histidine's two N are both donors; pocket residues cut at
+    the pocket boundary lose a neighbour.
+
+    Returns ``XsTypes(xs_type, status)``: int32 ``[B,N]`` - the element in bits 0-3, ``_lib.DL_XS_HYDROPHOBIC`` / ``DL_XS_DONOR``
+    / ``DL_XS_ACCEPTOR`` above, -1 on rows of group 0 - and int32 ``[B]``: ``_lib.DL_INTERACT_NONFINITE`` when a typed row is
+    not finite, the molecule's rows are then all -1.  No host synchronisation."""
+    tensors = (one_hot, x, group)
+    if not all(t.is_cuda for t in tensors):
+        raise _lib.HipLibraryError('interaction_types runs on the HIP device only (no CPU fallback): '
+                                   f'got tensors on {", ".join(str(t.device) for t in tensors)}')
+    if one_hot.dim() != 3:
+        raise ValueError(f'one_hot {tuple(one_hot.shape)} is not [B,N,nf]')
+    B, N, nf = one_hot.shape
+    if x.shape != (B, N, 3) or group.numel() != B * N:
+        raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, x {tuple(x.shape)}, group {tuple(group.shape)}')
+    dev = one_hot.device
+    one_hot, x = _f32(one_hot, dev), _f32(x, dev)
+    group = group.to(device=dev, dtype=torch.int32).contiguous().reshape(B, N)
+    table = const.bond_threshold_table(is_geom, margins)[..., 0].contiguous().to(dev)
+    if table.shape != (nf, nf):
+        raise ValueError(f'{nf} atom types in one_hot, {table.shape[0]} in the vocabulary')
+    out = XsTypes(torch.empty((B, N), dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+    if N == 0:
+        return out
+    args = _lib.DLInteractTypesArgs(B=B, N=N, nf=nf, x=x.data_ptr(), one_hot=one_hot.data_ptr(), group=group.data_ptr(),
+                                    table=table.data_ptr(), xs_type=out.xs_type.data_ptr(), status=out.status.data_ptr())
+    with torch.cuda.device(dev):
+        args.stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(_lib.load().dl_interaction_types(ctypes.byref(args)), 'dl_interaction_types')
+    return out
+
+
+def protein_types(positions, types, is_geom=True):
+    """The ``xs_types`` int32 ``[M]`` of a shared target list ``positions [M,3]``, ``types [M]`` (element indices), typed as
+    one group in one launch, for the caller to keep per protein and hand to ``analyze_interactions`` as
+    ``protein = (positions, types, xs_types)``.  An atom whose type is outside the vocabulary is not typed (-1) and is then
+    skipped by the score."""
+    if not (positions.is_cuda and types.is_cuda):
+        raise _lib.HipLibraryError('protein_types runs on the HIP device only (no CPU fallback): '
+                                   f'got tensors on {positions.device}, {types.device}')
+    M = types.numel()
+    if positions.shape != (M, 3):
+        raise ValueError(f'shapes disagree: protein positions {tuple(positions.shape)}, types {tuple(types.shape)}')
+    dev = positions.device
+    nf = const.GEOM_NUMBER_OF_ATOM_TYPES if is_geom else const.NUMBER_OF_ATOM_TYPES
+    if M == 0:
+        return torch.empty(0, dtype=torch.int32, device=dev)
+    types = types.to(device=dev, dtype=torch.int64).reshape(M)
+    known = (types >= 0) & (types < nf)
+    one_hot = torch.nn.functional.one_hot(types.clamp(0, nf - 1), nf).to(torch.float32)
+    return interaction_types(one_hot[None], positions.reshape(1, M, 3), known.to(torch.int32)[None], is_geom).xs_type[0]
+
+
+def analyze_interactions(one_hot, x, query_mask, ligand_mask, target_mask=None, protein=None, is_geom=True,
+                         margins=const.MARGINS_EDM):
+    """Contacts of generated atoms with the protein: the empirical intermolecular terms of Trott & Olson (AutoDock Vina, J.
+    Comput. Chem. 2010) for every molecule of a batch, in two launches on the HIP device (``dl_interaction_types``, then
+    ``dl_interaction_scores``, ``csrc/interaction.hip``).
+
+    THE RULE (this project's own after that published functional form).  QUERY atoms are the rows of ``query_mask`` (the
+    generated atoms); they are typed in the context of the whole ligand, the rows of ``ligand_mask`` (group 1; query rows
+    belong to it whatever ``ligand_mask`` says).  TARGET atoms are the rows of ``target_mask`` that are no query rows (the
+    batch's ``pocket_mask``; typed among themselves as group 2 - a row in both masks is a ligand row) and the atoms of
+    ``protein = (positions [M,3], types [M], xs_types [M])``, a list shared by all molecules, in the frame of ``x``, typed
+    once by ``protein_types``.  Masks are ``[B,N]`` or ``[B,N,1]``.  The typing is ``interaction_types``'s.  For a query atom
+    ``a`` and a target atom ``b``, in fp64 without fused multiply-adds from the fp32 coordinates: the pair counts when
+    ``d2 < 64`` (8 A, strict); ``s = sqrt(d2) - (R[a] + R[b])`` with ``const.XS_RADII``;
+    ``gauss1 = exp(-(s / 0.5)^2)``, ``gauss2 = exp(-((s - 3) / 2)^2)``, ``repulsion = s^2`` when ``s < 0``,
+    ``hydrophobic`` (both atoms HYDROPHOBIC) 1 below ``s = 0.5`` falling to 0 at 1.5, ``hbond`` (a donor facing an acceptor)
+    1 below ``s = -0.7`` falling to 0 at 0.  Every pair term is rounded to a 64-bit fixed point with 32 fractional bits and
+    all sums are integer sums: the same bits on every run.
+
+    Returns an ``Interactions`` of device tensors: ``n_query``, ``n_target``, ``n_pairs`` (inside the cut), ``n_hbonds``,
+    ``n_hydrophobic`` (int32 ``[B]``), ``terms`` (int64 ``[B,5]`` fixed point: gauss1, gauss2, repulsion, hydrophobic, hbond),
+    ``status`` (int32 ``[B]``: ``_lib.DL_INTERACT_*`` bits; with ``NONFINITE``, ``TOO_LARGE`` - more than 1024 query atoms -
+    or ``UNTYPED`` everything else is 0), ``atom_terms`` (int64 ``[B,N,5]``, 0 on non-query rows), ``xs_type`` and
+    ``type_status`` of the typing launch and the ``query_mask`` it was given.  ``interactions_to_host`` forms the weighted
+    score.  No host synchronisation.
+
+    What this is NOT: AutoDock Vina's numbers.  No hydrogens, no PDBQT typing, no search or pose optimisation, no
+    intramolecular term and no rotor normalisation (the published rotor weight is not used)."""
+    shared = () if protein is None else tuple(protein)
+    tensors = (one_hot, x, query_mask, ligand_mask) + (() if target_mask is None else (target_mask,)) + shared
+    if not all(t.is_cuda for t in tensors):
+        raise _lib.HipLibraryError('analyze_interactions runs on the HIP device only (no CPU fallback): '
+                                   f'got tensors on {", ".join(str(t.device) for t in tensors)}')
+    if one_hot.dim() != 3:
+        raise ValueError(f'one_hot {tuple(one_hot.shape)} is not [B,N,nf]')
+    B, N, nf = one_hot.shape
+    if x.shape != (B, N, 3) or any(m.numel() != B * N for m in (query_mask, ligand_mask)) or \
+            (target_mask is not None and target_mask.numel() != B * N):
+        raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, x {tuple(x.shape)}, query_mask '
+                         f'{tuple(query_mask.shape)}, ligand_mask {tuple(ligand_mask.shape)}')
+    if protein is not None and len(shared) != 3:
+        raise ValueError(f'protein is (positions, types, xs_types): got {len(shared)} members')
+    dev = one_hot.device
+    radius = const.xs_radius_table(is_geom).to(dev)
+    if radius.numel() != nf:
+        raise ValueError(f'{nf} atom types in one_hot, {radius.numel()} in the vocabulary')
+    one_hot, x, qm = _f32(one_hot, dev), _f32(x, dev), _f32(query_mask, dev).reshape(B, N)
+    lig = (_f32(ligand_mask, dev).reshape(B, N) != 0) | (qm != 0)
+    tm = None if target_mask is None else _f32(target_mask, dev).reshape(B, N)
+    M, px, pxs = 0, None, None
+    if protein is not None:
+        px, pxs = _f32(shared[0], dev), shared[2].to(device=dev, dtype=torch.int32).contiguous()
+        M = pxs.numel()
+        if px.shape != (M, 3) or shared[1].numel() != M:
+            raise ValueError(f'shapes disagree: protein positions {tuple(px.shape)}, types {tuple(shared[1].shape)}, xs_types '
+                             f'{tuple(pxs.shape)}')
+    group = lig.to(torch.int32)
+    if tm is not None:
+        group = group + 2 * ((tm != 0) & ~lig).to(torch.int32)
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    if N == 0:
+        zero = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)  # noqa: E731
+        return Interactions(zero(B), zero(B), zero(B), zero(B), zero(B), torch.zeros((B, 5), dtype=torch.int64, device=dev),
+                            zero(B), torch.zeros((B, 0, 5), dtype=torch.int64, device=dev), i32(B, 0), zero(B), qm)
+    typed = interaction_types(one_hot, x, group, is_geom, margins)
+    out = Interactions(i32(B), i32(B), i32(B), i32(B), i32(B), torch.empty((B, 5), dtype=torch.int64, device=dev), i32(B),
+                       torch.empty((B, N, 5), dtype=torch.int64, device=dev), typed.xs_type, typed.status, qm)
+    args = _lib.DLInteractArgs(
+        B=B, N=N, nf=nf, x=x.data_ptr(), xs_type=typed.xs_type.data_ptr(), query_mask=qm.data_ptr(),
+        target_mask=None if tm is None else tm.data_ptr(), M=M, target_x=px.data_ptr() if M else None,
+        target_xs=pxs.data_ptr() if M else None, radius=radius.data_ptr(),
+        n_query=out.n_query.data_ptr(), n_target=out.n_target.data_ptr(), n_pairs=out.n_pairs.data_ptr(),
+        n_hbonds=out.n_hbonds.data_ptr(), n_hydrophobic=out.n_hydrophobic.data_ptr(), terms=out.terms.data_ptr(),
+        status=out.status.data_ptr(), atom_terms=out.atom_terms.data_ptr())
+    with torch.cuda.device(dev):
+        args.stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(_lib.load().dl_interaction_scores(ctypes.byref(args)), 'dl_interaction_scores')
+    return out
+
+
+def interaction_score(terms):
+    """The weighted score of five fixed-point term sums, in fp64: ``sum(w_k * terms_k) / 2^32`` with
+    ``const.INTERACTION_WEIGHTS``, the terms taken in order.  Negative is favourable."""
+    total = 0.0
+    for w, t in zip(const.INTERACTION_WEIGHTS, terms):
+        total += w * float(t)
+    return total / FIXED_ONE
+
+
+def interactions_to_host(result):
+    """The ``InteractionRecord`` values ``compute_interactions`` reads, one per molecule of an ``Interactions``, on the host:
+    the counts as ints, ``terms`` as the five fixed-point integers, ``score`` (``interaction_score`` of them), ``status``, and
+    ``atom_scores``: the weighted score of every QUERY atom, in row order."""
+    cols = [getattr(result, name).cpu().tolist() for name in ('n_query', 'n_target', 'n_pairs', 'n_hbonds', 'n_hydrophobic')]
+    terms, status = result.terms.cpu().tolist(), result.status.cpu().tolist()
+    rows = result.query_mask.cpu() != 0
+    atom = result.atom_terms.cpu()
+    return [InteractionRecord(cols[0][b], cols[1][b], cols[2][b], cols[3][b], cols[4][b], terms[b], interaction_score(terms[b]),
+                              status[b], [interaction_score(t) for t in atom[b][rows[b]].tolist()])
+            for b in range(len(status))]
+
+
+def _interaction_scored(record):
+    return not record.status & (_lib.DL_INTERACT_NONFINITE | _lib.DL_INTERACT_TOO_LARGE | _lib.DL_INTERACT_UNTYPED)
+
+
+def compute_interactions(pred, true=None):
+    """Scores of the ``InteractionRecord`` values ``pred`` (``interactions_to_host``), plain numbers:
+
+    ``interaction_molecules``               records scored: the flagged ones (``DL_INTERACT_NONFINITE`` / ``TOO_LARGE`` /
+                                            ``UNTYPED``: their sums mean nothing) are left out of everything below
+    ``interaction_flagged``                 how many were left out
+    ``interaction_score``                   mean weighted sum (negative is favourable)
+    ``interaction_gauss1`` ... ``_hbond``   mean raw terms, unweighted
+    ``hbonds_per_molecule``                 mean number of pairs with a hydrogen-bond term above 0
+    ``hydrophobic_contacts_per_molecule``   mean number of pairs with a hydrophobic term above 0
+    ``interaction_score_per_atom``          the weighted sums over the query atoms, both summed over the scored records
+
+    With ``true`` - one record per prediction: the data set's own linker scored in the same pocket - three more keys, over the
+    positions where both records are scored: ``true_interaction_score``, ``true_hbonds_per_molecule`` and
+    ``interaction_excess`` (the mean of ``pred - true`` weighted sums: positive means the sample binds worse under this rule).
+    Without ``true`` they are absent.  Nothing scored: every mean is 0."""
+    if true is not None and len(true) != len(pred):
+        raise ValueError(f'{len(pred)} predictions, {len(true)} true records')
+    good = [m for m in pred if _interaction_scored(m)]
+    n = len(good)
+    mean = lambda values: float(sum(values) / len(values)) if values else 0.0      # noqa: E731
+    queries = sum(m.n_query for m in good)
+    out = {'interaction_molecules': n, 'interaction_flagged': len(pred) - n, 'interaction_score': mean([m.score for m in good])}
+    for k, name in enumerate(INTERACTION_TERMS):
+        out[f'interaction_{name}'] = mean([m.terms[k] / FIXED_ONE for m in good])
+    out['hbonds_per_molecule'] = mean([m.n_hbonds for m in good])
+    out['hydrophobic_contacts_per_molecule'] = mean([m.n_hydrophobic for m in good])
+    out['interaction_score_per_atom'] = float(sum(m.score for m in good) / queries) if queries else 0.0
+    if true is not None:
+        both = [(p, t) for p, t in zip(pred, true) if _interaction_scored(p) and _interaction_scored(t)]
+        out['true_interaction_score'] = mean([t.score for _, t in both])
+        out['true_hbonds_per_molecule'] = mean([t.n_hbonds for _, t in both])
+        out['interaction_excess'] = mean([p.score - t.score for p, t in both])
     return out
 
 

@@ -57,7 +57,8 @@ def _prepare(checkpoint, prefix, data, n_steps, device):
 
 def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=None, linker_size_model=None,
            output_format='xyz', metrics=False, geometry=False, clashes=False, shape=False, rings=False,
-           bond_orders='distance', aromatic=False, diversity=False, diversity_reference=None, pharmacophore=False):
+           bond_orders='distance', aromatic=False, diversity=False, diversity_reference=None, pharmacophore=False,
+           interactions=False):
     """``sample.py``.  Returns the output directory.  ``metrics=True`` scores the molecules sampled in this call against
     the data set's own (``metrics.compute_metrics``: valence rule, connectivity, uniqueness, novelty, recovery) and writes
     the result to ``metrics.json`` in the output directory; with ``geometry=True`` as well, the symmetry-aware RMSD of the
@@ -88,7 +89,11 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
     (``metrics.analyze_pharmacophores`` / ``compute_pharmacophores``), on the pairs and rows of ``shape=True``: ligand rows
     without the pocket, the linker marked.  ``feature_similarity`` and ``feature_similarity_linker`` go into ``metrics.json``,
     and with ``shape=True`` as well ``sc_similarity`` and ``sc_similarity_7/8/9``, where the reference has SC-RDKit.  The
-    features are this project's own, after RDKit's ``BaseFeatures.fdef`` and ``FeatMapParams`` defaults, not RDKit's numbers."""
+    features are this project's own, after RDKit's ``BaseFeatures.fdef`` and ``FeatMapParams`` defaults, not RDKit's numbers.
+    ``interactions=True`` (pocket data sets only; others raise ``ValueError``) scores the contacts of every sample's LINKER
+    atoms, typed in the context of the whole ligand, with its pocket atoms, and of the data set's own linker in the same
+    pocket as ``true`` (``metrics.analyze_interactions`` / ``compute_interactions``: the intermolecular terms of Trott &
+    Olson under this project's own heavy-atom typing - not AutoDock Vina's numbers); the keys go into ``metrics.json``."""
     if output_format not in OUTPUT_FORMATS:
         raise ValueError(f'output_format must be one of {OUTPUT_FORMATS}, got {output_format!r}')
     if bond_orders not in BOND_ORDERS:
@@ -97,6 +102,7 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
     found, pred, true, input_index = [], [], [], []
     pred_x, true_x, n_linker = [], [], []
     pred_clashes, true_clashes = [], []
+    pred_contacts, true_contacts = [], []
     shapes, linker_shapes = [], []
     pharm, linker_pharm = [], []
     pred_rings, true_rings = [], []
@@ -128,6 +134,8 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
     moad = isinstance(model.val_dataset, MOADDataset)
     if clashes and not (len(model.val_dataset) and 'pocket_mask' in model.val_dataset[0]):
         raise ValueError('clashes are scored against the pocket atoms: this data set has no pocket_mask')
+    if interactions and not (len(model.val_dataset) and 'pocket_mask' in model.val_dataset[0]):
+        raise ValueError('interactions are scored against the pocket atoms: this data set has no pocket_mask')
     for batch_idx, batch in enumerate(model.val_dataloader(collate_fn=collate_fn)):
         uuids = [str(u) for u in batch['uuid']]
         for u in uuids:
@@ -156,6 +164,10 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
         if clashes:                                            # the data set's own linker in the same pocket
             true_clash_batch = mol_metrics.clashes_to_host(mol_metrics.analyze_clashes(
                 h[:, :, :model.num_classes], x, batch['linker_mask'], batch['pocket_mask'], is_geom=model.is_geom))
+        if interactions:                                       # likewise; typed in the context of the whole true ligand
+            true_contact_batch = mol_metrics.interactions_to_host(mol_metrics.analyze_interactions(
+                h[:, :, :model.num_classes], x, batch['linker_mask'], batch['atom_mask'] - batch['pocket_mask'],
+                batch['pocket_mask'], is_geom=model.is_geom))
         if rings:                                              # the data set's own molecule, without the pocket
             true_ring_batch = mol_metrics.rings_to_host(*mol_metrics.analyze_rings(
                 h[:, :, :model.num_classes], x, node_mask, model.is_geom, batch['linker_mask']))
@@ -177,6 +189,12 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                     hs[:, :, :model.num_classes], xs, out_mask * (1 - pad(batch['fragment_mask'])), pad(batch['pocket_mask']),
                     is_geom=model.is_geom))
                 true_clashes += true_clash_batch
+            if interactions:                                   # the same rows; the ligand is the template without its pocket
+                pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, out_mask.shape[1] - m.shape[1]))      # noqa: E731
+                pred_contacts += mol_metrics.interactions_to_host(mol_metrics.analyze_interactions(
+                    hs[:, :, :model.num_classes], xs, out_mask * (1 - pad(batch['fragment_mask'])),
+                    out_mask * (1 - pad(batch['pocket_mask'])), pad(batch['pocket_mask']), is_geom=model.is_geom))
+                true_contacts += true_contact_batch
             if moad:
                 pock = batch['pocket_mask']
                 if pock.shape[1] < out_mask.shape[1]:          # template wider than the input (sampled sizes)
@@ -232,7 +250,7 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 n_linker += n_linker_batch
     if found:
         print(json.dumps(summary(found)))
-    if metrics or clashes or shape or rings or aromatic or diversity or pharmacophore:
+    if metrics or clashes or shape or rings or aromatic or diversity or pharmacophore or interactions:
         with open(os.path.join(output_dir, 'metrics.json'), 'w') as f:
             scores = {}
             if metrics:
@@ -241,6 +259,8 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 scores.update(mol_metrics.compute_geometry(pred, true, pred_x, true_x, n_linker))
             if clashes:
                 scores.update(mol_metrics.compute_clashes(pred_clashes, true_clashes))
+            if interactions:
+                scores.update(mol_metrics.compute_interactions(pred_contacts, true_contacts))
             if shape:
                 scores.update(mol_metrics.compute_shapes(shapes, linker_shapes, pred if metrics else None))
             if pharmacophore:
@@ -363,6 +383,10 @@ def main(argv=None):
                         'feature-map score to metrics.json (feature_similarity, feature_similarity_linker; with --shape also '
                         'sc_similarity and sc_similarity_7/8/9 - this project\'s features after RDKit\'s BaseFeatures.fdef, not '
                         'SC-RDKit\'s numbers)')
+    p.add_argument('--interactions', action='store_true',
+                   help='pocket data sets: score the contacts of the sampled linkers (and of the true ones) with the pocket '
+                        'atoms on the GPU - the intermolecular terms of Trott & Olson under this project\'s heavy-atom typing, '
+                        'not AutoDock Vina\'s numbers - and write the scores to metrics.json')
     a = p.parse_args(argv)
     if a.keep_frames is not None:
         print(sample_trajectories(a.checkpoint, a.samples, a.prefix, a.keep_frames, a.device, a.data, a.n_steps))
@@ -374,7 +398,8 @@ def main(argv=None):
                      **({'bond_orders': a.bond_orders} if a.bond_orders != 'distance' else {}),
                      **({'aromatic': True} if a.aromatic else {}), **({'diversity': True} if a.diversity else {}),
                      **({'diversity_reference': a.diversity_reference} if a.diversity_reference else {}),
-                     **({'pharmacophore': True} if a.pharmacophore else {})))
+                     **({'pharmacophore': True} if a.pharmacophore else {}),
+                     **({'interactions': True} if a.interactions else {})))
 
 
 if __name__ == '__main__':

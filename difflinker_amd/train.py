@@ -112,6 +112,10 @@ def main(argv=None):
                    help='with --sample_every_epochs: add the feature-map score of every sample\'s pharmacophore features '
                         'against its true molecule\'s to the epoch scores (feature_similarity(_linker); with --shape also '
                         'sc_similarity; this project\'s features after RDKit\'s BaseFeatures.fdef, not RDKit\'s numbers)')
+    p.add_argument('--interactions', action='store_true',
+                   help='with --sample_every_epochs, pocket models: add the contact scores of the sampled linkers with the '
+                        'pocket atoms to the epoch scores (the intermolecular terms of Trott & Olson under this project\'s '
+                        'heavy-atom typing, not AutoDock Vina\'s numbers)')
     a = p.parse_args(argv)
     cfg = dict(DEFAULTS)
     if a.config is not None:
@@ -146,6 +150,7 @@ def main(argv=None):
         model.test_epochs = a.sample_every_epochs
     model.geometry_metrics = bool(a.geometry)
     model.clash_metrics = bool(a.clashes)
+    model.interaction_metrics = bool(a.interactions)
     model.shape_metrics = bool(a.shape)
     model.ring_metrics = bool(a.rings)
     model.aromatic_metrics = bool(a.aromatic)

@@ -45,6 +45,13 @@
  *   dl_clash_scores                      <- (no reference counterpart: the paper reports clash counts of pocket samples, the
  *                                           scripts do not compute them) generated atoms against protein atoms under a
  *                                           van der Waals rule stated below, one launch per batch
+ *   dl_interaction_types / dl_interaction_scores
+ *                                        <- (no reference counterpart: the field answers "does it make contacts?" with an
+ *                                           external docking program) heavy atoms typed as hydrophobic, donor or acceptor
+ *                                           from elements and geometry, and the intermolecular terms of Trott & Olson
+ *                                           (AutoDock Vina, J. Comput. Chem. 2010) between generated and protein atoms, in
+ *                                           place.  The rule stated below is this project's own after that published
+ *                                           form, NOT AutoDock Vina's numbers
  *   dl_shape_scores                      <- the shape half of SC-RDKit (src/delinker_utils/calc_SC_RDKit.py:36-38,
  *                                           1 - rdShapeHelpers.ShapeProtrudeDist, compute_metrics.py:404-441): the gridded
  *                                           van der Waals overlap of every sample with its true molecule.  The rule stated
@@ -815,6 +822,116 @@ typedef struct dl_clash_args {
     float* atom_min_dist2;          /* device f32 [B,N] out */
 } dl_clash_args;
 int32_t dl_clash_scores(const dl_clash_args* args, void* stream);
+
+/* ---- contacts of generated atoms with the protein: interaction terms (interaction.hip) ------------------------------
+ * Does the linker make contacts, and more or fewer than the data set's own linker in the same pocket?  dl_clash_scores
+ * cannot say: a linker that runs out into the solvent is clash free.  These two entry points evaluate the empirical
+ * intermolecular terms of Trott & Olson (AutoDock Vina, J. Comput. Chem. 31, 455 (2010)): two steric Gaussians, a
+ * repulsion, a hydrophobic term and a hydrogen-bond term over surface distances.  THE RULE IS THIS PROJECT'S OWN after that
+ * published functional form.  It is NOT AutoDock Vina's numbers: no hydrogens, no PDBQT typing, no search or pose
+ * optimisation, no intramolecular term and no rotor normalisation (the published rotor weight is not used).
+ * tests/interaction_ref.py restates both entry points in numpy.
+ *
+ * dl_interaction_types: TYPING from elements and geometry alone.  An atom's element is the index of the first largest
+ * entry of its one_hot row, in the project's atom order C O N F S Cl Br I P (indices 0 to 8; further indices carry no flag).
+ * `group` says which rows are typed together: 0 = the row is not typed and is never read; rows of one molecule with the
+ * same non-zero id are typed among themselves (the callers use 1 for the ligand and 2 for the pocket; a whole protein is
+ * B = 1, N = M, all in group 1).  Two rows i > j of a group are NEIGHBOURS when dl_perceive_bonds would give them an
+ * order >= 1: d = 100 * sqrtf(dx*dx + dy*dy + dz*dz) in fp32 exactly as bonds.hip evaluates it (one shared device function),
+ * and d < table[element of i][element of j], STRICTLY; `table` is the [nf][nf] single-bond bound in pm,
+ * const.bond_threshold_table(...)[..., 0] (a negative entry: never neighbours).  deg is the number of neighbours of a row,
+ * hetero says that some neighbour is not carbon.  xs_type = element | flags:
+ *     C               DL_XS_HYDROPHOBIC when not hetero
+ *     F, Cl, Br, I    DL_XS_HYDROPHOBIC
+ *     N               DL_XS_DONOR when deg < 3; never an acceptor
+ *     O               DL_XS_ACCEPTOR always; DL_XS_DONOR too when deg == 0 (a water), or when deg == 1 and its one
+ *                     neighbour lies at d2 >= 1.6875 A^2, d2 = ((dx*dx) + (dy*dy)) + (dz*dz) in fp32 as dl_clash_scores
+ *                     computes it (27/16, 1.299 A: a hydroxyl, not a carbonyl or carboxylate oxygen)
+ *     S, P            no flag
+ * Rows of group 0 get -1.  KNOWN MISREADINGS: a pyridine or nitrile N is typed a donor; both N of a histidine ring are
+ * donors; pocket residues cut at the pocket boundary lose a neighbour (the peptide bond to a residue outside the pocket
+ * is missing, so a proline N there has two neighbours and is typed a donor).  A molecule with a typed row whose coordinates are not finite gets
+ * status DL_INTERACT_NONFINITE and -1 on every row; the other molecules of the launch are not touched.  One 256-thread
+ * workgroup per molecule, any N: candidates stream through a 256-entry LDS tile.
+ *
+ * dl_interaction_scores: THE PAIR TERMS.  Queries and targets as for dl_clash_scores: the query atoms of a molecule are its
+ * rows with query_mask != 0, its targets the rows with target_mask != 0 that are not query rows, followed by the shared list
+ * target_x / target_xs; rows in neither mask are never read.  xs_type [B,N] and target_xs [M] are what dl_interaction_types
+ * wrote; radius[nf] is an fp64 table in Angstrom (const.XS_RADII).  For a query atom a and a target atom b, in fp64 with no
+ * fused multiply-add, from the fp32 coordinates widened to fp64:
+ *     dx = xq - xt (dy, dz alike);  d2 = ((dx*dx) + (dy*dy)) + (dz*dz)
+ *     the pair counts when d2 < 64.0            (8 A, strict)
+ *     r = sqrt(d2);  s = r - (radius[a] + radius[b])
+ *     gauss1      = exp(-((s / 0.5) * (s / 0.5)))
+ *     gauss2      = exp(-(((s - 3.0) / 2.0) * ((s - 3.0) / 2.0)))
+ *     repulsion   = s < 0 ? s * s : 0
+ *     hydrophobic = both DL_XS_HYDROPHOBIC ? (s < 0.5 ? 1 : s < 1.5 ? 1.5 - s : 0) : 0
+ *     hbond       = (a donor and b acceptor) or (a acceptor and b donor) ? (s < -0.7 ? 1 : s < 0 ? -s / 0.7 : 0) : 0
+ * Every pair term becomes a signed 64-bit fixed point, llrint(term * 2^32), and ALL sums are integer sums: the same bits on
+ * every run and under every mapping of pairs to lanes.  THE RANGE: a term is below 20 (the repulsion at s = -4.4, the
+ * largest radius sum), so 1024 queries x 65536 targets x 20 x 2^32 stays below 2^63 - and only pairs inside 8 A add anything.
+ *
+ *   n_query, n_target   atoms on either side (in-batch targets plus the shared atoms that have a type)
+ *   n_pairs             pairs inside the cut
+ *   n_hbonds            pairs with hbond > 0
+ *   n_hydrophobic       pairs with hydrophobic > 0
+ *   terms               [B,5] fixed point: gauss1, gauss2, repulsion, hydrophobic, hbond summed over the pairs
+ *   atom_terms          [B,N,5] fixed point: the same per query row; 0 on non-query rows
+ *   status              0, or DL_INTERACT_* bits.  A molecule with a bit set does not touch the other molecules of the launch.
+ * The host forms the weighted score in fp64, sum(w_k * terms_k) / 2^32 with the published weights
+ * (const.INTERACTION_WEIGHTS).
+ *
+ * With DL_INTERACT_NONFINITE (a query or target coordinate is NaN or infinite), DL_INTERACT_TOO_LARGE (more than 1024
+ * query atoms; decided first, the molecule is not looked at further) or DL_INTERACT_UNTYPED (a query row or in-batch target
+ * row whose xs_type is negative or whose element is not below nf) every output of the molecule but `status` is 0.  A shared
+ * atom whose target_xs is negative or whose element is not below nf is skipped, coordinates and all, and sets
+ * DL_INTERACT_BAD_TYPE on every molecule; the other outputs stay valid.
+ *
+ * Both take their struct alone, with the stream as its last field, as dl_fingerprints does.  Global memory is written with plain stores only, no atomics, every output element is written; the callee allocates
+ * nothing.  A null `args`, B < 0, N < 1, nf < 1 or > 16 (or M < 0) return DL_ERR_BAD_ARG; then B == 0 returns DL_OK without a
+ * launch; then null pointers (`target_mask` may always be NULL; `target_x` and `target_xs` may be NULL when M is 0) return
+ * DL_ERR_BAD_ARG, all before any device work. */
+#define DL_XS_HYDROPHOBIC 16        /* xs_type bit 4 (bits 0-3: the element index) */
+#define DL_XS_DONOR 32              /* xs_type bit 5 */
+#define DL_XS_ACCEPTOR 64           /* xs_type bit 6 */
+#define DL_INTERACT_TERMS 5         /* gauss1, gauss2, repulsion, hydrophobic, hbond */
+#define DL_INTERACT_NONFINITE 1     /* status bit: a typed row, a query or a target coordinate is NaN or infinite */
+#define DL_INTERACT_TOO_LARGE 2     /* status bit: more than 1024 query atoms */
+#define DL_INTERACT_BAD_TYPE 4      /* status bit: a shared atom without a usable target_xs was skipped */
+#define DL_INTERACT_UNTYPED 8       /* status bit: a query or in-batch target row without a usable xs_type */
+typedef struct dl_interact_types_args {
+    int32_t B, N, nf;
+    const float* x;                 /* device f32 [B,N,3], Angstrom */
+    const float* one_hot;           /* device f32 [B,N,nf] */
+    const int32_t* group;           /* device int32 [B,N]: 0 = not typed */
+    const float* table;             /* device f32 [nf,nf]: single-bond upper bounds, pm */
+    int32_t* xs_type;               /* device int32 [B,N] out */
+    int32_t* status;                /* device int32 [B] out */
+    void* stream;                   /* hipStream_t; NULL: the default stream */
+} dl_interact_types_args;
+int32_t dl_interaction_types(const dl_interact_types_args* args);
+
+typedef struct dl_interact_args {
+    int32_t B, N, nf;
+    const float* x;                 /* device f32 [B,N,3], Angstrom */
+    const int32_t* xs_type;         /* device int32 [B,N] */
+    const float* query_mask;        /* device f32 [B,N] */
+    const float* target_mask;       /* device f32 [B,N] or NULL: in-batch targets (the reference's pocket_mask) */
+    int32_t M;                      /* atoms of the shared target list, may be 0 */
+    const float* target_x;          /* device f32 [M,3], in the frame of `x` */
+    const int32_t* target_xs;       /* device int32 [M] */
+    const double* radius;           /* device f64 [nf], Angstrom */
+    int32_t* n_query;               /* device int32 [B] out */
+    int32_t* n_target;              /* device int32 [B] out */
+    int32_t* n_pairs;               /* device int32 [B] out */
+    int32_t* n_hbonds;              /* device int32 [B] out */
+    int32_t* n_hydrophobic;         /* device int32 [B] out */
+    int64_t* terms;                 /* device int64 [B,5] out */
+    int32_t* status;                /* device int32 [B] out */
+    int64_t* atom_terms;            /* device int64 [B,N,5] out */
+    void* stream;                   /* hipStream_t; NULL: the default stream */
+} dl_interact_args;
+int32_t dl_interaction_scores(const dl_interact_args* args);
 
 /* ---- gridded shape overlap of two molecules in one frame (shape.hip) ---------------------------------------------
  * Where does a sample lie in space, compared with the molecule it was sampled for?  The reference answers with SC-RDKit; half
