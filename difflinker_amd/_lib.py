@@ -345,6 +345,24 @@ class DLPharmArgs(ctypes.Structure):                  # the stream is the last F
     ]
 
 
+DL_HYDRO_MAX_ATOMS = 256                              # dl_hydrogens_args: kept atoms per molecule
+DL_HYDRO_TOO_LARGE, DL_HYDRO_BAD_BOND = 4, 8          # dl_hydrogens_args.status bits, beside the DL_BONDS_* bits carried forward
+DL_HYDRO_OVERFLOW, DL_HYDRO_NONFINITE = 32, 64
+
+
+class DLHydrogensArgs(ctypes.Structure):                # the stream is the last FIELD, as for dl_fingerprints
+    _fields_ = [
+        ('B', ctypes.c_int32), ('N', ctypes.c_int32), ('nf', ctypes.c_int32),
+        ('x', ctypes.c_void_p), ('one_hot', ctypes.c_void_p), ('node_mask', ctypes.c_void_p),
+        ('drop_mask', ctypes.c_void_p), ('atom_planar', ctypes.c_void_p), ('default_valence', ctypes.c_void_p),
+        ('xh_length', ctypes.c_void_p), ('capacity', ctypes.c_int32),
+        ('n_bonds_in', ctypes.c_void_p), ('bonds', ctypes.c_void_p), ('status_in', ctypes.c_void_p),
+        ('Hcap', ctypes.c_int32),
+        ('n_h', ctypes.c_void_p), ('h_count', ctypes.c_void_p), ('h_parent', ctypes.c_void_p), ('h_x', ctypes.c_void_p),
+        ('status', ctypes.c_void_p), ('stream', ctypes.c_void_p),
+    ]
+
+
 class DLFeatureMatchArgs(ctypes.Structure):           # likewise
     _fields_ = [
         ('B', ctypes.c_int32), ('Fa', ctypes.c_int32), ('Fb', ctypes.c_int32),
@@ -369,7 +387,7 @@ EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_stri
            'dl_egnn_backward_pocket_workspace_bytes', 'dl_egnn_backward_pocket',
            'dl_size_train_num_params', 'dl_size_train_workspace_bytes', 'dl_size_train_forward', 'dl_size_train_backward',
            'dl_join_workspace_bytes', 'dl_sample_chain_fc_join', 'dl_bonds_workspace_bytes', 'dl_perceive_bonds',
-           'dl_interaction_types', 'dl_interaction_scores',
+           'dl_interaction_types', 'dl_interaction_scores', 'dl_add_hydrogens',
            'dl_molecule_keys', 'dl_clash_scores', 'dl_shape_scores', 'dl_ring_scores', 'dl_fragment_cuts',
            'dl_pocket_select', 'dl_fragment_multicuts', 'dl_aromatic_rings', 'dl_fingerprints',
            'dl_tanimoto_nearest', 'dl_pharmacophore_features', 'dl_feature_match', 'dl_best_rmsd')
@@ -518,6 +536,8 @@ def _open(path):
     lib.dl_pharmacophore_features.argtypes = [ctypes.POINTER(DLPharmArgs)]
     lib.dl_feature_match.restype = i32
     lib.dl_feature_match.argtypes = [ctypes.POINTER(DLFeatureMatchArgs)]
+    lib.dl_add_hydrogens.restype = i32
+    lib.dl_add_hydrogens.argtypes = [ctypes.POINTER(DLHydrogensArgs)]
     lib.dl_pocket_select.restype = i32
     lib.dl_pocket_select.argtypes = [ctypes.POINTER(DLPocketArgs), vp]
     lib.dl_best_rmsd.restype = i32

@@ -132,6 +132,17 @@ def default_valence_table(is_geom):
     return torch.tensor([DEFAULT_VALENCE[idx2atom[k]] for k in range(len(idx2atom))], dtype=torch.int32)
 
 
+# X-H bond lengths in Angstrom at which ``molecule_builder.add_hydrogens`` places a hydrogen on an atom of every element
+# (the usual textbook single-bond lengths to hydrogen; the rule itself is stated in ``include/difflinker_hip.h``)
+XH_LENGTH = {'C': 1.09, 'N': 1.01, 'O': 0.96, 'F': 0.92, 'S': 1.34, 'Cl': 1.27, 'Br': 1.41, 'I': 1.61, 'P': 1.42}
+
+
+def xh_length_table(is_geom):
+    """fp64 ``[n_types]``: the X-H bond length of every element of the vocabulary, in index order (``XH_LENGTH``)."""
+    idx2atom = GEOM_IDX2ATOM if is_geom else IDX2ATOM
+    return torch.tensor([XH_LENGTH[idx2atom[k]] for k in range(len(idx2atom))], dtype=torch.float64)
+
+
 # Bondi's van der Waals radii in Angstrom (J. Phys. Chem. 68, 441 (1964)) by GEOM atom index (C O N F S Cl Br I P; the ZINC
 # vocabulary is the leading 8): what the clash rule of ``metrics.analyze_clashes`` is built from
 VDW_RADII = (1.70, 1.52, 1.55, 1.47, 1.80, 1.75, 1.85, 1.98, 1.80)

@@ -22,7 +22,7 @@ from .datasets import MOADDataset, collate_with_fragment_edges, collate_with_fra
 from .io import get_pocket, get_protein_atoms, parse_molecule, pocket_arrays, read_molecule, read_pocket, save_sdf_file, save_xyz_file
 from .lightning import DDPM
 from .linker_size import SizeClassifier
-from .molecule_builder import perceive_all_bonds, refine_bond_orders, summary
+from .molecule_builder import add_hydrogens, perceive_all_bonds, refine_bond_orders, summary
 from .utils import FoundNaNException
 
 
@@ -79,13 +79,21 @@ OUTPUT_FORMATS = ('xyz', 'sdf', 'both')
 BOND_ORDERS = ('distance', 'geometric')
 
 
+def _check_hydrogens(hydrogens, output_format):
+    if hydrogens and output_format == 'xyz':
+        raise ValueError('hydrogens are written to the .sdf files: pass output_format sdf or both (--output_format); the '
+                         '.xyz files stay the heavy-atom format of the reference')
+
+
 def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_dir, name, com_key, hide_pocket,
                      output_format='xyz', metrics=False, clashes=False, protein=None, rings=False, bond_orders='distance',
-                     aromatic=False, diversity=False, interactions=False, typed_protein=None):
+                     aromatic=False, diversity=False, interactions=False, typed_protein=None, hydrogens=False):
     if output_format not in OUTPUT_FORMATS:
         raise ValueError(f'output_format must be one of {OUTPUT_FORMATS}, got {output_format!r}')
     if bond_orders not in BOND_ORDERS:
         raise ValueError(f'bond_orders must be one of {BOND_ORDERS}, got {bond_orders!r}')
+    _check_hydrogens(hydrogens, output_format)
+    n_hydrogens = []
     written, found, scored, clash_records, ring_records, aromatic_records = [], [], [], [], [], []
     prints, contact_records = [], []
     for batch_i, data in enumerate(_batches(dataset, batch_size, collate_fn)):
@@ -135,10 +143,17 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
         if output_format != 'xyz':                            # on the chain's output, before it leaves the device
             found.append(perceive_all_bonds(h, x, node_mask, ddpm.is_geom))
             shown = found[-1]
+            planar = None
             if bond_orders == 'geometric':                    # Kekule orders for the planar rings, from the same geometry
-                shown = refine_bond_orders(shown, h[:, :, :ddpm.num_classes], x, node_mask, ddpm.is_geom)[0]
+                shown, ring_atoms = refine_bond_orders(shown, h[:, :, :ddpm.num_classes], x, node_mask, ddpm.is_geom)
+                planar = ring_atoms.atom_aromatic
+            more = {}
+            if hydrogens:                                     # on the list the file is written with
+                more['hydrogens'] = add_hydrogens(shown, h[:, :, :ddpm.num_classes], x, node_mask, ddpm.is_geom,
+                                                  atom_planar=planar)
+                n_hydrogens.append(more['hydrogens'].n_h)
             save_sdf_file(output_dir, h, x, node_mask, shown.bonds, shown.n_bonds, names=names,
-                          is_geom=ddpm.is_geom, suffix='')
+                          is_geom=ddpm.is_geom, suffix='', **more)
             written += [os.path.join(output_dir, f'{nm}_.sdf') for nm in names]
         if metrics:                                           # the molecules as written: without the pocket
             types = h[:, :, :ddpm.num_classes]
@@ -156,7 +171,10 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
             prints.append(mol_metrics.analyze_fingerprints(
                 h[:, :, :ddpm.num_classes], x, node_mask, ddpm.is_geom, node_mask * (1 - pad(data['fragment_mask']))))
     if found:
-        print(json.dumps(summary(found)))
+        line = summary(found)
+        if hydrogens:
+            line['hydrogens_per_molecule'] = float(torch.cat(n_hydrogens).float().mean()) if line['molecules'] else 0.0
+        print(json.dumps(line))
     if metrics or clashes or rings or aromatic or diversity or interactions:
         scores = {}
         if metrics:                                           # no true molecule here: no novelty, no recovery
@@ -193,7 +211,8 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
 
 
 def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anchors=None, device=None, output_format='xyz',
-             metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False, diversity=False):
+             metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False, diversity=False,
+             hydrogens=False):
     """``generate.py`` main(): fragments file -> ``n_samples`` molecules with a sampled linker, as ``.xyz`` files
     (``output_format='sdf'``: ``.sdf`` files with perceived bonds instead, ``'both'``: both; one JSON line with the number of
     molecules, the share in one piece and the mean bond count is printed then).  ``metrics=True`` also writes
@@ -206,7 +225,12 @@ def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anc
     geometric rule of this project's own, not on OpenBabel's or RDKit's, and the pocket variants take them as well.
     ``diversity=True`` adds ``internal_diversity`` and ``internal_diversity_linker`` of the samples of this one input
     (``metrics.analyze_fingerprints`` / ``compute_diversity``): one minus the mean pairwise Tanimoto similarity on this
-    project's own circular fingerprint, not RDKit's Morgan fingerprint."""
+    project's own circular fingerprint, not RDKit's Morgan fingerprint.  ``hydrogens=True`` adds explicit hydrogens with 3D
+    positions to the ``.sdf`` files (``molecule_builder.add_hydrogens`` on the bond list the files are written with, a rule
+    of this project's own, not RDKit's ``AddHs`` and not OpenBabel's; ``bond_orders='geometric'`` is recommended, because the
+    distance table's arbitrary orders inside aromatic rings give arbitrary counts there) and ``hydrogens_per_molecule`` to
+    the JSON line; with ``output_format='xyz'`` it raises ``ValueError``, and the pocket variants take it as well."""
+    _check_hydrogens(hydrogens, output_format)
     if clashes:
         raise ValueError('clashes are scored against a protein: pass a pocket or a protein file (--pocket / --protein)')
     device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
@@ -229,12 +253,13 @@ def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anc
     }] * n_samples
     return _sample_and_save(ddpm, dataset, collate_with_fragment_edges, sample_fn, min(n_samples, 64), output_dir, name,
                             com_key='fragment_mask', hide_pocket=False, output_format=output_format, metrics=metrics,
-                            rings=rings, bond_orders=bond_orders, aromatic=aromatic, diversity=diversity)
+                            rings=rings, bond_orders=bond_orders, aromatic=aromatic, diversity=diversity,
+                            **({'hydrogens': True} if hydrogens else {}))
 
 
 def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size, device,
                             output_format, metrics=False, clashes=False, protein=None, rings=False, bond_orders='distance',
-                            aromatic=False, interactions=False, typed_protein=None):
+                            aromatic=False, interactions=False, typed_protein=None, hydrogens=False):
     frag_pos, frag_one_hot, frag_charges = frag
     pocket_pos, pocket_one_hot, pocket_charges = pocket
     positions = np.concatenate([frag_pos, pocket_pos], axis=0)
@@ -256,12 +281,13 @@ def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_s
                             min(n_samples, max_batch_size), output_dir, name, com_key='fragment_only_mask',
                             hide_pocket=True, output_format=output_format, metrics=metrics, clashes=clashes, protein=protein,
                             rings=rings, bond_orders=bond_orders, aromatic=aromatic, interactions=interactions,
-                            typed_protein=typed_protein)
+                            typed_protein=typed_protein, **({'hydrogens': True} if hydrogens else {}))
 
 
 def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, output_dir, n_samples, n_steps, linker_size,
                          anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz',
-                         metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False, interactions=False):
+                         metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False, interactions=False,
+                         hydrogens=False):
     """``generate_with_pocket.py`` main(): the pocket is given as its own PDB file.  ``clashes=True`` scores every sample's
     generated atoms against the pocket atoms (``metrics.analyze_clashes``), adds the ``metrics.compute_clashes`` keys to
     ``metrics.json`` and writes ``clashes.json``: ``n_clashes``, ``n_clash_atoms`` and ``min_distance`` per written file.
@@ -269,7 +295,9 @@ def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, ou
     (``metrics.analyze_interactions``: the intermolecular terms of Trott & Olson under this project's own typing, not
     AutoDock Vina's numbers), adds the ``metrics.compute_interactions`` keys to ``metrics.json`` and writes
     ``interactions.json``: ``score``, the five fixed-point ``terms`` (units of 2^-32), ``n_pairs``, ``n_hbonds``,
-    ``n_hydrophobic`` and ``status`` per written file."""
+    ``n_hydrophobic`` and ``status`` per written file.  ``hydrogens=True`` as in ``generate``: the scores above keep counting
+    heavy atoms alone."""
+    _check_hydrogens(hydrogens, output_format)
     device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
     os.makedirs(output_dir, exist_ok=True)
     if random_seed is not None:
@@ -289,18 +317,19 @@ def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, ou
     pocket = pocket_arrays(read_pocket(pocket_path), backbone_atoms_only)
     return _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size,
                                    device, output_format, metrics, clashes, rings=rings, bond_orders=bond_orders,
-                                   aromatic=aromatic, interactions=interactions)
+                                   aromatic=aromatic, interactions=interactions, **({'hydrogens': True} if hydrogens else {}))
 
 
 def generate_with_protein(input_path, protein_path, backbone_atoms_only, model, output_dir, n_samples, n_steps,
                           linker_size, anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz',
                           metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False,
-                          interactions=False):
+                          interactions=False, hydrogens=False):
     """``generate_with_protein.py`` main(): the pocket = residues of the protein within 6 A of the fragments.
     ``clashes=True`` as in ``generate_with_pocket``, but against ALL protein atoms whose element is in the vocabulary
     (``io.get_protein_atoms``), residues outside the pocket the model saw included; the pocket rows of the batch are then not
     targets, so no atom counts twice.  ``interactions=True`` likewise scores against the whole protein, which is typed once
-    (``metrics.protein_types``), so no residue is cut at a pocket boundary."""
+    (``metrics.protein_types``), so no residue is cut at a pocket boundary.  ``hydrogens=True`` as in ``generate``."""
+    _check_hydrogens(hydrogens, output_format)
     device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
     os.makedirs(output_dir, exist_ok=True)
     if random_seed is not None:
@@ -324,7 +353,7 @@ def generate_with_protein(input_path, protein_path, backbone_atoms_only, model, 
     return _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size,
                                    device, output_format, metrics, clashes, protein if clashes else None, rings=rings,
                                    bond_orders=bond_orders, aromatic=aromatic, interactions=interactions,
-                                   typed_protein=typed_protein)
+                                   typed_protein=typed_protein, **({'hydrogens': True} if hydrogens else {}))
 
 
 def main(argv=None):
@@ -371,6 +400,11 @@ def main(argv=None):
                    help='without --pocket / --protein: fingerprint the generated molecules on the GPU (this project\'s '
                         'circular fingerprint, not RDKit\'s Morgan) and add internal_diversity and internal_diversity_linker '
                         'to metrics.json')
+    p.add_argument('--hydrogens', action='store_true',
+                   help='add explicit hydrogens with 3D positions to the .sdf files on the GPU (needs --output_format sdf or '
+                        'both; a rule of this project, not RDKit\'s AddHs and not OpenBabel\'s).  --bond_orders geometric is '
+                        'recommended: the distance table\'s arbitrary orders inside aromatic rings give arbitrary hydrogen '
+                        'counts there')
     a = p.parse_args(argv)
     if a.clashes and a.pocket is None and a.protein is None:
         raise ValueError('--clashes scores the generated atoms against a protein: pass --pocket or --protein')
@@ -384,6 +418,8 @@ def main(argv=None):
         more['bond_orders'] = a.bond_orders
     if a.aromatic:
         more['aromatic'] = True
+    if a.hydrogens:
+        more['hydrogens'] = True
     if a.pocket is not None:
         files = generate_with_pocket(a.fragments, a.pocket, a.backbone_atoms_only, a.model, a.output, a.n_samples,
                                      a.n_steps, a.linker_size, a.anchors, a.max_batch_size, a.random_seed,

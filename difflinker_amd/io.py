@@ -18,7 +18,7 @@ symbols and coordinates, so the few record types involved are parsed here direct
 * ``save_xyz_file`` / ``load_xyz_files`` / ``load_molecule_xyz``: byte-compatible with src/visualizer.py:14-59;
 * ``save_sdf_file``: V2000 mol blocks from the bond lists of ``molecule_builder.perceive_bonds``, in place of the
   reference's ``obabel xyz -> sdf`` call (generate.py:179-180).  The bonds are the reference's own ``molecule_builder``
-  rule, not OpenBabel's.
+  rule, not OpenBabel's.  With ``hydrogens=`` it also writes the explicit hydrogens of ``molecule_builder.add_hydrogens``.
 """
 import os
 from collections import namedtuple
@@ -435,36 +435,60 @@ def save_xyz_file(path, one_hot, positions, node_mask, names, is_geom, suffix=''
                                                  positions[batch_i, atom_i, 1], positions[batch_i, atom_i, 2]))
 
 
-def save_sdf_file(path, one_hot, positions, node_mask, bonds, n_bonds, names, is_geom, suffix=''):
+HYDROGENS_OVERFLOW = 32             # DL_HYDRO_OVERFLOW of include/difflinker_hip.h: the list of hydrogens was cut at its capacity
+
+
+def save_sdf_file(path, one_hot, positions, node_mask, bonds, n_bonds, names, is_geom, suffix='', hydrogens=None):
     """One ``<name>_<suffix>.sdf`` per molecule (the naming of ``save_xyz_file``): a CTfile V2000 mol block of the masked
     atoms, in the order ``save_xyz_file`` writes them, with ``%10.4f`` coordinates, and the first ``n_bonds[b]`` rows
     ``(i, j, order)`` of ``bonds[b]`` (0-based atom numbers as ``perceive_bonds`` gives them) as 1-based bond lines
     ``i j order`` - the orientation of the reference's ``mol.AddBond(i, j)``, ``j < i``.  V2000 counts are three digits wide:
-    more than 999 atoms or bonds raise ``ValueError``, and so does a bond list cut short by its capacity."""
+    more than 999 atoms or bonds raise ``ValueError``, and so does a bond list cut short by its capacity.
+    ``hydrogens`` (a ``molecule_builder.Hydrogens`` for the same batch; ``None`` writes heavy atoms alone) adds its first
+    ``n_h[b]`` hydrogens after the heavy atoms (symbol ``H``, the same ``%10.4f``) and, after the heavy bonds, one bond line
+    ``n + t + 1, parent + 1, 1`` for hydrogen ``t`` of a molecule of ``n`` heavy atoms; the counts line and the 999 limit
+    then hold the totals, and a hydrogen list cut short by its capacity (``DL_HYDRO_OVERFLOW``) raises ``ValueError``."""
     idx2atom = const.GEOM_IDX2ATOM if is_geom else const.IDX2ATOM
     one_hot, positions, node_mask = one_hot.detach().cpu(), positions.detach().cpu(), node_mask.detach().cpu()
     bonds, n_bonds = torch.as_tensor(bonds).detach().cpu(), torch.as_tensor(n_bonds).detach().cpu()
+    if hydrogens is not None:
+        n_h, h_parent, h_x, h_status = (torch.as_tensor(t).detach().cpu() for t in
+                                        (hydrogens.n_h, hydrogens.parent, hydrogens.x, hydrogens.status))
     for batch_i in range(one_hot.size(0)):
         atom_idx = torch.where(node_mask[batch_i].reshape(-1))[0]
         atoms = torch.argmax(one_hot[batch_i], dim=1)
         n_atoms, nb = len(atom_idx), int(n_bonds[batch_i])
         if nb > bonds.shape[1]:
             raise ValueError(f'molecule {batch_i} has {nb} bonds, its list holds {bonds.shape[1]}')
-        if n_atoms > 999 or nb > 999:
-            raise ValueError(f'molecule {batch_i} has {n_atoms} atoms and {nb} bonds: a V2000 mol block holds 999 of each')
+        nh = 0
+        if hydrogens is not None:
+            nh = int(n_h[batch_i])
+            if int(h_status[batch_i]) & HYDROGENS_OVERFLOW or nh > h_parent.shape[1]:
+                raise ValueError(f'molecule {batch_i} has {nh} hydrogens, their list holds {h_parent.shape[1]}')
+        if n_atoms + nh > 999 or nb + nh > 999:
+            raise ValueError(f'molecule {batch_i} has {n_atoms + nh} atoms and {nb + nh} bonds: a V2000 mol block holds 999 '
+                             'of each')
         rows = bonds[batch_i, :nb].tolist()
         if any(not (0 <= j < i < n_atoms and 1 <= order <= 3) for i, j, order in rows):
             raise ValueError(f'molecule {batch_i}: a bond is not (i, j, order) with j < i < {n_atoms} and order 1..3')
+        parents = h_parent[batch_i, :nh].tolist() if nh else []
+        if any(not 0 <= parent < n_atoms for parent in parents):
+            raise ValueError(f'molecule {batch_i}: a hydrogen\'s parent is not an atom number below {n_atoms}')
         name = f'{names[batch_i]}_{suffix}'
         with open(os.path.join(path, f'{name}.sdf'), 'w') as f:
             f.write(f'{os.path.basename(name)}\n  difflinker_amd          3D\n\n')
-            f.write('%3d%3d  0  0  0  0  0  0  0  0999 V2000\n' % (n_atoms, nb))
+            f.write('%3d%3d  0  0  0  0  0  0  0  0999 V2000\n' % (n_atoms + nh, nb + nh))
             for atom_i in atom_idx:
                 f.write('%10.4f%10.4f%10.4f %-3s 0  0  0  0  0  0  0  0  0  0  0  0\n' % (
                     positions[batch_i, atom_i, 0], positions[batch_i, atom_i, 1], positions[batch_i, atom_i, 2],
                     idx2atom[atoms[atom_i].item()]))
+            for t in range(nh):
+                f.write('%10.4f%10.4f%10.4f %-3s 0  0  0  0  0  0  0  0  0  0  0  0\n' % (
+                    h_x[batch_i, t, 0], h_x[batch_i, t, 1], h_x[batch_i, t, 2], 'H'))
             for i, j, order in rows:
                 f.write('%3d%3d%3d  0  0  0  0\n' % (i + 1, j + 1, order))
+            for t, parent in enumerate(parents):
+                f.write('%3d%3d%3d  0  0  0  0\n' % (n_atoms + t + 1, parent + 1, 1))
             f.write('M  END\n$$$$\n')
 
 

@@ -16,9 +16,11 @@ from . import _lib, const
 
 Bonds = namedtuple('Bonds', 'n_bonds bonds valence n_components component status')
 Aromatic = namedtuple('Aromatic', 'bond_aromatic atom_aromatic n_planar_rings n_aromatic_rings n_aromatic_marked status')
+Hydrogens = namedtuple('Hydrogens', 'n_h h_count parent x status')
 
 _TABLES = {}
 _RING_CLASSES = {}
+_HYDROGEN_TABLES = {}
 
 
 def _table(device, is_geom, margins):
@@ -177,6 +179,71 @@ def refine_bond_orders(found, one_hot, x, node_mask, is_geom, drop_mask=None, ma
         _lib.check(_lib.load().dl_aromatic_rings(ctypes.byref(args), stream), 'dl_aromatic_rings')
     refined = found._replace(bonds=torch.cat([bonds[:, :, :2], order[:, :, None]], dim=2), valence=valence)
     return refined, out
+
+
+def _hydrogen_tables(device, is_geom):
+    key = (device, bool(is_geom))
+    if key not in _HYDROGEN_TABLES:
+        _HYDROGEN_TABLES[key] = (const.default_valence_table(is_geom).to(device).contiguous(),
+                                 const.xh_length_table(is_geom).to(device).contiguous())
+    return _HYDROGEN_TABLES[key]
+
+
+def add_hydrogens(found, one_hot, x, node_mask, is_geom, drop_mask=None, atom_planar=None, capacity=None):
+    """Explicit hydrogens with 3D positions for every molecule of a batch (``dl_add_hydrogens``, ``csrc/hydrogens.hip``):
+    ONE launch on the result ``found`` of ``perceive_bonds`` or ``refine_bond_orders`` for the same ``one_hot``, ``x`` and
+    ``node_mask``, without a host synchronisation.
+
+    THE RULE is this project's own (``include/difflinker_hip.h`` states it in full; ``tests/hydrogens_ref.py`` restates it): it
+    is NOT RDKit's ``AddHs(addCoords=True)`` and NOT OpenBabel's.  An atom gets ``default valence - sum of its bond orders``
+    hydrogens (``const.DEFAULT_VALENCE``; none when it is over-valent) at ``const.XH_LENGTH`` from it: linear with a triple or
+    two double bonds, trigonal with one double bond (or with ``atom_planar`` set, two neighbours and one hydrogen: a pyrrole
+    N-H), tetrahedral otherwise, staggered or trans to the neighbour's first other neighbour.  With the distance table's
+    orders the counts inside aromatic rings are arbitrary: pass the ``refined`` list of ``refine_bond_orders`` and its
+    ``atom_aromatic`` as ``atom_planar``.  An amide or aniline N comes out pyramidal; there are no charges, so a carboxylate
+    is written as an acid and an ammonium as an amine; P and S above their default valence get none.
+
+    ``drop_mask`` (the pocket) removes atoms together with their bonds, ``[B,N]`` or ``[B,N,1]`` by row; ``atom_planar`` is
+    ``[B,N]`` by atom number.  Returns a ``Hydrogens`` of device tensors: ``n_h [B]`` (the true count), ``h_count [B,N]`` by
+    atom number, ``parent [B,capacity]`` (atom numbers) and ``x [B,capacity,3]`` (fp64), valid up to ``n_h`` and zero beyond,
+    and ``status [B]``: the bits of ``found.status`` plus ``_lib.DL_HYDRO_*`` (more than 256 kept atoms or a non-finite
+    coordinate: no hydrogens; ``DL_HYDRO_OVERFLOW``: more than ``capacity``).  ``capacity`` defaults to ``4 * N``, which
+    cannot overflow."""
+    masks = (node_mask,) + ((drop_mask,) if drop_mask is not None else ())
+    others = masks + ((atom_planar,) if atom_planar is not None else ())
+    if not (one_hot.is_cuda and x.is_cuda and all(m.is_cuda for m in others)):
+        raise _lib.HipLibraryError('add_hydrogens runs on the HIP device only (no CPU fallback): '
+                                   f'got tensors on {one_hot.device}, {x.device}, {[str(m.device) for m in others]}')
+    B, N, nf = one_hot.shape
+    if x.shape != (B, N, 3) or any(m.numel() != B * N for m in others):
+        raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, x {tuple(x.shape)}, masks '
+                         f'{[tuple(m.shape) for m in others]}')
+    dev = one_hot.device
+    given = normalize_bonds(found, B, dev, 'add_hydrogens')
+    f32 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()     # noqa: E731
+    one_hot, x, node_mask, drop_mask = f32(one_hot), f32(x), f32(node_mask), f32(drop_mask)
+    if atom_planar is not None:
+        atom_planar = (atom_planar.reshape(B, N) != 0).to(device=dev, dtype=torch.int32).contiguous()
+    valence, length = _hydrogen_tables(dev, is_geom)
+    if valence.numel() < nf:
+        raise ValueError(f'one_hot has {nf} types, the vocabulary {valence.numel()}')
+    capacity = 4 * N if capacity is None else int(capacity)
+    bond_capacity = given.bonds.shape[1]
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    out = Hydrogens(i32(B), i32(B, N), torch.zeros((B, capacity), dtype=torch.int32, device=dev),
+                    torch.zeros((B, capacity, 3), dtype=torch.float64, device=dev), i32(B))
+    opt = lambda t: None if t is None else t.data_ptr()                     # noqa: E731
+    args = _lib.DLHydrogensArgs(
+        B=B, N=N, nf=nf, x=x.data_ptr(), one_hot=one_hot.data_ptr(), node_mask=node_mask.data_ptr(), drop_mask=opt(drop_mask),
+        atom_planar=opt(atom_planar), default_valence=valence.data_ptr(), xh_length=length.data_ptr(), capacity=bond_capacity,
+        n_bonds_in=given.n_bonds.data_ptr(), bonds=given.bonds.data_ptr() if bond_capacity else None,
+        status_in=opt(given.status), Hcap=capacity, n_h=out.n_h.data_ptr(), h_count=out.h_count.data_ptr(),
+        h_parent=out.parent.data_ptr() if capacity else None, h_x=out.x.data_ptr() if capacity else None,
+        status=out.status.data_ptr())
+    with torch.cuda.device(dev):
+        args.stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(_lib.load().dl_add_hydrogens(ctypes.byref(args)), 'dl_add_hydrogens')
+    return out
 
 
 def build_xae_molecules(one_hot, x, node_mask, is_geom, margins=const.MARGINS_EDM):

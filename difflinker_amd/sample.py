@@ -20,7 +20,7 @@ from .generate import BOND_ORDERS, OUTPUT_FORMATS
 from .io import save_sdf_file, save_xyz_file
 from .lightning import DDPM
 from .linker_size import SizeClassifier
-from .molecule_builder import perceive_all_bonds, refine_bond_orders, summary
+from .molecule_builder import add_hydrogens, perceive_all_bonds, refine_bond_orders, summary
 
 
 def check_if_generated(_output_dir, _uuids, n_samples):
@@ -58,7 +58,7 @@ def _prepare(checkpoint, prefix, data, n_steps, device):
 def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=None, linker_size_model=None,
            output_format='xyz', metrics=False, geometry=False, clashes=False, shape=False, rings=False,
            bond_orders='distance', aromatic=False, diversity=False, diversity_reference=None, pharmacophore=False,
-           interactions=False):
+           interactions=False, hydrogens=False):
     """``sample.py``.  Returns the output directory.  ``metrics=True`` scores the molecules sampled in this call against
     the data set's own (``metrics.compute_metrics``: valence rule, connectivity, uniqueness, novelty, recovery) and writes
     the result to ``metrics.json`` in the output directory; with ``geometry=True`` as well, the symmetry-aware RMSD of the
@@ -93,7 +93,16 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
     ``interactions=True`` (pocket data sets only; others raise ``ValueError``) scores the contacts of every sample's LINKER
     atoms, typed in the context of the whole ligand, with its pocket atoms, and of the data set's own linker in the same
     pocket as ``true`` (``metrics.analyze_interactions`` / ``compute_interactions``: the intermolecular terms of Trott &
-    Olson under this project's own heavy-atom typing - not AutoDock Vina's numbers); the keys go into ``metrics.json``."""
+    Olson under this project's own heavy-atom typing - not AutoDock Vina's numbers); the keys go into ``metrics.json``.
+    ``hydrogens=True`` adds explicit hydrogens with 3D positions to the ``.sdf`` files (``molecule_builder.add_hydrogens`` on
+    the bond list the files are written with; a rule of this project's own, not RDKit's ``AddHs`` and not OpenBabel's;
+    ``bond_orders='geometric'`` is recommended, because the distance table's arbitrary orders inside aromatic rings give
+    arbitrary counts there) and ``hydrogens_per_molecule`` to the JSON line; with ``output_format='xyz'`` it raises
+    ``ValueError``.  No score counts them."""
+    if hydrogens and output_format == 'xyz':
+        raise ValueError('hydrogens are written to the .sdf files: pass output_format sdf or both (--output_format); the '
+                         '.xyz files stay the heavy-atom format of the reference')
+    n_hydrogens = []
     if output_format not in OUTPUT_FORMATS:
         raise ValueError(f'output_format must be one of {OUTPUT_FORMATS}, got {output_format!r}')
     if bond_orders not in BOND_ORDERS:
@@ -235,10 +244,17 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
             if output_format != 'xyz':
                 found.append(perceive_all_bonds(hs, xs, out_mask, model.is_geom))
                 shown = found[-1]
+                planar = None
                 if bond_orders == 'geometric':                 # Kekule orders for the planar rings, from the same geometry
-                    shown = refine_bond_orders(shown, hs[:, :, :model.num_classes], xs, out_mask, model.is_geom)[0]
+                    shown, ring_atoms = refine_bond_orders(shown, hs[:, :, :model.num_classes], xs, out_mask, model.is_geom)
+                    planar = ring_atoms.atom_aromatic
+                more = {}
+                if hydrogens:                                  # on the list the file is written with
+                    more['hydrogens'] = add_hydrogens(shown, hs[:, :, :model.num_classes], xs, out_mask, model.is_geom,
+                                                      atom_planar=planar)
+                    n_hydrogens.append(more['hydrogens'].n_h)
                 save_sdf_file(output_dir, hs, xs, out_mask, shown.bonds, shown.n_bonds, [f'{u}/{i}' for u in uuids],
-                              is_geom=model.is_geom)
+                              is_geom=model.is_geom, **more)
             if metrics:
                 types = hs[:, :, :model.num_classes]
                 pred += mol_metrics.to_host(mol_metrics.analyze(types, xs, out_mask, model.is_geom), types, out_mask)
@@ -249,7 +265,10 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 true_x += true_x_batch
                 n_linker += n_linker_batch
     if found:
-        print(json.dumps(summary(found)))
+        line = summary(found)
+        if hydrogens:
+            line['hydrogens_per_molecule'] = float(torch.cat(n_hydrogens).float().mean()) if line['molecules'] else 0.0
+        print(json.dumps(line))
     if metrics or clashes or shape or rings or aromatic or diversity or pharmacophore or interactions:
         with open(os.path.join(output_dir, 'metrics.json'), 'w') as f:
             scores = {}
@@ -387,6 +406,11 @@ def main(argv=None):
                    help='pocket data sets: score the contacts of the sampled linkers (and of the true ones) with the pocket '
                         'atoms on the GPU - the intermolecular terms of Trott & Olson under this project\'s heavy-atom typing, '
                         'not AutoDock Vina\'s numbers - and write the scores to metrics.json')
+    p.add_argument('--hydrogens', action='store_true',
+                   help='add explicit hydrogens with 3D positions to the .sdf files on the GPU (needs --output_format sdf or '
+                        'both; a rule of this project, not RDKit\'s AddHs and not OpenBabel\'s).  --bond_orders geometric is '
+                        'recommended: the distance table\'s arbitrary orders inside aromatic rings give arbitrary hydrogen '
+                        'counts there')
     a = p.parse_args(argv)
     if a.keep_frames is not None:
         print(sample_trajectories(a.checkpoint, a.samples, a.prefix, a.keep_frames, a.device, a.data, a.n_steps))
@@ -399,7 +423,8 @@ def main(argv=None):
                      **({'aromatic': True} if a.aromatic else {}), **({'diversity': True} if a.diversity else {}),
                      **({'diversity_reference': a.diversity_reference} if a.diversity_reference else {}),
                      **({'pharmacophore': True} if a.pharmacophore else {}),
-                     **({'interactions': True} if a.interactions else {})))
+                     **({'interactions': True} if a.interactions else {}),
+                     **({'hydrogens': True} if a.hydrogens else {})))
 
 
 if __name__ == '__main__':

@@ -1632,6 +1632,105 @@ typedef struct dl_feature_match_args {
 } dl_feature_match_args;
 int32_t dl_feature_match(const dl_feature_match_args* args);
 
+/* ---- explicit hydrogens with 3D positions (hydrogens.hip) --------------------------------------------------------
+ * Every molecule this project writes is a heavy-atom skeleton: the models have no hydrogen type.  This entry point turns
+ * the open valences of a bond graph with orders (dl_perceive_bonds, or the Kekule orders of dl_aromatic_rings) into
+ * hydrogen atoms with coordinates: one workgroup per molecule, ONE launch per batch, no host round trip.  It takes its
+ * arguments alone, the stream as the last field, as dl_pharmacophore_features does.  THE RULE BELOW IS THIS PROJECT'S OWN.  It is NOT RDKit's AddHs with addCoords and NOT OpenBabel's; tests/hydrogens_ref.py restates it in
+ * plain Python and the kernel agrees with that bit for bit.
+ *
+ * CONVENTIONS, those of dl_aromatic_rings.  Atom k is the k-th row with node_mask != 0; its type t is the FIRST largest
+ * entry of its one_hot row.  `drop_mask` (may be NULL) removes atoms AFTER that numbering, together with their bonds.  An
+ * entry (i, j, order) is a bond when 0 <= i, j < atoms, i != j and 1 <= order <= 3, in either orientation; any other entry
+ * is skipped and sets DL_HYDRO_BAD_BOND.  A repeated pair sets DL_HYDRO_BAD_BOND too and counts once, with its FIRST
+ * entry's order.  Entries from min(n_bonds_in, capacity) on are not read.  "Kept" means: not dropped, both ends for a bond;
+ * a "neighbour" is the other end of a kept pair.
+ *
+ * Per kept atom a of type t:
+ * 1. d is the number of its neighbours, vs the sum of the orders of those pairs.
+ * 2. h0 = max(0, default_valence[t] - vs).  An over-valent atom (a sulfone S, a five-bonded C) gets none.
+ * 3. GEOMETRY CLASS, by the first condition that holds.  T2 (linear, 2 sites): a pair of order 3, or two or more of order
+ *    2.  T3 (trigonal, 3 sites): exactly one pair of order 2; or atom_planar[a] != 0 with d == 2 and h0 == 1 (`atom_planar`,
+ *    by atom number, may be NULL: the atom_aromatic of dl_aromatic_rings puts a pyrrole N-H in plane).  T4 (tetrahedral,
+ *    4 sites): otherwise.  The count is h = min(h0, max(0, sites - d)).
+ * 4. L = xh_length[t], in A: C 1.09, N 1.01, O 0.96, F 0.92, S 1.34, Cl 1.27, Br 1.41, I 1.61, P 1.42.
+ *
+ * ARITHMETIC.  fp64 on (double) x, contraction off, every + - * / and sqrt rounded on its own in the order written, as
+ * step 3 of dl_aromatic_rings.  v . w is (v_x*w_x + v_y*w_y) + v_z*w_z; v x w is (v_y*w_z - v_z*w_y, v_z*w_x - v_x*w_z,
+ * v_x*w_y - v_y*w_x); v / |v| is n = sqrt(v . v), then (v_x/n, v_y/n, v_z/n); -v / |v| negates those quotients; sums,
+ * differences and products with a scalar go by component.  EPS = 1e-6.  u_k = (x_k - x_a) / |x_k - x_a| for the
+ * neighbours k of a in increasing atom number.  perp(u): m is the axis with the smallest |u_m| (the lowest m of equal ones),
+ * v = e_m - u_m * u (v_j = [j == m] - u_m * u_j), and perp(u) = v / |v|.  The constants are the doubles nearest to
+ * sqrt(3) = 0x1.bb67ae8584caap+0, sqrt(2/3) = 0x1.a20bd700c2c3ep-1, sqrt(8)/3 = 0x1.e2b7dddfefa67p-1 and
+ * sqrt(3)/2 = 0x1.bb67ae8584caap-1.
+ *
+ * DIRECTIONS.
+ *   T4, d = 3   s = (u1 + u2) + u3.  If s . s > EPS: -s / |s|.  Otherwise w = (u2 - u1) x (u3 - u1), and w / |w| when
+ *               w . w > EPS, else perp(u1).
+ *   d = 2       s = u1 + u2, c = u1 x u2.  If s . s <= EPS (anti-parallel): b = perp(u1), n = u1 x b.  Otherwise
+ *               b = -s / |s|, and n = c / |c| when c . c > EPS, else perp(u1).  T3: b.  T4: b / sqrt(3) + sqrt(2/3) * n,
+ *               then b / sqrt(3) - sqrt(2/3) * n; the first h of them.
+ *   d = 1       k is the neighbour, r the smallest-numbered neighbour of k other than a.  w = x_r - x_k,
+ *               p = w - (w . u1) * u1.  e1 = -p / |p| when r exists and p . p > EPS * (w . w), else perp(u1) - negated
+ *               when there is no r and a > k: perp(u) = perp(-u), so the two atoms of a molecule of two heavy atoms would
+ *               choose the same e1 and eclipse each other; negated at the second of them, ethane comes out staggered.
+ *               e2 = u1 x e1.
+ *               T4: -(u1 / 3) + (sqrt(8)/3) * (cos * e1 + sin * e2) with (cos, sin) = (1, 0), (-0.5, sqrt(3)/2),
+ *               (-0.5, -sqrt(3)/2), both products formed for each; the first h.  The first is anti to r (staggered).
+ *               T3: -(u1 / 2) + (sqrt(3)/2) * e1, then -(u1 / 2) - (sqrt(3)/2) * e1; the first h.  The first is trans
+ *               to r.  T2: -u1.
+ *   T4, d = 0   g = 1 / sqrt(3); the first h of (g, g, g), (g, -g, -g), (-g, g, -g), (-g, -g, g).
+ * A hydrogen sits at x_a + L * direction by component.  Two atoms at one point divide by zero: the positions that depend
+ * on them are not finite, and nothing is flagged.
+ *
+ * THE LIST.  Hydrogens are listed by parent atom number, within a parent in the order above.
+ *
+ *   n_h       [B]: the true count, which may exceed Hcap
+ *   h_count   [B,N] by atom number, written in full: h; 0 for dropped atoms and from the atom count on
+ *   h_parent  [B,Hcap]: the parent's atom number; written up to min(n_h, Hcap) and left UNTOUCHED from there on
+ *   h_x       [B,Hcap,3] f64, A: likewise
+ *   status    [B]: the bits of `status_in` (may be NULL: none), plus DL_BONDS_OVERFLOW when n_bonds_in > capacity (a negative
+ *             n_bonds_in counts as 0), DL_HYDRO_BAD_BOND, and the limits.  None disturbs the other molecules of the launch.
+ *             DL_HYDRO_TOO_LARGE: more than DL_HYDRO_MAX_ATOMS KEPT atoms (N itself may be 1024): nothing is listed, every
+ *               count is 0, and neither the list of bonds nor the coordinates are looked at.
+ *             DL_HYDRO_OVERFLOW: n_h > Hcap; the list holds the first Hcap.
+ *             DL_HYDRO_NONFINITE: a kept atom has a NaN or inf coordinate; the molecule gets no hydrogens (every count 0).
+ *
+ * The same bits on every run and under every order of the list.  Global memory is written with plain stores only; the callee
+ * allocates nothing and needs no workspace.  A null `args`, B < 0, N < 1, N > 1024, nf < 1, capacity < 0 or Hcap < 0 return
+ * DL_ERR_BAD_ARG; then B == 0 returns DL_OK without a launch; then a null pointer (other than drop_mask, atom_planar,
+ * status_in, stream, `bonds` when capacity is 0, and the two lists when Hcap is 0) returns DL_ERR_BAD_ARG, all before any device work.
+ * Limits of the rule: an amide or aniline N comes out pyramidal; no formal charges, so a carboxylate is written as an acid and
+ * an ammonium as an amine; P and S above their default valence get none; the torsions of -OH and -NH2 are the staggered
+ * default, not oriented towards a pocket.  Not here: protonation states, energy minimisation, hydrogens in any score. */
+#define DL_HYDRO_MAX_ATOMS 256      /* kept atoms per molecule */
+#define DL_HYDRO_TOO_LARGE 4        /* status bit, same value as DL_PHARM_TOO_LARGE */
+#define DL_HYDRO_BAD_BOND 8         /* status bit, same value as DL_PHARM_BAD_BOND */
+#define DL_HYDRO_OVERFLOW 32        /* status bit, same value as DL_PHARM_OVERFLOW: n_h > Hcap */
+#define DL_HYDRO_NONFINITE 64       /* status bit, same value as DL_PHARM_NONFINITE */
+typedef struct dl_hydrogens_args {
+    int32_t B, N, nf;
+    const float* x;                 /* device f32 [B,N,3], Angstrom */
+    const float* one_hot;           /* device f32 [B,N,nf] */
+    const float* node_mask;         /* device f32 [B,N] */
+    const float* drop_mask;         /* device f32 [B,N] or NULL */
+    const int32_t* atom_planar;     /* device int32 [B,N] by atom number, or NULL: dl_aromatic_args.atom_aromatic */
+    const int32_t* default_valence; /* device int32 [nf]: C 4, N 3, O 2, F 1, S 2, Cl 1, Br 1, I 1, P 3 */
+    const double* xh_length;        /* device f64 [nf]: the X-H bond lengths, A */
+    int32_t capacity;               /* bonds the list holds per molecule */
+    const int32_t* n_bonds_in;      /* device int32 [B]: dl_bonds_args.n_bonds */
+    const int32_t* bonds;           /* device int32 [B,capacity,3] (may be NULL when capacity is 0) */
+    const int32_t* status_in;       /* device int32 [B] or NULL: dl_bonds_args.status or dl_aromatic_args.status */
+    int32_t Hcap;                   /* hydrogens the list holds per molecule */
+    int32_t* n_h;                   /* device int32 [B] out */
+    int32_t* h_count;               /* device int32 [B,N] out */
+    int32_t* h_parent;              /* device int32 [B,Hcap] out (may be NULL when Hcap is 0, as the next) */
+    double* h_x;                    /* device f64 [B,Hcap,3] out */
+    int32_t* status;                /* device int32 [B] out */
+    void* stream;                   /* hipStream_t; NULL: the default stream */
+} dl_hydrogens_args;
+int32_t dl_add_hydrogens(const dl_hydrogens_args* args);
+
 const char* dl_error_string(int32_t status);
 int32_t dl_last_hip_error(void);
 int32_t dl_abi_version(void);
