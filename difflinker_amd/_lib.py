@@ -363,6 +363,23 @@ class DLHydrogensArgs(ctypes.Structure):                # the stream is the last
     ]
 
 
+DL_POSE_MAX_ATOMS, DL_POSE_COUNTS = 256, 8            # dl_pose_args: kept atoms per molecule; values per row of counts
+DL_POSE_TOO_LARGE, DL_POSE_BAD_BOND, DL_POSE_NONFINITE = 4, 8, 64     # dl_pose_args.status bits, beside the DL_BONDS_* bits carried forward
+
+
+class DLPoseArgs(ctypes.Structure):                   # the stream is the last FIELD, as for dl_add_hydrogens
+    _fields_ = [
+        ('B', ctypes.c_int32), ('N', ctypes.c_int32), ('nf', ctypes.c_int32),
+        ('x', ctypes.c_void_p), ('one_hot', ctypes.c_void_p), ('node_mask', ctypes.c_void_p),
+        ('drop_mask', ctypes.c_void_p), ('mark_mask', ctypes.c_void_p), ('atom_planar', ctypes.c_void_p),
+        ('length_bounds2', ctypes.c_void_p), ('angle_cos', ctypes.c_void_p), ('clash2', ctypes.c_void_p),
+        ('capacity', ctypes.c_int32),
+        ('n_bonds_in', ctypes.c_void_p), ('bonds', ctypes.c_void_p), ('status_in', ctypes.c_void_p),
+        ('counts', ctypes.c_void_p), ('atom_flags', ctypes.c_void_p), ('status', ctypes.c_void_p),
+        ('stream', ctypes.c_void_p),
+    ]
+
+
 class DLFeatureMatchArgs(ctypes.Structure):           # likewise
     _fields_ = [
         ('B', ctypes.c_int32), ('Fa', ctypes.c_int32), ('Fb', ctypes.c_int32),
@@ -387,6 +404,7 @@ EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_stri
            'dl_egnn_backward_pocket_workspace_bytes', 'dl_egnn_backward_pocket',
            'dl_size_train_num_params', 'dl_size_train_workspace_bytes', 'dl_size_train_forward', 'dl_size_train_backward',
            'dl_join_workspace_bytes', 'dl_sample_chain_fc_join', 'dl_bonds_workspace_bytes', 'dl_perceive_bonds',
+           'dl_pose_checks',
            'dl_interaction_types', 'dl_interaction_scores', 'dl_add_hydrogens',
            'dl_molecule_keys', 'dl_clash_scores', 'dl_shape_scores', 'dl_ring_scores', 'dl_fragment_cuts',
            'dl_pocket_select', 'dl_fragment_multicuts', 'dl_aromatic_rings', 'dl_fingerprints',
@@ -538,6 +556,8 @@ def _open(path):
     lib.dl_feature_match.argtypes = [ctypes.POINTER(DLFeatureMatchArgs)]
     lib.dl_add_hydrogens.restype = i32
     lib.dl_add_hydrogens.argtypes = [ctypes.POINTER(DLHydrogensArgs)]
+    lib.dl_pose_checks.restype = i32
+    lib.dl_pose_checks.argtypes = [ctypes.POINTER(DLPoseArgs)]
     lib.dl_pocket_select.restype = i32
     lib.dl_pocket_select.argtypes = [ctypes.POINTER(DLPocketArgs), vp]
     lib.dl_best_rmsd.restype = i32

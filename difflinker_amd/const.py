@@ -2,6 +2,8 @@
 typical bond lengths behind ``get_bond_order`` (``src/const.py:64-139,175``) as matrices over this project's atom indices,
 from which ``bond_threshold_table`` builds the table of upper bounds the HIP kernel reads.  The RDKit enumerations of the
 reference (``BOND_DICT``, ``BOND2IDX``) have no counterpart: bond orders are the integers 1, 2, 3."""
+import math
+
 import torch
 
 TORCH_FLOAT = torch.float32
@@ -159,6 +161,46 @@ def clash_threshold_table(is_geom, scale=0.75, tolerance=0.0):
         for b in range(n):
             table[a, b] = float(scale) * (VDW_RADII[a] + VDW_RADII[b]) - float(tolerance)
     return table.to(TORCH_FLOAT)
+
+
+# ---- the tables of ``metrics.analyze_pose_checks`` (``dl_pose_checks``): every threshold is formed here, once, in fp64 as
+# plain Python floats with one rounding per operation, so that the kernel only compares
+ANGLE_CLASSES = ('linear', 'trigonal', 'tetrahedral')     # the order of ``angle_cos_table``'s rows
+ANGLE_IDEALS = (180.0, 120.0, 109.47122063449069)         # degrees; the last is acos(-1/3)
+
+
+def length_bounds_table(is_geom, lo=0.75, hi=1.25):
+    """fp64 ``[n_types][n_types][3][2]`` SQUARED bond-length bounds in Angstrom^2: for a pair of types ``(s, t)`` of order
+    ``k + 1`` with the typical length ``L0 = BOND_LENGTHS[k][s][t] / 100.0``, entry ``[s][t][k]`` is ``((lo * L0) ** 2,
+    (hi * L0) ** 2)``; ``(0, 0)`` where the reference has no length for that order.  0.75 and 1.25 are PoseBusters' factors."""
+    n = GEOM_NUMBER_OF_ATOM_TYPES if is_geom else NUMBER_OF_ATOM_TYPES
+    rows = [[[[0.0, 0.0] for _ in range(3)] for _ in range(n)] for _ in range(n)]
+    for k in range(3):
+        for a in range(n):
+            for b in range(n):
+                if BOND_LENGTHS[k][a][b]:
+                    length = BOND_LENGTHS[k][a][b] / 100.0
+                    low, high = float(lo) * length, float(hi) * length
+                    rows[a][b][k] = [low * low, high * high]
+    return torch.tensor(rows, dtype=torch.float64)
+
+
+def angle_cos_table(tolerance_deg=25.0):
+    """fp64 ``[3][2]``: the lowest and the highest cosine a bond angle of the classes ``ANGLE_CLASSES`` may have,
+    ``cos(theta0 + tol)`` and ``cos(theta0 - tol)`` for ``ANGLE_IDEALS``; -2 where ``theta0 + tol`` reaches 180 degrees and 2
+    where ``theta0 - tol`` reaches 0, which no cosine is below or above."""
+    tol = float(tolerance_deg)
+    return torch.tensor([[math.cos(math.radians(t + tol)) if t + tol < 180.0 else -2.0,
+                          math.cos(math.radians(t - tol)) if t - tol > 0.0 else 2.0] for t in ANGLE_IDEALS], dtype=torch.float64)
+
+
+def internal_clash_table(is_geom, scale=0.75):
+    """fp64 ``[n_types][n_types]`` SQUARED distances in Angstrom^2: two atoms of one molecule four or more bonds apart clash
+    when ``d2 < (scale * (VDW_RADII[a] + VDW_RADII[b])) ** 2``.  0.75 is the heavy-atom convention of
+    ``clash_threshold_table``."""
+    n = GEOM_NUMBER_OF_ATOM_TYPES if is_geom else NUMBER_OF_ATOM_TYPES
+    reach = [[float(scale) * (VDW_RADII[a] + VDW_RADII[b]) for b in range(n)] for a in range(n)]
+    return torch.tensor([[v * v for v in row] for row in reach], dtype=torch.float64)
 
 
 # The atom radii of Trott & Olson's scoring function (AutoDock Vina, J. Comput. Chem. 31, 455 (2010)) in Angstrom by GEOM atom

@@ -65,27 +65,6 @@ __device__ __forceinline__ V3 point(const float* xs, int atom) {
     return {double(xs[atom * 3]), double(xs[atom * 3 + 1]), double(xs[atom * 3 + 2])};
 }
 
-// the first `limit` atoms of row u of m other than `skip`, ascending; returns how many were written
-__device__ __forceinline__ int first_members(const u64* m, int u, int skip, int* out, int limit) {
-    int c = 0;
-#pragma unroll
-    for (int w = 0; w < WORDS; ++w) {
-        u64 f = m[u * WORDS + w] & ~bit_in_word(skip, w);
-        while (f && c < limit) {
-            out[c++] = w * 64 + __builtin_ctzll(f);
-            f &= f - 1;
-        }
-    }
-    return c;
-}
-
-__device__ __forceinline__ int count_row(const u64* m, int u) {
-    int c = 0;
-#pragma unroll
-    for (int w = 0; w < WORDS; ++w) c += __popcll(m[u * WORDS + w]);
-    return c;
-}
-
 enum : int { T2 = 2, T3 = 3, T4 = 4 };           // the class is its number of sites
 
 // the directions of atom u's hydrogens, h of them (h <= sites - d); xs and adj are the LDS copies by kept index

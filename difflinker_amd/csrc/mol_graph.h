@@ -133,6 +133,27 @@ __device__ __forceinline__ bool add_pair(u64* adj, int u, int v) {
     return !(old & one);
 }
 
+// the first `limit` atoms of row u of m other than `skip`, ascending; returns how many were written
+__device__ __forceinline__ int first_members(const u64* m, int u, int skip, int* out, int limit) {
+    int c = 0;
+#pragma unroll
+    for (int w = 0; w < MATRIX_WORDS; ++w) {
+        u64 f = m[u * MATRIX_WORDS + w] & ~bit_in_word(skip, w);
+        while (f && c < limit) {
+            out[c++] = w * 64 + __builtin_ctzll(f);
+            f &= f - 1;
+        }
+    }
+    return c;
+}
+
+__device__ __forceinline__ int count_row(const u64* m, int u) {
+    int c = 0;
+#pragma unroll
+    for (int w = 0; w < MATRIX_WORDS; ++w) c += __popcll(m[u * MATRIX_WORDS + w]);
+    return c;
+}
+
 // Breadth-first search from u over the matrix, level-synchronous, frontier and visited set in registers.  `masked` (or -1)
 // is taken out of u's row at level 0 only: the bond (u, masked) can be walked nowhere else, because u is visited from the
 // start.  Ends when a level contains `target` (returns its distance in bonds from u) or is empty (returns -1: visited[] is

@@ -87,7 +87,8 @@ def _check_hydrogens(hydrogens, output_format):
 
 def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_dir, name, com_key, hide_pocket,
                      output_format='xyz', metrics=False, clashes=False, protein=None, rings=False, bond_orders='distance',
-                     aromatic=False, diversity=False, interactions=False, typed_protein=None, hydrogens=False):
+                     aromatic=False, diversity=False, interactions=False, typed_protein=None, hydrogens=False,
+                     pose_checks=False):
     if output_format not in OUTPUT_FORMATS:
         raise ValueError(f'output_format must be one of {OUTPUT_FORMATS}, got {output_format!r}')
     if bond_orders not in BOND_ORDERS:
@@ -95,7 +96,7 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
     _check_hydrogens(hydrogens, output_format)
     n_hydrogens = []
     written, found, scored, clash_records, ring_records, aromatic_records = [], [], [], [], [], []
-    prints, contact_records = [], []
+    prints, contact_records, pose_records = [], [], []
     for batch_i, data in enumerate(_batches(dataset, batch_size, collate_fn)):
         n = len(data['positions'])
         chain = None
@@ -166,6 +167,11 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
             pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, x.shape[1] - m.shape[1]))     # noqa: E731
             aromatic_records += mol_metrics.aromatic_to_host(mol_metrics.analyze_aromatic(
                 h[:, :, :ddpm.num_classes], x, node_mask, ddpm.is_geom, node_mask * (1 - pad(data['fragment_mask']))))
+        if pose_checks:                                       # likewise; always on the geometric orders
+            pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, x.shape[1] - m.shape[1]))     # noqa: E731
+            pose_records += mol_metrics.pose_checks_to_host(mol_metrics.analyze_pose_checks(
+                h[:, :, :ddpm.num_classes], x, node_mask, ddpm.is_geom, node_mask * (1 - pad(data['fragment_mask'])),
+                drop_mask=pad(data['pocket_mask']) if 'pocket_mask' in data else None))
         if diversity:                                         # likewise; the bits stay on the device
             pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, x.shape[1] - m.shape[1]))     # noqa: E731
             prints.append(mol_metrics.analyze_fingerprints(
@@ -175,7 +181,7 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
         if hydrogens:
             line['hydrogens_per_molecule'] = float(torch.cat(n_hydrogens).float().mean()) if line['molecules'] else 0.0
         print(json.dumps(line))
-    if metrics or clashes or rings or aromatic or diversity or interactions:
+    if metrics or clashes or rings or aromatic or diversity or interactions or pose_checks:
         scores = {}
         if metrics:                                           # no true molecule here: no novelty, no recovery
             scores = dict(mol_metrics.compute_metrics(scored), molecules=len(scored))
@@ -187,6 +193,8 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
             scores.update(mol_metrics.compute_rings(ring_records))
         if aromatic:
             scores.update(mol_metrics.compute_aromatic(aromatic_records))
+        if pose_checks:                                       # no true molecule here either
+            scores.update(mol_metrics.compute_pose_checks(pose_records))
         if diversity:                                         # one input: every sample against every other
             whole, linker = (mol_metrics.cat_fingerprints([p[k] for p in prints]) for k in range(2))
             records = mol_metrics.diversity_records(whole, linker, [0] * whole.bits.shape[0])
@@ -207,12 +215,19 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
                                                 'n_pairs': m.n_pairs, 'n_hbonds': m.n_hbonds,
                                                 'n_hydrophobic': m.n_hydrophobic, 'status': m.status}
                        for path in written for m in [by_name[os.path.basename(path).rsplit('_.', 1)[0]]]}, f, indent=1)
+    if pose_checks:                                           # likewise
+        by_name = {f'output_{i}_{name}': m for i, m in enumerate(pose_records)}
+        with open(os.path.join(output_dir, 'pose_checks.json'), 'w') as f:
+            json.dump({os.path.basename(path): {'counts': dict(zip(mol_metrics.POSE_COUNTS, m.counts)),
+                                                'linker_counts': dict(zip(mol_metrics.POSE_COUNTS, m.linker_counts)),
+                                                'n_flagged_atoms': m.n_flagged_atoms, 'status': m.status}
+                       for path in written for m in [by_name[os.path.basename(path).rsplit('_.', 1)[0]]]}, f, indent=1)
     return written
 
 
 def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anchors=None, device=None, output_format='xyz',
              metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False, diversity=False,
-             hydrogens=False):
+             hydrogens=False, pose_checks=False):
     """``generate.py`` main(): fragments file -> ``n_samples`` molecules with a sampled linker, as ``.xyz`` files
     (``output_format='sdf'``: ``.sdf`` files with perceived bonds instead, ``'both'``: both; one JSON line with the number of
     molecules, the share in one piece and the mean bond count is printed then).  ``metrics=True`` also writes
@@ -229,7 +244,13 @@ def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anc
     positions to the ``.sdf`` files (``molecule_builder.add_hydrogens`` on the bond list the files are written with, a rule
     of this project's own, not RDKit's ``AddHs`` and not OpenBabel's; ``bond_orders='geometric'`` is recommended, because the
     distance table's arbitrary orders inside aromatic rings give arbitrary counts there) and ``hydrogens_per_molecule`` to
-    the JSON line; with ``output_format='xyz'`` it raises ``ValueError``, and the pocket variants take it as well."""
+    the JSON line; with ``output_format='xyz'`` it raises ``ValueError``, and the pocket variants take it as well.
+    ``pose_checks=True`` checks the internal geometry of every sample - bond lengths, bond angles, clashes between atoms four
+    or more bonds apart - on the geometric bond orders, whatever ``bond_orders`` says about the files
+    (``metrics.analyze_pose_checks`` / ``compute_pose_checks``: a rule of this project's own after the idea of PoseBusters'
+    intramolecular checks, NOT PoseBusters' numbers), adds ``pose_valid``, ``bond_lengths_valid``, ``bond_angles_valid``,
+    ``internal_clash_free``, their ``_linker`` variants and the per-molecule means to ``metrics.json`` and writes
+    ``pose_checks.json`` with the counts per written file; the pocket variants take it as well, pocket atoms left out."""
     _check_hydrogens(hydrogens, output_format)
     if clashes:
         raise ValueError('clashes are scored against a protein: pass a pocket or a protein file (--pocket / --protein)')
@@ -254,12 +275,12 @@ def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anc
     return _sample_and_save(ddpm, dataset, collate_with_fragment_edges, sample_fn, min(n_samples, 64), output_dir, name,
                             com_key='fragment_mask', hide_pocket=False, output_format=output_format, metrics=metrics,
                             rings=rings, bond_orders=bond_orders, aromatic=aromatic, diversity=diversity,
-                            **({'hydrogens': True} if hydrogens else {}))
+                            **({'hydrogens': True} if hydrogens else {}), **({'pose_checks': True} if pose_checks else {}))
 
 
 def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size, device,
                             output_format, metrics=False, clashes=False, protein=None, rings=False, bond_orders='distance',
-                            aromatic=False, interactions=False, typed_protein=None, hydrogens=False):
+                            aromatic=False, interactions=False, typed_protein=None, hydrogens=False, pose_checks=False):
     frag_pos, frag_one_hot, frag_charges = frag
     pocket_pos, pocket_one_hot, pocket_charges = pocket
     positions = np.concatenate([frag_pos, pocket_pos], axis=0)
@@ -281,13 +302,14 @@ def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_s
                             min(n_samples, max_batch_size), output_dir, name, com_key='fragment_only_mask',
                             hide_pocket=True, output_format=output_format, metrics=metrics, clashes=clashes, protein=protein,
                             rings=rings, bond_orders=bond_orders, aromatic=aromatic, interactions=interactions,
-                            typed_protein=typed_protein, **({'hydrogens': True} if hydrogens else {}))
+                            typed_protein=typed_protein, **({'hydrogens': True} if hydrogens else {}),
+                            **({'pose_checks': True} if pose_checks else {}))
 
 
 def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, output_dir, n_samples, n_steps, linker_size,
                          anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz',
                          metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False, interactions=False,
-                         hydrogens=False):
+                         hydrogens=False, pose_checks=False):
     """``generate_with_pocket.py`` main(): the pocket is given as its own PDB file.  ``clashes=True`` scores every sample's
     generated atoms against the pocket atoms (``metrics.analyze_clashes``), adds the ``metrics.compute_clashes`` keys to
     ``metrics.json`` and writes ``clashes.json``: ``n_clashes``, ``n_clash_atoms`` and ``min_distance`` per written file.
@@ -296,7 +318,7 @@ def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, ou
     AutoDock Vina's numbers), adds the ``metrics.compute_interactions`` keys to ``metrics.json`` and writes
     ``interactions.json``: ``score``, the five fixed-point ``terms`` (units of 2^-32), ``n_pairs``, ``n_hbonds``,
     ``n_hydrophobic`` and ``status`` per written file.  ``hydrogens=True`` as in ``generate``: the scores above keep counting
-    heavy atoms alone."""
+    heavy atoms alone.  ``pose_checks=True`` as in ``generate``, on the ligand without the pocket atoms."""
     _check_hydrogens(hydrogens, output_format)
     device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
     os.makedirs(output_dir, exist_ok=True)
@@ -317,18 +339,20 @@ def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, ou
     pocket = pocket_arrays(read_pocket(pocket_path), backbone_atoms_only)
     return _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size,
                                    device, output_format, metrics, clashes, rings=rings, bond_orders=bond_orders,
-                                   aromatic=aromatic, interactions=interactions, **({'hydrogens': True} if hydrogens else {}))
+                                   aromatic=aromatic, interactions=interactions, **({'hydrogens': True} if hydrogens else {}),
+                                   **({'pose_checks': True} if pose_checks else {}))
 
 
 def generate_with_protein(input_path, protein_path, backbone_atoms_only, model, output_dir, n_samples, n_steps,
                           linker_size, anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz',
                           metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False,
-                          interactions=False, hydrogens=False):
+                          interactions=False, hydrogens=False, pose_checks=False):
     """``generate_with_protein.py`` main(): the pocket = residues of the protein within 6 A of the fragments.
     ``clashes=True`` as in ``generate_with_pocket``, but against ALL protein atoms whose element is in the vocabulary
     (``io.get_protein_atoms``), residues outside the pocket the model saw included; the pocket rows of the batch are then not
     targets, so no atom counts twice.  ``interactions=True`` likewise scores against the whole protein, which is typed once
-    (``metrics.protein_types``), so no residue is cut at a pocket boundary.  ``hydrogens=True`` as in ``generate``."""
+    (``metrics.protein_types``), so no residue is cut at a pocket boundary.  ``hydrogens=True`` and ``pose_checks=True`` as in
+    ``generate``."""
     _check_hydrogens(hydrogens, output_format)
     device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
     os.makedirs(output_dir, exist_ok=True)
@@ -353,7 +377,8 @@ def generate_with_protein(input_path, protein_path, backbone_atoms_only, model, 
     return _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size,
                                    device, output_format, metrics, clashes, protein if clashes else None, rings=rings,
                                    bond_orders=bond_orders, aromatic=aromatic, interactions=interactions,
-                                   typed_protein=typed_protein, **({'hydrogens': True} if hydrogens else {}))
+                                   typed_protein=typed_protein, **({'hydrogens': True} if hydrogens else {}),
+                                   **({'pose_checks': True} if pose_checks else {}))
 
 
 def main(argv=None):
@@ -405,6 +430,11 @@ def main(argv=None):
                         'both; a rule of this project, not RDKit\'s AddHs and not OpenBabel\'s).  --bond_orders geometric is '
                         'recommended: the distance table\'s arbitrary orders inside aromatic rings give arbitrary hydrogen '
                         'counts there')
+    p.add_argument('--pose_checks', action='store_true',
+                   help='check the internal geometry of the generated molecules on the GPU - bond lengths, bond angles, '
+                        'clashes between atoms four or more bonds apart, always on the geometric bond orders (a rule of this '
+                        'project after the idea of PoseBusters\' intramolecular checks, NOT PoseBusters\' numbers) - add '
+                        'pose_valid and its parts to metrics.json and write pose_checks.json with one record per written file')
     a = p.parse_args(argv)
     if a.clashes and a.pocket is None and a.protein is None:
         raise ValueError('--clashes scores the generated atoms against a protein: pass --pocket or --protein')
@@ -420,6 +450,8 @@ def main(argv=None):
         more['aromatic'] = True
     if a.hydrogens:
         more['hydrogens'] = True
+    if a.pose_checks:
+        more['pose_checks'] = True
     if a.pocket is not None:
         files = generate_with_pocket(a.fragments, a.pocket, a.backbone_atoms_only, a.model, a.output, a.n_samples,
                                      a.n_steps, a.linker_size, a.anchors, a.max_batch_size, a.random_seed,

@@ -107,6 +107,7 @@ class DDPM(_Base):
         self.aromatic_metrics = False           # it adds metrics.compute_aromatic's keys: aromatic rings of the linker, ring filter, valence rule on geometric orders (train --aromatic)
         self.diversity_metrics = False          # it adds metrics.compute_diversity's keys: internal diversity of each input's samples, similarity to the true molecule (train --diversity)
         self.ring_metrics = False               # it adds metrics.compute_rings' keys: ring count of the linker, small rings, macrocycles (train --rings)
+        self.pose_metrics = False               # it adds metrics.compute_pose_checks' keys: bond lengths, bond angles and internal clashes of every sample and of its true molecule (train --pose_checks)
         if _Base is nn.Module:
             self.current_epoch = 0              # Lightning's Trainer keeps this; here the training loop sets it
 
@@ -337,8 +338,14 @@ class DDPM(_Base):
         and every true molecule is fingerprinted (``metrics.analyze_fingerprints`` / ``compute_diversity``; this project's own
         circular fingerprint, not RDKit's Morgan; pocket rows dropped): ``internal_diversity`` and
         ``internal_diversity_linker`` among each input's samples, ``similarity_to_true`` and ``similarity_to_true_linker``.
+        With ``self.pose_metrics`` the internal geometry of every sample and of its true molecule is checked
+        (``metrics.analyze_pose_checks`` / ``compute_pose_checks``; a rule of this project's own after the idea of PoseBusters'
+        intramolecular checks, NOT PoseBusters' numbers; pocket rows dropped, the linker rows marked): ``pose_valid``,
+        ``bond_lengths_valid``, ``bond_angles_valid``, ``internal_clash_free``, their ``_linker`` variants, the per-molecule
+        means and the ``true_`` values.
         No animation, no WandB."""
         pred, true, input_index = [], [], []
+        pred_poses, true_poses = [], []
         pred_aromatic, true_aromatic = [], []
         pred_rings, true_rings = [], []
         pred_prints, true_prints, print_input = [], [], []
@@ -369,6 +376,10 @@ class DDPM(_Base):
                     data['linker_mask'], drop_mask=drop))
             if self.aromatic_metrics:
                 true_aromatic_batch = mol_metrics.aromatic_to_host(mol_metrics.analyze_aromatic(
+                    data['one_hot'][:, :, :self.num_classes], data['positions'], data['atom_mask'], self.is_geom,
+                    data['linker_mask'], drop_mask=drop))
+            if self.pose_metrics:
+                true_pose_batch = mol_metrics.pose_checks_to_host(mol_metrics.analyze_pose_checks(
                     data['one_hot'][:, :, :self.num_classes], data['positions'], data['atom_mask'], self.is_geom,
                     data['linker_mask'], drop_mask=drop))
             if self.diversity_metrics:                                             # one row per input, kept on the device
@@ -426,6 +437,11 @@ class DDPM(_Base):
                     pred_aromatic += mol_metrics.aromatic_to_host(mol_metrics.analyze_aromatic(
                         one_hot, x, node_mask, self.is_geom, node_mask * (1 - frag), drop_mask=out_drop))
                     true_aromatic += true_aromatic_batch
+                if self.pose_metrics:                                              # the template's linker rows marked
+                    frag = torch.nn.functional.pad(data['fragment_mask'], (0, 0, 0, node_mask.shape[1] - data['fragment_mask'].shape[1]))
+                    pred_poses += mol_metrics.pose_checks_to_host(mol_metrics.analyze_pose_checks(
+                        one_hot, x, node_mask, self.is_geom, node_mask * (1 - frag), drop_mask=out_drop))
+                    true_poses += true_pose_batch
                 if self.diversity_metrics:                                         # the template's linker rows the centres
                     frag = torch.nn.functional.pad(data['fragment_mask'], (0, 0, 0, node_mask.shape[1] - data['fragment_mask'].shape[1]))
                     pred_prints.append(mol_metrics.analyze_fingerprints(
@@ -453,6 +469,8 @@ class DDPM(_Base):
             scores.update(mol_metrics.compute_rings(pred_rings, true_rings))
         if self.aromatic_metrics:
             scores.update(mol_metrics.compute_aromatic(pred_aromatic, true_aromatic))
+        if self.pose_metrics:
+            scores.update(mol_metrics.compute_pose_checks(pred_poses, true_poses))
         if self.diversity_metrics:
             records = []
             if pred_prints:

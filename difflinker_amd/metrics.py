@@ -48,6 +48,11 @@ the protein, and more or fewer than the data set's own linker in the same pocket
 acceptor from elements and geometry, and the intermolecular terms of Trott & Olson (AutoDock Vina, 2010) over them
 (``dl_interaction_types`` and ``dl_interaction_scores``, ``csrc/interaction.hip``).  This project's own rule after that
 published form - NOT AutoDock Vina's numbers: no hydrogens, no PDBQT typing, no search, no intramolecular term.
+
+``analyze_pose_checks`` / ``compute_pose_checks`` ask what none of the above does: is the molecule's own 3D geometry
+physically plausible?  Bond lengths against the typical lengths of the bond table, bond angles against the ideal of the
+centre's class, and clashes between atoms four or more bonds apart (``dl_pose_checks``, ``csrc/pose_checks.hip``), on the
+geometric bond orders.  This project's own rule after the idea of PoseBusters' intramolecular checks - NOT PoseBusters.
 """
 import ctypes
 import math
@@ -1596,4 +1601,151 @@ def compute_pharmacophores(records, linker_records=None, shape_records=None):
               if _pharm_scored(m) and _shape_scored(s)]
         above = lambda bar: 100.0 * sum(v > bar for v in sc) / len(sc) if sc else None   # noqa: E731
         out.update(sc_similarity=mean(sc), sc_similarity_7=above(0.7), sc_similarity_8=above(0.8), sc_similarity_9=above(0.9))
+    return out
+
+
+PoseChecks = namedtuple('PoseChecks', 'counts atom_flags status refined aromatic')
+PoseRecord = namedtuple('PoseRecord', 'counts linker_counts n_flagged_atoms status')
+POSE_COUNTS = ('bonds_checked', 'bonds_untabled', 'bonds_short', 'bonds_long', 'angles_checked', 'angles_bad', 'pairs_checked',
+               'clashes')
+POSE_NAMES = ('bond_lengths_valid', 'bond_angles_valid', 'internal_clash_free', 'pose_valid',
+              'bond_lengths_valid_linker', 'bond_angles_valid_linker', 'internal_clash_free_linker', 'pose_valid_linker',
+              'bad_bonds_per_molecule', 'bad_angles_per_molecule', 'internal_clashes_per_molecule')
+_POSE_TABLES = {}
+
+
+def _pose_tables(device, is_geom, length_bounds, angle_tolerance, clash_scale):
+    key = (device, bool(is_geom), tuple(float(v) for v in length_bounds), float(angle_tolerance), float(clash_scale))
+    if key not in _POSE_TABLES:
+        _POSE_TABLES[key] = tuple(t.to(device).contiguous() for t in (
+            const.length_bounds_table(is_geom, *length_bounds), const.angle_cos_table(angle_tolerance),
+            const.internal_clash_table(is_geom, clash_scale)))
+    return _POSE_TABLES[key]
+
+
+def pose_checks(one_hot, x, node_mask, found, is_geom, drop_mask=None, mark_mask=None, atom_planar=None,
+                length_bounds=(0.75, 1.25), angle_tolerance=25.0, clash_scale=0.75):
+    """ONE launch of ``dl_pose_checks`` (``csrc/pose_checks.hip``) on the bond list ``found`` of ``perceive_bonds`` or
+    ``refine_bond_orders`` for the same ``one_hot``, ``x`` and ``node_mask``, without a host synchronisation.  ``drop_mask``
+    and ``mark_mask`` are ``[B,N]`` or ``[B,N,1]`` by row, ``atom_planar`` is ``[B,N]`` by atom number.  Returns device int32
+    tensors ``(counts [B,2,8], atom_flags [B,N], status [B])``; ``analyze_pose_checks`` states the rule."""
+    others = tuple(m for m in (node_mask, drop_mask, mark_mask, atom_planar) if m is not None)
+    if not (one_hot.is_cuda and x.is_cuda and all(m.is_cuda for m in others)):
+        raise _lib.HipLibraryError('pose_checks runs on the HIP device only (no CPU fallback): '
+                                   f'got tensors on {one_hot.device}, {x.device}, {[str(m.device) for m in others]}')
+    B, N, nf = one_hot.shape
+    if x.shape != (B, N, 3) or any(m.numel() != B * N for m in others):
+        raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, x {tuple(x.shape)}, masks '
+                         f'{[tuple(m.shape) for m in others]}')
+    dev = one_hot.device
+    given = normalize_bonds(found, B, dev, 'pose_checks')
+    f32 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()     # noqa: E731
+    one_hot, x, node_mask, drop_mask, mark_mask = f32(one_hot), f32(x), f32(node_mask), f32(drop_mask), f32(mark_mask)
+    if atom_planar is not None:
+        atom_planar = (atom_planar.reshape(B, N) != 0).to(device=dev, dtype=torch.int32).contiguous()
+    bounds, cosines, clash = _pose_tables(dev, is_geom, length_bounds, angle_tolerance, clash_scale)
+    if clash.shape[0] < nf:
+        raise ValueError(f'one_hot has {nf} types, the vocabulary {clash.shape[0]}')
+    if clash.shape[0] > nf:                                  # the kernel indexes the tables with nf
+        bounds, clash = bounds[:nf, :nf].contiguous(), clash[:nf, :nf].contiguous()
+    capacity = given.bonds.shape[1]
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    counts, atom_flags, status = i32(B, 2, _lib.DL_POSE_COUNTS), i32(B, N), i32(B)
+    opt = lambda t: None if t is None else t.data_ptr()                     # noqa: E731
+    args = _lib.DLPoseArgs(
+        B=B, N=N, nf=nf, x=x.data_ptr(), one_hot=one_hot.data_ptr(), node_mask=node_mask.data_ptr(), drop_mask=opt(drop_mask),
+        mark_mask=opt(mark_mask), atom_planar=opt(atom_planar), length_bounds2=bounds.data_ptr(), angle_cos=cosines.data_ptr(),
+        clash2=clash.data_ptr(), capacity=capacity, n_bonds_in=given.n_bonds.data_ptr(),
+        bonds=given.bonds.data_ptr() if capacity else None, status_in=opt(given.status), counts=counts.data_ptr(),
+        atom_flags=atom_flags.data_ptr(), status=status.data_ptr())
+    with torch.cuda.device(dev):
+        args.stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(_lib.load().dl_pose_checks(ctypes.byref(args)), 'dl_pose_checks')
+    return counts, atom_flags, status
+
+
+def analyze_pose_checks(one_hot, x, node_mask, is_geom, linker_mask, drop_mask=None, margins=const.MARGINS_EDM,
+                        length_bounds=(0.75, 1.25), angle_tolerance=25.0, clash_scale=0.75):
+    """Is the internal 3D geometry of every molecule of a batch plausible?  Three launches on the HIP device and no host round
+    trip between them: ``perceive_bonds``, ``refine_bond_orders`` and ``dl_pose_checks``.  The check ALWAYS runs on the
+    geometric (Kekule) orders and on ``atom_aromatic``, whatever orders the files are written with: the distance table's
+    arbitrary orders inside aromatic rings would misclass ring atoms.
+
+    THE RULE is this project's own, after the idea of PoseBusters' intramolecular checks (``include/difflinker_hip.h`` states
+    it in full; ``tests/pose_checks_ref.py`` restates it).  It is NOT PoseBusters and these are NOT PoseBusters' numbers: no
+    RDKit distance-geometry bounds, no hydrogens, no energy, no ring or double-bond flatness.  A bond of order k between two
+    elements is SHORT below ``length_bounds[0]`` and LONG above ``length_bounds[1]`` times the typical length of that order
+    (``const.BOND_LENGTHS``; a pair without one is ``untabled`` and not checked).  An angle j-a-k at an atom with 2 to 4
+    neighbours is BAD when it is more than ``angle_tolerance`` degrees from 180 (a triple or two double bonds at a), 120 (a
+    double bond at an atom of at most three neighbours, or an aromatic atom) or 109.47 degrees (otherwise); the angles of
+    three- and four-rings are exempt.  Two atoms with no path of three or fewer bonds between them CLASH when they are closer
+    than ``clash_scale`` times the sum of their van der Waals radii (``const.VDW_RADII``).  fp64 throughout.
+
+    ``linker_mask`` rows are marked - an item counts as the linker's when one of its atoms is a linker atom - and
+    ``drop_mask`` rows (the pocket of a pocket model) are left out, both ``[B,N]`` or ``[B,N,1]``.  Returns a ``PoseChecks`` of
+    device tensors: ``counts [B,2,8]`` (row 0 all items, row 1 the linker's; ``POSE_COUNTS`` names the eight values),
+    ``atom_flags [B,N]`` by atom number (1 an end of a short or long bond, 2 the centre of a bad angle, 4 in a clash),
+    ``status [B]`` (the bits of the two launches before plus ``_lib.DL_POSE_*``; more than 256 kept atoms or a non-finite
+    coordinate: nothing is counted), and ``refined`` / ``aromatic`` as ``refine_bond_orders`` returns them."""
+    if not (one_hot.is_cuda and x.is_cuda and node_mask.is_cuda and linker_mask.is_cuda):
+        raise _lib.HipLibraryError('analyze_pose_checks runs on the HIP device only (no CPU fallback): '
+                                   f'got tensors on {one_hot.device}, {x.device}, {node_mask.device}, {linker_mask.device}')
+    B, N = one_hot.shape[:2]
+    if linker_mask.numel() != B * N:
+        raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, linker_mask {tuple(linker_mask.shape)}')
+    found = perceive_bonds(one_hot, x, node_mask, is_geom, margins)
+    linker = linker_mask.reshape(B, N).to(torch.float32)
+    refined, aromatic = refine_bond_orders(found, one_hot, x, node_mask, is_geom, drop_mask, linker)
+    counts, atom_flags, status = pose_checks(one_hot, x, node_mask, refined._replace(status=aromatic.status), is_geom, drop_mask,
+                                             linker, aromatic.atom_aromatic, length_bounds, angle_tolerance, clash_scale)
+    return PoseChecks(counts, atom_flags, status, refined, aromatic)
+
+
+def pose_checks_to_host(result):
+    """One ``PoseRecord`` of plain values per molecule of a ``PoseChecks``: the eight counts over all items and over the
+    linker's, the number of flagged atoms, and ``status``."""
+    counts, status = result.counts.cpu().tolist(), result.status.cpu().tolist()
+    flagged = (result.atom_flags != 0).sum(dim=1).cpu().tolist()
+    return [PoseRecord(tuple(counts[b][0]), tuple(counts[b][1]), flagged[b], status[b]) for b in range(len(status))]
+
+
+def _pose_scores(records, prefix=''):
+    short, long_, bad_angles, clashes = (POSE_COUNTS.index(name) for name in ('bonds_short', 'bonds_long', 'angles_bad', 'clashes'))
+    mean = lambda values: float(sum(values) / len(values)) if values else None      # noqa: E731
+    good = [m for m in records if m.status == 0]
+    out = {}
+    for suffix, row in (('', 'counts'), ('_linker', 'linker_counts')):
+        tests = {'bond_lengths_valid': lambda c: c[short] + c[long_] == 0, 'bond_angles_valid': lambda c: c[bad_angles] == 0,
+                 'internal_clash_free': lambda c: c[clashes] == 0,
+                 'pose_valid': lambda c: c[short] + c[long_] + c[bad_angles] + c[clashes] == 0}
+        for name, passes in tests.items():
+            out[prefix + name + suffix] = mean([m.status == 0 and passes(getattr(m, row)) for m in records])
+    out[prefix + 'bad_bonds_per_molecule'] = mean([m.counts[short] + m.counts[long_] for m in good])
+    out[prefix + 'bad_angles_per_molecule'] = mean([m.counts[bad_angles] for m in good])
+    out[prefix + 'internal_clashes_per_molecule'] = mean([m.counts[clashes] for m in good])
+    return out
+
+
+def compute_pose_checks(pred, true=None):
+    """Scores of the ``PoseRecord`` values ``pred`` (``pose_checks_to_host``), in fp64.  The rule is this project's own, after
+    the idea of PoseBusters' intramolecular checks, NOT PoseBusters: the numbers compare runs of this project with each other.
+
+    ``bond_lengths_valid``             share of the records with status 0 and no short or long bond
+    ``bond_angles_valid``              share with status 0 and no bad angle
+    ``internal_clash_free``            share with status 0 and no internal clash
+    ``pose_valid``                     share with status 0 and none of the three
+    ``..._linker``                     the same four over the items that touch a linker atom.  THE INFORMATIVE ONES: the
+                                       fragments are input, and crystal fragments are noisy
+    ``bad_bonds_per_molecule``         mean number of short or long bonds, over the records with status 0
+    ``bad_angles_per_molecule``        mean number of bad angles, likewise
+    ``internal_clashes_per_molecule``  mean number of clashing pairs, likewise
+
+    A record with any status bit (a cut list, an entry that is no bond, more than 256 atoms, a non-finite coordinate) is valid
+    in nothing.  With ``true`` - one record per prediction, the data set's own molecule - the same eleven values of those
+    records under ``true_`` + name.  A share or a mean over nothing is ``None``, as in ``compute_aromatic``."""
+    if true is not None and len(true) != len(pred):
+        raise ValueError(f'{len(pred)} predictions, {len(true)} true records')
+    out = _pose_scores(pred)
+    if true is not None:
+        out.update(_pose_scores(true, 'true_'))
     return out

@@ -58,7 +58,7 @@ def _prepare(checkpoint, prefix, data, n_steps, device):
 def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=None, linker_size_model=None,
            output_format='xyz', metrics=False, geometry=False, clashes=False, shape=False, rings=False,
            bond_orders='distance', aromatic=False, diversity=False, diversity_reference=None, pharmacophore=False,
-           interactions=False, hydrogens=False):
+           interactions=False, hydrogens=False, pose_checks=False):
     """``sample.py``.  Returns the output directory.  ``metrics=True`` scores the molecules sampled in this call against
     the data set's own (``metrics.compute_metrics``: valence rule, connectivity, uniqueness, novelty, recovery) and writes
     the result to ``metrics.json`` in the output directory; with ``geometry=True`` as well, the symmetry-aware RMSD of the
@@ -98,7 +98,13 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
     the bond list the files are written with; a rule of this project's own, not RDKit's ``AddHs`` and not OpenBabel's;
     ``bond_orders='geometric'`` is recommended, because the distance table's arbitrary orders inside aromatic rings give
     arbitrary counts there) and ``hydrogens_per_molecule`` to the JSON line; with ``output_format='xyz'`` it raises
-    ``ValueError``.  No score counts them."""
+    ``ValueError``.  No score counts them.
+    ``pose_checks=True`` checks the internal geometry of every sample and of its true molecule, pocket rows left out and the
+    linker rows marked - bond lengths, bond angles, clashes between atoms four or more bonds apart, always on the geometric
+    bond orders (``metrics.analyze_pose_checks`` / ``compute_pose_checks``: a rule of this project's own after the idea of
+    PoseBusters' intramolecular checks, NOT PoseBusters' numbers) - and writes ``pose_valid``, ``bond_lengths_valid``,
+    ``bond_angles_valid``, ``internal_clash_free``, their ``_linker`` variants, the per-molecule means and the ``true_``
+    values of all of them to ``metrics.json``."""
     if hydrogens and output_format == 'xyz':
         raise ValueError('hydrogens are written to the .sdf files: pass output_format sdf or both (--output_format); the '
                          '.xyz files stay the heavy-atom format of the reference')
@@ -108,6 +114,7 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
     if bond_orders not in BOND_ORDERS:
         raise ValueError(f'bond_orders must be one of {BOND_ORDERS}, got {bond_orders!r}')
     pred_aromatic, true_aromatic = [], []
+    pred_poses, true_poses = [], []
     found, pred, true, input_index = [], [], [], []
     pred_x, true_x, n_linker = [], [], []
     pred_clashes, true_clashes = [], []
@@ -183,6 +190,10 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
         if aromatic:
             true_aromatic_batch = mol_metrics.aromatic_to_host(mol_metrics.analyze_aromatic(
                 h[:, :, :model.num_classes], x, node_mask, model.is_geom, batch['linker_mask']))
+        if pose_checks:
+            true_pose_batch = mol_metrics.pose_checks_to_host(mol_metrics.analyze_pose_checks(
+                h[:, :, :model.num_classes], x, node_mask, model.is_geom, batch['linker_mask'],
+                drop_mask=batch['pocket_mask'] if moad else None))
         if diversity:                                          # likewise; one row per input, kept on the device
             true_prints.append(mol_metrics.analyze_fingerprints(
                 h[:, :, :model.num_classes], x, node_mask, model.is_geom, batch['linker_mask']))
@@ -234,6 +245,12 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 pred_aromatic += mol_metrics.aromatic_to_host(mol_metrics.analyze_aromatic(
                     hs[:, :, :model.num_classes], xs, out_mask, model.is_geom, out_mask * (1 - pad(batch['fragment_mask']))))
                 true_aromatic += true_aromatic_batch
+            if pose_checks:                                    # likewise; the pocket rows, gone from out_mask, dropped as well
+                pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, out_mask.shape[1] - m.shape[1]))      # noqa: E731
+                pred_poses += mol_metrics.pose_checks_to_host(mol_metrics.analyze_pose_checks(
+                    hs[:, :, :model.num_classes], xs, out_mask, model.is_geom, out_mask * (1 - pad(batch['fragment_mask'])),
+                    drop_mask=pad(batch['pocket_mask']) if moad else None))
+                true_poses += true_pose_batch
             if diversity:                                      # likewise
                 pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, out_mask.shape[1] - m.shape[1]))      # noqa: E731
                 pred_prints.append(mol_metrics.analyze_fingerprints(
@@ -269,7 +286,7 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
         if hydrogens:
             line['hydrogens_per_molecule'] = float(torch.cat(n_hydrogens).float().mean()) if line['molecules'] else 0.0
         print(json.dumps(line))
-    if metrics or clashes or shape or rings or aromatic or diversity or pharmacophore or interactions:
+    if metrics or clashes or shape or rings or aromatic or diversity or pharmacophore or interactions or pose_checks:
         with open(os.path.join(output_dir, 'metrics.json'), 'w') as f:
             scores = {}
             if metrics:
@@ -288,6 +305,8 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 scores.update(mol_metrics.compute_rings(pred_rings, true_rings))
             if aromatic:
                 scores.update(mol_metrics.compute_aromatic(pred_aromatic, true_aromatic))
+            if pose_checks:
+                scores.update(mol_metrics.compute_pose_checks(pred_poses, true_poses))
             if diversity:
                 reference = None if diversity_reference is None else reference_fingerprints(model, diversity_reference)
                 scores.update(_diversity_scores(pred_prints, true_prints, print_input, reference))
@@ -411,6 +430,11 @@ def main(argv=None):
                         'both; a rule of this project, not RDKit\'s AddHs and not OpenBabel\'s).  --bond_orders geometric is '
                         'recommended: the distance table\'s arbitrary orders inside aromatic rings give arbitrary hydrogen '
                         'counts there')
+    p.add_argument('--pose_checks', action='store_true',
+                   help='check the internal geometry of every sample and of its true molecule on the GPU - bond lengths, bond '
+                        'angles, clashes between atoms four or more bonds apart, always on the geometric bond orders (a rule of '
+                        'this project after the idea of PoseBusters\' intramolecular checks, NOT PoseBusters\' numbers) - and '
+                        'write pose_valid, its parts, their _linker variants and the true_ values to metrics.json')
     a = p.parse_args(argv)
     if a.keep_frames is not None:
         print(sample_trajectories(a.checkpoint, a.samples, a.prefix, a.keep_frames, a.device, a.data, a.n_steps))
@@ -424,7 +448,8 @@ def main(argv=None):
                      **({'diversity_reference': a.diversity_reference} if a.diversity_reference else {}),
                      **({'pharmacophore': True} if a.pharmacophore else {}),
                      **({'interactions': True} if a.interactions else {}),
-                     **({'hydrogens': True} if a.hydrogens else {})))
+                     **({'hydrogens': True} if a.hydrogens else {}),
+                     **({'pose_checks': True} if a.pose_checks else {})))
 
 
 if __name__ == '__main__':

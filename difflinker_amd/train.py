@@ -116,6 +116,11 @@ def main(argv=None):
                    help='with --sample_every_epochs, pocket models: add the contact scores of the sampled linkers with the '
                         'pocket atoms to the epoch scores (the intermolecular terms of Trott & Olson under this project\'s '
                         'heavy-atom typing, not AutoDock Vina\'s numbers)')
+    p.add_argument('--pose_checks', action='store_true',
+                   help='with --sample_every_epochs: check the internal geometry of every sample and of its true molecule - bond '
+                        'lengths, bond angles, clashes between atoms four or more bonds apart, on the geometric bond orders (a '
+                        'rule of this project after the idea of PoseBusters\' intramolecular checks, NOT PoseBusters\' numbers) - '
+                        'and add pose_valid, its parts and their _linker variants to the epoch scores')
     a = p.parse_args(argv)
     cfg = dict(DEFAULTS)
     if a.config is not None:
@@ -156,6 +161,7 @@ def main(argv=None):
     model.aromatic_metrics = bool(a.aromatic)
     model.diversity_metrics = bool(a.diversity)
     model.pharmacophore_metrics = bool(a.pharmacophore)
+    model.pose_metrics = bool(a.pose_checks)
     kept = lambda: {'best_validity_and_connectivity': best} if a.sample_every_epochs else {}   # noqa: E731
     step, epoch = start_step, start_epoch
     n_epochs = int(cfg['n_epochs'])

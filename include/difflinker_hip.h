@@ -85,6 +85,10 @@
  *                                           one linker joined to three, four or five fragments
  *   dl_pocket_select                     <- get_pocket of data/pocket/prepare_dataset.py (residues with an atom within 6 A
  *                                           of the ligand), for every (ligand, protein) pair of a batch
+ *   dl_pose_checks                       <- (no reference counterpart: the field asks PoseBusters whether a generated molecule's own
+ *                                           geometry is plausible) bond lengths against the reference's typical lengths, bond
+ *                                           angles against the ideal of the centre's class, and clashes between atoms four or
+ *                                           more bonds apart.  The rule stated below is this project's own, NOT PoseBusters'
  *   dl_size_train_forward / dl_size_train_backward
  *                                        <- SizeClassifier.forward in training mode + loss.backward()
  *                                           (src/linker_size_lightning.py:83-117, :163-167)
@@ -1730,6 +1734,91 @@ typedef struct dl_hydrogens_args {
     void* stream;                   /* hipStream_t; NULL: the default stream */
 } dl_hydrogens_args;
 int32_t dl_add_hydrogens(const dl_hydrogens_args* args);
+
+/* ---- internal geometry of a molecule: bond lengths, bond angles, internal clashes (pose_checks.hip) ----------------
+ * Is the molecule's own 3D geometry physically plausible?  One workgroup per molecule, ONE launch per batch, on the bond list
+ * with orders that dl_perceive_bonds or dl_aromatic_rings left on the device; the entry point takes its arguments alone, the
+ * stream as the last field, as dl_add_hydrogens does.  THE RULE BELOW IS THIS PROJECT'S OWN, after the idea of PoseBusters'
+ * intramolecular checks (Buttenschoen, Morris & Deane, Chem. Sci. 2024).  It is NOT PoseBusters and gives NOT PoseBusters'
+ * numbers: there is no RDKit distance-geometry bounds matrix, no hydrogens, no energy, no ring or double-bond flatness term.
+ * tests/pose_checks_ref.py restates it in plain Python and the kernel agrees with that bit for bit.
+ *
+ * CONVENTIONS, those of dl_add_hydrogens.  Atom k is the k-th row with node_mask != 0; its type t is the FIRST largest
+ * entry of its one_hot row.  `drop_mask` (may be NULL) removes atoms AFTER that numbering, together with their bonds.  An
+ * entry (i, j, order) is a bond when 0 <= i, j < atoms, i != j and 1 <= order <= 3, in either orientation; any other entry
+ * is skipped and sets DL_POSE_BAD_BOND.  A repeated pair sets DL_POSE_BAD_BOND too and counts once, with its FIRST
+ * entry's order.  Entries from min(n_bonds_in, capacity) on are not read.  "Kept" means: not dropped, both ends for a bond;
+ * a "neighbour" is the other end of a kept pair.  `mark_mask` (may be NULL: nothing is marked) marks atoms by row - the
+ * linker; an item (a bond, an angle, a far pair) is MARKED when at least one of its atoms is.
+ *
+ * ARITHMETIC.  fp64 on (double) x, contraction off, every + - * / and sqrt rounded on its own in the order written, as in
+ * dl_add_hydrogens: v = x_j - x_a by component, v . w = (v_x*w_x + v_y*w_y) + v_z*w_z.  Every threshold is formed by the host
+ * in fp64 and passed as a table; the kernel only compares.
+ *
+ * 1. BOND LENGTHS.  For every kept pair (a, j) of order k with types (s, t): d2 = v . v with v = x_j - x_a, a < j.
+ *    lo2 = length_bounds2[s][t][k-1][0] and hi2 = length_bounds2[s][t][k-1][1], in A^2: ((lo * L0)^2, (hi * L0)^2) of the typical
+ *    length L0 of that order between those elements (the host's const.BOND_LENGTHS / 100; lo, hi = 0.75, 1.25 by default,
+ *    PoseBusters' factors).  A pair with both bounds 0 has no typical length: it counts as UNTABLED and is not checked.
+ *    Otherwise it is checked, SHORT when d2 < lo2 and LONG when d2 > hi2, both strict.
+ * 2. BOND ANGLES.  The centre a is a kept atom with 2 <= d <= 4 neighbours; n2 and n3 count its pairs of order 2 and 3.  Its
+ *    class is the first that holds.  LINEAR (0): d == 2, and n3 >= 1 or n2 == 2.  TRIGONAL (1): d <= 3 and n2 >= 1, or
+ *    atom_planar[a] != 0 (by atom number, may be NULL: the atom_aromatic of dl_aromatic_rings).  TETRAHEDRAL (2): otherwise.
+ *    This is not the class rule of dl_add_hydrogens: a sulfone S with four neighbours is tetrahedral here.  Atoms with d > 4
+ *    are not checked.  Every pair of neighbours j < k of a is one angle, except when j and k are bonded (a three-ring) or
+ *    share a neighbour other than a (a four-ring).  With u = x_j - x_a and v = x_k - x_a,
+ *    c = (u . v) / sqrt((u . u) * (v . v)), and the angle is BAD when c < angle_cos[class][0] or c > angle_cos[class][1]:
+ *    the host's cos(theta0 + tol) and cos(theta0 - tol) for theta0 = 180, 120 and acos(-1/3) degrees and tol = 25 by default,
+ *    -2 where theta0 + tol reaches 180 (and 2 where theta0 - tol reaches 0), which never fires.  A zero-length u or v gives a
+ *    NaN that no comparison flags: two atoms at one point are caught as a short bond or as a clash instead, not here.
+ * 3. INTERNAL CLASHES.  The FAR PAIRS are the unordered pairs of kept atoms with NO path of three or fewer bonds between
+ *    them: four or more bonds apart, or in different pieces.  A far pair (a, b), a < b, with types (s, t) CLASHES when
+ *    d2 < clash2[s][t] and that entry is positive: the host's (scale * (R[s] + R[t]))^2 over Bondi's radii, scale 0.75 by
+ *    default, in A^2.
+ *
+ *   counts      [B][2][8], written in full.  Row 0: all items; row 1: the marked ones.  The eight values: bonds checked, bonds
+ *               untabled, short, long, angles checked, angles bad, far pairs checked, clashes.
+ *   atom_flags  [B][N] by atom number, written in full: bit 1 an end of a short or long bond, bit 2 the centre of a bad angle,
+ *               bit 4 in a clashing pair; 0 for dropped atoms and from the atom count on.
+ *   status      [B]: the bits of `status_in` (may be NULL: none), plus DL_BONDS_OVERFLOW when n_bonds_in > capacity (a negative
+ *               n_bonds_in counts as 0), DL_POSE_BAD_BOND, and the limits.  None disturbs the other molecules of the launch.
+ *               DL_POSE_TOO_LARGE: more than DL_POSE_MAX_ATOMS KEPT atoms (N itself may be 1024): every count and flag is 0,
+ *                 and neither the list of bonds nor the coordinates are looked at.
+ *               DL_POSE_NONFINITE: a kept atom has a NaN or inf coordinate; every count and flag is 0.
+ *
+ * The same bits on every run and under every order of the list: every sum is a sum of integers.  Global memory is written
+ * with plain stores only; the callee allocates nothing and needs no workspace.  A null `args`, B < 0, N < 1, N > 1024, nf < 1
+ * or capacity < 0 return DL_ERR_BAD_ARG; then B == 0 returns DL_OK without a launch; then a null pointer (other than drop_mask,
+ * mark_mask, atom_planar, status_in, stream, and `bonds` when capacity is 0) returns DL_ERR_BAD_ARG, all before any device work.
+ * Limits of the rule: heavy atoms only; three- and four-ring angles are exempt, not checked against their own ideals; an
+ * amide or aniline N is held to the tetrahedral angle (its 120 degrees are within the default tolerance); the typical
+ * lengths know no aromatic order, so a Kekule ring bond is compared as the single or double bond its order says.  Not here:
+ * flatness of rings and double bonds, torsions, strain energies, minimisation. */
+#define DL_POSE_MAX_ATOMS 256       /* kept atoms per molecule */
+#define DL_POSE_TOO_LARGE 4         /* status bit, same value as DL_HYDRO_TOO_LARGE */
+#define DL_POSE_BAD_BOND 8          /* status bit, same value as DL_HYDRO_BAD_BOND */
+#define DL_POSE_NONFINITE 64        /* status bit, same value as DL_HYDRO_NONFINITE */
+#define DL_POSE_COUNTS 8            /* values per row of `counts` */
+typedef struct dl_pose_args {
+    int32_t B, N, nf;
+    const float* x;                 /* device f32 [B,N,3], Angstrom */
+    const float* one_hot;           /* device f32 [B,N,nf] */
+    const float* node_mask;         /* device f32 [B,N] */
+    const float* drop_mask;         /* device f32 [B,N] or NULL */
+    const float* mark_mask;         /* device f32 [B,N] or NULL */
+    const int32_t* atom_planar;     /* device int32 [B,N] by atom number, or NULL: dl_aromatic_args.atom_aromatic */
+    const double* length_bounds2;   /* device f64 [nf,nf,3,2]: squared lower and upper bond length, A^2; 0, 0: no entry */
+    const double* angle_cos;        /* device f64 [3,2]: lowest and highest cosine of the classes LINEAR, TRIGONAL, TETRAHEDRAL */
+    const double* clash2;           /* device f64 [nf,nf]: squared clash distance, A^2 */
+    int32_t capacity;               /* bonds the list holds per molecule */
+    const int32_t* n_bonds_in;      /* device int32 [B]: dl_bonds_args.n_bonds */
+    const int32_t* bonds;           /* device int32 [B,capacity,3] (may be NULL when capacity is 0) */
+    const int32_t* status_in;       /* device int32 [B] or NULL: dl_bonds_args.status or dl_aromatic_args.status */
+    int32_t* counts;                /* device int32 [B,2,8] out */
+    int32_t* atom_flags;            /* device int32 [B,N] out */
+    int32_t* status;                /* device int32 [B] out */
+    void* stream;                   /* hipStream_t; NULL: the default stream */
+} dl_pose_args;
+int32_t dl_pose_checks(const dl_pose_args* args);
 
 const char* dl_error_string(int32_t status);
 int32_t dl_last_hip_error(void);
