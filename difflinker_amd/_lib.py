@@ -411,6 +411,26 @@ EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_stri
            'dl_tanimoto_nearest', 'dl_pharmacophore_features', 'dl_feature_match', 'dl_best_rmsd')
 TEST_HOOK_EXPORTS = ('dl_debug_team_fault', 'dl_debug_slot_order')       # declared under #ifdef DL_TEST_HOOKS: the test-hooks build only
 
+# The entry points that take one struct and return a status: ``int32 f(const STRUCT*)`` when the struct's last field is
+# ``stream``, ``int32 f(const STRUCT*, void* stream)`` otherwise.  ``_open`` declares them from this table and ``launch``
+# calls them; which of the two forms an entry point has is read from the struct (``_stream_is_field``) and stated nowhere else.
+STRUCT_ENTRY_POINTS = {
+    'dl_edm_loss_prologue': DLLossArgs, 'dl_edm_loss_epilogue': DLLossArgs, 'dl_egnn_backward_fc': DLBackwardArgs,
+    'dl_size_train_forward': DLSizeTrainArgs, 'dl_size_train_backward': DLSizeTrainArgs,
+    'dl_perceive_bonds': DLBondsArgs, 'dl_molecule_keys': DLMolKeysArgs, 'dl_best_rmsd': DLRmsdArgs,
+    'dl_clash_scores': DLClashArgs, 'dl_shape_scores': DLShapeArgs, 'dl_ring_scores': DLRingsArgs,
+    'dl_fragment_cuts': DLFragmentArgs, 'dl_fragment_multicuts': DLFragmentMultiArgs, 'dl_aromatic_rings': DLAromaticArgs,
+    'dl_pocket_select': DLPocketArgs,
+    'dl_interaction_types': DLInteractTypesArgs, 'dl_interaction_scores': DLInteractArgs,
+    'dl_fingerprints': DLFingerprintArgs, 'dl_tanimoto_nearest': DLTanimotoArgs,
+    'dl_pharmacophore_features': DLPharmArgs, 'dl_feature_match': DLFeatureMatchArgs,
+    'dl_add_hydrogens': DLHydrogensArgs, 'dl_pose_checks': DLPoseArgs,
+}
+
+
+def _stream_is_field(struct):
+    return any(name == 'stream' for name, _ in struct._fields_)
+
 _lib = None
 
 
@@ -501,9 +521,9 @@ def _open(path):
     lib.dl_inpaint_step.argtypes = [i32, i32, i32] + [vp] * 10 + [DLInpaintCoef, vp, vp]
     lib.dl_philox_fill.restype = i32
     lib.dl_philox_fill.argtypes = [ctypes.c_uint64, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp]
-    for name in ('dl_edm_loss_prologue', 'dl_edm_loss_epilogue'):
+    for name, struct in STRUCT_ENTRY_POINTS.items():
         getattr(lib, name).restype = i32
-        getattr(lib, name).argtypes = [ctypes.POINTER(DLLossArgs), vp]
+        getattr(lib, name).argtypes = [ctypes.POINTER(struct)] if _stream_is_field(struct) else [ctypes.POINTER(struct), vp]
     lib.dl_edm_loss_grad.restype = i32
     lib.dl_edm_loss_grad.argtypes = [ctypes.POINTER(DLLossArgs), vp, vp, vp]
     lib.dl_egnn_backward_fc_num_params.restype = ctypes.c_int64
@@ -511,8 +531,6 @@ def _open(path):
     lib.dl_egnn_backward_fc_workspace_bytes.restype = ctypes.c_size_t
     lib.dl_egnn_backward_fc_workspace_bytes.argtypes = [ctypes.POINTER(DLBackwardArgs)]
     lib.dl_egnn_backward_max_atoms.restype = i32
-    lib.dl_egnn_backward_fc.restype = i32
-    lib.dl_egnn_backward_fc.argtypes = [ctypes.POINTER(DLBackwardArgs), vp]
     lib.dl_egnn_backward_pocket_workspace_bytes.restype = ctypes.c_size_t
     lib.dl_egnn_backward_pocket_workspace_bytes.argtypes = [ctypes.POINTER(DLBackwardArgs), i32]
     lib.dl_egnn_backward_pocket.restype = i32
@@ -521,47 +539,8 @@ def _open(path):
     lib.dl_size_train_num_params.argtypes = [ctypes.POINTER(DLSizeTrainArgs)]
     lib.dl_size_train_workspace_bytes.restype = ctypes.c_size_t
     lib.dl_size_train_workspace_bytes.argtypes = [ctypes.POINTER(DLSizeTrainArgs)]
-    for name in ('dl_size_train_forward', 'dl_size_train_backward'):
-        getattr(lib, name).restype = i32
-        getattr(lib, name).argtypes = [ctypes.POINTER(DLSizeTrainArgs), vp]
     lib.dl_bonds_workspace_bytes.restype = ctypes.c_size_t
     lib.dl_bonds_workspace_bytes.argtypes = [i32, i32]
-    lib.dl_perceive_bonds.restype = i32
-    lib.dl_perceive_bonds.argtypes = [ctypes.POINTER(DLBondsArgs), vp]
-    lib.dl_molecule_keys.restype = i32
-    lib.dl_molecule_keys.argtypes = [ctypes.POINTER(DLMolKeysArgs), vp]
-    lib.dl_clash_scores.restype = i32
-    lib.dl_clash_scores.argtypes = [ctypes.POINTER(DLClashArgs), vp]
-    lib.dl_interaction_types.restype = i32
-    lib.dl_interaction_types.argtypes = [ctypes.POINTER(DLInteractTypesArgs)]
-    lib.dl_interaction_scores.restype = i32
-    lib.dl_interaction_scores.argtypes = [ctypes.POINTER(DLInteractArgs)]
-    lib.dl_shape_scores.restype = i32
-    lib.dl_shape_scores.argtypes = [ctypes.POINTER(DLShapeArgs), vp]
-    lib.dl_ring_scores.restype = i32
-    lib.dl_ring_scores.argtypes = [ctypes.POINTER(DLRingsArgs), vp]
-    lib.dl_fragment_cuts.restype = i32
-    lib.dl_fragment_cuts.argtypes = [ctypes.POINTER(DLFragmentArgs), vp]
-    lib.dl_fragment_multicuts.restype = i32
-    lib.dl_fragment_multicuts.argtypes = [ctypes.POINTER(DLFragmentMultiArgs), vp]
-    lib.dl_aromatic_rings.restype = i32
-    lib.dl_aromatic_rings.argtypes = [ctypes.POINTER(DLAromaticArgs), vp]
-    lib.dl_fingerprints.restype = i32
-    lib.dl_fingerprints.argtypes = [ctypes.POINTER(DLFingerprintArgs)]
-    lib.dl_tanimoto_nearest.restype = i32
-    lib.dl_tanimoto_nearest.argtypes = [ctypes.POINTER(DLTanimotoArgs)]
-    lib.dl_pharmacophore_features.restype = i32
-    lib.dl_pharmacophore_features.argtypes = [ctypes.POINTER(DLPharmArgs)]
-    lib.dl_feature_match.restype = i32
-    lib.dl_feature_match.argtypes = [ctypes.POINTER(DLFeatureMatchArgs)]
-    lib.dl_add_hydrogens.restype = i32
-    lib.dl_add_hydrogens.argtypes = [ctypes.POINTER(DLHydrogensArgs)]
-    lib.dl_pose_checks.restype = i32
-    lib.dl_pose_checks.argtypes = [ctypes.POINTER(DLPoseArgs)]
-    lib.dl_pocket_select.restype = i32
-    lib.dl_pocket_select.argtypes = [ctypes.POINTER(DLPocketArgs), vp]
-    lib.dl_best_rmsd.restype = i32
-    lib.dl_best_rmsd.argtypes = [ctypes.POINTER(DLRmsdArgs), vp]
     lib.dl_size_model_num_tensors.restype = i32
     lib.dl_size_model_num_tensors.argtypes = [ctypes.POINTER(DLSizeConfig)]
     lib.dl_size_model_create.restype = i32
@@ -584,3 +563,34 @@ def check(status, what):
 def ptr(t):
     """Device/host pointer of a tensor (or NULL for None)."""
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def launch(name, args, device):
+    """Call the entry point ``name`` of ``STRUCT_ENTRY_POINTS`` on ``args`` with ``device`` current and on torch's current
+    stream of that device, handed over as the entry point takes it, and raise ``HipLibraryError`` unless it answers ``DL_OK``.
+    Nothing is built, allocated or synchronised here."""
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream(device).cuda_stream
+        if _stream_is_field(STRUCT_ENTRY_POINTS[name]):
+            args.stream = stream
+            status = getattr(load(), name)(ctypes.byref(args))
+        else:
+            status = getattr(load(), name)(ctypes.byref(args), ctypes.c_void_p(stream))
+        check(status, name)
+
+
+def require_device(who, **tensors):
+    """Raise ``HipLibraryError`` when one of the named tensors (``None``: not given) is not on a HIP device."""
+    given = {name: t for name, t in tensors.items() if t is not None}
+    if not all(t.is_cuda for t in given.values()):
+        raise HipLibraryError(f'{who} runs on the HIP device only (no CPU fallback): got '
+                              + ', '.join(f'{name} on {t.device}' for name, t in given.items()))
+
+
+def dense(t, device, dtype):
+    """``t`` as a contiguous tensor of ``dtype`` on ``device`` - what a kernel reads at its ``data_ptr()``; ``None`` stays."""
+    return None if t is None else t.to(device=device, dtype=dtype).contiguous()
+
+
+def empty_i32(device, *shape):
+    return torch.empty(shape, dtype=torch.int32, device=device)

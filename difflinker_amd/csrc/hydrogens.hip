@@ -6,9 +6,8 @@
 //
 //   stage    rows ranked by number_rows; type, default valence, planar flag, atom number and coordinates of the kept atoms
 //            go to LDS by kept index
-//   build    three 256 x 256 bit matrices over the kept atoms: the pairs, the pairs of order 2 and of order 3.  add_pair
-//            tells whether any pair is repeated; only then an entry looks through the entries before it, so that the first
-//            entry of a pair alone gives the pair its order
+//   build    three 256 x 256 bit matrices over the kept atoms: the pairs, the pairs of order 2 and of order 3 (the two
+//            passes of mol_graph.h): the first entry of a pair alone gives the pair its order
 //   atoms    thread u owns kept atom u: its three rows give d, the valence sum, the class and the count h; a block scan
 //            over h gives its hydrogens their places, and the thread computes their directions in fp64, one rounding per
 //            operation, from at most three neighbours and one neighbour's neighbour
@@ -17,6 +16,7 @@
 // LDS: 3 x 8 KiB matrices + 4 KiB map + 3 KiB coordinates + per-atom arrays: about 33 KiB, static.
 // Global memory is written with plain vector stores only; no atomics on global memory; no workspace.
 #include "mol_graph.h"
+#include "points.h"
 
 #pragma clang fp contract(off)
 
@@ -34,18 +34,10 @@ constexpr double EPS = 1e-6;
 constexpr double SQRT3 = 0x1.bb67ae8584caap+0, SQRT2_3 = 0x1.a20bd700c2c3ep-1, SQRT8_3 = 0x1.e2b7dddfefa67p-1,
                  SQRT3_2 = 0x1.bb67ae8584caap-1;
 
-__device__ __forceinline__ bool nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
-
-struct V3 {
-    double x, y, z;
-};
-
 __device__ __forceinline__ V3 add(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
 __device__ __forceinline__ V3 scale(double s, V3 a) { return {s * a.x, s * a.y, s * a.z}; }
 __device__ __forceinline__ V3 over(V3 a, double s) { return {a.x / s, a.y / s, a.z / s}; }
 __device__ __forceinline__ V3 neg(V3 a) { return {-a.x, -a.y, -a.z}; }
-__device__ __forceinline__ double dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 __device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 __device__ __forceinline__ V3 unit(V3 a) { return over(a, sqrt(dot(a, a))); }
 
@@ -59,10 +51,6 @@ __device__ __forceinline__ V3 perp(V3 u) {
     const double um = m == 0 ? u.x : m == 1 ? u.y : u.z;
     const V3 e = {m == 0 ? 1.0 : 0.0, m == 1 ? 1.0 : 0.0, m == 2 ? 1.0 : 0.0};
     return unit(sub(e, scale(um, u)));
-}
-
-__device__ __forceinline__ V3 point(const float* xs, int atom) {
-    return {double(xs[atom * 3]), double(xs[atom * 3 + 1]), double(xs[atom * 3 + 2])};
 }
 
 enum : int { T2 = 2, T3 = 3, T4 = 4 };           // the class is its number of sites
@@ -196,12 +184,7 @@ __global__ __launch_bounds__(WG) void hydrogens_kernel(dl_hydrogens_args a) {
         s_dv[kk] = a.default_valence[type];
         s_planar[kk] = planar && planar[k] != 0;
         s_atom[kk] = short(k);
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            const float v = xs[size_t(r) * 3 + d];
-            s_x[kk * 3 + d] = v;
-            bad_x |= nonfinite(v);
-        }
+        bad_x |= stage_point(xs, r, s_x, kk);
     });
 #pragma unroll
     for (int w = 0; w < WORDS; ++w) s_adj[tid * WORDS + w] = s_o2[tid * WORDS + w] = s_o3[tid * WORDS + w] = 0;
@@ -209,25 +192,11 @@ __global__ __launch_bounds__(WG) void hydrogens_kernel(dl_hydrogens_args a) {
 
     // ---- build: the pairs first, then what the first entry of every pair says about it
     const int* list = a.bonds + size_t(b) * capacity * 3;        // never read when nb == 0
-    int bad = 0, repeated = 0;
-    for (int e = tid; e < nb; e += WG) {
-        Bond bd;
-        if (!load_bond(list, e, n, bd, bad)) continue;
-        const int u = s_map[bd.i], v = s_map[bd.j];
-        if ((u | v) < 0) continue;                               // an end is dropped: no bond of this graph, and no error
-        if (!add_pair(s_adj, u, v)) repeated = 1;
-    }
-    repeated = __syncthreads_or(repeated);
-    bad = __syncthreads_or(bad) | repeated;
-    for (int e = tid; e < nb; e += WG) {
-        Bond bd;
-        int ignored = 0;
-        if (!load_bond(list, e, n, bd, ignored)) continue;
-        const int u = s_map[bd.i], v = s_map[bd.j];
-        if ((u | v) < 0 || (repeated && seen_before<3>(list, e, n, bd.i, bd.j))) continue;
+    const PairBuild pairs = build_pairs(list, nb, n, s_map, s_adj);
+    for_each_first_entry(list, nb, n, s_map, pairs.repeated, [&](int, const Bond& bd, int u, int v) {
         if (bd.order == 2) set_pair(s_o2, u, v);
         if (bd.order == 3) set_pair(s_o3, u, v);
-    }
+    });
     bad_x = __syncthreads_or(bad_x);             // also orders the matrices before their reads
 
     // ---- atoms: count, class and places; a molecule with a non-finite coordinate gets none
@@ -248,7 +217,7 @@ __global__ __launch_bounds__(WG) void hydrogens_kernel(dl_hydrogens_args a) {
     }
     if (tid == 0) {
         a.n_h[b] = n_h;
-        a.status[b] = in.status | (bad ? DL_HYDRO_BAD_BOND : 0) | (n_h > Hcap ? DL_HYDRO_OVERFLOW : 0) |
+        a.status[b] = in.status | (pairs.bad ? DL_HYDRO_BAD_BOND : 0) | (n_h > Hcap ? DL_HYDRO_OVERFLOW : 0) |
                       (bad_x ? DL_HYDRO_NONFINITE : 0);
     }
     if (h == 0 || place >= Hcap) return;         // nothing after this point is shared

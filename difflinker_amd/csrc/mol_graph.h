@@ -1,7 +1,9 @@
 // mol_graph.h — what the kernels that read a perceived bond list with 256 threads per molecule share (mol_keys.hip,
-// fingerprint.hip, rings.hip, aromatic.hip), on top of workgroup.h: the 64-bit mixing function of the colour
-// refinement, the test that says whether a list entry is a bond, the list's length and overflow bit, the numbering of the real
-// and of the kept rows, and the 256 x 256 bit matrix in LDS with its breadth-first search.  Small functions that each kernel
+// fingerprint.hip, rings.hip, aromatic.hip, pharmacophore.hip, hydrogens.hip, pose_checks.hip), on top of workgroup.h: the
+// 64-bit mixing function of the colour refinement, the test that says whether a list entry is a bond, the list's length and
+// overflow bit, the numbering of the real and of the kept rows, the 256 x 256 bit matrix in LDS with its breadth-first search,
+// and the two-pass build of the matrices by bond order that the last three share (rings.hip and aromatic.hip build through
+// tagged maps, in their own text; pose_checks.hip has the second pass in its own text: profiles/graph_build/README.md).  Integers only: those three's coordinates are in points.h.  Small functions that each kernel
 // calls in its own order; what a kernel counts and flags around them is its own and is specified in include/difflinker_hip.h.
 // fragment.hip is to use them too and still carries its own copies of the scan, load_bond, seen_before, bit_in_word, has and
 // search: with the shared ones its star enumeration measured 3 to 7 % slower although its text is the same, so it waits
@@ -131,6 +133,44 @@ __device__ __forceinline__ bool add_pair(u64* adj, int u, int v) {
     const u64 old = atomicOr(&adj[lo * MATRIX_WORDS + (hi >> 6)], one);
     atomicOr(&adj[hi * MATRIX_WORDS + (lo >> 6)], 1ull << (lo & 63));
     return !(old & one);
+}
+
+// ---- the ordered build ------------------------------------------------------------------------------------------------------------
+// The matrices of a list of dl_perceive_bonds whose ends go through a plain map from atom number to kept index, or -1 for a
+// dropped atom: "the first entry of a repeated pair gives the pair its order" (include/difflinker_hip.h), written once.
+// build_pairs is the first pass: every bond of the kept graph into adj.  Before the call `map` is written and `adj` is cleared,
+// and a barrier of the kernel's has run since.  Its two workgroup reductions also complete adj; the result is uniform: `bad`
+// (an entry that is no bond, or a repeated pair) and `repeated`
+struct PairBuild {
+    int bad, repeated;
+};
+
+__device__ __forceinline__ PairBuild build_pairs(const int* list, int nb, int n, const int* map, u64* adj) {
+    int bad = 0, repeated = 0;
+    for (int e = threadIdx.x; e < nb; e += WG) {
+        Bond bd;
+        if (!load_bond(list, e, n, bd, bad)) continue;
+        const int u = map[bd.i], v = map[bd.j];
+        if ((u | v) < 0) continue;                               // an end is dropped: no bond of this graph, and no error
+        if (!add_pair(adj, u, v)) repeated = 1;
+    }
+    repeated = __syncthreads_or(repeated);
+    bad = __syncthreads_or(bad) | repeated;
+    return {bad, repeated};
+}
+
+// the second pass: f(e, bond, u, v) for every entry e that is a bond of the kept graph (kept ends u, v) and the first entry of
+// its pair.  What f writes is ordered by the kernel's own barrier after the pass
+template <class F>
+__device__ __forceinline__ void for_each_first_entry(const int* list, int nb, int n, const int* map, int repeated, F&& f) {
+    for (int e = threadIdx.x; e < nb; e += WG) {
+        Bond bd;
+        int ignored = 0;
+        if (!load_bond(list, e, n, bd, ignored)) continue;
+        const int u = map[bd.i], v = map[bd.j];
+        if ((u | v) < 0 || (repeated && seen_before<3>(list, e, n, bd.i, bd.j))) continue;
+        f(e, bd, u, v);
+    }
 }
 
 // the first `limit` atoms of row u of m other than `skip`, ascending; returns how many were written

@@ -8,8 +8,7 @@
 //   stage    rows ranked by number_rows; class, default valence, mark, atom number and coordinates of the kept atoms go to
 //            LDS by kept index
 //   build    four 256 x 256 bit matrices over the kept atoms: the pairs, the pairs of order 2, of order 3, and the aromatic
-//            pairs.  add_pair tells whether any pair is repeated; only then an entry looks through the entries before it, so
-//            that the first entry of a pair alone gives the pair its order and its aromatic flag
+//            pairs (the two passes of mol_graph.h): the first entry of a pair alone gives it its order and its aromatic flag
 //   atoms    thread u owns kept atom u: one pass over its four rows gives deg, val, h, arom and multi; a ballot per wave
 //            writes the 256-bit sets (classes, arom, multi, terminal oxygens) that the neighbour tests AND a row with
 //   rings    thread s walks the aromatic pairs from atom s over larger atoms with two or three aromatic pairs, at most six
@@ -24,6 +23,7 @@
 // scratch per lane for the walk's arrays.
 // Global memory is written with plain vector stores only; no global atomics of any kind; every output element is written.
 #include "mol_graph.h"
+#include "points.h"
 
 #pragma clang fp contract(off)
 
@@ -38,8 +38,6 @@ constexpr int ATOM_FAMILIES = 5;                 // 0 .. 4 sit on an atom, 5 and
 enum : int { CLS_C = 1, CLS_N, CLS_O, CLS_S, CLS_P, CLS_F, CLS_HALOGEN };
 enum : int { SET_C = 0, SET_N, SET_O, SET_S, SET_AROM, SET_MULTI, SET_O1, SET_ELIG, SETS };
 static_assert(DL_PHARM_MAX_ATOMS == MATRIX_ATOMS && MAX_RINGS <= WG, "the matrix holds a molecule; one thread per ring");
-
-__device__ __forceinline__ bool nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
 
 struct Row {
     u64 w[WORDS];
@@ -152,12 +150,7 @@ __global__ __launch_bounds__(WG) void pharmacophore_kernel(dl_pharm_args a) {
         s_dv[kk] = a.default_valence[type];
         s_mark[kk] = mark && mark[r] != 0.0f;
         s_atom[kk] = short(k);
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            const float v = xs[r * 3 + d];
-            s_x[kk * 3 + d] = v;
-            bad_x |= nonfinite(v);
-        }
+        bad_x |= stage_point(xs, r, s_x, kk);
     });
 #pragma unroll
     for (int w = 0; w < WORDS; ++w) s_adj[tid * WORDS + w] = s_o2[tid * WORDS + w] = s_o3[tid * WORDS + w] = s_ar[tid * WORDS + w] = 0;
@@ -168,26 +161,12 @@ __global__ __launch_bounds__(WG) void pharmacophore_kernel(dl_pharm_args a) {
     // ---- build: the pairs first, then what the first entry of every pair says about it
     const int* list = a.bonds + size_t(b) * capacity * 3;        // never read when nb == 0
     const int* arom_in = a.bond_aromatic + size_t(b) * capacity;
-    int bad = 0, repeated = 0;
-    for (int e = tid; e < nb; e += WG) {
-        Bond bd;
-        if (!load_bond(list, e, n, bd, bad)) continue;
-        const int u = s_map[bd.i], v = s_map[bd.j];
-        if ((u | v) < 0) continue;                               // an end is dropped: no bond of this graph, and no error
-        if (!add_pair(s_adj, u, v)) repeated = 1;
-    }
-    repeated = __syncthreads_or(repeated);
-    bad = __syncthreads_or(bad) | repeated;
-    for (int e = tid; e < nb; e += WG) {
-        Bond bd;
-        int ignored = 0;
-        if (!load_bond(list, e, n, bd, ignored)) continue;
-        const int u = s_map[bd.i], v = s_map[bd.j];
-        if ((u | v) < 0 || (repeated && seen_before<3>(list, e, n, bd.i, bd.j))) continue;
+    const PairBuild pairs = build_pairs(list, nb, n, s_map, s_adj);
+    for_each_first_entry(list, nb, n, s_map, pairs.repeated, [&](int e, const Bond& bd, int u, int v) {
         if (bd.order == 2) set_pair(s_o2, u, v);
         if (bd.order == 3) set_pair(s_o3, u, v);
         if (arom_in[e] != 0) set_pair(s_ar, u, v);
-    }
+    });
     __syncthreads();
 
     // ---- atoms: the numbers of every atom, and the sets the neighbour tests need (bit t of word w is thread 64 w + t)
@@ -355,7 +334,7 @@ __global__ __launch_bounds__(WG) void pharmacophore_kernel(dl_pharm_args a) {
         family_count[DL_PHARM_AROMATIC] = n_rings;
         family_count[DL_PHARM_AROMATIC + 1] = s_count[1];
         a.n_features[b] = n_features;
-        a.status[b] = in.status | (bad ? DL_PHARM_BAD_BOND : 0) | (many ? DL_PHARM_MANY_RINGS : 0) |
+        a.status[b] = in.status | (pairs.bad ? DL_PHARM_BAD_BOND : 0) | (many ? DL_PHARM_MANY_RINGS : 0) |
                       (n_features > Fcap ? DL_PHARM_OVERFLOW : 0) | (bad_x ? DL_PHARM_NONFINITE : 0);
     }
 }

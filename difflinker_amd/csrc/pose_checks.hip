@@ -5,9 +5,9 @@
 // dl_pose_checks: one 256-thread workgroup per molecule, one launch per batch, with the conventions of mol_graph.h.
 //
 //   stage    rows ranked by number_rows; type, planar flag, mark and coordinates of the kept atoms go to LDS by kept index
-//   build    three 256 x 256 bit matrices over the kept atoms: the pairs, the pairs of order 2 and of order 3.  add_pair
-//            tells whether any pair is repeated; only then an entry looks through the entries before it, so that the first
-//            entry of a pair alone gives the pair its order.  That entry's thread compares the pair's length with its bounds
+//   build    three 256 x 256 bit matrices over the kept atoms: the pairs (build_pairs of mol_graph.h), those of order 2 and 3:
+//            the first entry of a pair alone gives the pair its order, and its thread compares the pair's length with its
+//            bounds (for_each_first_entry's text written out: as a functor 2 % slower, profiles/graph_build/README.md)
 //   atoms    thread u owns kept atom u: its rows give d and the class, its (at most six) angles are compared with the class's
 //            cosines; three rounds of OR over its neighbours' rows give its ball of radius 3, and of the half of the molecule
 //            that follows u cyclically the atoms outside the ball are its far pairs (every pair at exactly one of its atoms)
@@ -18,6 +18,7 @@
 // LDS: 3 x 8 KiB matrices + 4 KiB map + 3 KiB coordinates + 2 KiB clash table + per-atom arrays: about 35 KiB, static.
 // Global memory is written with plain vector stores only; no atomics on global memory; no workspace.
 #include "mol_graph.h"
+#include "points.h"
 
 #pragma clang fp contract(off)
 
@@ -36,18 +37,6 @@ static_assert(DL_POSE_COUNTS == 8, "eight counts per row");
 enum : int { BONDS_CHECKED, BONDS_UNTABLED, BONDS_SHORT, BONDS_LONG, ANGLES_CHECKED, ANGLES_BAD, PAIRS_CHECKED, PAIRS_CLASH };
 enum : int { LINEAR = 0, TRIGONAL = 1, TETRAHEDRAL = 2 };
 enum : int { FLAG_BOND = 1, FLAG_ANGLE = 2, FLAG_CLASH = 4 };
-
-__device__ __forceinline__ bool nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
-
-struct V3 {
-    double x, y, z;
-};
-
-__device__ __forceinline__ V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ double dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ V3 point(const float* xs, int atom) {
-    return {double(xs[atom * 3]), double(xs[atom * 3 + 1]), double(xs[atom * 3 + 2])};
-}
 
 // one item in the low half, one more in the high half when it is marked: all and marked counts travel in one word
 __device__ __forceinline__ long long item(bool marked) { return 1ll + (static_cast<long long>(marked) << 32); }
@@ -102,12 +91,7 @@ __global__ __launch_bounds__(WG) void pose_kernel(dl_pose_args a) {
         s_type[kk] = (unsigned char)first_maximum(hot + size_t(r) * nf, nf);
         s_planar[kk] = planar && planar[k] != 0;
         s_mark[kk] = mark && mark[r] != 0.0f;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            const float v = xs[size_t(r) * 3 + d];
-            s_x[kk * 3 + d] = v;
-            bad_x |= nonfinite(v);
-        }
+        bad_x |= stage_point(xs, r, s_x, kk);
     });
 #pragma unroll
     for (int w = 0; w < WORDS; ++w) s_adj[tid * WORDS + w] = s_o2[tid * WORDS + w] = s_o3[tid * WORDS + w] = 0;
@@ -121,22 +105,13 @@ __global__ __launch_bounds__(WG) void pose_kernel(dl_pose_args a) {
 
     // ---- build: the pairs first, then what the first entry of every pair says about it, and the pair's length
     const int* list = a.bonds + size_t(b) * capacity * 3;        // never read when nb == 0
-    int bad = 0, repeated = 0;
-    for (int e = tid; e < nb; e += WG) {
-        Bond bd;
-        if (!load_bond(list, e, n, bd, bad)) continue;
-        const int u = s_map[bd.i], v = s_map[bd.j];
-        if ((u | v) < 0) continue;                               // an end is dropped: no bond of this graph, and no error
-        if (!add_pair(s_adj, u, v)) repeated = 1;
-    }
-    repeated = __syncthreads_or(repeated);
-    bad = __syncthreads_or(bad) | repeated;
+    const PairBuild pairs = build_pairs(list, nb, n, s_map, s_adj);
     for (int e = tid; e < nb; e += WG) {
         Bond bd;
         int ignored = 0;
         if (!load_bond(list, e, n, bd, ignored)) continue;
         const int u = s_map[bd.i], v = s_map[bd.j];
-        if ((u | v) < 0 || (repeated && seen_before<3>(list, e, n, bd.i, bd.j))) continue;
+        if ((u | v) < 0 || (pairs.repeated && seen_before<3>(list, e, n, bd.i, bd.j))) continue;
         if (bd.order == 2) set_pair(s_o2, u, v);
         if (bd.order == 3) set_pair(s_o3, u, v);
         if (bad_x) continue;
@@ -256,7 +231,7 @@ __global__ __launch_bounds__(WG) void pose_kernel(dl_pose_args a) {
         const int kk = k < n ? s_map[k] : -1;
         atom_flags[k] = kk >= 0 ? s_flags[kk] : 0;
     }
-    if (tid == 0) a.status[b] = in.status | (bad ? DL_POSE_BAD_BOND : 0) | (bad_x ? DL_POSE_NONFINITE : 0);
+    if (tid == 0) a.status[b] = in.status | (pairs.bad ? DL_POSE_BAD_BOND : 0) | (bad_x ? DL_POSE_NONFINITE : 0);
 }
 
 }  // namespace

@@ -348,17 +348,13 @@ class EDM(torch.nn.Module):
             noise_seed=seed, mol_offset=int(mol_offset), t_given=int(t_given), t_int=t_int_d.data_ptr(), t=t_f.data_ptr(),
             gamma=gam.data_ptr(), z_t=z_t.data_ptr(), eps_hat=None, norm_h=float(self.norm_values[1]),
             bias_h=float(self.norm_biases[1]), prior=prior.data_ptr(), rows=rows.data_ptr())
-        with torch.cuda.device(dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(lib.dl_edm_loss_prologue(ctypes.byref(args), stream), 'dl_edm_loss_prologue')
+        _lib.launch('dl_edm_loss_prologue', args, dev)
         # (InpaintingEDM denoises every atom: linker_mask=None, edm.py:499-506)
         eps_hat = self._loss_denoise(z_t, t_f.reshape(bs, 1), node_mask, None if self._inpainting else linker_mask, edge_mask,
                                      context, train=train_state is not None)
         eps_hat = eps_hat.to(torch.float32).contiguous()
         args.eps_hat = eps_hat.data_ptr()
-        with torch.cuda.device(dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(lib.dl_edm_loss_epilogue(ctypes.byref(args), stream), 'dl_edm_loss_epilogue')
+        _lib.launch('dl_edm_loss_epilogue', args, dev)
         if train_state is not None:
             train_state.update(args=args, eps_hat=eps_hat, keep=(xh, nm, fm, lm, table, nx, nh, t_int_d, t_f, gam, z_t, prior,
                                                                  rows))

@@ -743,12 +743,12 @@ def _dynamics_parameter_grad(self, t, xh, node_mask, linker_mask, edge_mask, con
     args.context = ctx_.data_ptr() if ctx_ is not None else None
     args.grad_out, args.grad_params = go.data_ptr(), grad.data_ptr()
     args.workspace, args.workspace_bytes = ws.data_ptr(), need
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        if pocket:
-            _lib.check(lib.dl_egnn_backward_pocket(ctypes.byref(args), graph, ctypes.c_void_p(stream)), 'dl_egnn_backward_pocket')
-        else:
-            _lib.check(lib.dl_egnn_backward_fc(ctypes.byref(args), ctypes.c_void_p(stream)), 'dl_egnn_backward_fc')
+    if pocket:
+        with torch.cuda.device(dev):
+            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(lib.dl_egnn_backward_pocket(ctypes.byref(args), graph, stream), 'dl_egnn_backward_pocket')
+    else:
+        _lib.launch('dl_egnn_backward_fc', args, dev)
     out, k = [], 0
     for p in params:
         out.append(grad[k:k + p.numel()].view_as(p).to(p.dtype))

@@ -12,8 +12,8 @@ pair is its own example), conformers, BRICS, aromaticity perception, hydrogens. 
 (``fragment_by_mmpa(min_cuts=3, max_cuts=5, min_frag_size=3)`` on molecules of at most 40 atoms with three rings,
 ``data/geom/generate_geom_multifrag.py:227-231``): one linker joined to three, four or five fragments.  Their rule is stated in
 ``include/difflinker_hip.h`` and restated in ``tests/multicut_ref.py``; no run of the reference pins it."""
-import ctypes
 from collections import namedtuple
+from functools import partial
 
 import numpy as np
 import torch
@@ -52,10 +52,8 @@ def fragment_cuts(one_hot, node_mask, bonds, n_bonds, *, charge=None, is_geom, c
     atom ``i``, else 0; ``cuts [B,R,10]``: ``CUT_FIELDS`` of the first ``min(n_cuts, R)`` kept pairs, zeros after them;
     ``labels`` uint8 ``[B,R,N]`` by atom number: 0 fragment 1, 1 fragment 2, 2 linker, 255 from the atom count on and in unused
     records.  More than 256 atoms: ``DL_FRAG_TOO_LARGE`` and nothing but ``n_atoms``."""
-    given = (one_hot, node_mask, bonds, n_bonds) + tuple(t for t in (charge, status) if t is not None)
-    if not all(t.is_cuda for t in given):
-        raise _lib.HipLibraryError('fragment_cuts runs on the HIP device only (no CPU fallback): '
-                                   f'got tensors on {", ".join(str(t.device) for t in given)}')
+    _lib.require_device('fragment_cuts', one_hot=one_hot, node_mask=node_mask, bonds=bonds, n_bonds=n_bonds, charge=charge,
+                        status=status)
     if one_hot.dim() != 3 or bonds.dim() != 3 or bonds.shape[2] != 3:
         raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, bonds {tuple(bonds.shape)}')
     B, N, nf = one_hot.shape
@@ -65,24 +63,21 @@ def fragment_cuts(one_hot, node_mask, bonds, n_bonds, *, charge=None, is_geom, c
         raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, node_mask {tuple(node_mask.shape)}, '
                          f'bonds {tuple(bonds.shape)}, n_bonds {tuple(n_bonds.shape)}, capacity {capacity}')
     dev = one_hot.device
-    cast = lambda t, dtype: None if t is None else t.to(device=dev, dtype=dtype).contiguous()      # noqa: E731
-    one_hot, node_mask = cast(one_hot, torch.float32), cast(node_mask, torch.float32)
-    bonds, n_bonds, charge, status = (cast(t, torch.int32) for t in (bonds, n_bonds, charge, status))
-    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    one_hot, node_mask = _lib.dense(one_hot, dev, torch.float32), _lib.dense(node_mask, dev, torch.float32)
+    bonds, n_bonds, charge, status = (_lib.dense(t, dev, torch.int32) for t in (bonds, n_bonds, charge, status))
+    i32 = partial(_lib.empty_i32, dev)
     out = Cuts(i32(B), i32(B), i32(B), i32(B), i32(B), i32(B, E), i32(B, R, _lib.DL_FRAG_CUT_FIELDS),
                torch.empty((B, R, N), dtype=torch.uint8, device=dev))
-    opt = lambda t, used=True: t.data_ptr() if t is not None and used else None                    # noqa: E731
     args = _lib.DLFragmentArgs(
-        B=B, N=N, nf=nf, one_hot=one_hot.data_ptr(), node_mask=node_mask.data_ptr(), charge=opt(charge),
+        B=B, N=N, nf=nf, one_hot=one_hot.data_ptr(), node_mask=node_mask.data_ptr(), charge=_lib.ptr(charge),
         carbon_type=(const.GEOM_ATOM2IDX if is_geom else const.ATOM2IDX)['C'], capacity=E, n_bonds_in=n_bonds.data_ptr(),
-        bonds=opt(bonds, E), status_in=opt(status), min_linker=int(min_linker), min_fragment=int(min_fragment),
-        min_path_atoms=int(min_path_atoms), linker_leq_frags=int(bool(linker_leq_frags)), R=R,
+        bonds=bonds.data_ptr() if E else None, status_in=_lib.ptr(status), min_linker=int(min_linker),
+        min_fragment=int(min_fragment), min_path_atoms=int(min_path_atoms), linker_leq_frags=int(bool(linker_leq_frags)), R=R,
         n_atoms=out.n_atoms.data_ptr(), n_bonds=out.n_bonds.data_ptr(), n_cuttable=out.n_cuttable.data_ptr(),
-        n_cuts=out.n_cuts.data_ptr(), status=out.status.data_ptr(), bond_side=opt(out.bond_side, E),
-        cuts=opt(out.cuts, R), labels=opt(out.labels, R))
-    with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.load().dl_fragment_cuts(ctypes.byref(args), stream), 'dl_fragment_cuts')
+        n_cuts=out.n_cuts.data_ptr(), status=out.status.data_ptr(),
+        bond_side=out.bond_side.data_ptr() if E else None, cuts=out.cuts.data_ptr() if R else None,
+        labels=out.labels.data_ptr() if R else None)
+    _lib.launch('dl_fragment_cuts', args, dev)
     return out
 
 
@@ -154,10 +149,8 @@ def multi_cuts(one_hot, node_mask, bonds, n_bonds, *, charge=None, is_geom, capa
     ``n_cuts`` counts ALL kept stars, ``n_cuts_k [B,3]`` those of 3, 4 and 5 bonds; ``cuts [B,R,22]``: ``k, n_linker, e[5],
     anchor[5], exit[5], n_frag[5]`` with -1 in the slots from ``k`` on, zeros in unused records; ``labels`` uint8 ``[B,R,N]``:
     ``q`` for fragment ``q``, 5 for the linker, 255 from the atom count on and in unused records."""
-    given = (one_hot, node_mask, bonds, n_bonds) + tuple(t for t in (charge, status) if t is not None)
-    if not all(t.is_cuda for t in given):
-        raise _lib.HipLibraryError('multi_cuts runs on the HIP device only (no CPU fallback): '
-                                   f'got tensors on {", ".join(str(t.device) for t in given)}')
+    _lib.require_device('multi_cuts', one_hot=one_hot, node_mask=node_mask, bonds=bonds, n_bonds=n_bonds, charge=charge,
+                        status=status)
     if one_hot.dim() != 3 or bonds.dim() != 3 or bonds.shape[2] != 3:
         raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, bonds {tuple(bonds.shape)}')
     B, N, nf = one_hot.shape
@@ -167,24 +160,20 @@ def multi_cuts(one_hot, node_mask, bonds, n_bonds, *, charge=None, is_geom, capa
         raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, node_mask {tuple(node_mask.shape)}, '
                          f'bonds {tuple(bonds.shape)}, n_bonds {tuple(n_bonds.shape)}, capacity {capacity}')
     dev = one_hot.device
-    cast = lambda t, dtype: None if t is None else t.to(device=dev, dtype=dtype).contiguous()      # noqa: E731
-    one_hot, node_mask = cast(one_hot, torch.float32), cast(node_mask, torch.float32)
-    bonds, n_bonds, charge, status = (cast(t, torch.int32) for t in (bonds, n_bonds, charge, status))
-    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    one_hot, node_mask = _lib.dense(one_hot, dev, torch.float32), _lib.dense(node_mask, dev, torch.float32)
+    bonds, n_bonds, charge, status = (_lib.dense(t, dev, torch.int32) for t in (bonds, n_bonds, charge, status))
+    i32 = partial(_lib.empty_i32, dev)
     out = MultiCuts(i32(B), i32(B), i32(B), i32(B), i32(B), i32(B, 3), i32(B, R, _lib.DL_FRAG_MULTI_FIELDS),
                     torch.empty((B, R, N), dtype=torch.uint8, device=dev))
-    opt = lambda t, used=True: t.data_ptr() if t is not None and used else None                    # noqa: E731
     args = _lib.DLFragmentMultiArgs(
-        B=B, N=N, nf=nf, one_hot=one_hot.data_ptr(), node_mask=node_mask.data_ptr(), charge=opt(charge),
+        B=B, N=N, nf=nf, one_hot=one_hot.data_ptr(), node_mask=node_mask.data_ptr(), charge=_lib.ptr(charge),
         carbon_type=(const.GEOM_ATOM2IDX if is_geom else const.ATOM2IDX)['C'], capacity=E, n_bonds_in=n_bonds.data_ptr(),
-        bonds=opt(bonds, E), status_in=opt(status), min_cuts=int(min_cuts), max_cuts=int(max_cuts), min_linker=int(min_linker),
-        min_fragment=int(min_fragment), max_atoms=int(max_atoms), min_rings=int(min_rings), R=R,
+        bonds=bonds.data_ptr() if E else None, status_in=_lib.ptr(status), min_cuts=int(min_cuts), max_cuts=int(max_cuts),
+        min_linker=int(min_linker), min_fragment=int(min_fragment), max_atoms=int(max_atoms), min_rings=int(min_rings), R=R,
         n_atoms=out.n_atoms.data_ptr(), n_bonds=out.n_bonds.data_ptr(), n_cuttable=out.n_cuttable.data_ptr(),
         n_cuts=out.n_cuts.data_ptr(), status=out.status.data_ptr(), n_cuts_k=out.n_cuts_k.data_ptr(),
-        cuts=opt(out.cuts, R), labels=opt(out.labels, R))
-    with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.load().dl_fragment_multicuts(ctypes.byref(args), stream), 'dl_fragment_multicuts')
+        cuts=out.cuts.data_ptr() if R else None, labels=out.labels.data_ptr() if R else None)
+    _lib.launch('dl_fragment_multicuts', args, dev)
     return out
 
 

@@ -220,9 +220,7 @@ class SizeGNN(nn.Module):
         args.one_hot, args.positions, args.fragment_mask, args.edge_mask = [t.data_ptr() for t in inputs]
         args.logits, args.batch_stats, args.flags = logits.data_ptr(), stats.data_ptr(), flags.data_ptr()
         args.workspace, args.workspace_bytes = ws.data_ptr(), need
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(lib.dl_size_train_forward(ctypes.byref(args), ctypes.c_void_p(stream)), 'dl_size_train_forward')
+        _lib.launch('dl_size_train_forward', args, dev)
         if bool((flags.cpu() & 4).any()):
             raise ValueError(f'more than {lib.dl_size_max_fragment_atoms()} fragment atoms in a molecule: '
                              'outside the size-predictor kernels')
@@ -234,10 +232,7 @@ class SizeGNN(nn.Module):
         go = grad_logits.to(dev, torch.float32).contiguous()
         grad = torch.empty_like(flat)
         args.grad_logits, args.grad_params = go.data_ptr(), grad.data_ptr()
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(_lib.load().dl_size_train_backward(ctypes.byref(args), ctypes.c_void_p(stream)),
-                       'dl_size_train_backward')
+        _lib.launch('dl_size_train_backward', args, dev)
         out, k = [], 0
         for p in self.parameters():
             out.append(grad[k:k + p.numel()].view_as(p).to(p.dtype))

@@ -54,9 +54,9 @@ physically plausible?  Bond lengths against the typical lengths of the bond tabl
 centre's class, and clashes between atoms four or more bonds apart (``dl_pose_checks``, ``csrc/pose_checks.hip``), on the
 geometric bond orders.  This project's own rule after the idea of PoseBusters' intramolecular checks - NOT PoseBusters.
 """
-import ctypes
 import math
 from collections import namedtuple
+from functools import partial
 
 import numpy as np
 import torch
@@ -82,33 +82,27 @@ def _max_valence(device, is_geom):
 def molecule_keys(one_hot, node_mask, found, is_geom, drop_mask=None):
     """``dl_molecule_keys`` on the result ``found`` of ``perceive_bonds`` for the same ``one_hot`` and ``node_mask``; device
     tensors in, an ``Analysis`` of device tensors out, no host synchronisation."""
-    if not (one_hot.is_cuda and node_mask.is_cuda and (drop_mask is None or drop_mask.is_cuda)):
-        raise _lib.HipLibraryError('molecule_keys runs on the HIP device only (no CPU fallback): '
-                                   f'got tensors on {one_hot.device}, {node_mask.device}')
+    _lib.require_device('molecule_keys', one_hot=one_hot, node_mask=node_mask, drop_mask=drop_mask)
     B, N, nf = one_hot.shape
     if node_mask.numel() != B * N or (drop_mask is not None and drop_mask.numel() != B * N):
         raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, node_mask {tuple(node_mask.shape)}')
     dev = one_hot.device
-    f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()     # noqa: E731
-    one_hot, node_mask = f32(one_hot), f32(node_mask)
-    drop_mask = None if drop_mask is None else f32(drop_mask)
+    one_hot, node_mask, drop_mask = (_lib.dense(t, dev, torch.float32) for t in (one_hot, node_mask, drop_mask))
     limits = _max_valence(dev, is_geom)
-    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
-    i64 = lambda *shape: torch.empty(shape, dtype=torch.int64, device=dev)  # noqa: E731
-    out = Analysis(i32(B), i32(B), i32(B), i32(B), i64(B), i64(B, N), i32(B), found)
+    i32 = partial(_lib.empty_i32, dev)
+    out = Analysis(i32(B), i32(B), i32(B), i32(B), torch.empty(B, dtype=torch.int64, device=dev),
+                   torch.empty((B, N), dtype=torch.int64, device=dev), i32(B), found)
     found = normalize_bonds(found, B, dev, 'molecule_keys')          # (what the kernel reads; the result keeps the caller's object)
     capacity = found.bonds.shape[1]
     args = _lib.DLMolKeysArgs(
         B=B, N=N, nf=nf, one_hot=one_hot.data_ptr(), node_mask=node_mask.data_ptr(),
-        drop_mask=None if drop_mask is None else drop_mask.data_ptr(), capacity=capacity,
+        drop_mask=_lib.ptr(drop_mask), capacity=capacity,
         n_bonds_in=found.n_bonds.data_ptr(), bonds=found.bonds.data_ptr() if capacity else None,
         valence_in=found.valence.data_ptr(), n_components_in=found.n_components.data_ptr(),
         status_in=found.status.data_ptr(), max_valence=limits.data_ptr(), max_valence_len=limits.numel(),
         n_atoms=out.n_atoms.data_ptr(), n_over=out.n_over.data_ptr(), n_components=out.n_components.data_ptr(),
         n_bonds=out.n_bonds.data_ptr(), key=out.key.data_ptr(), colour=out.colour.data_ptr(), status=out.status.data_ptr())
-    with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.load().dl_molecule_keys(ctypes.byref(args), stream), 'dl_molecule_keys')
+    _lib.launch('dl_molecule_keys', args, dev)
     return out
 
 
@@ -121,9 +115,7 @@ def analyze(one_hot, x, node_mask, is_geom, drop_mask=None, margins=const.MARGIN
     for dropped atoms and beyond the atom count), ``status`` (int32 ``[B]``: ``_lib.DL_BONDS_*`` / ``_lib.DL_KEYS_*`` bits) and
     ``bonds``, the ``perceive_all_bonds`` result it was computed from.  The bond list is never cut short
     (``perceive_all_bonds`` widens it), and nothing synchronises beyond what that call does."""
-    if not (one_hot.is_cuda and x.is_cuda and node_mask.is_cuda):
-        raise _lib.HipLibraryError('analyze runs on the HIP device only (no CPU fallback): '
-                                   f'got tensors on {one_hot.device}, {x.device}, {node_mask.device}')
+    _lib.require_device('analyze', one_hot=one_hot, x=x, node_mask=node_mask)
     found = perceive_all_bonds(one_hot, x, node_mask, is_geom, margins)
     return molecule_keys(one_hot, node_mask, found, is_geom, drop_mask)
 
@@ -404,10 +396,7 @@ def best_rmsd(xa, xb, n_atoms, maps, offsets):
     ``[P]``, and the table and offsets of ``pack_maps``, all on the HIP device.  Returns device tensors ``(rmsd, best,
     status)``: fp32 ``[P]`` (NaN where ``status`` is not 0), the winning map's index within its pair (of equal ones the
     lowest) and the ``_lib.DL_RMSD_*`` bits.  One launch, no host synchronisation."""
-    tensors = (xa, xb, n_atoms, maps, offsets)
-    if not all(t.is_cuda for t in tensors):
-        raise _lib.HipLibraryError('best_rmsd runs on the HIP device only (no CPU fallback): '
-                                   f'got tensors on {", ".join(str(t.device) for t in tensors)}')
+    _lib.require_device('best_rmsd', xa=xa, xb=xb, n_atoms=n_atoms, maps=maps, offsets=offsets)
     P, n_max = xa.shape[:2]
     if xa.shape != (P, n_max, 3) or xb.shape != xa.shape or n_atoms.numel() != P or offsets.numel() != P + 1 or n_max < 1 \
             or maps.numel() % n_max:
@@ -416,18 +405,16 @@ def best_rmsd(xa, xb, n_atoms, maps, offsets):
     if maps.dtype not in (torch.int16, torch.uint16):
         raise ValueError(f'maps must hold 16-bit indices, got {maps.dtype}')
     dev = xa.device
-    xa, xb = (t.to(device=dev, dtype=torch.float32).contiguous() for t in (xa, xb))
-    n_atoms, offsets = (t.to(device=dev, dtype=torch.int32).contiguous() for t in (n_atoms, offsets))
+    xa, xb = (_lib.dense(t, dev, torch.float32) for t in (xa, xb))
+    n_atoms, offsets = (_lib.dense(t, dev, torch.int32) for t in (n_atoms, offsets))
     maps = maps.to(dev).contiguous()
     rmsd = torch.empty(P, dtype=torch.float32, device=dev)
-    best, status = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(2))
+    best, status = _lib.empty_i32(dev, P), _lib.empty_i32(dev, P)
     args = _lib.DLRmsdArgs(P=P, n_max=n_max, xa=xa.data_ptr(), xb=xb.data_ptr(), n_atoms=n_atoms.data_ptr(),
                            map_offsets=offsets.data_ptr(), maps=maps.data_ptr() if maps.numel() else None,
                            maps_capacity=maps.numel() // n_max, rmsd=rmsd.data_ptr(), best=best.data_ptr(),
                            status=status.data_ptr())
-    with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.load().dl_best_rmsd(ctypes.byref(args), stream), 'dl_best_rmsd')
+    _lib.launch('dl_best_rmsd', args, dev)
     return rmsd, best, status
 
 
@@ -517,22 +504,19 @@ def analyze_clashes(one_hot, x, query_mask, target_mask=None, protein=None, is_g
 
     What this is NOT: no hydrogens, no clashes inside the ligand, no energy or docking score."""
     shared = () if protein is None else tuple(protein)
-    tensors = (one_hot, x, query_mask) + (() if target_mask is None else (target_mask,)) + shared + \
-        (() if thresholds is None else (thresholds,))
-    if not all(t.is_cuda for t in tensors):
-        raise _lib.HipLibraryError('analyze_clashes runs on the HIP device only (no CPU fallback): '
-                                   f'got tensors on {", ".join(str(t.device) for t in tensors)}')
+    _lib.require_device('analyze_clashes', one_hot=one_hot, x=x, query_mask=query_mask, target_mask=target_mask,
+                        thresholds=thresholds, **{f'protein[{k}]': t for k, t in enumerate(shared)})
     B, N, nf = one_hot.shape
     if x.shape != (B, N, 3) or query_mask.numel() != B * N or (target_mask is not None and target_mask.numel() != B * N):
         raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, x {tuple(x.shape)}, query_mask '
                          f'{tuple(query_mask.shape)}')
     dev = one_hot.device
-    f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()     # noqa: E731
+    f32 = partial(_lib.dense, device=dev, dtype=torch.float32)
     one_hot, x, qm = f32(one_hot), f32(x), f32(query_mask).reshape(B, N)
     tm = None if target_mask is None else f32(target_mask).reshape(B, N)
     M, px, pt = 0, None, None
     if protein is not None:
-        px, pt = f32(shared[0]), shared[1].to(device=dev, dtype=torch.int32).contiguous()
+        px, pt = f32(shared[0]), _lib.dense(shared[1], dev, torch.int32)
         M = pt.numel()
         if px.shape != (M, 3):
             raise ValueError(f'shapes disagree: protein positions {tuple(px.shape)}, types {tuple(pt.shape)}')
@@ -541,19 +525,17 @@ def analyze_clashes(one_hot, x, query_mask, target_mask=None, protein=None, is_g
     thresholds = f32(thresholds)
     if thresholds.shape != (nf, nf):
         raise ValueError(f'thresholds {tuple(thresholds.shape)} for {nf} atom types')
-    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    i32 = partial(_lib.empty_i32, dev)
     out = Clashes(i32(B), i32(B), i32(B), i32(B), i32(B), torch.empty(B, dtype=torch.float32, device=dev), i32(B), i32(B, N),
                   torch.empty(B, N, dtype=torch.float32, device=dev), qm)
     args = _lib.DLClashArgs(
         B=B, N=N, nf=nf, x=x.data_ptr(), one_hot=one_hot.data_ptr(), query_mask=qm.data_ptr(),
-        target_mask=None if tm is None else tm.data_ptr(), M=M, target_x=px.data_ptr() if M else None,
+        target_mask=_lib.ptr(tm), M=M, target_x=px.data_ptr() if M else None,
         target_type=pt.data_ptr() if M else None, threshold=thresholds.data_ptr(), contact_cutoff=float(contact_cutoff),
         n_query=out.n_query.data_ptr(), n_target=out.n_target.data_ptr(), n_clashes=out.n_clashes.data_ptr(),
         n_clash_atoms=out.n_clash_atoms.data_ptr(), n_contacts=out.n_contacts.data_ptr(), min_dist2=out.min_dist2.data_ptr(),
         status=out.status.data_ptr(), atom_clashes=out.atom_clashes.data_ptr(), atom_min_dist2=out.atom_min_dist2.data_ptr())
-    with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.load().dl_clash_scores(ctypes.byref(args), stream), 'dl_clash_scores')
+    _lib.launch('dl_clash_scores', args, dev)
     return out
 
 
@@ -625,10 +607,6 @@ INTERACTION_TRUE_NAMES = ('true_interaction_score', 'true_hbonds_per_molecule', 
 FIXED_ONE = 4294967296.0            # 2^32: one unit of the fixed-point terms
 
 
-def _f32(t, dev):
-    return t.to(device=dev, dtype=torch.float32).contiguous()
-
-
 def interaction_types(one_hot, x, group, is_geom=True, margins=const.MARGINS_EDM):
     """Heavy atoms typed as hydrophobic, hydrogen-bond donor or acceptor from elements and geometry alone, for every molecule
     of a batch in one launch of ``dl_interaction_types`` (``csrc/interaction.hip``) on the HIP device.
@@ -647,29 +625,24 @@ def interaction_types(one_hot, x, group, is_geom=True, margins=const.MARGINS_EDM
     Returns ``XsTypes(xs_type, status)``: int32 ``[B,N]`` - the element in bits 0-3, ``_lib.DL_XS_HYDROPHOBIC`` / ``DL_XS_DONOR``
     / ``DL_XS_ACCEPTOR`` above, -1 on rows of group 0 - and int32 ``[B]``: ``_lib.DL_INTERACT_NONFINITE`` when a typed row is
     not finite, the molecule's rows are then all -1.  No host synchronisation."""
-    tensors = (one_hot, x, group)
-    if not all(t.is_cuda for t in tensors):
-        raise _lib.HipLibraryError('interaction_types runs on the HIP device only (no CPU fallback): '
-                                   f'got tensors on {", ".join(str(t.device) for t in tensors)}')
+    _lib.require_device('interaction_types', one_hot=one_hot, x=x, group=group)
     if one_hot.dim() != 3:
         raise ValueError(f'one_hot {tuple(one_hot.shape)} is not [B,N,nf]')
     B, N, nf = one_hot.shape
     if x.shape != (B, N, 3) or group.numel() != B * N:
         raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, x {tuple(x.shape)}, group {tuple(group.shape)}')
     dev = one_hot.device
-    one_hot, x = _f32(one_hot, dev), _f32(x, dev)
-    group = group.to(device=dev, dtype=torch.int32).contiguous().reshape(B, N)
+    one_hot, x = _lib.dense(one_hot, dev, torch.float32), _lib.dense(x, dev, torch.float32)
+    group = _lib.dense(group, dev, torch.int32).reshape(B, N)
     table = const.bond_threshold_table(is_geom, margins)[..., 0].contiguous().to(dev)
     if table.shape != (nf, nf):
         raise ValueError(f'{nf} atom types in one_hot, {table.shape[0]} in the vocabulary')
-    out = XsTypes(torch.empty((B, N), dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+    out = XsTypes(_lib.empty_i32(dev, B, N), _lib.empty_i32(dev, B))
     if N == 0:
         return out
     args = _lib.DLInteractTypesArgs(B=B, N=N, nf=nf, x=x.data_ptr(), one_hot=one_hot.data_ptr(), group=group.data_ptr(),
                                     table=table.data_ptr(), xs_type=out.xs_type.data_ptr(), status=out.status.data_ptr())
-    with torch.cuda.device(dev):
-        args.stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(_lib.load().dl_interaction_types(ctypes.byref(args)), 'dl_interaction_types')
+    _lib.launch('dl_interaction_types', args, dev)
     return out
 
 
@@ -678,9 +651,7 @@ def protein_types(positions, types, is_geom=True):
     one group in one launch, for the caller to keep per protein and hand to ``analyze_interactions`` as
     ``protein = (positions, types, xs_types)``.  An atom whose type is outside the vocabulary is not typed (-1) and is then
     skipped by the score."""
-    if not (positions.is_cuda and types.is_cuda):
-        raise _lib.HipLibraryError('protein_types runs on the HIP device only (no CPU fallback): '
-                                   f'got tensors on {positions.device}, {types.device}')
+    _lib.require_device('protein_types', positions=positions, types=types)
     M = types.numel()
     if positions.shape != (M, 3):
         raise ValueError(f'shapes disagree: protein positions {tuple(positions.shape)}, types {tuple(types.shape)}')
@@ -723,10 +694,8 @@ def analyze_interactions(one_hot, x, query_mask, ligand_mask, target_mask=None, 
     What this is NOT: AutoDock Vina's numbers.  No hydrogens, no PDBQT typing, no search or pose optimisation, no
     intramolecular term and no rotor normalisation (the published rotor weight is not used)."""
     shared = () if protein is None else tuple(protein)
-    tensors = (one_hot, x, query_mask, ligand_mask) + (() if target_mask is None else (target_mask,)) + shared
-    if not all(t.is_cuda for t in tensors):
-        raise _lib.HipLibraryError('analyze_interactions runs on the HIP device only (no CPU fallback): '
-                                   f'got tensors on {", ".join(str(t.device) for t in tensors)}')
+    _lib.require_device('analyze_interactions', one_hot=one_hot, x=x, query_mask=query_mask, ligand_mask=ligand_mask,
+                        target_mask=target_mask, **{f'protein[{k}]': t for k, t in enumerate(shared)})
     if one_hot.dim() != 3:
         raise ValueError(f'one_hot {tuple(one_hot.shape)} is not [B,N,nf]')
     B, N, nf = one_hot.shape
@@ -740,12 +709,13 @@ def analyze_interactions(one_hot, x, query_mask, ligand_mask, target_mask=None, 
     radius = const.xs_radius_table(is_geom).to(dev)
     if radius.numel() != nf:
         raise ValueError(f'{nf} atom types in one_hot, {radius.numel()} in the vocabulary')
-    one_hot, x, qm = _f32(one_hot, dev), _f32(x, dev), _f32(query_mask, dev).reshape(B, N)
-    lig = (_f32(ligand_mask, dev).reshape(B, N) != 0) | (qm != 0)
-    tm = None if target_mask is None else _f32(target_mask, dev).reshape(B, N)
+    f32 = partial(_lib.dense, device=dev, dtype=torch.float32)
+    one_hot, x, qm = f32(one_hot), f32(x), f32(query_mask).reshape(B, N)
+    lig = (f32(ligand_mask).reshape(B, N) != 0) | (qm != 0)
+    tm = None if target_mask is None else f32(target_mask).reshape(B, N)
     M, px, pxs = 0, None, None
     if protein is not None:
-        px, pxs = _f32(shared[0], dev), shared[2].to(device=dev, dtype=torch.int32).contiguous()
+        px, pxs = f32(shared[0]), _lib.dense(shared[2], dev, torch.int32)
         M = pxs.numel()
         if px.shape != (M, 3) or shared[1].numel() != M:
             raise ValueError(f'shapes disagree: protein positions {tuple(px.shape)}, types {tuple(shared[1].shape)}, xs_types '
@@ -753,7 +723,7 @@ def analyze_interactions(one_hot, x, query_mask, ligand_mask, target_mask=None, 
     group = lig.to(torch.int32)
     if tm is not None:
         group = group + 2 * ((tm != 0) & ~lig).to(torch.int32)
-    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    i32 = partial(_lib.empty_i32, dev)
     if N == 0:
         zero = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)  # noqa: E731
         return Interactions(zero(B), zero(B), zero(B), zero(B), zero(B), torch.zeros((B, 5), dtype=torch.int64, device=dev),
@@ -763,14 +733,12 @@ def analyze_interactions(one_hot, x, query_mask, ligand_mask, target_mask=None, 
                        torch.empty((B, N, 5), dtype=torch.int64, device=dev), typed.xs_type, typed.status, qm)
     args = _lib.DLInteractArgs(
         B=B, N=N, nf=nf, x=x.data_ptr(), xs_type=typed.xs_type.data_ptr(), query_mask=qm.data_ptr(),
-        target_mask=None if tm is None else tm.data_ptr(), M=M, target_x=px.data_ptr() if M else None,
+        target_mask=_lib.ptr(tm), M=M, target_x=px.data_ptr() if M else None,
         target_xs=pxs.data_ptr() if M else None, radius=radius.data_ptr(),
         n_query=out.n_query.data_ptr(), n_target=out.n_target.data_ptr(), n_pairs=out.n_pairs.data_ptr(),
         n_hbonds=out.n_hbonds.data_ptr(), n_hydrophobic=out.n_hydrophobic.data_ptr(), terms=out.terms.data_ptr(),
         status=out.status.data_ptr(), atom_terms=out.atom_terms.data_ptr())
-    with torch.cuda.device(dev):
-        args.stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(_lib.load().dl_interaction_scores(ctypes.byref(args)), 'dl_interaction_scores')
+    _lib.launch('dl_interaction_scores', args, dev)
     return out
 
 
@@ -865,10 +833,8 @@ def analyze_shapes(one_hot_a, x_a, mask_a, one_hot_b, x_b, mask_b, is_geom=True,
     What this is NOT: no alignment (the molecules are compared where they are), no pharmacophore features (the other half
     of SC-RDKit is ``analyze_pharmacophores``), no hydrogens, not RDKit's numbers.  The lattice is fixed in space: a common shift of both molecules by
     less than the spacing moves the counts a little."""
-    tensors = (one_hot_a, x_a, mask_a, one_hot_b, x_b, mask_b)
-    if not all(t.is_cuda for t in tensors):
-        raise _lib.HipLibraryError('analyze_shapes runs on the HIP device only (no CPU fallback): '
-                                   f'got tensors on {", ".join(str(t.device) for t in tensors)}')
+    _lib.require_device('analyze_shapes', one_hot_a=one_hot_a, x_a=x_a, mask_a=mask_a, one_hot_b=one_hot_b, x_b=x_b,
+                        mask_b=mask_b)
     B, Na, nf = one_hot_a.shape
     Nb = one_hot_b.shape[1]
     if (one_hot_b.shape != (B, Nb, nf) or x_a.shape != (B, Na, 3) or x_b.shape != (B, Nb, 3) or mask_a.numel() != B * Na
@@ -882,17 +848,15 @@ def analyze_shapes(one_hot_a, x_a, mask_a, one_hot_b, x_b, mask_b, is_geom=True,
     if not bool((torch.isfinite(r2) & (r2 <= SHAPE_R2_MAX)).all()):
         raise ValueError(f'scale {scale} and step {step} give a radius that is not finite or is above 20 A')
     dev = one_hot_a.device
-    f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()     # noqa: E731
+    f32 = partial(_lib.dense, device=dev, dtype=torch.float32)
     one_hot_a, x_a, ma = f32(one_hot_a), f32(x_a), f32(mask_a).reshape(B, Na)
     one_hot_b, x_b, mb = f32(one_hot_b), f32(x_b), f32(mask_b).reshape(B, Nb)
     r2 = r2.to(dev).contiguous()
-    out = Shapes(*(torch.empty(B, dtype=torch.int32, device=dev) for _ in Shapes._fields))
+    out = Shapes(*(_lib.empty_i32(dev, B) for _ in Shapes._fields))
     args = _lib.DLShapeArgs(B=B, Na=Na, Nb=Nb, nf=nf, x_a=x_a.data_ptr(), one_hot_a=one_hot_a.data_ptr(), mask_a=ma.data_ptr(),
                             x_b=x_b.data_ptr(), one_hot_b=one_hot_b.data_ptr(), mask_b=mb.data_ptr(), r2=r2.data_ptr(),
                             **{name: getattr(out, name).data_ptr() for name in Shapes._fields})
-    with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.load().dl_shape_scores(ctypes.byref(args), stream), 'dl_shape_scores')
+    _lib.launch('dl_shape_scores', args, dev)
     return out
 
 
@@ -962,9 +926,7 @@ def ring_scores(node_mask, found, drop_mask=None, mark_mask=None):
     ``DL_RINGS_BAD_BOND`` and ``DL_RINGS_TOO_LARGE`` (more than 256 kept atoms: everything but ``n_atoms`` is 0); ``bonds``
     is ``found``."""
     masks = (node_mask,) + tuple(m for m in (drop_mask, mark_mask) if m is not None)
-    if not (all(m.is_cuda for m in masks) and found.bonds.is_cuda):
-        raise _lib.HipLibraryError('ring_scores runs on the HIP device only (no CPU fallback): '
-                                   f'got tensors on {", ".join(str(m.device) for m in masks)}, {found.bonds.device}')
+    _lib.require_device('ring_scores', node_mask=node_mask, drop_mask=drop_mask, mark_mask=mark_mask, bonds=found.bonds)
     B = found.n_bonds.shape[0]
     if node_mask.numel() % max(B, 1) or (B == 0 and node_mask.dim() < 2):
         raise ValueError(f'shapes disagree: node_mask {tuple(node_mask.shape)}, {B} bond lists')
@@ -972,23 +934,19 @@ def ring_scores(node_mask, found, drop_mask=None, mark_mask=None):
     if any(m.numel() != B * N for m in masks) or found.bonds.dim() != 3 or found.bonds.shape[0] != B:
         raise ValueError(f'shapes disagree: masks {[tuple(m.shape) for m in masks]}, bonds {tuple(found.bonds.shape)}')
     dev = node_mask.device
-    f32 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()     # noqa: E731
-    node_mask, drop_mask, mark_mask = f32(node_mask), f32(drop_mask), f32(mark_mask)
+    node_mask, drop_mask, mark_mask = (_lib.dense(t, dev, torch.float32) for t in (node_mask, drop_mask, mark_mask))
     capacity = found.bonds.shape[1]
-    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    i32 = partial(_lib.empty_i32, dev)
     out = Rings(i32(B), i32(B), i32(B), i32(B), i32(B, capacity), i32(B, N), i32(B, 2, _lib.DL_RING_BINS), i32(B), found)
     found = normalize_bonds(found, B, dev, 'ring_scores')
-    opt = lambda t: None if t is None else t.data_ptr()                     # noqa: E731
     args = _lib.DLRingsArgs(
-        B=B, N=N, node_mask=node_mask.data_ptr(), drop_mask=opt(drop_mask), mark_mask=opt(mark_mask), capacity=capacity,
+        B=B, N=N, node_mask=node_mask.data_ptr(), drop_mask=_lib.ptr(drop_mask), mark_mask=_lib.ptr(mark_mask), capacity=capacity,
         n_bonds_in=found.n_bonds.data_ptr(), bonds=found.bonds.data_ptr() if capacity else None,
         status_in=found.status.data_ptr(), n_atoms=out.n_atoms.data_ptr(), n_bonds=out.n_bonds.data_ptr(),
         n_components=out.n_components.data_ptr(), n_rings=out.n_rings.data_ptr(),
         bond_ring=out.bond_ring.data_ptr() if capacity else None, atom_ring=out.atom_ring.data_ptr(),
         ring_hist=out.ring_hist.data_ptr(), status=out.status.data_ptr())
-    with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.load().dl_ring_scores(ctypes.byref(args), stream), 'dl_ring_scores')
+    _lib.launch('dl_ring_scores', args, dev)
     return out
 
 
@@ -1001,9 +959,7 @@ def analyze_rings(one_hot, x, node_mask, is_geom, linker_mask, drop_mask=None, m
                 included
     ``linker``  everything that is not a linker row dropped: the linker as a molecule of its own, as the reference takes it
                 for ``rings_n`` (compute_metrics.py:128-145).  A ring closed through a fragment atom is absent here."""
-    if not (one_hot.is_cuda and x.is_cuda and node_mask.is_cuda and linker_mask.is_cuda):
-        raise _lib.HipLibraryError('analyze_rings runs on the HIP device only (no CPU fallback): '
-                                   f'got tensors on {one_hot.device}, {x.device}, {node_mask.device}, {linker_mask.device}')
+    _lib.require_device('analyze_rings', one_hot=one_hot, x=x, node_mask=node_mask, linker_mask=linker_mask)
     B, N = one_hot.shape[:2]
     if linker_mask.numel() != B * N:
         raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, linker_mask {tuple(linker_mask.shape)}')
@@ -1084,9 +1040,7 @@ def analyze_aromatic(one_hot, x, node_mask, is_geom, linker_mask, drop_mask=None
     (``bond_ring > 0``) and are not aromatic - what the reference's ring filter rejects; ``n_over``, the atoms over their
     valence limit with the new orders; ``status``, the bits of all three launches; and ``refined`` / ``aromatic`` as
     ``refine_bond_orders`` returns them.  Aromaticity is this project's own geometric rule, not RDKit's or OpenBabel's."""
-    if not (one_hot.is_cuda and x.is_cuda and node_mask.is_cuda and linker_mask.is_cuda):
-        raise _lib.HipLibraryError('analyze_aromatic runs on the HIP device only (no CPU fallback): '
-                                   f'got tensors on {one_hot.device}, {x.device}, {node_mask.device}, {linker_mask.device}')
+    _lib.require_device('analyze_aromatic', one_hot=one_hot, x=x, node_mask=node_mask, linker_mask=linker_mask)
     B, N = one_hot.shape[:2]
     if linker_mask.numel() != B * N:
         raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, linker_mask {tuple(linker_mask.shape)}')
@@ -1167,9 +1121,8 @@ def fingerprints(one_hot, node_mask, found, drop_mask=None, centre_mask=None, ra
     ``k // 32``), ``n_on``, ``n_atoms`` (kept), ``n_centres`` and ``status`` int32 ``[B]``: the ``_lib.DL_BONDS_*`` bits of
     ``found`` plus ``DL_FP_BAD_BOND`` and ``DL_FP_TOO_LARGE`` (more than 256 kept atoms: no bits)."""
     masks = (node_mask,) + tuple(m for m in (drop_mask, centre_mask) if m is not None)
-    if not (one_hot.is_cuda and all(m.is_cuda for m in masks) and found.n_bonds.is_cuda):
-        raise _lib.HipLibraryError('fingerprints runs on the HIP device only (no CPU fallback): '
-                                   f'got tensors on {one_hot.device}, {", ".join(str(m.device) for m in masks)}')
+    _lib.require_device('fingerprints', one_hot=one_hot, node_mask=node_mask, drop_mask=drop_mask, centre_mask=centre_mask,
+                        n_bonds=found.n_bonds)
     if radius not in range(_lib.DL_FP_MAX_RADIUS + 1) or n_bits not in _lib.DL_FP_BITS:
         raise ValueError(f'radius must be 0..{_lib.DL_FP_MAX_RADIUS} and n_bits one of {_lib.DL_FP_BITS}: got {radius}, {n_bits}')
     B, N, nf = one_hot.shape
@@ -1177,22 +1130,19 @@ def fingerprints(one_hot, node_mask, found, drop_mask=None, centre_mask=None, ra
         raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, masks {[tuple(m.shape) for m in masks]}, bonds '
                          f'{tuple(found.bonds.shape)}')
     dev = one_hot.device
-    f32 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()     # noqa: E731
-    one_hot, node_mask, drop_mask, centre_mask = f32(one_hot), f32(node_mask), f32(drop_mask), f32(centre_mask)
-    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    one_hot, node_mask, drop_mask, centre_mask = (_lib.dense(t, dev, torch.float32)
+                                                  for t in (one_hot, node_mask, drop_mask, centre_mask))
+    i32 = partial(_lib.empty_i32, dev)
     out = Fingerprints(i32(B, n_bits // 32), i32(B), i32(B), i32(B), i32(B))
     found = normalize_bonds(found, B, dev, 'fingerprints')
     capacity = found.bonds.shape[1]
-    opt = lambda t: None if t is None else t.data_ptr()                     # noqa: E731
-    with torch.cuda.device(dev):
-        args = _lib.DLFingerprintArgs(
-            B=B, N=N, nf=nf, one_hot=one_hot.data_ptr(), node_mask=node_mask.data_ptr(), drop_mask=opt(drop_mask),
-            centre_mask=opt(centre_mask), capacity=capacity, n_bonds_in=found.n_bonds.data_ptr(),
-            bonds=found.bonds.data_ptr() if capacity else None, status_in=found.status.data_ptr(), radius=int(radius),
-            n_bits=int(n_bits), bits=out.bits.data_ptr(), n_on=out.n_on.data_ptr(), n_atoms=out.n_atoms.data_ptr(),
-            n_centres=out.n_centres.data_ptr(), status=out.status.data_ptr(),
-            stream=torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.load().dl_fingerprints(ctypes.byref(args)), 'dl_fingerprints')
+    args = _lib.DLFingerprintArgs(
+        B=B, N=N, nf=nf, one_hot=one_hot.data_ptr(), node_mask=node_mask.data_ptr(), drop_mask=_lib.ptr(drop_mask),
+        centre_mask=_lib.ptr(centre_mask), capacity=capacity, n_bonds_in=found.n_bonds.data_ptr(),
+        bonds=found.bonds.data_ptr() if capacity else None, status_in=found.status.data_ptr(), radius=int(radius),
+        n_bits=int(n_bits), bits=out.bits.data_ptr(), n_on=out.n_on.data_ptr(), n_atoms=out.n_atoms.data_ptr(),
+        n_centres=out.n_centres.data_ptr(), status=out.status.data_ptr())
+    _lib.launch('dl_fingerprints', args, dev)
     return out
 
 
@@ -1204,9 +1154,7 @@ def analyze_fingerprints(one_hot, x, node_mask, is_geom, linker_mask, drop_mask=
     environments still reach into the fragments.  ``drop_mask`` rows (the pocket of a pocket model) are left out of both.
     All samples of one input share their fragments, so ``whole`` mostly measures the fragments; ``linker`` is the one that
     tells the samples of an input apart."""
-    if not (one_hot.is_cuda and x.is_cuda and node_mask.is_cuda and linker_mask.is_cuda):
-        raise _lib.HipLibraryError('analyze_fingerprints runs on the HIP device only (no CPU fallback): '
-                                   f'got tensors on {one_hot.device}, {x.device}, {node_mask.device}, {linker_mask.device}')
+    _lib.require_device('analyze_fingerprints', one_hot=one_hot, x=x, node_mask=node_mask, linker_mask=linker_mask)
     B, N = one_hot.shape[:2]
     if linker_mask.numel() != B * N:
         raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, linker_mask {tuple(linker_mask.shape)}')
@@ -1233,10 +1181,7 @@ def tanimoto_nearest(a_bits, b_bits, a_offsets=None, b_offsets=None, exclude_dia
     candidate of the greatest similarity, compared exactly; of equal ones the lowest; -1 without candidates), ``common`` and
     ``union`` (that pair's ``c`` and ``u``), ``sum_q20`` (int64: the sum over the candidates of ``floor(c * 2**20 / u)``, or
     ``None`` without ``want_sum``) and ``n_pairs`` (candidates).  All integers: the same bits on every run."""
-    given = (a_bits, b_bits) + tuple(t for t in (a_offsets, b_offsets) if t is not None)
-    if not all(t.is_cuda for t in given):
-        raise _lib.HipLibraryError('tanimoto_nearest runs on the HIP device only (no CPU fallback): '
-                                   f'got tensors on {", ".join(str(t.device) for t in given)}')
+    _lib.require_device('tanimoto_nearest', a_bits=a_bits, b_bits=b_bits, a_offsets=a_offsets, b_offsets=b_offsets)
     if a_bits.dim() != 2 or b_bits.dim() != 2 or a_bits.shape[1] != b_bits.shape[1] or a_bits.shape[1] * 32 not in _lib.DL_FP_BITS:
         raise ValueError(f'shapes disagree: a_bits {tuple(a_bits.shape)}, b_bits {tuple(b_bits.shape)}')
     if a_bits.dtype != torch.int32 or b_bits.dtype != torch.int32:
@@ -1254,18 +1199,16 @@ def tanimoto_nearest(a_bits, b_bits, a_offsets=None, b_offsets=None, exclude_dia
     if a_offsets is None:
         a_offsets, b_offsets = (torch.full((2,), m, dtype=torch.int32, device=dev) for m in (Ma, Mb))     # [0, M], filled on
         a_offsets[0], b_offsets[0] = 0, 0                                                                  # the device
-    a_offsets, b_offsets = (t.to(device=dev, dtype=torch.int32).contiguous() for t in (a_offsets, b_offsets))
+    a_offsets, b_offsets = (_lib.dense(t, dev, torch.int32) for t in (a_offsets, b_offsets))
     G = max(a_offsets.numel() - 1, 0)
-    i32 = lambda: torch.empty(Ma, dtype=torch.int32, device=dev)            # noqa: E731
+    i32 = partial(_lib.empty_i32, dev, Ma)
     out = Nearest(i32(), i32(), i32(), torch.empty(Ma, dtype=torch.int64, device=dev) if want_sum else None, i32())
-    with torch.cuda.device(dev):
-        args = _lib.DLTanimotoArgs(
-            Ma=Ma, Mb=Mb, W=W, G=G, a_bits=a_bits.data_ptr() if Ma else None, b_bits=b_bits.data_ptr() if Mb else None,
-            a_offsets=a_offsets.data_ptr() if G else None, b_offsets=b_offsets.data_ptr() if G else None,
-            exclude_diagonal=int(bool(exclude_diagonal)), nn_index=out.index.data_ptr(), nn_common=out.common.data_ptr(),
-            nn_union=out.union.data_ptr(), n_pairs=out.n_pairs.data_ptr(),
-            sum_q20=out.sum_q20.data_ptr() if want_sum else None, stream=torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.load().dl_tanimoto_nearest(ctypes.byref(args)), 'dl_tanimoto_nearest')
+    args = _lib.DLTanimotoArgs(
+        Ma=Ma, Mb=Mb, W=W, G=G, a_bits=a_bits.data_ptr() if Ma else None, b_bits=b_bits.data_ptr() if Mb else None,
+        a_offsets=a_offsets.data_ptr() if G else None, b_offsets=b_offsets.data_ptr() if G else None,
+        exclude_diagonal=int(bool(exclude_diagonal)), nn_index=out.index.data_ptr(), nn_common=out.common.data_ptr(),
+        nn_union=out.union.data_ptr(), n_pairs=out.n_pairs.data_ptr(), sum_q20=_lib.ptr(out.sum_q20))
+    _lib.launch('dl_tanimoto_nearest', args, dev)
     return out
 
 
@@ -1425,9 +1368,8 @@ def pharmacophore_features(one_hot, x, node_mask, found, bond_aromatic, is_geom,
     ``_lib.DL_PHARM_*`` (more than 256 kept atoms: nothing is listed; more than 64 rings: no ring features; the list too short;
     a NaN coordinate)."""
     masks = (node_mask,) + tuple(m for m in (drop_mask, mark_mask) if m is not None)
-    if not (one_hot.is_cuda and x.is_cuda and bond_aromatic.is_cuda and found.bonds.is_cuda and all(m.is_cuda for m in masks)):
-        raise _lib.HipLibraryError('pharmacophore_features runs on the HIP device only (no CPU fallback): '
-                                   f'got tensors on {one_hot.device}, {x.device}, {bond_aromatic.device}, {found.bonds.device}')
+    _lib.require_device('pharmacophore_features', one_hot=one_hot, x=x, bond_aromatic=bond_aromatic, bonds=found.bonds,
+                        node_mask=node_mask, drop_mask=drop_mask, mark_mask=mark_mask)
     B, N, nf = one_hot.shape
     if x.shape != (B, N, 3) or any(m.numel() != B * N for m in masks) or found.bonds.dim() != 3 or found.bonds.shape[0] != B \
             or bond_aromatic.shape != found.bonds.shape[:2]:
@@ -1436,9 +1378,9 @@ def pharmacophore_features(one_hot, x, node_mask, found, bond_aromatic, is_geom,
                          f'{tuple(bond_aromatic.shape)}')
     dev = one_hot.device
     found = normalize_bonds(found, B, dev, 'pharmacophore_features')
-    f32 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()     # noqa: E731
-    one_hot, x, node_mask, drop_mask, mark_mask = f32(one_hot), f32(x), f32(node_mask), f32(drop_mask), f32(mark_mask)
-    bond_aromatic = bond_aromatic.to(device=dev, dtype=torch.int32).contiguous()
+    one_hot, x, node_mask, drop_mask, mark_mask = (_lib.dense(t, dev, torch.float32)
+                                                   for t in (one_hot, x, node_mask, drop_mask, mark_mask))
+    bond_aromatic = _lib.dense(bond_aromatic, dev, torch.int32)
     classes, valences = _pharm_tables(dev, is_geom)
     if classes.numel() < nf:
         raise ValueError(f'one_hot has {nf} types, the vocabulary {classes.numel()}')
@@ -1446,21 +1388,18 @@ def pharmacophore_features(one_hot, x, node_mask, found, bond_aromatic, is_geom,
     Fcap = max(3 * N, 16) if capacity is None else int(capacity)
     if Fcap < 0:
         raise ValueError(f'capacity must not be negative, got {capacity}')
-    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    i32 = partial(_lib.empty_i32, dev)
     out = Features(i32(B, Fcap), i32(B, Fcap), torch.empty((B, Fcap, 3), dtype=torch.float32, device=dev), i32(B, Fcap), i32(B),
                    i32(B, _lib.DL_PHARM_FAMILIES), i32(B))
-    opt = lambda t: None if t is None else t.data_ptr()                     # noqa: E731
-    with torch.cuda.device(dev):
-        args = _lib.DLPharmArgs(
-            B=B, N=N, nf=nf, x=x.data_ptr(), one_hot=one_hot.data_ptr(), node_mask=node_mask.data_ptr(), drop_mask=opt(drop_mask),
-            mark_mask=opt(mark_mask), feature_class=classes.data_ptr(), default_valence=valences.data_ptr(),
-            capacity=bond_capacity, n_bonds_in=found.n_bonds.data_ptr(), bonds=found.bonds.data_ptr() if bond_capacity else None,
-            bond_aromatic=bond_aromatic.data_ptr() if bond_capacity else None, status_in=found.status.data_ptr(), Fcap=Fcap,
-            family=out.family.data_ptr() if Fcap else None, anchor=out.anchor.data_ptr() if Fcap else None,
-            position=out.position.data_ptr() if Fcap else None, marked=out.marked.data_ptr() if Fcap else None,
-            n_features=out.n_features.data_ptr(), family_count=out.family_count.data_ptr(), status=out.status.data_ptr(),
-            stream=torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.load().dl_pharmacophore_features(ctypes.byref(args)), 'dl_pharmacophore_features')
+    args = _lib.DLPharmArgs(
+        B=B, N=N, nf=nf, x=x.data_ptr(), one_hot=one_hot.data_ptr(), node_mask=node_mask.data_ptr(), drop_mask=_lib.ptr(drop_mask),
+        mark_mask=_lib.ptr(mark_mask), feature_class=classes.data_ptr(), default_valence=valences.data_ptr(),
+        capacity=bond_capacity, n_bonds_in=found.n_bonds.data_ptr(), bonds=found.bonds.data_ptr() if bond_capacity else None,
+        bond_aromatic=bond_aromatic.data_ptr() if bond_capacity else None, status_in=found.status.data_ptr(), Fcap=Fcap,
+        family=out.family.data_ptr() if Fcap else None, anchor=out.anchor.data_ptr() if Fcap else None,
+        position=out.position.data_ptr() if Fcap else None, marked=out.marked.data_ptr() if Fcap else None,
+        n_features=out.n_features.data_ptr(), family_count=out.family_count.data_ptr(), status=out.status.data_ptr())
+    _lib.launch('dl_pharmacophore_features', args, dev)
     return out
 
 
@@ -1475,10 +1414,8 @@ def feature_match(a, b, radius=2.5, marked_only=False):
     of equal distances the lowest index.  Returns a ``FeatureMatch``: ``best_index`` int32 and ``best_d2`` fp32 ``[B,Fb]``
     (-1 and +inf for none), ``n_a``, ``n_b`` (features taking part) and ``n_matched`` ``[B]``.  ``feature_score`` turns a row
     into the score.  This is RDKit's ``FeatMapScoreMode.Best`` with its default radius - on this project's features, NOT RDKit's."""
-    tensors = (a.family, a.position, a.marked, a.n_features, b.family, b.position, b.marked, b.n_features)
-    if not all(t.is_cuda for t in tensors):
-        raise _lib.HipLibraryError('feature_match runs on the HIP device only (no CPU fallback): '
-                                   f'got tensors on {", ".join(str(t.device) for t in tensors)}')
+    _lib.require_device('feature_match', **{f'{side}.{name}': getattr(features, name) for side, features in (('a', a), ('b', b))
+                                            for name in ('family', 'position', 'marked', 'n_features')})
     radius2 = float(radius) * float(radius)
     if not radius2 >= 0.0:
         raise ValueError(f'radius must be a number, got {radius}')
@@ -1492,22 +1429,20 @@ def feature_match(a, b, radius=2.5, marked_only=False):
         if tuple(t.shape) != shape:
             raise ValueError(f'shapes disagree: {name} {tuple(t.shape)}, expected {shape}')
     dev = a.family.device
-    i32 = lambda t: t.to(device=dev, dtype=torch.int32).contiguous()        # noqa: E731
-    f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()      # noqa: E731
-    fam_a, mk_a, n_a, pos_a = i32(a.family), i32(a.marked), i32(a.n_features), f32(a.position)
-    fam_b, mk_b, n_b, pos_b = i32(b.family), i32(b.marked), i32(b.n_features), f32(b.position)
-    new = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    fam_a, mk_a, n_a, fam_b, mk_b, n_b = (_lib.dense(t, dev, torch.int32)
+                                          for t in (a.family, a.marked, a.n_features, b.family, b.marked, b.n_features))
+    pos_a, pos_b = _lib.dense(a.position, dev, torch.float32), _lib.dense(b.position, dev, torch.float32)
+    new = partial(_lib.empty_i32, dev)
     out = FeatureMatch(new(B, Fb), torch.empty((B, Fb), dtype=torch.float32, device=dev), new(B), new(B), new(B))
-    with torch.cuda.device(dev):
-        args = _lib.DLFeatureMatchArgs(
-            B=B, Fa=Fa, Fb=Fb, family_a=fam_a.data_ptr() if Fa else None, position_a=pos_a.data_ptr() if Fa else None,
-            marked_a=mk_a.data_ptr() if Fa else None, n_features_a=n_a.data_ptr(),
-            family_b=fam_b.data_ptr() if Fb else None, position_b=pos_b.data_ptr() if Fb else None,
-            marked_b=mk_b.data_ptr() if Fb else None, n_features_b=n_b.data_ptr(), radius2=radius2,
-            marked_only=int(bool(marked_only)), best_index=out.best_index.data_ptr() if Fb else None,
-            best_d2=out.best_d2.data_ptr() if Fb else None, n_a=out.n_a.data_ptr(), n_b=out.n_b.data_ptr(),
-            n_matched=out.n_matched.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.load().dl_feature_match(ctypes.byref(args)), 'dl_feature_match')
+    args = _lib.DLFeatureMatchArgs(
+        B=B, Fa=Fa, Fb=Fb, family_a=fam_a.data_ptr() if Fa else None, position_a=pos_a.data_ptr() if Fa else None,
+        marked_a=mk_a.data_ptr() if Fa else None, n_features_a=n_a.data_ptr(),
+        family_b=fam_b.data_ptr() if Fb else None, position_b=pos_b.data_ptr() if Fb else None,
+        marked_b=mk_b.data_ptr() if Fb else None, n_features_b=n_b.data_ptr(), radius2=radius2,
+        marked_only=int(bool(marked_only)), best_index=out.best_index.data_ptr() if Fb else None,
+        best_d2=out.best_d2.data_ptr() if Fb else None, n_a=out.n_a.data_ptr(), n_b=out.n_b.data_ptr(),
+        n_matched=out.n_matched.data_ptr())
+    _lib.launch('dl_feature_match', args, dev)
     return out
 
 
@@ -1534,10 +1469,8 @@ def analyze_pharmacophores(one_hot_a, x_a, mask_a, linker_a, one_hot_b, x_b, mas
     ``status [B]``, the bits of both sides.  ``perceive_bonds`` is used with its default capacity, so a molecule whose atoms
     are piled on one another carries ``DL_BONDS_OVERFLOW`` and is left out of the scores.  The features are this project's
     own, after RDKit's ``BaseFeatures.fdef``, NOT RDKit's."""
-    tensors = (one_hot_a, x_a, mask_a, linker_a, one_hot_b, x_b, mask_b, linker_b)
-    if not all(t.is_cuda for t in tensors):
-        raise _lib.HipLibraryError('analyze_pharmacophores runs on the HIP device only (no CPU fallback): '
-                                   f'got tensors on {", ".join(str(t.device) for t in tensors)}')
+    _lib.require_device('analyze_pharmacophores', one_hot_a=one_hot_a, x_a=x_a, mask_a=mask_a, linker_a=linker_a,
+                        one_hot_b=one_hot_b, x_b=x_b, mask_b=mask_b, linker_b=linker_b)
     sides = []
     for one_hot, x, mask, linker, drop in ((one_hot_a, x_a, mask_a, linker_a, drop_a), (one_hot_b, x_b, mask_b, linker_b, drop_b)):
         B, N = one_hot.shape[:2]
@@ -1630,37 +1563,32 @@ def pose_checks(one_hot, x, node_mask, found, is_geom, drop_mask=None, mark_mask
     and ``mark_mask`` are ``[B,N]`` or ``[B,N,1]`` by row, ``atom_planar`` is ``[B,N]`` by atom number.  Returns device int32
     tensors ``(counts [B,2,8], atom_flags [B,N], status [B])``; ``analyze_pose_checks`` states the rule."""
     others = tuple(m for m in (node_mask, drop_mask, mark_mask, atom_planar) if m is not None)
-    if not (one_hot.is_cuda and x.is_cuda and all(m.is_cuda for m in others)):
-        raise _lib.HipLibraryError('pose_checks runs on the HIP device only (no CPU fallback): '
-                                   f'got tensors on {one_hot.device}, {x.device}, {[str(m.device) for m in others]}')
+    _lib.require_device('pose_checks', one_hot=one_hot, x=x, node_mask=node_mask, drop_mask=drop_mask, mark_mask=mark_mask,
+                        atom_planar=atom_planar)
     B, N, nf = one_hot.shape
     if x.shape != (B, N, 3) or any(m.numel() != B * N for m in others):
         raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, x {tuple(x.shape)}, masks '
                          f'{[tuple(m.shape) for m in others]}')
     dev = one_hot.device
     given = normalize_bonds(found, B, dev, 'pose_checks')
-    f32 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()     # noqa: E731
-    one_hot, x, node_mask, drop_mask, mark_mask = f32(one_hot), f32(x), f32(node_mask), f32(drop_mask), f32(mark_mask)
+    one_hot, x, node_mask, drop_mask, mark_mask = (_lib.dense(t, dev, torch.float32)
+                                                   for t in (one_hot, x, node_mask, drop_mask, mark_mask))
     if atom_planar is not None:
-        atom_planar = (atom_planar.reshape(B, N) != 0).to(device=dev, dtype=torch.int32).contiguous()
+        atom_planar = _lib.dense(atom_planar.reshape(B, N) != 0, dev, torch.int32)
     bounds, cosines, clash = _pose_tables(dev, is_geom, length_bounds, angle_tolerance, clash_scale)
     if clash.shape[0] < nf:
         raise ValueError(f'one_hot has {nf} types, the vocabulary {clash.shape[0]}')
     if clash.shape[0] > nf:                                  # the kernel indexes the tables with nf
         bounds, clash = bounds[:nf, :nf].contiguous(), clash[:nf, :nf].contiguous()
     capacity = given.bonds.shape[1]
-    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
-    counts, atom_flags, status = i32(B, 2, _lib.DL_POSE_COUNTS), i32(B, N), i32(B)
-    opt = lambda t: None if t is None else t.data_ptr()                     # noqa: E731
+    counts, atom_flags, status = (_lib.empty_i32(dev, *shape) for shape in ((B, 2, _lib.DL_POSE_COUNTS), (B, N), (B,)))
     args = _lib.DLPoseArgs(
-        B=B, N=N, nf=nf, x=x.data_ptr(), one_hot=one_hot.data_ptr(), node_mask=node_mask.data_ptr(), drop_mask=opt(drop_mask),
-        mark_mask=opt(mark_mask), atom_planar=opt(atom_planar), length_bounds2=bounds.data_ptr(), angle_cos=cosines.data_ptr(),
-        clash2=clash.data_ptr(), capacity=capacity, n_bonds_in=given.n_bonds.data_ptr(),
-        bonds=given.bonds.data_ptr() if capacity else None, status_in=opt(given.status), counts=counts.data_ptr(),
+        B=B, N=N, nf=nf, x=x.data_ptr(), one_hot=one_hot.data_ptr(), node_mask=node_mask.data_ptr(), drop_mask=_lib.ptr(drop_mask),
+        mark_mask=_lib.ptr(mark_mask), atom_planar=_lib.ptr(atom_planar), length_bounds2=bounds.data_ptr(),
+        angle_cos=cosines.data_ptr(), clash2=clash.data_ptr(), capacity=capacity, n_bonds_in=given.n_bonds.data_ptr(),
+        bonds=given.bonds.data_ptr() if capacity else None, status_in=_lib.ptr(given.status), counts=counts.data_ptr(),
         atom_flags=atom_flags.data_ptr(), status=status.data_ptr())
-    with torch.cuda.device(dev):
-        args.stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(_lib.load().dl_pose_checks(ctypes.byref(args)), 'dl_pose_checks')
+    _lib.launch('dl_pose_checks', args, dev)
     return counts, atom_flags, status
 
 
@@ -1687,9 +1615,7 @@ def analyze_pose_checks(one_hot, x, node_mask, is_geom, linker_mask, drop_mask=N
     ``atom_flags [B,N]`` by atom number (1 an end of a short or long bond, 2 the centre of a bad angle, 4 in a clash),
     ``status [B]`` (the bits of the two launches before plus ``_lib.DL_POSE_*``; more than 256 kept atoms or a non-finite
     coordinate: nothing is counted), and ``refined`` / ``aromatic`` as ``refine_bond_orders`` returns them."""
-    if not (one_hot.is_cuda and x.is_cuda and node_mask.is_cuda and linker_mask.is_cuda):
-        raise _lib.HipLibraryError('analyze_pose_checks runs on the HIP device only (no CPU fallback): '
-                                   f'got tensors on {one_hot.device}, {x.device}, {node_mask.device}, {linker_mask.device}')
+    _lib.require_device('analyze_pose_checks', one_hot=one_hot, x=x, node_mask=node_mask, linker_mask=linker_mask)
     B, N = one_hot.shape[:2]
     if linker_mask.numel() != B * N:
         raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, linker_mask {tuple(linker_mask.shape)}')

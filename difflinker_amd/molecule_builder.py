@@ -7,7 +7,6 @@ before it builds it), so atom ``k`` of ``bonds``, ``valence`` and ``component`` 
 file of the same molecule.  RDKit objects are not built: ``build_xae_molecules`` stops at the reference's ``(X, A, E)``
 triple, and validity is reported as numbers (valences, component counts), never as RDKit's sanitisation.
 """
-import ctypes
 from collections import namedtuple
 
 import torch
@@ -39,30 +38,23 @@ def perceive_bonds(one_hot, x, node_mask, is_geom, margins=const.MARGINS_EDM, ca
     -1 beyond the atom count); ``status [B]`` (``_lib.DL_BONDS_OVERFLOW``: more bonds than ``capacity``, ``n_bonds`` is
     still the true count; ``_lib.DL_BONDS_NONFINITE``: a NaN / inf coordinate, which bonds to nothing).
     ``capacity`` defaults to ``4 * N`` bonds per molecule (a valid heavy-atom graph has at most ``2 * N``)."""
-    if not (one_hot.is_cuda and x.is_cuda and node_mask.is_cuda):
-        raise _lib.HipLibraryError('perceive_bonds runs on the HIP device only (no CPU fallback): '
-                                   f'got tensors on {one_hot.device}, {x.device}, {node_mask.device}')
+    _lib.require_device('perceive_bonds', one_hot=one_hot, x=x, node_mask=node_mask)
     B, N, nf = one_hot.shape
     if x.shape != (B, N, 3) or node_mask.numel() != B * N:
         raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, x {tuple(x.shape)}, '
                          f'node_mask {tuple(node_mask.shape)}')
     dev = one_hot.device
-    f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()     # noqa: E731
-    one_hot, x, node_mask = f32(one_hot), f32(x), f32(node_mask)
+    one_hot, x, node_mask = (_lib.dense(t, dev, torch.float32) for t in (one_hot, x, node_mask))
     table = _table(dev, is_geom, margins)
     capacity = 4 * N if capacity is None else int(capacity)
-    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
-    out = Bonds(i32(B), i32(B, capacity, 3), i32(B, N), i32(B), i32(B, N), i32(B))
-    lib = _lib.load()
+    out = Bonds(*(_lib.empty_i32(dev, *shape) for shape in ((B,), (B, capacity, 3), (B, N), (B,), (B, N), (B,))))
     args = _lib.DLBondsArgs(B=B, N=N, nf=nf, one_hot=one_hot.data_ptr(), x=x.data_ptr(), node_mask=node_mask.data_ptr(),
                             table=table.data_ptr(), table_len=table.numel(), capacity=capacity,
                             n_bonds=out.n_bonds.data_ptr(), bonds=out.bonds.data_ptr() if capacity else None,
                             valence=out.valence.data_ptr(), n_components=out.n_components.data_ptr(),
                             component=out.component.data_ptr(), status=out.status.data_ptr(), workspace=None,
                             workspace_bytes=0)
-    with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.dl_perceive_bonds(ctypes.byref(args), stream), 'dl_perceive_bonds')
+    _lib.launch('dl_perceive_bonds', args, dev)
     return out
 
 
@@ -104,11 +96,7 @@ def normalize_bonds(found, B, device, who):
     capacity slice ``wider[:, :capacity]`` of a longer one, the counts any integer dtype, strided or sliced - and every member
     the kernel reads becomes dense int32 (``_canonical_members``; a ``Bonds`` of ``perceive_bonds`` is not copied).  Members on
     the host raise ``HipLibraryError``: there is no CPU fallback."""
-    where = [(name, getattr(found, name).device) for name in _KERNEL_READS
-             if getattr(found, name) is not None and not getattr(found, name).is_cuda]
-    if where:
-        raise _lib.HipLibraryError(f'{who} runs on the HIP device only (no CPU fallback): got the Bonds members '
-                                   + ', '.join(f'{name} on {d}' for name, d in where))
+    _lib.require_device(who, **{name: getattr(found, name) for name in _KERNEL_READS})
     return _canonical_members(found, B, device)
 
 
@@ -145,38 +133,33 @@ def refine_bond_orders(found, one_hot, x, node_mask, is_geom, drop_mask=None, ma
     of ``found.status`` plus ``_lib.DL_AROM_*`` (more than 256 kept atoms or 64 planar rings: the orders pass through; a
     system of more than 32 atoms keeps its orders)."""
     masks = (node_mask,) + tuple(m for m in (drop_mask, mark_mask) if m is not None)
-    if not (one_hot.is_cuda and x.is_cuda and found.bonds.is_cuda and all(m.is_cuda for m in masks)):
-        raise _lib.HipLibraryError('refine_bond_orders runs on the HIP device only (no CPU fallback): '
-                                   f'got tensors on {one_hot.device}, {x.device}, {found.bonds.device}')
+    _lib.require_device('refine_bond_orders', one_hot=one_hot, x=x, bonds=found.bonds, node_mask=node_mask,
+                        drop_mask=drop_mask, mark_mask=mark_mask)
     B, N, nf = one_hot.shape
     if x.shape != (B, N, 3) or any(m.numel() != B * N for m in masks) or found.bonds.dim() != 3 or found.bonds.shape[0] != B:
         raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, x {tuple(x.shape)}, masks '
                          f'{[tuple(m.shape) for m in masks]}, bonds {tuple(found.bonds.shape)}')
     dev = one_hot.device
     given = normalize_bonds(found, B, dev, 'refine_bond_orders')
-    f32 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()     # noqa: E731
-    one_hot, x, node_mask, drop_mask, mark_mask = f32(one_hot), f32(x), f32(node_mask), f32(drop_mask), f32(mark_mask)
+    one_hot, x, node_mask, drop_mask, mark_mask = (_lib.dense(t, dev, torch.float32)
+                                                   for t in (one_hot, x, node_mask, drop_mask, mark_mask))
     classes = _ring_classes(dev, is_geom)
     if classes.numel() < nf:
         raise ValueError(f'one_hot has {nf} types, the vocabulary {classes.numel()}')
     capacity = given.bonds.shape[1]
     bonds = given.bonds
-    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
-    order, valence = i32(B, capacity), i32(B, N)
-    out = Aromatic(i32(B, capacity), i32(B, N), i32(B), i32(B), i32(B), i32(B))
-    opt = lambda t: None if t is None else t.data_ptr()                     # noqa: E731
+    order, valence = _lib.empty_i32(dev, B, capacity), _lib.empty_i32(dev, B, N)
+    out = Aromatic(*(_lib.empty_i32(dev, *shape) for shape in ((B, capacity), (B, N), (B,), (B,), (B,), (B,))))
     args = _lib.DLAromaticArgs(
-        B=B, N=N, nf=nf, x=x.data_ptr(), one_hot=one_hot.data_ptr(), node_mask=node_mask.data_ptr(), drop_mask=opt(drop_mask),
-        mark_mask=opt(mark_mask), ring_class=classes.data_ptr(), capacity=capacity, n_bonds_in=given.n_bonds.data_ptr(),
+        B=B, N=N, nf=nf, x=x.data_ptr(), one_hot=one_hot.data_ptr(), node_mask=node_mask.data_ptr(),
+        drop_mask=_lib.ptr(drop_mask), mark_mask=_lib.ptr(mark_mask), ring_class=classes.data_ptr(), capacity=capacity, n_bonds_in=given.n_bonds.data_ptr(),
         bonds=bonds.data_ptr() if capacity else None, status_in=given.status.data_ptr(),
         tol2_ring=float(planarity) ** 2, tol2_sub=float(substituent) ** 2,
         order_out=order.data_ptr() if capacity else None, bond_aromatic=out.bond_aromatic.data_ptr() if capacity else None,
         atom_aromatic=out.atom_aromatic.data_ptr(), valence_out=valence.data_ptr(),
         n_planar_rings=out.n_planar_rings.data_ptr(), n_aromatic_rings=out.n_aromatic_rings.data_ptr(),
         n_aromatic_marked=out.n_aromatic_marked.data_ptr(), status=out.status.data_ptr())
-    with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.load().dl_aromatic_rings(ctypes.byref(args), stream), 'dl_aromatic_rings')
+    _lib.launch('dl_aromatic_rings', args, dev)
     refined = found._replace(bonds=torch.cat([bonds[:, :, :2], order[:, :, None]], dim=2), valence=valence)
     return refined, out
 
@@ -211,38 +194,32 @@ def add_hydrogens(found, one_hot, x, node_mask, is_geom, drop_mask=None, atom_pl
     cannot overflow."""
     masks = (node_mask,) + ((drop_mask,) if drop_mask is not None else ())
     others = masks + ((atom_planar,) if atom_planar is not None else ())
-    if not (one_hot.is_cuda and x.is_cuda and all(m.is_cuda for m in others)):
-        raise _lib.HipLibraryError('add_hydrogens runs on the HIP device only (no CPU fallback): '
-                                   f'got tensors on {one_hot.device}, {x.device}, {[str(m.device) for m in others]}')
+    _lib.require_device('add_hydrogens', one_hot=one_hot, x=x, node_mask=node_mask, drop_mask=drop_mask,
+                        atom_planar=atom_planar)
     B, N, nf = one_hot.shape
     if x.shape != (B, N, 3) or any(m.numel() != B * N for m in others):
         raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, x {tuple(x.shape)}, masks '
                          f'{[tuple(m.shape) for m in others]}')
     dev = one_hot.device
     given = normalize_bonds(found, B, dev, 'add_hydrogens')
-    f32 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()     # noqa: E731
-    one_hot, x, node_mask, drop_mask = f32(one_hot), f32(x), f32(node_mask), f32(drop_mask)
+    one_hot, x, node_mask, drop_mask = (_lib.dense(t, dev, torch.float32) for t in (one_hot, x, node_mask, drop_mask))
     if atom_planar is not None:
-        atom_planar = (atom_planar.reshape(B, N) != 0).to(device=dev, dtype=torch.int32).contiguous()
+        atom_planar = _lib.dense(atom_planar.reshape(B, N) != 0, dev, torch.int32)
     valence, length = _hydrogen_tables(dev, is_geom)
     if valence.numel() < nf:
         raise ValueError(f'one_hot has {nf} types, the vocabulary {valence.numel()}')
     capacity = 4 * N if capacity is None else int(capacity)
     bond_capacity = given.bonds.shape[1]
-    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
-    out = Hydrogens(i32(B), i32(B, N), torch.zeros((B, capacity), dtype=torch.int32, device=dev),
-                    torch.zeros((B, capacity, 3), dtype=torch.float64, device=dev), i32(B))
-    opt = lambda t: None if t is None else t.data_ptr()                     # noqa: E731
+    out = Hydrogens(_lib.empty_i32(dev, B), _lib.empty_i32(dev, B, N), torch.zeros((B, capacity), dtype=torch.int32, device=dev),
+                    torch.zeros((B, capacity, 3), dtype=torch.float64, device=dev), _lib.empty_i32(dev, B))
     args = _lib.DLHydrogensArgs(
-        B=B, N=N, nf=nf, x=x.data_ptr(), one_hot=one_hot.data_ptr(), node_mask=node_mask.data_ptr(), drop_mask=opt(drop_mask),
-        atom_planar=opt(atom_planar), default_valence=valence.data_ptr(), xh_length=length.data_ptr(), capacity=bond_capacity,
+        B=B, N=N, nf=nf, x=x.data_ptr(), one_hot=one_hot.data_ptr(), node_mask=node_mask.data_ptr(),
+        drop_mask=_lib.ptr(drop_mask), atom_planar=_lib.ptr(atom_planar), default_valence=valence.data_ptr(), xh_length=length.data_ptr(), capacity=bond_capacity,
         n_bonds_in=given.n_bonds.data_ptr(), bonds=given.bonds.data_ptr() if bond_capacity else None,
-        status_in=opt(given.status), Hcap=capacity, n_h=out.n_h.data_ptr(), h_count=out.h_count.data_ptr(),
+        status_in=_lib.ptr(given.status), Hcap=capacity, n_h=out.n_h.data_ptr(), h_count=out.h_count.data_ptr(),
         h_parent=out.parent.data_ptr() if capacity else None, h_x=out.x.data_ptr() if capacity else None,
         status=out.status.data_ptr())
-    with torch.cuda.device(dev):
-        args.stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(_lib.load().dl_add_hydrogens(ctypes.byref(args)), 'dl_add_hydrogens')
+    _lib.launch('dl_add_hydrogens', args, dev)
     return out
 
 

@@ -5,7 +5,6 @@ In place of the pocket half of the reference's preparation: ``get_pocket`` of ``
 numpy distance matrix, once per ligand) and ``MOADDataset.preprocess`` (``src/datasets.py:131-222``).  Not here: SMILES and the
 matching of table rows to substructures, cuts at three or more bonds, the reference's list of skipped PDB codes, protein cleaning
 (``clean_and_split.py``), hydrogens."""
-import ctypes
 from collections import namedtuple
 
 import numpy as np
@@ -38,10 +37,8 @@ def select_pockets(protein_x, protein_group, protein_offset, pair_protein, ligan
     ``DL_POCKET_TRUNCATED``: ``n_pocket > R``.  More than 256 ligand atoms (``DL_POCKET_TOO_LARGE``), a group id outside
     ``[0, DL_POCKET_MAX_GROUPS)`` (``_TOO_MANY_GROUPS``), a non-finite coordinate (``_NONFINITE``) or a protein that is not
     there or wider than ``max_atoms`` (``_BAD_PROTEIN``): nothing but ``n_ligand``."""
-    given = (protein_x, protein_group, protein_offset, pair_protein, ligand_x, ligand_mask)
-    if not all(t.is_cuda for t in given):
-        raise _lib.HipLibraryError('select_pockets runs on the HIP device only (no CPU fallback): '
-                                   f'got tensors on {", ".join(str(t.device) for t in given)}')
+    _lib.require_device('select_pockets', protein_x=protein_x, protein_group=protein_group, protein_offset=protein_offset,
+                        pair_protein=pair_protein, ligand_x=ligand_x, ligand_mask=ligand_mask)
     if protein_x.dim() != 2 or protein_x.shape[1] != 3 or ligand_x.dim() != 3 or ligand_x.shape[2] != 3:
         raise ValueError(f'shapes disagree: protein_x {tuple(protein_x.shape)}, ligand_x {tuple(ligand_x.shape)}')
     M_total, (B, L) = protein_x.shape[0], ligand_x.shape[:2]
@@ -52,21 +49,20 @@ def select_pockets(protein_x, protein_group, protein_offset, pair_protein, ligan
                          f'protein_offset {tuple(protein_offset.shape)}, pair_protein {tuple(pair_protein.shape)}, ligand_x '
                          f'{tuple(ligand_x.shape)}, ligand_mask {tuple(ligand_mask.shape)}, capacity {capacity}, max_atoms {max_atoms}')
     dev = protein_x.device
-    cast = lambda t, dtype: t.to(device=dev, dtype=dtype).contiguous()                             # noqa: E731
-    protein_x, ligand_mask, ligand_x = cast(protein_x, torch.float32), cast(ligand_mask, torch.float32), cast(ligand_x, torch.float64)
-    protein_group, protein_offset, pair_protein = (cast(t, torch.int32) for t in (protein_group, protein_offset, pair_protein))
-    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
-    out = Pockets(i32(B), i32(B), i32(B), i32(B), i32(B), torch.empty((B, Mmax), dtype=torch.uint8, device=dev), i32(B, R))
-    opt = lambda t: t.data_ptr() if t.numel() else None                                            # noqa: E731
+    protein_x, ligand_mask = _lib.dense(protein_x, dev, torch.float32), _lib.dense(ligand_mask, dev, torch.float32)
+    ligand_x = _lib.dense(ligand_x, dev, torch.float64)
+    protein_group, protein_offset, pair_protein = (_lib.dense(t, dev, torch.int32)
+                                                   for t in (protein_group, protein_offset, pair_protein))
+    out = Pockets(*(_lib.empty_i32(dev, B) for _ in range(5)), torch.empty((B, Mmax), dtype=torch.uint8, device=dev),
+                  _lib.empty_i32(dev, B, R))
+    opt = lambda t: t.data_ptr() if t.numel() else None            # noqa: E731  (NULL for an EMPTY tensor, not for None)
     args = _lib.DLPocketArgs(
         B=B, L=L, P=P, M_total=M_total, protein_x=opt(protein_x), protein_group=opt(protein_group),
         protein_offset=protein_offset.data_ptr(), pair_protein=opt(pair_protein), ligand_x=opt(ligand_x),
         ligand_mask=opt(ligand_mask), cutoff=float(cutoff), Mmax=Mmax, capacity=R, n_ligand=opt(out.n_ligand),
         n_contact_atoms=opt(out.n_contact_atoms), n_groups_selected=opt(out.n_groups_selected), n_pocket=opt(out.n_pocket),
         status=opt(out.status), member=opt(out.member), index=opt(out.index))
-    with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.load().dl_pocket_select(ctypes.byref(args), stream), 'dl_pocket_select')
+    _lib.launch('dl_pocket_select', args, dev)
     return out
 
 
