@@ -326,7 +326,30 @@ class DLTanimotoArgs(ctypes.Structure):               # likewise
     ]
 
 
-DL_PHARM_MAX_ATOMS, DL_PHARM_MAX_RINGS, DL_PHARM_FAMILIES = 256, 64, 7    # dl_pharm_args: kept atoms, aromatic rings; families
+DL_SELECT_MAX_ROWS = 4096                             # rows per group of dl_tanimoto_cluster and dl_tanimoto_pick
+DL_SELECT_TOO_LARGE, DL_SELECT_BAD_FIRST = 4, 16      # dl_cluster_args.status / dl_pick_args.status bits
+
+
+class DLClusterArgs(ctypes.Structure):                # the stream is the last FIELD, as for dl_tanimoto_nearest
+    _fields_ = [
+        ('M', ctypes.c_int32), ('W', ctypes.c_int32), ('G', ctypes.c_int32),
+        ('bits', ctypes.c_void_p), ('offsets', ctypes.c_void_p), ('num', ctypes.c_int32), ('den', ctypes.c_int32),
+        ('cluster', ctypes.c_void_p), ('centroid', ctypes.c_void_p), ('n_neighbours', ctypes.c_void_p),
+        ('n_clusters', ctypes.c_void_p), ('status', ctypes.c_void_p), ('stream', ctypes.c_void_p),
+    ]
+
+
+class DLPickArgs(ctypes.Structure):                   # likewise
+    _fields_ = [
+        ('M', ctypes.c_int32), ('W', ctypes.c_int32), ('G', ctypes.c_int32), ('K', ctypes.c_int32),
+        ('bits', ctypes.c_void_p), ('offsets', ctypes.c_void_p), ('first', ctypes.c_void_p),
+        ('picks', ctypes.c_void_p), ('pick_common', ctypes.c_void_p), ('pick_union', ctypes.c_void_p),
+        ('n_picked', ctypes.c_void_p), ('status', ctypes.c_void_p), ('pick_rank', ctypes.c_void_p),
+        ('stream', ctypes.c_void_p),
+    ]
+
+
+DL_PHARM_MAX_ATOMS, DL_PHARM_MAX_RINGS, DL_PHARM_FAMILIES = 256, 64, 7   # dl_pharm_args: kept atoms, aromatic rings; families
 DL_PHARM_TOO_LARGE, DL_PHARM_BAD_BOND = 4, 8          # dl_pharm_args.status bits, beside the DL_BONDS_* bits carried forward
 DL_PHARM_MANY_RINGS, DL_PHARM_OVERFLOW, DL_PHARM_NONFINITE = 16, 32, 64
 
@@ -403,7 +426,8 @@ EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_stri
            'dl_egnn_backward_fc_workspace_bytes', 'dl_egnn_backward_max_atoms', 'dl_egnn_backward_fc',
            'dl_egnn_backward_pocket_workspace_bytes', 'dl_egnn_backward_pocket',
            'dl_size_train_num_params', 'dl_size_train_workspace_bytes', 'dl_size_train_forward', 'dl_size_train_backward',
-           'dl_join_workspace_bytes', 'dl_sample_chain_fc_join', 'dl_bonds_workspace_bytes', 'dl_perceive_bonds',
+           'dl_join_workspace_bytes', 'dl_sample_chain_fc_join', 'dl_tanimoto_cluster', 'dl_tanimoto_pick',
+           'dl_bonds_workspace_bytes', 'dl_perceive_bonds',
            'dl_pose_checks',
            'dl_interaction_types', 'dl_interaction_scores', 'dl_add_hydrogens',
            'dl_molecule_keys', 'dl_clash_scores', 'dl_shape_scores', 'dl_ring_scores', 'dl_fragment_cuts',
@@ -426,6 +450,14 @@ STRUCT_ENTRY_POINTS = {
     'dl_pharmacophore_features': DLPharmArgs, 'dl_feature_match': DLFeatureMatchArgs,
     'dl_add_hydrogens': DLHydrogensArgs, 'dl_pose_checks': DLPoseArgs,
 }
+# The selections over fingerprint sets (select.hip), declared and called in the same way: a table of its own, because
+# tests/test_lib_host.py pins the table above name by name.
+SELECT_ENTRY_POINTS = {'dl_tanimoto_cluster': DLClusterArgs, 'dl_tanimoto_pick': DLPickArgs}
+
+
+def entry_struct(name):
+    """The args struct of a struct-taking entry point, from whichever of the two tables lists it."""
+    return STRUCT_ENTRY_POINTS[name] if name in STRUCT_ENTRY_POINTS else SELECT_ENTRY_POINTS[name]
 
 
 def _stream_is_field(struct):
@@ -521,7 +553,7 @@ def _open(path):
     lib.dl_inpaint_step.argtypes = [i32, i32, i32] + [vp] * 10 + [DLInpaintCoef, vp, vp]
     lib.dl_philox_fill.restype = i32
     lib.dl_philox_fill.argtypes = [ctypes.c_uint64, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp]
-    for name, struct in STRUCT_ENTRY_POINTS.items():
+    for name, struct in {**STRUCT_ENTRY_POINTS, **SELECT_ENTRY_POINTS}.items():
         getattr(lib, name).restype = i32
         getattr(lib, name).argtypes = [ctypes.POINTER(struct)] if _stream_is_field(struct) else [ctypes.POINTER(struct), vp]
     lib.dl_edm_loss_grad.restype = i32
@@ -566,12 +598,12 @@ def ptr(t):
 
 
 def launch(name, args, device):
-    """Call the entry point ``name`` of ``STRUCT_ENTRY_POINTS`` on ``args`` with ``device`` current and on torch's current
+    """Call the entry point ``name`` of ``STRUCT_ENTRY_POINTS`` or ``SELECT_ENTRY_POINTS`` on ``args`` with ``device`` current and on torch's current
     stream of that device, handed over as the entry point takes it, and raise ``HipLibraryError`` unless it answers ``DL_OK``.
     Nothing is built, allocated or synchronised here."""
     with torch.cuda.device(device):
         stream = torch.cuda.current_stream(device).cuda_stream
-        if _stream_is_field(STRUCT_ENTRY_POINTS[name]):
+        if _stream_is_field(entry_struct(name)):
             args.stream = stream
             status = getattr(load(), name)(ctypes.byref(args))
         else:

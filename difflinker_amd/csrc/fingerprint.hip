@@ -122,15 +122,7 @@ __global__ __launch_bounds__(WG) void fingerprints_kernel(dl_fingerprint_args a)
 constexpr int TT = 256;                          // lanes = A rows per workgroup
 constexpr int TILE = DL_TANIMOTO_TILE;
 
-__device__ __forceinline__ int clamp_offset(int v, int m) { return min(max(v, 0), m); }
-
-// popcount(x) + acc in ONE instruction.  Written as `__popc(x) + acc` the compiler re-associates the 64 sums of a row into
-// popcounts onto zero and a tree of three-operand adds: 2.5 W instructions per pair where 2 W do.
-__device__ __forceinline__ unsigned popc_add(unsigned x, unsigned acc) {
-    unsigned out;
-    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(out) : "v"(x), "v"(acc));
-    return out;
-}
+// (clamp_offset and popc_add: workgroup.h, shared with select.hip)
 
 template <int W, bool SUM>
 __global__ __launch_bounds__(TT) void tanimoto_kernel(dl_tanimoto_args a) {

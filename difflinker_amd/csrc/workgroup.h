@@ -63,6 +63,19 @@ __device__ __forceinline__ int block_min(int v, int* lds /* [WG_WAVES] */) {
     return s;
 }
 
+// maximum of one int per thread over the workgroup, the same in every thread
+__device__ __forceinline__ int block_max(int v, int* lds /* [WG_WAVES] */) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int s = lds[0];
+#pragma unroll
+    for (int k = 1; k < WG_WAVES; ++k) s = max(s, lds[k]);
+    __syncthreads();
+    return s;
+}
+
 // the same for floats.  `o < v ? o : v` and no fminf: the comparison decides what a NaN does (it never wins against the
 // value a thread holds), and clash.hip's contract for non-finite coordinates is written against exactly this
 __device__ __forceinline__ float block_min(float v, float* lds /* [WG_WAVES] */) {
@@ -91,6 +104,17 @@ __device__ __forceinline__ long long block_sum(long long v, long long* lds /* [W
     for (int k = 0; k < WG_WAVES; ++k) s += lds[k];
     __syncthreads();
     return s;
+}
+
+// an offset into a set of m rows, as the fingerprint kernels read every offset: clamped to [0, m]
+__device__ __forceinline__ int clamp_offset(int v, int m) { return min(max(v, 0), m); }
+
+// popcount(x) + acc in ONE instruction.  Written as `__popc(x) + acc` the compiler re-associates the 64 sums of a row into
+// popcounts onto zero and a tree of three-operand adds: 2.5 W instructions per pair where 2 W do.
+__device__ __forceinline__ unsigned popc_add(unsigned x, unsigned acc) {
+    unsigned out;
+    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(out) : "v"(x), "v"(acc));
+    return out;
 }
 
 // the distance in pm that bond perception compares with its table (bonds.hip's rule `100 |x_i - x_j| < T`, strict): the one

@@ -88,15 +88,16 @@ def _check_hydrogens(hydrogens, output_format):
 def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_dir, name, com_key, hide_pocket,
                      output_format='xyz', metrics=False, clashes=False, protein=None, rings=False, bond_orders='distance',
                      aromatic=False, diversity=False, interactions=False, typed_protein=None, hydrogens=False,
-                     pose_checks=False):
+                     pose_checks=False, cluster=None, pick=None, select_view='linker'):
     if output_format not in OUTPUT_FORMATS:
         raise ValueError(f'output_format must be one of {OUTPUT_FORMATS}, got {output_format!r}')
     if bond_orders not in BOND_ORDERS:
         raise ValueError(f'bond_orders must be one of {BOND_ORDERS}, got {bond_orders!r}')
     _check_hydrogens(hydrogens, output_format)
+    select = _check_selection(cluster, pick, select_view)
     n_hydrogens = []
     written, found, scored, clash_records, ring_records, aromatic_records = [], [], [], [], [], []
-    prints, contact_records, pose_records = [], [], []
+    prints, contact_records, pose_records, eligible = [], [], [], []
     for batch_i, data in enumerate(_batches(dataset, batch_size, collate_fn)):
         n = len(data['positions'])
         chain = None
@@ -172,16 +173,26 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
             pose_records += mol_metrics.pose_checks_to_host(mol_metrics.analyze_pose_checks(
                 h[:, :, :ddpm.num_classes], x, node_mask, ddpm.is_geom, node_mask * (1 - pad(data['fragment_mask'])),
                 drop_mask=pad(data['pocket_mask']) if 'pocket_mask' in data else None))
-        if diversity:                                         # likewise; the bits stay on the device
+        if diversity or select:                               # likewise; the bits stay on the device
             pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, x.shape[1] - m.shape[1]))     # noqa: E731
+            drop = pad(data['pocket_mask']) if select and 'pocket_mask' in data else None      # as pose_checks passes them
             prints.append(mol_metrics.analyze_fingerprints(
-                h[:, :, :ddpm.num_classes], x, node_mask, ddpm.is_geom, node_mask * (1 - pad(data['fragment_mask']))))
+                h[:, :, :ddpm.num_classes], x, node_mask, ddpm.is_geom, node_mask * (1 - pad(data['fragment_mask'])),
+                drop_mask=drop))
+            if select:                                        # only valid molecules in one piece are clustered and picked
+                types = h[:, :, :ddpm.num_classes]
+                eligible += mol_metrics.good_molecules(mol_metrics.to_host(
+                    mol_metrics.analyze(types, x, node_mask, ddpm.is_geom, drop_mask=drop), types, node_mask, drop))
     if found:
         line = summary(found)
         if hydrogens:
             line['hydrogens_per_molecule'] = float(torch.cat(n_hydrogens).float().mean()) if line['molecules'] else 0.0
         print(json.dumps(line))
-    if metrics or clashes or rings or aromatic or diversity or interactions or pose_checks:
+    if select:                                                # one input: its samples are one group
+        whole, linker = (mol_metrics.cat_fingerprints([p[k] for p in prints]) for k in range(2))
+        selection = mol_metrics.select_records(whole, linker, [0] * whole.bits.shape[0], eligible, view=select_view,
+                                               threshold=cluster, k=pick)
+    if metrics or clashes or rings or aromatic or diversity or interactions or pose_checks or select:
         scores = {}
         if metrics:                                           # no true molecule here: no novelty, no recovery
             scores = dict(mol_metrics.compute_metrics(scored), molecules=len(scored))
@@ -199,6 +210,8 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
             whole, linker = (mol_metrics.cat_fingerprints([p[k] for p in prints]) for k in range(2))
             records = mol_metrics.diversity_records(whole, linker, [0] * whole.bits.shape[0])
             scores.update(mol_metrics.compute_diversity(records, with_true=False, with_reference=False))
+        if select:
+            scores.update(mol_metrics.compute_selection(selection))
         with open(os.path.join(output_dir, 'metrics.json'), 'w') as f:
             json.dump(scores, f, indent=1)
     if clashes:                                               # one record per written file, by its name
@@ -222,12 +235,42 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
                                                 'linker_counts': dict(zip(mol_metrics.POSE_COUNTS, m.linker_counts)),
                                                 'n_flagged_atoms': m.n_flagged_atoms, 'status': m.status}
                        for path in written for m in [by_name[os.path.basename(path).rsplit('_.', 1)[0]]]}, f, indent=1)
+    if select:                                                # likewise, and the two answers a reader came for
+        with open(os.path.join(output_dir, 'selection.json'), 'w') as f:
+            json.dump(mol_metrics.selection_report(selection, _files_of_samples(written, name, len(selection))), f, indent=1)
     return written
+
+
+def _selection_arguments(cluster, pick, select_view):
+    """The keyword arguments ``_sample_and_save`` takes for a selection; none when none is asked for."""
+    if not _check_selection(cluster, pick, select_view):
+        return {}
+    return {'cluster': cluster, 'pick': pick, 'select_view': select_view}
+
+
+def _check_selection(cluster, pick, select_view):
+    """Is a selection asked for?  Raises ``ValueError`` for a threshold, a number of picks or a view that cannot be."""
+    if select_view not in mol_metrics.SELECT_VIEWS:
+        raise ValueError(f'select_view must be one of {mol_metrics.SELECT_VIEWS}, got {select_view!r}')
+    if cluster is not None:
+        mol_metrics.threshold_fraction(cluster)
+    if pick is not None and int(pick) < 1:
+        raise ValueError(f'pick must be at least 1, got {pick!r}')
+    return cluster is not None or pick is not None
+
+
+def _files_of_samples(written, name, n):
+    """The base names of the files sample ``0 .. n - 1`` wrote (``output_{i}_{name}_.*``; two with ``output_format='both'``)."""
+    files = {}
+    for path in written:
+        base = os.path.basename(path)
+        files.setdefault(base.rsplit('_.', 1)[0], []).append(base)
+    return [files.get(f'output_{i}_{name}', []) for i in range(n)]
 
 
 def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anchors=None, device=None, output_format='xyz',
              metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False, diversity=False,
-             hydrogens=False, pose_checks=False):
+             hydrogens=False, pose_checks=False, cluster=None, pick=None, select_view='linker'):
     """``generate.py`` main(): fragments file -> ``n_samples`` molecules with a sampled linker, as ``.xyz`` files
     (``output_format='sdf'``: ``.sdf`` files with perceived bonds instead, ``'both'``: both; one JSON line with the number of
     molecules, the share in one piece and the mean bond count is printed then).  ``metrics=True`` also writes
@@ -250,8 +293,16 @@ def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anc
     (``metrics.analyze_pose_checks`` / ``compute_pose_checks``: a rule of this project's own after the idea of PoseBusters'
     intramolecular checks, NOT PoseBusters' numbers), adds ``pose_valid``, ``bond_lengths_valid``, ``bond_angles_valid``,
     ``internal_clash_free``, their ``_linker`` variants and the per-molecule means to ``metrics.json`` and writes
-    ``pose_checks.json`` with the counts per written file; the pocket variants take it as well, pocket atoms left out."""
+    ``pose_checks.json`` with the counts per written file; the pocket variants take it as well, pocket atoms left out.
+    ``cluster='0.65'`` (a similarity threshold) and / or ``pick=K`` say which few of the samples to look at: the valid samples
+    in one piece are clustered (Taylor-Butina) and a diverse subset of ``K`` is picked (MaxMin, starting from the most typical
+    sample) on the fingerprint ``select_view`` names (``metrics.select_records``: this project's own statement of both rules
+    on this project's own fingerprint, NOT RDKit's ``Butina.ClusterData`` or ``MaxMinPicker``).  ``selection.json`` gets the
+    record of every written file, ``picked`` and ``clusters`` (``metrics.selection_report``), ``metrics.json`` the
+    ``metrics.compute_selection`` keys; no file is removed, renamed or rewritten.  The pocket variants take them as well,
+    pocket atoms left out."""
     _check_hydrogens(hydrogens, output_format)
+    selection = _selection_arguments(cluster, pick, select_view)
     if clashes:
         raise ValueError('clashes are scored against a protein: pass a pocket or a protein file (--pocket / --protein)')
     device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
@@ -275,12 +326,14 @@ def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anc
     return _sample_and_save(ddpm, dataset, collate_with_fragment_edges, sample_fn, min(n_samples, 64), output_dir, name,
                             com_key='fragment_mask', hide_pocket=False, output_format=output_format, metrics=metrics,
                             rings=rings, bond_orders=bond_orders, aromatic=aromatic, diversity=diversity,
-                            **({'hydrogens': True} if hydrogens else {}), **({'pose_checks': True} if pose_checks else {}))
+                            **({'hydrogens': True} if hydrogens else {}), **({'pose_checks': True} if pose_checks else {}),
+                            **selection)
 
 
 def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size, device,
                             output_format, metrics=False, clashes=False, protein=None, rings=False, bond_orders='distance',
-                            aromatic=False, interactions=False, typed_protein=None, hydrogens=False, pose_checks=False):
+                            aromatic=False, interactions=False, typed_protein=None, hydrogens=False, pose_checks=False,
+                            selection=None):
     frag_pos, frag_one_hot, frag_charges = frag
     pocket_pos, pocket_one_hot, pocket_charges = pocket
     positions = np.concatenate([frag_pos, pocket_pos], axis=0)
@@ -303,13 +356,13 @@ def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_s
                             hide_pocket=True, output_format=output_format, metrics=metrics, clashes=clashes, protein=protein,
                             rings=rings, bond_orders=bond_orders, aromatic=aromatic, interactions=interactions,
                             typed_protein=typed_protein, **({'hydrogens': True} if hydrogens else {}),
-                            **({'pose_checks': True} if pose_checks else {}))
+                            **({'pose_checks': True} if pose_checks else {}), **(selection or {}))
 
 
 def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, output_dir, n_samples, n_steps, linker_size,
                          anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz',
                          metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False, interactions=False,
-                         hydrogens=False, pose_checks=False):
+                         hydrogens=False, pose_checks=False, cluster=None, pick=None, select_view='linker'):
     """``generate_with_pocket.py`` main(): the pocket is given as its own PDB file.  ``clashes=True`` scores every sample's
     generated atoms against the pocket atoms (``metrics.analyze_clashes``), adds the ``metrics.compute_clashes`` keys to
     ``metrics.json`` and writes ``clashes.json``: ``n_clashes``, ``n_clash_atoms`` and ``min_distance`` per written file.
@@ -318,8 +371,10 @@ def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, ou
     AutoDock Vina's numbers), adds the ``metrics.compute_interactions`` keys to ``metrics.json`` and writes
     ``interactions.json``: ``score``, the five fixed-point ``terms`` (units of 2^-32), ``n_pairs``, ``n_hbonds``,
     ``n_hydrophobic`` and ``status`` per written file.  ``hydrogens=True`` as in ``generate``: the scores above keep counting
-    heavy atoms alone.  ``pose_checks=True`` as in ``generate``, on the ligand without the pocket atoms."""
+    heavy atoms alone.  ``pose_checks=True`` as in ``generate``, on the ligand without the pocket atoms; ``cluster``, ``pick``
+    and ``select_view`` likewise."""
     _check_hydrogens(hydrogens, output_format)
+    selection = _selection_arguments(cluster, pick, select_view)
     device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
     os.makedirs(output_dir, exist_ok=True)
     if random_seed is not None:
@@ -340,20 +395,23 @@ def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, ou
     return _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size,
                                    device, output_format, metrics, clashes, rings=rings, bond_orders=bond_orders,
                                    aromatic=aromatic, interactions=interactions, **({'hydrogens': True} if hydrogens else {}),
-                                   **({'pose_checks': True} if pose_checks else {}))
+                                   **({'pose_checks': True} if pose_checks else {}),
+                                   **({'selection': selection} if selection else {}))
 
 
 def generate_with_protein(input_path, protein_path, backbone_atoms_only, model, output_dir, n_samples, n_steps,
                           linker_size, anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz',
                           metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False,
-                          interactions=False, hydrogens=False, pose_checks=False):
+                          interactions=False, hydrogens=False, pose_checks=False, cluster=None, pick=None,
+                          select_view='linker'):
     """``generate_with_protein.py`` main(): the pocket = residues of the protein within 6 A of the fragments.
     ``clashes=True`` as in ``generate_with_pocket``, but against ALL protein atoms whose element is in the vocabulary
     (``io.get_protein_atoms``), residues outside the pocket the model saw included; the pocket rows of the batch are then not
     targets, so no atom counts twice.  ``interactions=True`` likewise scores against the whole protein, which is typed once
-    (``metrics.protein_types``), so no residue is cut at a pocket boundary.  ``hydrogens=True`` and ``pose_checks=True`` as in
-    ``generate``."""
+    (``metrics.protein_types``), so no residue is cut at a pocket boundary.  ``hydrogens=True``, ``pose_checks=True``,
+    ``cluster``, ``pick`` and ``select_view`` as in ``generate``."""
     _check_hydrogens(hydrogens, output_format)
+    selection = _selection_arguments(cluster, pick, select_view)
     device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
     os.makedirs(output_dir, exist_ok=True)
     if random_seed is not None:
@@ -378,7 +436,30 @@ def generate_with_protein(input_path, protein_path, backbone_atoms_only, model, 
                                    device, output_format, metrics, clashes, protein if clashes else None, rings=rings,
                                    bond_orders=bond_orders, aromatic=aromatic, interactions=interactions,
                                    typed_protein=typed_protein, **({'hydrogens': True} if hydrogens else {}),
-                                   **({'pose_checks': True} if pose_checks else {}))
+                                   **({'pose_checks': True} if pose_checks else {}),
+                                   **({'selection': selection} if selection else {}))
+
+
+def add_selection_arguments(p):
+    """``--cluster``, ``--pick`` and ``--select_view``, shared with ``sample``."""
+    p.add_argument('--cluster', default=None, metavar='S',
+                   help='cluster the valid samples of every input on the GPU at the Tanimoto similarity threshold S, a decimal '
+                        'such as 0.65 (Taylor-Butina sphere exclusion, this project\'s own statement of the rule on this '
+                        'project\'s circular fingerprint, not RDKit\'s Butina.ClusterData) and add the cluster scores to '
+                        'metrics.json')
+    p.add_argument('--pick', type=int, default=None, metavar='K',
+                   help='pick a diverse subset of K of the valid samples of every input on the GPU (MaxMin from the most typical '
+                        'sample, this project\'s own tie rules on this project\'s fingerprint, not RDKit\'s MaxMinPicker)')
+    p.add_argument('--select_view', choices=mol_metrics.SELECT_VIEWS, default='linker',
+                   help='the fingerprint --cluster and --pick compare: linker (the centres are the linker atoms) or whole (all '
+                        'samples of an input share their fragments, so this mostly measures the fragments)')
+
+
+def selection_arguments(a):
+    """The keyword arguments the parsed ``--cluster`` / ``--pick`` / ``--select_view`` stand for; none when neither is given."""
+    if a.cluster is None and a.pick is None:
+        return {}
+    return {'cluster': a.cluster, 'pick': a.pick, 'select_view': a.select_view}
 
 
 def main(argv=None):
@@ -435,6 +516,7 @@ def main(argv=None):
                         'clashes between atoms four or more bonds apart, always on the geometric bond orders (a rule of this '
                         'project after the idea of PoseBusters\' intramolecular checks, NOT PoseBusters\' numbers) - add '
                         'pose_valid and its parts to metrics.json and write pose_checks.json with one record per written file')
+    add_selection_arguments(p)
     a = p.parse_args(argv)
     if a.clashes and a.pocket is None and a.protein is None:
         raise ValueError('--clashes scores the generated atoms against a protein: pass --pocket or --protein')
@@ -452,6 +534,7 @@ def main(argv=None):
         more['hydrogens'] = True
     if a.pose_checks:
         more['pose_checks'] = True
+    more.update(selection_arguments(a))
     if a.pocket is not None:
         files = generate_with_pocket(a.fragments, a.pocket, a.backbone_atoms_only, a.model, a.output, a.n_samples,
                                      a.n_steps, a.linker_size, a.anchors, a.max_batch_size, a.random_seed,

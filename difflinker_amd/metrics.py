@@ -53,9 +53,15 @@ published form - NOT AutoDock Vina's numbers: no hydrogens, no PDBQT typing, no 
 physically plausible?  Bond lengths against the typical lengths of the bond table, bond angles against the ideal of the
 centre's class, and clashes between atoms four or more bonds apart (``dl_pose_checks``, ``csrc/pose_checks.hip``), on the
 geometric bond orders.  This project's own rule after the idea of PoseBusters' intramolecular checks - NOT PoseBusters.
+
+``select_records`` / ``compute_selection`` answer which few samples of an input to look at and how many really different
+answers there are: Taylor-Butina clusters and MaxMin diverse subsets of the valid samples' fingerprints
+(``dl_tanimoto_cluster`` and ``dl_tanimoto_pick``, ``csrc/select.hip``).  This project's own statement of both rules, on this
+project's fingerprint - NOT RDKit's ``Butina.ClusterData`` or ``MaxMinPicker`` on ties.
 """
 import math
 from collections import namedtuple
+from fractions import Fraction
 from functools import partial
 
 import numpy as np
@@ -1328,6 +1334,236 @@ def compute_diversity(records, with_true=None, with_reference=None):
         if name == 'nearest_reference_similarity':
             out['nearest_reference_identical'] = mean([cc == uu for cc, uu in scored])
     return out
+
+
+Clusters = namedtuple('Clusters', 'cluster centroid n_neighbours n_clusters status num den')
+Picks = namedtuple('Picks', 'picks pick_common pick_union n_picked status pick_rank')
+SelectRecord = namedtuple('SelectRecord', 'input eligible cluster is_centroid cluster_size n_neighbours pick_rank pick_similarity')
+SELECTION_NAMES = ('selection_molecules', 'clusters_per_input', 'cluster_ratio', 'largest_cluster_share')
+SELECT_VIEWS = ('linker', 'whole')
+
+
+def threshold_fraction(threshold):
+    """The similarity threshold ``dl_tanimoto_cluster`` compares with, as ``(num, den)``: ``threshold`` (a decimal string, a
+    ``Fraction`` or a float) through ``fractions.Fraction(...).limit_denominator(1000)``.  It must lie in (0, 1]."""
+    value = Fraction(threshold).limit_denominator(1000)
+    if not 0 < value <= 1:
+        raise ValueError(f'the similarity threshold must lie in (0, 1], got {threshold!r}')
+    return value.numerator, value.denominator
+
+
+def _fingerprint_set(who, bits, offsets, **more):
+    """What the two selection wrappers do with their rows and offsets, as ``tanimoto_nearest`` does: ``(bits, offsets, G)``."""
+    _lib.require_device(who, bits=bits, offsets=offsets, **more)
+    if bits.dim() != 2 or bits.shape[1] * 32 not in _lib.DL_FP_BITS:
+        raise ValueError(f'bits must be [M,W] with W * 32 one of {_lib.DL_FP_BITS}: got {tuple(bits.shape)}')
+    if bits.dtype != torch.int32:
+        raise ValueError(f'fingerprint rows are int32 words, got {bits.dtype}')
+    dev = bits.device
+    bits = _aligned_rows(bits.contiguous())      # a row slice of a larger set is aligned to 4 bytes: handed over as a copy
+    if offsets is None:
+        offsets = torch.full((2,), bits.shape[0], dtype=torch.int32, device=dev)     # [0, M], filled on the device
+        offsets[0] = 0
+    offsets = _lib.dense(offsets, dev, torch.int32)
+    return bits, offsets, max(offsets.numel() - 1, 0)
+
+
+def tanimoto_clusters(bits, offsets=None, threshold='0.65'):
+    """``dl_tanimoto_cluster``: Taylor-Butina sphere-exclusion clusters of every group of the fingerprint rows ``bits [M,W]``
+    (``Fingerprints.bits``: int32 words, any other dtype is refused with a ``ValueError``; any strides and offset), on
+    torch's current stream with no host synchronisation.  ``offsets`` (int32 ``[G+1]``, not decreasing) splits the rows
+    into ``G`` groups of at most 4096 rows; without it: one group over everything.
+
+    THE RULE (this project's own statement after RDKit's ``Butina.ClusterData(reordering=False)``, on THIS PROJECT'S
+    fingerprint; NOT promised to reproduce RDKit's output on ties).  With ``num / den = threshold`` (``threshold_fraction``)
+    row ``j != i`` of the same group is a neighbour of ``i`` when ``c * den >= num * u`` (``c = popcount(a & b)``,
+    ``u = popcount(a | b)``; two empty rows are neighbours).  The rows are walked by their number of neighbours, descending,
+    among equals by index; a row not yet assigned becomes the centroid of the next cluster and takes its unassigned
+    neighbours.
+
+    Returns a ``Clusters``: ``cluster`` (group-local id), ``centroid`` (row index of the cluster's centroid) and
+    ``n_neighbours`` int32 ``[M]``; ``n_clusters`` and ``status`` (``_lib.DL_SELECT_TOO_LARGE``: more than 4096 rows, nothing
+    was clustered) int32 ``[G]``; and the ``num`` and ``den`` that were used.  A row of no group, or of a group that is too
+    large, has -1, -1 and 0."""
+    num, den = threshold_fraction(threshold)
+    bits, offsets, G = _fingerprint_set('tanimoto_clusters', bits, offsets)
+    dev = bits.device
+    M, W = bits.shape
+    i32 = partial(_lib.empty_i32, dev)
+    out = Clusters(i32(M), i32(M), i32(M), i32(G), i32(G), num, den)
+    args = _lib.DLClusterArgs(
+        M=M, W=W, G=G, bits=bits.data_ptr() if M else None, offsets=offsets.data_ptr() if G else None, num=num, den=den,
+        cluster=out.cluster.data_ptr(), centroid=out.centroid.data_ptr(), n_neighbours=out.n_neighbours.data_ptr(),
+        n_clusters=out.n_clusters.data_ptr(), status=out.status.data_ptr())
+    _lib.launch('dl_tanimoto_cluster', args, dev)
+    return out
+
+
+def tanimoto_picks(bits, k, offsets=None, first=None):
+    """``dl_tanimoto_pick``: a MaxMin diverse subset of up to ``k`` rows (1 .. 4096) of every group of the fingerprint rows
+    ``bits [M,W]``, rows and ``offsets`` as ``tanimoto_clusters`` takes them, on torch's current stream with no host
+    synchronisation.  ``first`` (int32 ``[G]``, optional) is the row index of each group's first pick; without it every
+    group starts from its lowest row.
+
+    THE RULE (MaxMin with this project's own tie rules on THIS PROJECT'S fingerprint, NOT RDKit's ``MaxMinPicker``).  Every
+    unpicked row keeps the greatest similarity to any pick so far (of equal ones the earliest pick's ``c`` and ``u``); the
+    next pick is the unpicked row for which that is SMALLEST, fractions compared exactly, of equal ones the lowest row.
+
+    Returns a ``Picks``: ``picks`` (row indices in pick order), ``pick_common`` and ``pick_union`` (the ``c`` and ``u`` of
+    the pick's greatest similarity to the picks before it; -1 for the first) int32 ``[G,k]``, all -1 from ``n_picked`` on;
+    ``n_picked`` and ``status`` (``_lib.DL_SELECT_TOO_LARGE``; ``_lib.DL_SELECT_BAD_FIRST``: ``first`` outside its group;
+    either way nothing was picked) int32 ``[G]``; ``pick_rank`` int32 ``[M]``, the row's position in its group's pick order
+    or -1."""
+    k = int(k)
+    if not 1 <= k <= _lib.DL_SELECT_MAX_ROWS:
+        raise ValueError(f'k must be 1..{_lib.DL_SELECT_MAX_ROWS}, got {k}')
+    bits, offsets, G = _fingerprint_set('tanimoto_picks', bits, offsets, first=first)
+    dev = bits.device
+    M, W = bits.shape
+    if first is not None:
+        if first.numel() != G:
+            raise ValueError(f'{G} groups, {first.numel()} first picks')
+        first = _lib.dense(first, dev, torch.int32)
+    i32 = partial(_lib.empty_i32, dev)
+    out = Picks(i32(G, k), i32(G, k), i32(G, k), i32(G), i32(G), i32(M))
+    args = _lib.DLPickArgs(
+        M=M, W=W, G=G, K=k, bits=bits.data_ptr() if M else None, offsets=offsets.data_ptr() if G else None,
+        first=first.data_ptr() if first is not None and G else None, picks=out.picks.data_ptr(),
+        pick_common=out.pick_common.data_ptr(), pick_union=out.pick_union.data_ptr(), n_picked=out.n_picked.data_ptr(),
+        status=out.status.data_ptr(), pick_rank=out.pick_rank.data_ptr())
+    _lib.launch('dl_tanimoto_pick', args, dev)
+    return out
+
+
+def good_molecules(molecules):
+    """For every ``Molecule`` of ``to_host``: is it valid under the valence rule, in one piece and clean?  The rule by which
+    ``compute_metrics`` counts a prediction, and the gate of ``select_records``."""
+    return [_good(m) for m in molecules]
+
+
+def _typical_rows(bits, offsets, group_of):
+    """The most typical row of every group, int32 ``[G]``: the one of the greatest summed similarity to the others of its
+    group (``tanimoto_nearest``'s ``sum_q20``), of equal ones the lowest; -1 for an empty group.  No host synchronisation."""
+    G = offsets.numel() - 1
+    dev = bits.device
+    total = tanimoto_nearest(bits, bits, offsets, offsets, exclude_diagonal=True).sum_q20
+    most = torch.full((G,), -1, dtype=torch.int64, device=dev).scatter_reduce(0, group_of, total, 'amax')
+    position = torch.arange(bits.shape[0], dtype=torch.int64, device=dev)
+    nowhere = torch.iinfo(torch.int64).max
+    candidate = torch.where(total == most[group_of], position, nowhere)
+    first = torch.full((G,), nowhere, dtype=torch.int64, device=dev).scatter_reduce(0, group_of, candidate, 'amin')
+    return torch.where(first == nowhere, -1, first).to(torch.int32)
+
+
+def select_records(whole, linker, input_index, good, view='linker', threshold=None, k=None):
+    """The ``SelectRecord`` values ``compute_selection`` and the tools read, one per sample: the clusters
+    (``tanimoto_clusters``, with ``threshold``) and the diverse subset (``tanimoto_picks``, with ``k``) of every input's
+    samples, from fingerprints kept on the device.
+
+    ``whole`` and ``linker`` are the two ``Fingerprints`` of ``analyze_fingerprints`` for ALL samples (``cat_fingerprints``),
+    ``input_index[k]`` names the input sample ``k`` came from and groups are the inputs, as in ``diversity_records``;
+    ``view`` says which of the two fingerprints is compared (all samples of an input share their fragments, so ``'whole'``
+    mostly measures the fragments).  Only ELIGIBLE samples are grouped: those with fingerprint status 0 in both views and
+    ``good[k]`` true (``good_molecules`` of ``to_host``: valid under the valence rule and in one piece).  The gate is part of
+    the rule: MaxMin prefers outliers, and a broken molecule is the furthest outlier there is.  An input's first pick is its
+    most typical eligible sample: the greatest summed similarity to the others (``tanimoto_nearest`` on the same view), of
+    equal ones the lowest.
+
+    A record holds ``input``, ``eligible``, and - ``None`` when not asked for, not eligible, or in an input of more than 4096
+    eligible samples - ``cluster`` (the id within its input), ``is_centroid``, ``cluster_size``, ``n_neighbours``,
+    ``pick_rank`` (``None`` when not picked) and ``pick_similarity`` (``c / u`` in fp64 of the pick's greatest similarity
+    to the picks before it; ``None`` for the first)."""
+    n = whole.bits.shape[0]
+    if not (linker.bits.shape[0] == n == len(input_index) == len(good)):
+        raise ValueError(f'{n} and {linker.bits.shape[0]} fingerprints, {len(input_index)} input indices, {len(good)} flags')
+    if view not in SELECT_VIEWS:
+        raise ValueError(f'view must be one of {SELECT_VIEWS}, got {view!r}')
+    dev = whole.bits.device
+    dense = {}
+    groups_host = [dense.setdefault(v, len(dense)) for v in input_index]
+    G = len(dense)
+    fields = {name: [None] * n for name in SelectRecord._fields[2:]}
+    eligible = [False] * n
+    if n:
+        groups = torch.tensor(groups_host, dtype=torch.int64, device=dev)
+        clean = ((whole.status | linker.status) == 0) & torch.tensor([bool(v) for v in good], dtype=torch.bool, device=dev)
+        rows, offsets = _grouped(torch.nonzero(clean).reshape(-1), groups, G)
+        bits = (linker if view == 'linker' else whole).bits[rows].contiguous()
+        found = tanimoto_clusters(bits, offsets, threshold) if threshold is not None else None
+        picked = tanimoto_picks(bits, min(int(k), _lib.DL_SELECT_MAX_ROWS), offsets,
+                                _typical_rows(bits, offsets, groups[rows])) if k is not None else None
+        rows = rows.cpu().tolist()               # the first host synchronisation
+        for pos in rows:
+            eligible[pos] = True
+        if found is not None:
+            cluster, centroid, n_neighbours = (t.cpu().tolist() for t in (found.cluster, found.centroid, found.n_neighbours))
+            sizes = {}
+            for at, pos in enumerate(rows):
+                if cluster[at] >= 0:
+                    sizes[centroid[at]] = sizes.get(centroid[at], 0) + 1
+            for at, pos in enumerate(rows):
+                if cluster[at] >= 0:
+                    fields['cluster'][pos], fields['is_centroid'][pos] = cluster[at], centroid[at] == at
+                    fields['cluster_size'][pos], fields['n_neighbours'][pos] = sizes[centroid[at]], n_neighbours[at]
+        if picked is not None:
+            order, common, union = (t.cpu().tolist() for t in (picked.picks, picked.pick_common, picked.pick_union))
+            for g in range(G):
+                for rank, at in enumerate(order[g]):
+                    if at < 0:
+                        break
+                    fields['pick_rank'][rows[at]] = rank
+                    if rank:
+                        fields['pick_similarity'][rows[at]] = _similarity(common[g][rank], union[g][rank])
+    return [SelectRecord(input=input_index[pos], eligible=eligible[pos], **{name: v[pos] for name, v in fields.items()})
+            for pos in range(n)]
+
+
+def compute_selection(records):
+    """Set-level scores of the ``SelectRecord`` values ``records`` (``select_records`` with a threshold), on the host.  The
+    clusters are Taylor-Butina clusters under THIS PROJECT'S rule on THIS PROJECT'S fingerprint, not RDKit's.
+
+    ``selection_molecules``     eligible records: the only ones that were grouped
+    ``clusters_per_input``      the mean number of clusters over the inputs with a clustered sample
+    ``cluster_ratio``           the mean over those inputs of clusters / clustered samples: 1 when every sample is its own
+                                cluster
+    ``largest_cluster_share``   the mean over those inputs of the largest cluster's size / clustered samples
+
+    A mean over nothing is ``None``, as in ``compute_diversity``."""
+    mean = lambda values: float(sum(values) / len(values)) if values else None      # noqa: E731
+    sizes = {}
+    for m in records:
+        if m.eligible and m.cluster is not None:
+            of_input = sizes.setdefault(m.input, {})
+            of_input[m.cluster] = of_input.get(m.cluster, 0) + 1
+    totals = {key: sum(of_input.values()) for key, of_input in sizes.items()}
+    return {'selection_molecules': sum(bool(m.eligible) for m in records),
+            'clusters_per_input': mean([len(of_input) for of_input in sizes.values()]),
+            'cluster_ratio': mean([len(of_input) / totals[key] for key, of_input in sizes.items()]),
+            'largest_cluster_share': mean([max(of_input.values()) / totals[key] for key, of_input in sizes.items()])}
+
+
+def selection_report(records, names):
+    """What the tools write as ``selection.json``, from the ``SelectRecord`` values of ``select_records`` and ``names[k]``,
+    the names of the files sample ``k`` wrote (none, one or several): every file's record by its name, ``picked`` (the file
+    names in pick order; several inputs: one input after the other, in order of first appearance) and ``clusters`` (a list:
+    the centroid's file name and the members' of every cluster, an input's clusters by id, inputs as for ``picked``)."""
+    if len(names) != len(records):
+        raise ValueError(f'{len(records)} records, {len(names)} lists of file names')
+    report = {name: m._asdict() for m, files in zip(records, names) for name in files}
+    inputs = {}
+    for m in records:
+        inputs.setdefault(m.input, len(inputs))
+    ranked = sorted((inputs[m.input], m.pick_rank, k) for k, m in enumerate(records) if m.pick_rank is not None)
+    report['picked'] = [name for _, _, k in ranked for name in names[k]]
+    clusters = {}
+    for k, m in enumerate(records):
+        if m.cluster is not None:
+            entry = clusters.setdefault((inputs[m.input], m.cluster), {'centroid': None, 'members': []})
+            entry['members'] += names[k]
+            if m.is_centroid and names[k]:
+                entry['centroid'] = names[k][0]
+    report['clusters'] = [clusters[key] for key in sorted(clusters)]
+    return report
 
 
 Features = namedtuple('Features', 'family anchor position marked n_features family_count status')

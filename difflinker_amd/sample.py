@@ -16,7 +16,7 @@ import torch
 from . import metrics as mol_metrics
 from . import utils
 from .datasets import MOADDataset, collate, collate_with_fragment_edges, get_dataloader
-from .generate import BOND_ORDERS, OUTPUT_FORMATS
+from .generate import BOND_ORDERS, OUTPUT_FORMATS, _check_selection, add_selection_arguments, selection_arguments
 from .io import save_sdf_file, save_xyz_file
 from .lightning import DDPM
 from .linker_size import SizeClassifier
@@ -58,7 +58,7 @@ def _prepare(checkpoint, prefix, data, n_steps, device):
 def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=None, linker_size_model=None,
            output_format='xyz', metrics=False, geometry=False, clashes=False, shape=False, rings=False,
            bond_orders='distance', aromatic=False, diversity=False, diversity_reference=None, pharmacophore=False,
-           interactions=False, hydrogens=False, pose_checks=False):
+           interactions=False, hydrogens=False, pose_checks=False, cluster=None, pick=None, select_view='linker'):
     """``sample.py``.  Returns the output directory.  ``metrics=True`` scores the molecules sampled in this call against
     the data set's own (``metrics.compute_metrics``: valence rule, connectivity, uniqueness, novelty, recovery) and writes
     the result to ``metrics.json`` in the output directory; with ``geometry=True`` as well, the symmetry-aware RMSD of the
@@ -104,7 +104,14 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
     bond orders (``metrics.analyze_pose_checks`` / ``compute_pose_checks``: a rule of this project's own after the idea of
     PoseBusters' intramolecular checks, NOT PoseBusters' numbers) - and writes ``pose_valid``, ``bond_lengths_valid``,
     ``bond_angles_valid``, ``internal_clash_free``, their ``_linker`` variants, the per-molecule means and the ``true_``
-    values of all of them to ``metrics.json``."""
+    values of all of them to ``metrics.json``.
+    ``cluster='0.65'`` (a similarity threshold) clusters the valid samples in one piece of every input (Taylor-Butina) on the
+    fingerprint ``select_view`` names and writes ``metrics.compute_selection``'s keys to ``metrics.json``; ``pick=K`` picks a
+    diverse subset of ``K`` of them per input (MaxMin from the most typical sample) and writes ``selection.json``
+    (``metrics.selection_report``: every sample's record by ``<uuid>/<i>_.<format>``, ``picked``, ``clusters``).  Both are
+    ``metrics.select_records``: this project's own statement of the rules on this project's own fingerprint, NOT RDKit's
+    ``Butina.ClusterData`` or ``MaxMinPicker``.  No file is removed, renamed or rewritten."""
+    select = _check_selection(cluster, pick, select_view)
     if hydrogens and output_format == 'xyz':
         raise ValueError('hydrogens are written to the .sdf files: pass output_format sdf or both (--output_format); the '
                          '.xyz files stay the heavy-atom format of the reference')
@@ -123,6 +130,7 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
     pharm, linker_pharm = [], []
     pred_rings, true_rings = [], []
     pred_prints, true_prints, print_input = [], [], []
+    eligible, select_input, select_names = [], [], []
     diversity = diversity or diversity_reference is not None
     geometry = geometry and metrics
     exp = 'model' if isinstance(checkpoint, DDPM) else checkpoint.split('/')[-1].replace('.ckpt', '')
@@ -251,11 +259,17 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                     hs[:, :, :model.num_classes], xs, out_mask, model.is_geom, out_mask * (1 - pad(batch['fragment_mask'])),
                     drop_mask=pad(batch['pocket_mask']) if moad else None))
                 true_poses += true_pose_batch
-            if diversity:                                      # likewise
+            if diversity or select:                            # likewise
                 pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, out_mask.shape[1] - m.shape[1]))      # noqa: E731
                 pred_prints.append(mol_metrics.analyze_fingerprints(
                     hs[:, :, :model.num_classes], xs, out_mask, model.is_geom, out_mask * (1 - pad(batch['fragment_mask']))))
                 print_input += [(batch_idx, k) for k in range(len(uuids))]
+            if select:                                         # only valid molecules in one piece are clustered and picked
+                types = hs[:, :, :model.num_classes]
+                eligible += mol_metrics.good_molecules(mol_metrics.to_host(
+                    mol_metrics.analyze(types, xs, out_mask, model.is_geom), types, out_mask))
+                select_input += uuids
+                select_names += [[f'{u}/{i}_.{ext}' for ext in ('xyz', 'sdf') if output_format in (ext, 'both')] for u in uuids]
             if output_format != 'sdf':
                 save_xyz_file(output_dir, hs, xs, out_mask, [f'{u}/{i}' for u in uuids], is_geom=model.is_geom)
             if output_format != 'xyz':
@@ -286,7 +300,12 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
         if hydrogens:
             line['hydrogens_per_molecule'] = float(torch.cat(n_hydrogens).float().mean()) if line['molecules'] else 0.0
         print(json.dumps(line))
-    if metrics or clashes or shape or rings or aromatic or diversity or pharmacophore or interactions or pose_checks:
+    if select:                                                 # groups are the inputs
+        selection = _selection_records(pred_prints, select_input, eligible, select_view, cluster, pick)
+        if pick is not None:
+            with open(os.path.join(output_dir, 'selection.json'), 'w') as f:
+                json.dump(mol_metrics.selection_report(selection, select_names), f, indent=1)
+    if metrics or clashes or shape or rings or aromatic or diversity or pharmacophore or interactions or pose_checks or select:
         with open(os.path.join(output_dir, 'metrics.json'), 'w') as f:
             scores = {}
             if metrics:
@@ -310,6 +329,8 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
             if diversity:
                 reference = None if diversity_reference is None else reference_fingerprints(model, diversity_reference)
                 scores.update(_diversity_scores(pred_prints, true_prints, print_input, reference))
+            if select:
+                scores.update(mol_metrics.compute_selection(selection))
             json.dump(scores, f, indent=1)
     return output_dir
 
@@ -331,6 +352,14 @@ def reference_fingerprints(model, prefix, radius=2, n_bits=2048):
     if not rows:
         return torch.zeros(0, n_bits // 32, dtype=torch.int32, device=model.torch_device)
     return torch.cat(rows).contiguous()
+
+
+def _selection_records(pred_prints, input_index, eligible, view, cluster, pick):
+    """``metrics.select_records`` of the per-batch ``(whole, linker)`` fingerprint pairs gathered while sampling."""
+    if not pred_prints:
+        return []
+    whole, linker = (mol_metrics.cat_fingerprints([p[k] for p in pred_prints]) for k in range(2))
+    return mol_metrics.select_records(whole, linker, input_index, eligible, view=view, threshold=cluster, k=pick)
 
 
 def _diversity_scores(pred_prints, true_prints, input_index, reference=None):
@@ -430,6 +459,7 @@ def main(argv=None):
                         'both; a rule of this project, not RDKit\'s AddHs and not OpenBabel\'s).  --bond_orders geometric is '
                         'recommended: the distance table\'s arbitrary orders inside aromatic rings give arbitrary hydrogen '
                         'counts there')
+    add_selection_arguments(p)
     p.add_argument('--pose_checks', action='store_true',
                    help='check the internal geometry of every sample and of its true molecule on the GPU - bond lengths, bond '
                         'angles, clashes between atoms four or more bonds apart, always on the geometric bond orders (a rule of '
@@ -449,7 +479,7 @@ def main(argv=None):
                      **({'pharmacophore': True} if a.pharmacophore else {}),
                      **({'interactions': True} if a.interactions else {}),
                      **({'hydrogens': True} if a.hydrogens else {}),
-                     **({'pose_checks': True} if a.pose_checks else {})))
+                     **({'pose_checks': True} if a.pose_checks else {}), **selection_arguments(a)))
 
 
 if __name__ == '__main__':

@@ -71,6 +71,11 @@
  *                                           This project's own fingerprint, NOT RDKit's: stated below
  *   dl_tanimoto_nearest                  <- (no reference counterpart) for every row of one fingerprint set the most similar
  *                                           row and the summed Tanimoto similarity among a segment of another set
+ *   dl_tanimoto_cluster                  <- (no reference counterpart) Taylor-Butina sphere-exclusion clusters of every group
+ *                                           of a fingerprint set, in a fixed order.  This project's own statement of the rule
+ *                                           on this project's fingerprint, NOT RDKit's Butina.ClusterData on ties
+ *   dl_tanimoto_pick                     <- (no reference counterpart) a MaxMin diverse subset of every group of a
+ *                                           fingerprint set, with this project's own tie rules, NOT RDKit's MaxMinPicker
  *   dl_pharmacophore_features            <- the feature half of SC-RDKit (src/delinker_utils/calc_SC_RDKit.py:7-25,
  *                                           BuildFeatureFactory over BaseFeatures.fdef): donors, acceptors, ionizable
  *                                           groups, hydrophobes and aromatic rings of every molecule, from the bond graph.
@@ -1469,7 +1474,7 @@ int32_t dl_fingerprints(const dl_fingerprint_args* args);
  * or null offsets (unless G is 0) return DL_ERR_BAD_ARG; then Ma == 0 returns DL_OK without a launch; then a null output
  * other than sum_q20 returns DL_ERR_BAD_ARG, all before any device work.  G == 0 or Mb == 0 still write every row's "no
  * candidates" values.
- * Not here: the dense similarity matrix, clustering, picking diverse subsets. */
+ * Not here: the dense similarity matrix.  Clusters and diverse subsets: dl_tanimoto_cluster, dl_tanimoto_pick below. */
 #define DL_TANIMOTO_TILE 128        /* rows of B a workgroup stages in LDS at a time */
 typedef struct dl_tanimoto_args {
     int32_t Ma, Mb, W, G;
@@ -1486,6 +1491,86 @@ typedef struct dl_tanimoto_args {
     void* stream;                   /* hipStream_t; NULL: the default stream */
 } dl_tanimoto_args;
 int32_t dl_tanimoto_nearest(const dl_tanimoto_args* args);
+
+/* ---- clusters and diverse subsets of fingerprint sets (select.hip) -----------------------------------------------
+ * Two sequential-greedy selections over the rows dl_fingerprints wrote, with the similarity of dl_tanimoto_nearest.  Both
+ * read a fingerprint set the same way: bits uint32 [M,W] (W = 16, 32 or 64; 16-byte aligned) and the device array
+ * offsets[G+1], which does not decrease and splits the rows into G contiguous groups, group g the rows
+ * offsets[g] <= i < offsets[g+1].  Every offset is clamped to [0, M] first, so no offset can make a kernel read or write
+ * outside the set.  ONE workgroup handles one group, ONE launch takes all groups; there are no atomics and nothing depends
+ * on the order in which anything lands; all arithmetic is integer: the same bits on every run.  For a pair of rows
+ * c = popcount(a & b) and u = popcount(a | b); the similarity is the exact fraction c / u, and 1 / 1 when u is 0; fractions
+ * are compared by cross-multiplication in integers.
+ *
+ * A group of more than DL_SELECT_MAX_ROWS rows sets DL_SELECT_TOO_LARGE in its status and gets the "nothing" values below,
+ * for the group and for each of its rows.  A row in no group (before offsets[0] or from offsets[G] on) gets the "nothing"
+ * values too.  Every element of every output is written: the caller may hand over uninitialised memory.  The callee
+ * allocates nothing.
+ *
+ * CLUSTER.  Taylor-Butina sphere exclusion in a fixed order, THIS PROJECT'S OWN statement of the rule after RDKit's
+ * Butina.ClusterData(reordering=False); it is NOT promised to reproduce RDKit's output on ties.  The threshold is the
+ * rational num / den, 1 <= num <= den <= 65536.  Row j != i of the same group is a NEIGHBOUR of row i when
+ * c * den >= num * u (u == 0 included: two empty rows are neighbours).
+ *   n_neighbours[i]   the number of such rows; 0 for nothing
+ *   The group's rows are walked by n_neighbours descending, among equals by row index ascending.  A row that is not yet
+ *   assigned becomes the CENTROID of the next cluster (ids 0, 1, ... in order of creation) and takes every neighbour of its
+ *   own that is not yet assigned: a row that neighbours two centroids belongs to the earlier one.
+ *   cluster[i]        the group-local id of row i's cluster; -1 for nothing
+ *   centroid[i]       the global row index of that cluster's centroid; -1 for nothing
+ *   n_clusters[g]     clusters of group g; 0 for nothing
+ *   status[g]         0 or DL_SELECT_TOO_LARGE
+ *
+ * PICK.  MaxMin picking of up to K rows per group, 1 <= K <= DL_SELECT_MAX_ROWS, with THIS PROJECT'S tie rules (NOT
+ * RDKit's MaxMinPicker, which starts from a random row).  `first` (may be NULL) is int32 [G], the global row index of each
+ * group's first pick; without it the first pick is the group's lowest row.  A first[g] outside its non-empty group sets
+ * DL_SELECT_BAD_FIRST and gives that group nothing; an empty group does not look at its first[g].  Every unpicked row i keeps
+ * m(i), the greatest similarity to any pick so far, as the (c, u) of that pick, of equal ones the earliest pick.  The next
+ * pick is the unpicked row of the SMALLEST m(i), of equal ones the lowest row index.  Picking stops after K picks or when
+ * the group is used up.
+ *   picks [G,K]                      global row indices in pick order; -1 from n_picked on
+ *   pick_common, pick_union [G,K]    the (c, u) of m at the moment of picking (u == 0 is reported as it is); -1 and -1 for
+ *                                    the first pick and from n_picked on
+ *   n_picked [G]                     picks made; 0 for nothing
+ *   status [G]                       0, DL_SELECT_TOO_LARGE or DL_SELECT_BAD_FIRST
+ *   pick_rank [M]                    the row's position in its group's pick order; -1 when it was not picked, and for nothing
+ *
+ * Both: a null `args`, a negative M or G, another W, a threshold or K outside its range, a null or misaligned bits (unless M
+ * is 0) or null offsets (unless G is 0) return DL_ERR_BAD_ARG; then M == 0 and G == 0 returns DL_OK without a launch; then a
+ * null per-row output (unless M is 0) or per-group output (unless G is 0) returns DL_ERR_BAD_ARG, all before any device work.
+ * M == 0 or G == 0 alone still write the outputs there are (every group empty; every row in no group).
+ * Not here: groups split over several workgroups, clustering across groups, picking against a reference set, leader,
+ * hierarchical and k-medoid clustering, scaffold grouping. */
+#define DL_SELECT_MAX_ROWS 4096     /* rows per group */
+#define DL_SELECT_TOO_LARGE 4       /* status bit */
+#define DL_SELECT_BAD_FIRST 16      /* status bit */
+typedef struct dl_cluster_args {
+    int32_t M, W, G;
+    const uint32_t* bits;           /* device uint32 [M,W] (may be NULL when M is 0) */
+    const int32_t* offsets;         /* device int32 [G+1], not decreasing (may be NULL when G is 0) */
+    int32_t num, den;               /* the threshold num / den */
+    int32_t* cluster;               /* device int32 [M] out */
+    int32_t* centroid;              /* device int32 [M] out */
+    int32_t* n_neighbours;          /* device int32 [M] out */
+    int32_t* n_clusters;            /* device int32 [G] out */
+    int32_t* status;                /* device int32 [G] out */
+    void* stream;                   /* hipStream_t; NULL: the default stream */
+} dl_cluster_args;
+int32_t dl_tanimoto_cluster(const dl_cluster_args* args);
+
+typedef struct dl_pick_args {
+    int32_t M, W, G, K;
+    const uint32_t* bits;           /* device uint32 [M,W] (may be NULL when M is 0) */
+    const int32_t* offsets;         /* device int32 [G+1], not decreasing (may be NULL when G is 0) */
+    const int32_t* first;           /* device int32 [G], or NULL: every group starts from its lowest row */
+    int32_t* picks;                 /* device int32 [G,K] out */
+    int32_t* pick_common;           /* device int32 [G,K] out */
+    int32_t* pick_union;            /* device int32 [G,K] out */
+    int32_t* n_picked;              /* device int32 [G] out */
+    int32_t* status;                /* device int32 [G] out */
+    int32_t* pick_rank;             /* device int32 [M] out */
+    void* stream;                   /* hipStream_t; NULL: the default stream */
+} dl_pick_args;
+int32_t dl_tanimoto_pick(const dl_pick_args* args);
 
 /* ---- pharmacophore features and their feature-map match (pharmacophore.hip) ------------------------------------
  * The reference scores every sample with SC-RDKit = 0.5 * feature-map score + 0.5 * (1 - ShapeProtrudeDist).
