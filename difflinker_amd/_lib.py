@@ -403,6 +403,29 @@ class DLPoseArgs(ctypes.Structure):                   # the stream is the last F
     ]
 
 
+DL_RELAX_MAX_ATOMS, DL_RELAX_MAX_STEPS, DL_RELAX_TERMS = 256, 1000, 5     # dl_relax_args: kept atoms, steps, values per row of energy
+DL_RELAX_DIVERGED = 128                               # dl_relax_args.status bit, beside the DL_POSE_* and DL_BONDS_* bits
+RELAX_CONSTANTS = ('k_bond', 'k_angle', 'k_rep', 'k_wall', 'k_pos', 'dt0', 'dt_max', 'alpha0', 'f_inc', 'f_dec', 'f_alpha',
+                   'max_step', 'f_tol')               # the fp64 fields of dl_relax_args, in its order
+
+
+class DLRelaxArgs(ctypes.Structure):                  # the stream is the last FIELD, as for dl_pose_checks
+    _fields_ = [
+        ('B', ctypes.c_int32), ('N', ctypes.c_int32), ('nf', ctypes.c_int32),
+        ('x', ctypes.c_void_p), ('one_hot', ctypes.c_void_p), ('node_mask', ctypes.c_void_p),
+        ('drop_mask', ctypes.c_void_p), ('mark_mask', ctypes.c_void_p), ('atom_planar', ctypes.c_void_p),
+        ('length0', ctypes.c_void_p), ('aromatic_length0', ctypes.c_void_p), ('ideal_cos', ctypes.c_void_p),
+        ('reach2', ctypes.c_void_p), ('wall_reach2', ctypes.c_void_p),
+        ('capacity', ctypes.c_int32),
+        ('n_bonds_in', ctypes.c_void_p), ('bonds', ctypes.c_void_p), ('bond_aromatic', ctypes.c_void_p),
+        ('status_in', ctypes.c_void_p),
+        ('use_wall', ctypes.c_int32), ('steps', ctypes.c_int32), ('n_min', ctypes.c_int32),
+    ] + [(name, ctypes.c_double) for name in RELAX_CONSTANTS] + [
+        ('x_out', ctypes.c_void_p), ('energy', ctypes.c_void_p), ('steps_done', ctypes.c_void_p), ('f_max', ctypes.c_void_p),
+        ('moved2', ctypes.c_void_p), ('status', ctypes.c_void_p), ('stream', ctypes.c_void_p),
+    ]
+
+
 class DLFeatureMatchArgs(ctypes.Structure):           # likewise
     _fields_ = [
         ('B', ctypes.c_int32), ('Fa', ctypes.c_int32), ('Fb', ctypes.c_int32),
@@ -429,7 +452,7 @@ EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_stri
            'dl_join_workspace_bytes', 'dl_sample_chain_fc_join', 'dl_tanimoto_cluster', 'dl_tanimoto_pick',
            'dl_bonds_workspace_bytes', 'dl_perceive_bonds',
            'dl_pose_checks',
-           'dl_interaction_types', 'dl_interaction_scores', 'dl_add_hydrogens',
+           'dl_interaction_types', 'dl_relax_molecules', 'dl_interaction_scores', 'dl_add_hydrogens',
            'dl_molecule_keys', 'dl_clash_scores', 'dl_shape_scores', 'dl_ring_scores', 'dl_fragment_cuts',
            'dl_pocket_select', 'dl_fragment_multicuts', 'dl_aromatic_rings', 'dl_fingerprints',
            'dl_tanimoto_nearest', 'dl_pharmacophore_features', 'dl_feature_match', 'dl_best_rmsd')
@@ -453,11 +476,13 @@ STRUCT_ENTRY_POINTS = {
 # The selections over fingerprint sets (select.hip), declared and called in the same way: a table of its own, because
 # tests/test_lib_host.py pins the table above name by name.
 SELECT_ENTRY_POINTS = {'dl_tanimoto_cluster': DLClusterArgs, 'dl_tanimoto_pick': DLPickArgs}
+# The relaxation (relax.hip), likewise a table of its own: tests/test_select_host.py pins the one above.
+RELAX_ENTRY_POINTS = {'dl_relax_molecules': DLRelaxArgs}
 
 
 def entry_struct(name):
-    """The args struct of a struct-taking entry point, from whichever of the two tables lists it."""
-    return STRUCT_ENTRY_POINTS[name] if name in STRUCT_ENTRY_POINTS else SELECT_ENTRY_POINTS[name]
+    """The args struct of a struct-taking entry point, from whichever of the three tables lists it."""
+    return {**STRUCT_ENTRY_POINTS, **SELECT_ENTRY_POINTS, **RELAX_ENTRY_POINTS}[name]
 
 
 def _stream_is_field(struct):
@@ -553,7 +578,7 @@ def _open(path):
     lib.dl_inpaint_step.argtypes = [i32, i32, i32] + [vp] * 10 + [DLInpaintCoef, vp, vp]
     lib.dl_philox_fill.restype = i32
     lib.dl_philox_fill.argtypes = [ctypes.c_uint64, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp]
-    for name, struct in {**STRUCT_ENTRY_POINTS, **SELECT_ENTRY_POINTS}.items():
+    for name, struct in {**STRUCT_ENTRY_POINTS, **SELECT_ENTRY_POINTS, **RELAX_ENTRY_POINTS}.items():
         getattr(lib, name).restype = i32
         getattr(lib, name).argtypes = [ctypes.POINTER(struct)] if _stream_is_field(struct) else [ctypes.POINTER(struct), vp]
     lib.dl_edm_loss_grad.restype = i32
@@ -598,7 +623,7 @@ def ptr(t):
 
 
 def launch(name, args, device):
-    """Call the entry point ``name`` of ``STRUCT_ENTRY_POINTS`` or ``SELECT_ENTRY_POINTS`` on ``args`` with ``device`` current and on torch's current
+    """Call the entry point ``name`` of ``STRUCT_ENTRY_POINTS``, ``SELECT_ENTRY_POINTS`` or ``RELAX_ENTRY_POINTS`` on ``args`` with ``device`` current and on torch's current
     stream of that device, handed over as the entry point takes it, and raise ``HipLibraryError`` unless it answers ``DL_OK``.
     Nothing is built, allocated or synchronised here."""
     with torch.cuda.device(device):

@@ -203,6 +203,56 @@ def internal_clash_table(is_geom, scale=0.75):
     return torch.tensor([[v * v for v in row] for row in reach], dtype=torch.float64)
 
 
+# ---- the tables and constants of ``molecule_builder.relax`` (``dl_relax_molecules``): formed here in fp64 as plain Python
+# floats, one rounding per operation.  The force constants are design parameters of this project's own restraint energy, in
+# units of its own (NOT UFF or MMFF parameters); the FIRE constants are those of Bitzek et al., PRL 97, 170201 (2006)
+RELAX_DEFAULTS = dict(k_bond=100.0, k_angle=50.0, k_rep=10.0, k_wall=10.0, k_pos=1.0, dt0=0.03, dt_max=0.1, alpha0=0.1, n_min=5,
+                      f_inc=1.1, f_dec=0.5, f_alpha=0.99, max_step=0.1, f_tol=1e-3)
+RELAX_STEPS = 200
+RELAX_REACH_SCALE = 0.8             # just outside the 0.75 at which ``internal_clash_table`` flags a clash
+IDEAL_COS = (-1.0, -0.5, -1.0 / 3.0)                      # the cosines of ``ANGLE_IDEALS``, exact
+# ring bond lengths in Angstrom: benzene, pyridine, furan, thiophene and pyrazole (Allen et al., J. Chem. Soc., Perkin Trans. 2
+# 1987, S1-S19, the values every textbook table rounds to)
+AROMATIC_LENGTHS = {('C', 'C'): 1.39, ('C', 'N'): 1.34, ('C', 'O'): 1.36, ('C', 'S'): 1.71, ('N', 'N'): 1.35}
+
+
+def length0_table(is_geom):
+    """fp64 ``[n_types][n_types][3]``: the typical length ``BOND_LENGTHS[k][s][t] / 100.0`` of every order in Angstrom; 0 where
+    the reference has none (no bond term)."""
+    n = GEOM_NUMBER_OF_ATOM_TYPES if is_geom else NUMBER_OF_ATOM_TYPES
+    return torch.tensor([[[BOND_LENGTHS[k][a][b] / 100.0 for k in range(3)] for b in range(n)] for a in range(n)],
+                        dtype=torch.float64)
+
+
+def aromatic_length0_table(is_geom):
+    """fp64 ``[n_types][n_types]``: the length of a bond ``dl_aromatic_rings`` flags aromatic: ``AROMATIC_LENGTHS`` where it
+    has the pair, else the mean of the single and the double length, else the single length (0: no term)."""
+    n = GEOM_NUMBER_OF_ATOM_TYPES if is_geom else NUMBER_OF_ATOM_TYPES
+    rows = [[0.0] * n for _ in range(n)]
+    for a in range(n):
+        for b in range(n):
+            pair = (GEOM_IDX2ATOM[a], GEOM_IDX2ATOM[b])
+            single, double = BOND_LENGTHS[0][a][b] / 100.0, BOND_LENGTHS[1][a][b] / 100.0
+            if pair in AROMATIC_LENGTHS or pair[::-1] in AROMATIC_LENGTHS:
+                rows[a][b] = AROMATIC_LENGTHS.get(pair, AROMATIC_LENGTHS.get(pair[::-1]))
+            elif single and double:
+                rows[a][b] = (single + double) / 2.0
+            else:
+                rows[a][b] = single
+    return torch.tensor(rows, dtype=torch.float64)
+
+
+def ideal_cos_table():
+    """fp64 ``[3]``: the ideal cosine of the classes ``ANGLE_CLASSES``: -1, -1/2 and -1/3."""
+    return torch.tensor(IDEAL_COS, dtype=torch.float64)
+
+
+def relax_reach_table(is_geom, scale=RELAX_REACH_SCALE):
+    """fp64 ``[n_types][n_types]`` SQUARED distances in Angstrom^2 inside which two atoms repel in ``relax``:
+    ``(scale * (VDW_RADII[a] + VDW_RADII[b])) ** 2``, formed as ``internal_clash_table`` forms its own."""
+    return internal_clash_table(is_geom, scale)
+
+
 # The atom radii of Trott & Olson's scoring function (AutoDock Vina, J. Comput. Chem. 31, 455 (2010)) in Angstrom by GEOM atom
 # index (C O N F S Cl Br I P), from which ``metrics.analyze_interactions`` forms surface distances, and the published weights
 # of its five intermolecular terms: gauss1, gauss2, repulsion, hydrophobic, hydrogen bond.  The rotor weight is not used

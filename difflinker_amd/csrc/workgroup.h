@@ -106,6 +106,46 @@ __device__ __forceinline__ long long block_sum(long long v, long long* lds /* [W
     return s;
 }
 
+// The fp64 sum whose ORDER is part of a rule (relax.hip): the balanced tree over adjacent elements, T'[i] = T[2i] + T[2i+1].
+// Within a wave that is the xor-butterfly with offsets 1, 2, 4 ... 32, because an fp addition gives the same bits with its
+// operands exchanged; every lane ends with the tree's value.  (The integer sums above go 32 ... 1: their order is free.)
+__device__ __forceinline__ double wave_tree_sum(double v) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) v = v + __shfl_xor(v, off, 64);
+    return v;
+}
+
+// the tree over the workgroup's 256 values by thread: the waves' trees, then (w0 + w1) + (w2 + w3); the same in every thread
+__device__ __forceinline__ double block_tree_sum(double v, double* lds /* [WG_WAVES] */) {
+    v = wave_tree_sum(v);
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const double s = (lds[0] + lds[1]) + (lds[2] + lds[3]);
+    __syncthreads();
+    return s;
+}
+
+// maximum of one double per thread: `o > v ? o : v`, so a NaN never wins against the value a thread holds
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double o = __shfl_xor(v, off, 64);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+__device__ __forceinline__ double block_max(double v, double* lds /* [WG_WAVES] */) {
+    v = wave_max(v);
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double m = lds[0];
+#pragma unroll
+    for (int k = 1; k < WG_WAVES; ++k) m = lds[k] > m ? lds[k] : m;
+    __syncthreads();
+    return m;
+}
+
 // an offset into a set of m rows, as the fingerprint kernels read every offset: clamped to [0, m]
 __device__ __forceinline__ int clamp_offset(int v, int m) { return min(max(v, 0), m); }
 

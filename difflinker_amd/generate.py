@@ -22,7 +22,7 @@ from .datasets import MOADDataset, collate_with_fragment_edges, collate_with_fra
 from .io import get_pocket, get_protein_atoms, parse_molecule, pocket_arrays, read_molecule, read_pocket, save_sdf_file, save_xyz_file
 from .lightning import DDPM
 from .linker_size import SizeClassifier
-from .molecule_builder import add_hydrogens, perceive_all_bonds, refine_bond_orders, summary
+from .molecule_builder import add_hydrogens, perceive_all_bonds, perceive_bonds, refine_bond_orders, relax_samples, summary
 from .utils import FoundNaNException
 
 
@@ -88,7 +88,7 @@ def _check_hydrogens(hydrogens, output_format):
 def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_dir, name, com_key, hide_pocket,
                      output_format='xyz', metrics=False, clashes=False, protein=None, rings=False, bond_orders='distance',
                      aromatic=False, diversity=False, interactions=False, typed_protein=None, hydrogens=False,
-                     pose_checks=False, cluster=None, pick=None, select_view='linker'):
+                     pose_checks=False, cluster=None, pick=None, select_view='linker', relax=None):
     if output_format not in OUTPUT_FORMATS:
         raise ValueError(f'output_format must be one of {OUTPUT_FORMATS}, got {output_format!r}')
     if bond_orders not in BOND_ORDERS:
@@ -98,6 +98,7 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
     n_hydrogens = []
     written, found, scored, clash_records, ring_records, aromatic_records = [], [], [], [], [], []
     prints, contact_records, pose_records, eligible = [], [], [], []
+    relax_records, relaxed_pose_records = [], []
     for batch_i, data in enumerate(_batches(dataset, batch_size, collate_fn)):
         n = len(data['positions'])
         chain = None
@@ -135,26 +136,39 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
             contact_records += mol_metrics.interactions_to_host(mol_metrics.analyze_interactions(
                 h[:, :, :ddpm.num_classes], scored_x, node_mask * (1 - pad(data['fragment_mask'])), node_mask * (1 - pocket_rows),
                 pocket_rows if typed_protein is None else None, protein=typed_protein, is_geom=ddpm.is_geom))
+        shown_x = x                                           # what the files are written with; every score stays on x
+        if relax is not None:                                 # the linker cleaned up, the pocket rows of the batch as the wall
+            pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, x.shape[1] - m.shape[1]))     # noqa: E731
+            linker_rows = node_mask * (1 - pad(data['fragment_mask']))
+            pocket_rows = pad(data['pocket_mask']) if 'pocket_mask' in data else None
+            wall_x = x if pocket_rows is None else torch.where(pocket_rows.bool(), pad(data['positions']), x)
+            relaxed = relax_samples(h[:, :, :ddpm.num_classes], wall_x, node_mask, ddpm.is_geom, linker_rows,
+                                    drop_mask=pocket_rows, steps=relax)
+            shown_x = torch.where(linker_rows.bool(), relaxed.x, x)      # every other row as it was, bit for bit
         if hide_pocket:                                       # generate_with_pocket.py:272
             node_mask = node_mask.clone()
             width = data['pocket_mask'].shape[1]
             node_mask[:, :width][data['pocket_mask'].bool()] = 0
+        if relax is not None:                                 # did the clean-up change the distance table's bond list?
+            types = h[:, :, :ddpm.num_classes]
+            relax_records += mol_metrics.relax_to_host(relaxed, perceive_bonds(types, x, node_mask, ddpm.is_geom),
+                                                       perceive_bonds(types, shown_x, node_mask, ddpm.is_geom))
         if output_format != 'sdf':
-            save_xyz_file(output_dir, h, x, node_mask, names=names, is_geom=ddpm.is_geom, suffix='')
+            save_xyz_file(output_dir, h, shown_x, node_mask, names=names, is_geom=ddpm.is_geom, suffix='')
             written += [os.path.join(output_dir, f'{nm}_.xyz') for nm in names]
         if output_format != 'xyz':                            # on the chain's output, before it leaves the device
-            found.append(perceive_all_bonds(h, x, node_mask, ddpm.is_geom))
+            found.append(perceive_all_bonds(h, shown_x, node_mask, ddpm.is_geom))
             shown = found[-1]
             planar = None
             if bond_orders == 'geometric':                    # Kekule orders for the planar rings, from the same geometry
-                shown, ring_atoms = refine_bond_orders(shown, h[:, :, :ddpm.num_classes], x, node_mask, ddpm.is_geom)
+                shown, ring_atoms = refine_bond_orders(shown, h[:, :, :ddpm.num_classes], shown_x, node_mask, ddpm.is_geom)
                 planar = ring_atoms.atom_aromatic
             more = {}
             if hydrogens:                                     # on the list the file is written with
-                more['hydrogens'] = add_hydrogens(shown, h[:, :, :ddpm.num_classes], x, node_mask, ddpm.is_geom,
+                more['hydrogens'] = add_hydrogens(shown, h[:, :, :ddpm.num_classes], shown_x, node_mask, ddpm.is_geom,
                                                   atom_planar=planar)
                 n_hydrogens.append(more['hydrogens'].n_h)
-            save_sdf_file(output_dir, h, x, node_mask, shown.bonds, shown.n_bonds, names=names,
+            save_sdf_file(output_dir, h, shown_x, node_mask, shown.bonds, shown.n_bonds, names=names,
                           is_geom=ddpm.is_geom, suffix='', **more)
             written += [os.path.join(output_dir, f'{nm}_.sdf') for nm in names]
         if metrics:                                           # the molecules as written: without the pocket
@@ -173,6 +187,10 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
             pose_records += mol_metrics.pose_checks_to_host(mol_metrics.analyze_pose_checks(
                 h[:, :, :ddpm.num_classes], x, node_mask, ddpm.is_geom, node_mask * (1 - pad(data['fragment_mask'])),
                 drop_mask=pad(data['pocket_mask']) if 'pocket_mask' in data else None))
+            if relax is not None:                             # the same checks once more, on what the files hold
+                relaxed_pose_records += mol_metrics.pose_checks_to_host(mol_metrics.analyze_pose_checks(
+                    h[:, :, :ddpm.num_classes], shown_x, node_mask, ddpm.is_geom, node_mask * (1 - pad(data['fragment_mask'])),
+                    drop_mask=pad(data['pocket_mask']) if 'pocket_mask' in data else None))
         if diversity or select:                               # likewise; the bits stay on the device
             pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, x.shape[1] - m.shape[1]))     # noqa: E731
             drop = pad(data['pocket_mask']) if select and 'pocket_mask' in data else None      # as pose_checks passes them
@@ -192,7 +210,7 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
         whole, linker = (mol_metrics.cat_fingerprints([p[k] for p in prints]) for k in range(2))
         selection = mol_metrics.select_records(whole, linker, [0] * whole.bits.shape[0], eligible, view=select_view,
                                                threshold=cluster, k=pick)
-    if metrics or clashes or rings or aromatic or diversity or interactions or pose_checks or select:
+    if metrics or clashes or rings or aromatic or diversity or interactions or pose_checks or select or relax is not None:
         scores = {}
         if metrics:                                           # no true molecule here: no novelty, no recovery
             scores = dict(mol_metrics.compute_metrics(scored), molecules=len(scored))
@@ -206,6 +224,10 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
             scores.update(mol_metrics.compute_aromatic(aromatic_records))
         if pose_checks:                                       # no true molecule here either
             scores.update(mol_metrics.compute_pose_checks(pose_records))
+            if relax is not None:
+                scores.update({f'{k}_relaxed': v for k, v in mol_metrics.compute_pose_checks(relaxed_pose_records).items()})
+        if relax is not None:
+            scores.update(mol_metrics.compute_relaxation(relax_records))
         if diversity:                                         # one input: every sample against every other
             whole, linker = (mol_metrics.cat_fingerprints([p[k] for p in prints]) for k in range(2))
             records = mol_metrics.diversity_records(whole, linker, [0] * whole.bits.shape[0])
@@ -235,6 +257,11 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
                                                 'linker_counts': dict(zip(mol_metrics.POSE_COUNTS, m.linker_counts)),
                                                 'n_flagged_atoms': m.n_flagged_atoms, 'status': m.status}
                        for path in written for m in [by_name[os.path.basename(path).rsplit('_.', 1)[0]]]}, f, indent=1)
+    if relax is not None:                                     # likewise
+        by_name = {f'output_{i}_{name}': m for i, m in enumerate(relax_records)}
+        with open(os.path.join(output_dir, 'relax.json'), 'w') as f:
+            json.dump({os.path.basename(path): mol_metrics.relax_report(by_name[os.path.basename(path).rsplit('_.', 1)[0]])
+                       for path in written}, f, indent=1)
     if select:                                                # likewise, and the two answers a reader came for
         with open(os.path.join(output_dir, 'selection.json'), 'w') as f:
             json.dump(mol_metrics.selection_report(selection, _files_of_samples(written, name, len(selection))), f, indent=1)
@@ -270,7 +297,7 @@ def _files_of_samples(written, name, n):
 
 def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anchors=None, device=None, output_format='xyz',
              metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False, diversity=False,
-             hydrogens=False, pose_checks=False, cluster=None, pick=None, select_view='linker'):
+             hydrogens=False, pose_checks=False, cluster=None, pick=None, select_view='linker', relax=None):
     """``generate.py`` main(): fragments file -> ``n_samples`` molecules with a sampled linker, as ``.xyz`` files
     (``output_format='sdf'``: ``.sdf`` files with perceived bonds instead, ``'both'``: both; one JSON line with the number of
     molecules, the share in one piece and the mean bond count is printed then).  ``metrics=True`` also writes
@@ -300,7 +327,15 @@ def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anc
     on this project's own fingerprint, NOT RDKit's ``Butina.ClusterData`` or ``MaxMinPicker``).  ``selection.json`` gets the
     record of every written file, ``picked`` and ``clusters`` (``metrics.selection_report``), ``metrics.json`` the
     ``metrics.compute_selection`` keys; no file is removed, renamed or rewritten.  The pocket variants take them as well,
-    pocket atoms left out."""
+    pocket atoms left out.
+    ``relax=STEPS`` cleans the linker of every sample up before the files are written (``molecule_builder.relax_samples``:
+    ``STEPS`` steps of a restrained FIRE minimisation in fp64 under a rule of this project's own, NOT UFF, MMFF or RDKit's or
+    OpenBabel's optimiser; the fragments stay bit for bit, the topology is frozen, heavy atoms only, no torsion term): the
+    ``.xyz`` and ``.sdf`` files carry the relaxed linker, and bonds, ``bond_orders='geometric'`` and ``hydrogens`` run on it;
+    ``relax.json`` gets one record per written file and ``metrics.json`` the ``metrics.compute_relaxation`` keys.  EVERY
+    OTHER SCORE STAYS A SCORE OF THE RAW SAMPLE, because the scores measure the model; with ``pose_checks=True`` the pose
+    keys are written a second time, on the relaxed coordinates, under ``<key>_relaxed``.  The pocket variants take it as
+    well: there the wall is the pocket rows of the batch, not the whole protein of ``generate_with_protein``."""
     _check_hydrogens(hydrogens, output_format)
     selection = _selection_arguments(cluster, pick, select_view)
     if clashes:
@@ -327,13 +362,13 @@ def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anc
                             com_key='fragment_mask', hide_pocket=False, output_format=output_format, metrics=metrics,
                             rings=rings, bond_orders=bond_orders, aromatic=aromatic, diversity=diversity,
                             **({'hydrogens': True} if hydrogens else {}), **({'pose_checks': True} if pose_checks else {}),
-                            **selection)
+                            **({'relax': relax} if relax is not None else {}), **selection)
 
 
 def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size, device,
                             output_format, metrics=False, clashes=False, protein=None, rings=False, bond_orders='distance',
                             aromatic=False, interactions=False, typed_protein=None, hydrogens=False, pose_checks=False,
-                            selection=None):
+                            selection=None, relax=None):
     frag_pos, frag_one_hot, frag_charges = frag
     pocket_pos, pocket_one_hot, pocket_charges = pocket
     positions = np.concatenate([frag_pos, pocket_pos], axis=0)
@@ -356,13 +391,14 @@ def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_s
                             hide_pocket=True, output_format=output_format, metrics=metrics, clashes=clashes, protein=protein,
                             rings=rings, bond_orders=bond_orders, aromatic=aromatic, interactions=interactions,
                             typed_protein=typed_protein, **({'hydrogens': True} if hydrogens else {}),
-                            **({'pose_checks': True} if pose_checks else {}), **(selection or {}))
+                            **({'pose_checks': True} if pose_checks else {}), **({'relax': relax} if relax is not None else {}),
+                            **(selection or {}))
 
 
 def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, output_dir, n_samples, n_steps, linker_size,
                          anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz',
                          metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False, interactions=False,
-                         hydrogens=False, pose_checks=False, cluster=None, pick=None, select_view='linker'):
+                         hydrogens=False, pose_checks=False, cluster=None, pick=None, select_view='linker', relax=None):
     """``generate_with_pocket.py`` main(): the pocket is given as its own PDB file.  ``clashes=True`` scores every sample's
     generated atoms against the pocket atoms (``metrics.analyze_clashes``), adds the ``metrics.compute_clashes`` keys to
     ``metrics.json`` and writes ``clashes.json``: ``n_clashes``, ``n_clash_atoms`` and ``min_distance`` per written file.
@@ -372,7 +408,7 @@ def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, ou
     ``interactions.json``: ``score``, the five fixed-point ``terms`` (units of 2^-32), ``n_pairs``, ``n_hbonds``,
     ``n_hydrophobic`` and ``status`` per written file.  ``hydrogens=True`` as in ``generate``: the scores above keep counting
     heavy atoms alone.  ``pose_checks=True`` as in ``generate``, on the ligand without the pocket atoms; ``cluster``, ``pick``
-    and ``select_view`` likewise."""
+    and ``select_view`` likewise; ``relax=STEPS`` as in ``generate``, the pocket atoms as the wall."""
     _check_hydrogens(hydrogens, output_format)
     selection = _selection_arguments(cluster, pick, select_view)
     device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
@@ -396,6 +432,7 @@ def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, ou
                                    device, output_format, metrics, clashes, rings=rings, bond_orders=bond_orders,
                                    aromatic=aromatic, interactions=interactions, **({'hydrogens': True} if hydrogens else {}),
                                    **({'pose_checks': True} if pose_checks else {}),
+                                   **({'relax': relax} if relax is not None else {}),
                                    **({'selection': selection} if selection else {}))
 
 
@@ -403,13 +440,14 @@ def generate_with_protein(input_path, protein_path, backbone_atoms_only, model, 
                           linker_size, anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz',
                           metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False,
                           interactions=False, hydrogens=False, pose_checks=False, cluster=None, pick=None,
-                          select_view='linker'):
+                          select_view='linker', relax=None):
     """``generate_with_protein.py`` main(): the pocket = residues of the protein within 6 A of the fragments.
     ``clashes=True`` as in ``generate_with_pocket``, but against ALL protein atoms whose element is in the vocabulary
     (``io.get_protein_atoms``), residues outside the pocket the model saw included; the pocket rows of the batch are then not
     targets, so no atom counts twice.  ``interactions=True`` likewise scores against the whole protein, which is typed once
     (``metrics.protein_types``), so no residue is cut at a pocket boundary.  ``hydrogens=True``, ``pose_checks=True``,
-    ``cluster``, ``pick`` and ``select_view`` as in ``generate``."""
+    ``cluster``, ``pick`` and ``select_view`` as in ``generate``; ``relax=STEPS`` likewise, with the pocket rows of the batch
+    as the wall, not the whole protein."""
     _check_hydrogens(hydrogens, output_format)
     selection = _selection_arguments(cluster, pick, select_view)
     device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
@@ -437,7 +475,19 @@ def generate_with_protein(input_path, protein_path, backbone_atoms_only, model, 
                                    bond_orders=bond_orders, aromatic=aromatic, interactions=interactions,
                                    typed_protein=typed_protein, **({'hydrogens': True} if hydrogens else {}),
                                    **({'pose_checks': True} if pose_checks else {}),
+                                   **({'relax': relax} if relax is not None else {}),
                                    **({'selection': selection} if selection else {}))
+
+
+def add_relax_argument(p):
+    """``--relax [STEPS]``, shared with ``sample``."""
+    p.add_argument('--relax', type=int, nargs='?', const=const.RELAX_STEPS, default=None, metavar='STEPS',
+                   help='clean the linker of every sample up on the GPU before the files are written: STEPS steps (default '
+                        f'{const.RELAX_STEPS}, at most 1000) of a restrained FIRE minimisation in fp64 of bonds, angles, internal '
+                        'repulsion, the pocket rows as a wall and a restraint to the sampled position, the fragments fixed and '
+                        'the topology frozen (a rule of this project, NOT UFF, MMFF or RDKit\'s or OpenBabel\'s optimiser; heavy '
+                        'atoms only, no torsion term).  Writes relax.json and the relax_* keys of metrics.json; every other '
+                        'score stays a score of the raw sample')
 
 
 def add_selection_arguments(p):
@@ -516,6 +566,7 @@ def main(argv=None):
                         'clashes between atoms four or more bonds apart, always on the geometric bond orders (a rule of this '
                         'project after the idea of PoseBusters\' intramolecular checks, NOT PoseBusters\' numbers) - add '
                         'pose_valid and its parts to metrics.json and write pose_checks.json with one record per written file')
+    add_relax_argument(p)
     add_selection_arguments(p)
     a = p.parse_args(argv)
     if a.clashes and a.pocket is None and a.protein is None:
@@ -534,6 +585,8 @@ def main(argv=None):
         more['hydrogens'] = True
     if a.pose_checks:
         more['pose_checks'] = True
+    if a.relax is not None:
+        more['relax'] = a.relax
     more.update(selection_arguments(a))
     if a.pocket is not None:
         files = generate_with_pocket(a.fragments, a.pocket, a.backbone_atoms_only, a.model, a.output, a.n_samples,

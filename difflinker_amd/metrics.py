@@ -58,6 +58,10 @@ geometric bond orders.  This project's own rule after the idea of PoseBusters' i
 answers there are: Taylor-Butina clusters and MaxMin diverse subsets of the valid samples' fingerprints
 (``dl_tanimoto_cluster`` and ``dl_tanimoto_pick``, ``csrc/select.hip``).  This project's own statement of both rules, on this
 project's fingerprint - NOT RDKit's ``Butina.ClusterData`` or ``MaxMinPicker`` on ties.
+
+``relax_to_host`` / ``compute_relaxation`` report what ``molecule_builder.relax`` (``dl_relax_molecules``, ``csrc/relax.hip``)
+did to every sample: the restraint energy before and after, how far atoms moved, how many runs converged and how often the
+distance table's bond list changed.  This project's own restrained clean-up - NOT UFF, MMFF or any toolkit's optimiser.
 """
 import math
 from collections import namedtuple
@@ -1911,3 +1915,67 @@ def compute_pose_checks(pred, true=None):
     if true is not None:
         out.update(_pose_scores(true, 'true_'))
     return out
+
+
+# ---- relaxation: what ``molecule_builder.relax`` did to every sample ---------------------------------------------------------------
+RelaxRecord = namedtuple('RelaxRecord', 'energy_before energy_after steps_done f_max displacement status bonds_changed converged')
+RELAX_TERMS = ('bonds', 'angles', 'repulsion', 'wall', 'restraint')
+RELAX_NAMES = ('relax_molecules', 'relax_energy_before', 'relax_energy_after', 'relax_displacement_mean',
+               'relax_displacement_max', 'relax_converged', 'relax_bonds_changed')
+
+
+def bonds_changed(raw, relaxed):
+    """Device bool ``[B]``: does the list of ``perceive_bonds`` on the relaxed coordinates differ from the one on the raw
+    coordinates - another count, or another entry among those both lists hold?  ``perceive_bonds`` writes its list in a fixed
+    order, so equal lists are equal graphs with equal orders."""
+    capacity = min(raw.bonds.shape[1], relaxed.bonds.shape[1])
+    held = torch.arange(capacity, device=raw.bonds.device)[None, :] < torch.minimum(raw.n_bonds, relaxed.n_bonds)[:, None]
+    differ = (raw.bonds[:, :capacity] != relaxed.bonds[:, :capacity]).any(dim=2) & held
+    return (raw.n_bonds != relaxed.n_bonds) | differ.any(dim=1)
+
+
+def relax_to_host(result, raw=None, relaxed=None, f_tol=const.RELAX_DEFAULTS['f_tol']):
+    """One ``RelaxRecord`` of plain values per molecule of a ``Relaxed`` (``molecule_builder.relax``): the five energy terms
+    (``RELAX_TERMS``) before and after, the steps done, the last largest force component, the largest displacement of an atom
+    in Angstrom, ``status``, whether the distance-table bond list changed (``raw`` and ``relaxed``: the ``perceive_bonds`` of
+    the two sets of coordinates; ``None`` without them) and whether the run stopped on ``f_tol``."""
+    energy, steps, status = result.energy.cpu().tolist(), result.steps_done.cpu().tolist(), result.status.cpu().tolist()
+    f_max, moved = result.f_max.cpu().tolist(), result.moved2.sqrt().cpu().tolist()
+    changed = bonds_changed(raw, relaxed).cpu().tolist() if raw is not None and relaxed is not None else [None] * len(status)
+    return [RelaxRecord(tuple(energy[b][0]), tuple(energy[b][1]), steps[b], f_max[b], moved[b], status[b], changed[b],
+                        status[b] == 0 and f_max[b] < f_tol) for b in range(len(status))]
+
+
+def relax_report(record):
+    """The JSON record of one ``RelaxRecord``, as the drivers write it to ``relax.json`` per written file."""
+    return {'energy_before': dict(zip(RELAX_TERMS, record.energy_before)), 'energy_after': dict(zip(RELAX_TERMS, record.energy_after)),
+            'steps_done': record.steps_done, 'f_max': record.f_max, 'displacement': record.displacement,
+            'status': record.status, 'bonds_changed': record.bonds_changed, 'converged': record.converged}
+
+
+def compute_relaxation(records):
+    """Scores of the ``RelaxRecord`` values ``records`` (``relax_to_host``), in fp64, over the records with status 0.  The
+    energy is this project's own restraint energy in units of its own, NOT a force field's: the numbers compare runs of this
+    project with each other.
+
+    ``relax_molecules``            records with status 0
+    ``relax_energy_before``        mean of bonds + angles + repulsion + wall at the sampled coordinates (the restraint is not
+                                   a property of the molecule and is left out)
+    ``relax_energy_after``         the same at the relaxed coordinates
+    ``relax_displacement_mean``    mean over the molecules of the largest displacement of an atom, in Angstrom
+    ``relax_displacement_max``     the largest displacement of any atom
+    ``relax_converged``            share that stopped on ``f_tol`` before the steps ran out
+    ``relax_bonds_changed``        share whose distance-table bond list on the relaxed coordinates differs from the raw one:
+                                   the relaxation is a clean-up only while this stays small
+
+    A mean or a share over nothing is ``None``."""
+    good = [m for m in records if m.status == 0]
+    mean = lambda values: float(sum(values) / len(values)) if values else None      # noqa: E731
+    judged = [m.bonds_changed for m in good if m.bonds_changed is not None]
+    return {'relax_molecules': len(good),
+            'relax_energy_before': mean([sum(m.energy_before[:4]) for m in good]),
+            'relax_energy_after': mean([sum(m.energy_after[:4]) for m in good]),
+            'relax_displacement_mean': mean([m.displacement for m in good]),
+            'relax_displacement_max': max([m.displacement for m in good]) if good else None,
+            'relax_converged': mean([bool(m.converged) for m in good]),
+            'relax_bonds_changed': mean([bool(v) for v in judged])}

@@ -20,6 +20,8 @@ Hydrogens = namedtuple('Hydrogens', 'n_h h_count parent x status')
 _TABLES = {}
 _RING_CLASSES = {}
 _HYDROGEN_TABLES = {}
+Relaxed = namedtuple('Relaxed', 'x energy steps_done f_max moved2 status')
+_RELAX_TABLES = {}
 
 
 def _table(device, is_geom, margins):
@@ -221,6 +223,103 @@ def add_hydrogens(found, one_hot, x, node_mask, is_geom, drop_mask=None, atom_pl
         status=out.status.data_ptr())
     _lib.launch('dl_add_hydrogens', args, dev)
     return out
+
+
+def _relax_tables(device, is_geom, reach_scale):
+    key = (device, bool(is_geom), float(reach_scale))
+    if key not in _RELAX_TABLES:
+        _RELAX_TABLES[key] = tuple(t.to(device).contiguous() for t in (
+            const.length0_table(is_geom), const.aromatic_length0_table(is_geom), const.ideal_cos_table(),
+            const.relax_reach_table(is_geom, reach_scale)))
+    return _RELAX_TABLES[key]
+
+
+def relax(found, one_hot, x, node_mask, is_geom, mark_mask, drop_mask=None, atom_planar=None, bond_aromatic=None,
+          use_wall=True, steps=const.RELAX_STEPS, reach_scale=const.RELAX_REACH_SCALE, **constants):
+    """A restrained clean-up of the marked atoms of every molecule (``dl_relax_molecules``, ``csrc/relax.hip``): ONE launch on
+    the result ``found`` of ``perceive_bonds`` or ``refine_bond_orders`` for the same ``one_hot``, ``x`` and ``node_mask``,
+    without a host synchronisation.  Only the atoms of ``mark_mask`` (the linker; ``None``: every kept atom) move; every other
+    row of ``x`` comes back bit for bit.
+
+    THE RULE is this project's own (``include/difflinker_hip.h`` states it in full; ``tests/relax_ref.py`` restates it): it is
+    NOT UFF, NOT MMFF and NOT RDKit's or OpenBabel's optimiser, and its energies are in units of its own.  ``steps`` steps of
+    FIRE (Bitzek et al., PRL 97, 170201) in fp64 down the sum of: harmonic bonds to the typical length of their order
+    (``const.BOND_LENGTHS``; ``const.AROMATIC_LENGTHS`` for the bonds ``bond_aromatic`` flags), harmonic terms in the cosine
+    of the angles to the ideal of the centre's class (the classes of ``metrics.pose_checks``; three-, four- and five-ring
+    angles exempt), a soft repulsion between atoms four or more bonds apart inside ``reach_scale`` times the sum of their
+    van der Waals radii, the same against the WALL - the rows of ``drop_mask``, the pocket, when ``use_wall`` - and a
+    harmonic restraint to the input position.  The topology is frozen at ``found``.  Heavy atoms only; no torsion,
+    planarity or electrostatic term; at most 256 atoms after the pocket is dropped.  ``constants`` override
+    ``const.RELAX_DEFAULTS``.
+
+    ``mark_mask`` and ``drop_mask`` are ``[B,N]`` or ``[B,N,1]`` by row, ``atom_planar`` is ``[B,N]`` by atom number,
+    ``bond_aromatic`` ``[B,capacity]`` by list entry.  Returns a ``Relaxed`` of device tensors: ``x [B,N,3]`` fp32, ``energy
+    [B,2,5]`` fp64 (bonds, angles, repulsion, wall, restraint; before and after), ``steps_done [B]``, ``f_max [B]`` and
+    ``moved2 [B]`` fp64 (the last largest force component; the largest squared displacement) and ``status [B]``: the bits
+    of ``found.status`` plus ``_lib.DL_POSE_*`` (more than 256 kept atoms or a non-finite coordinate: ``x`` comes back) and
+    ``_lib.DL_RELAX_DIVERGED``."""
+    unknown = sorted(set(constants) - set(const.RELAX_DEFAULTS))
+    if unknown:
+        raise TypeError(f'relax: unknown constants {unknown}; known: {sorted(const.RELAX_DEFAULTS)}')
+    steps = int(steps)
+    if not 0 <= steps <= _lib.DL_RELAX_MAX_STEPS:
+        raise ValueError(f'steps must be 0..{_lib.DL_RELAX_MAX_STEPS}, got {steps}')
+    others = tuple(m for m in (node_mask, drop_mask, mark_mask, atom_planar) if m is not None)
+    _lib.require_device('relax', one_hot=one_hot, x=x, node_mask=node_mask, drop_mask=drop_mask, mark_mask=mark_mask,
+                        atom_planar=atom_planar, bond_aromatic=bond_aromatic)
+    B, N, nf = one_hot.shape
+    if x.shape != (B, N, 3) or any(m.numel() != B * N for m in others):
+        raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, x {tuple(x.shape)}, masks '
+                         f'{[tuple(m.shape) for m in others]}')
+    dev = one_hot.device
+    given = normalize_bonds(found, B, dev, 'relax')
+    capacity = given.bonds.shape[1]
+    if bond_aromatic is not None and tuple(bond_aromatic.shape) != (B, capacity):
+        raise ValueError(f'shapes disagree: bond_aromatic {tuple(bond_aromatic.shape)}, bonds {tuple(given.bonds.shape)}')
+    one_hot, x, node_mask, drop_mask, mark_mask = (_lib.dense(t, dev, torch.float32)
+                                                   for t in (one_hot, x, node_mask, drop_mask, mark_mask))
+    if atom_planar is not None:
+        atom_planar = _lib.dense(atom_planar.reshape(B, N) != 0, dev, torch.int32)
+    if bond_aromatic is not None:
+        bond_aromatic = _lib.dense(bond_aromatic != 0, dev, torch.int32)
+    length0, aromatic0, ideal, reach = _relax_tables(dev, is_geom, reach_scale)
+    if reach.shape[0] < nf:
+        raise ValueError(f'one_hot has {nf} types, the vocabulary {reach.shape[0]}')
+    if reach.shape[0] > nf:                                  # the kernel indexes the tables with nf
+        length0, aromatic0, reach = (t[:nf, :nf].contiguous() for t in (length0, aromatic0, reach))
+    values = dict(const.RELAX_DEFAULTS, **constants)
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)      # noqa: E731
+    out = Relaxed(torch.empty((B, N, 3), dtype=torch.float32, device=dev), f64(B, 2, _lib.DL_RELAX_TERMS), _lib.empty_i32(dev, B),
+                  f64(B), f64(B), _lib.empty_i32(dev, B))
+    args = _lib.DLRelaxArgs(
+        B=B, N=N, nf=nf, x=x.data_ptr(), one_hot=one_hot.data_ptr(), node_mask=node_mask.data_ptr(), drop_mask=_lib.ptr(drop_mask),
+        mark_mask=_lib.ptr(mark_mask), atom_planar=_lib.ptr(atom_planar), length0=length0.data_ptr(),
+        aromatic_length0=aromatic0.data_ptr(), ideal_cos=ideal.data_ptr(), reach2=reach.data_ptr(), wall_reach2=reach.data_ptr(),
+        capacity=capacity, n_bonds_in=given.n_bonds.data_ptr(), bonds=given.bonds.data_ptr() if capacity else None,
+        bond_aromatic=_lib.ptr(bond_aromatic) if capacity else None, status_in=_lib.ptr(given.status),
+        use_wall=int(bool(use_wall)), steps=steps, n_min=int(values['n_min']),
+        x_out=out.x.data_ptr(), energy=out.energy.data_ptr(), steps_done=out.steps_done.data_ptr(), f_max=out.f_max.data_ptr(),
+        moved2=out.moved2.data_ptr(), status=out.status.data_ptr(), **{name: float(values[name]) for name in _lib.RELAX_CONSTANTS})
+    _lib.launch('dl_relax_molecules', args, dev)
+    return out
+
+
+def relax_samples(one_hot, x, node_mask, is_geom, linker_mask, drop_mask=None, margins=const.MARGINS_EDM, use_wall=True,
+                  steps=const.RELAX_STEPS, **constants):
+    """``relax`` of the linker atoms of every molecule of a batch, three launches and no host round trip between them:
+    ``perceive_bonds``, ``refine_bond_orders`` and ``dl_relax_molecules``.  ALWAYS on the geometric (Kekule) orders, on
+    ``atom_aromatic`` and on ``bond_aromatic``, whatever orders the files are written with, as ``metrics.analyze_pose_checks``
+    does; the topology is that of the raw sample and stays frozen.  ``linker_mask`` and ``drop_mask`` (the pocket, which is
+    also the wall) are ``[B,N]`` or ``[B,N,1]``.  Returns the ``Relaxed`` of ``relax``, which states the rule."""
+    _lib.require_device('relax_samples', one_hot=one_hot, x=x, node_mask=node_mask, linker_mask=linker_mask)
+    B, N = one_hot.shape[:2]
+    if linker_mask.numel() != B * N:
+        raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, linker_mask {tuple(linker_mask.shape)}')
+    found = perceive_bonds(one_hot, x, node_mask, is_geom, margins)
+    linker = linker_mask.reshape(B, N).to(torch.float32)
+    refined, aromatic = refine_bond_orders(found, one_hot, x, node_mask, is_geom, drop_mask, linker)
+    return relax(refined._replace(status=aromatic.status), one_hot, x, node_mask, is_geom, linker, drop_mask,
+                 aromatic.atom_aromatic, aromatic.bond_aromatic, use_wall, steps, **constants)
 
 
 def build_xae_molecules(one_hot, x, node_mask, is_geom, margins=const.MARGINS_EDM):

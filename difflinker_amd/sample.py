@@ -16,11 +16,11 @@ import torch
 from . import metrics as mol_metrics
 from . import utils
 from .datasets import MOADDataset, collate, collate_with_fragment_edges, get_dataloader
-from .generate import BOND_ORDERS, OUTPUT_FORMATS, _check_selection, add_selection_arguments, selection_arguments
+from .generate import BOND_ORDERS, OUTPUT_FORMATS, _check_selection, add_relax_argument, add_selection_arguments, selection_arguments
 from .io import save_sdf_file, save_xyz_file
 from .lightning import DDPM
 from .linker_size import SizeClassifier
-from .molecule_builder import add_hydrogens, perceive_all_bonds, refine_bond_orders, summary
+from .molecule_builder import add_hydrogens, perceive_all_bonds, perceive_bonds, refine_bond_orders, relax_samples, summary
 
 
 def check_if_generated(_output_dir, _uuids, n_samples):
@@ -58,7 +58,7 @@ def _prepare(checkpoint, prefix, data, n_steps, device):
 def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=None, linker_size_model=None,
            output_format='xyz', metrics=False, geometry=False, clashes=False, shape=False, rings=False,
            bond_orders='distance', aromatic=False, diversity=False, diversity_reference=None, pharmacophore=False,
-           interactions=False, hydrogens=False, pose_checks=False, cluster=None, pick=None, select_view='linker'):
+           interactions=False, hydrogens=False, pose_checks=False, cluster=None, pick=None, select_view='linker', relax=None):
     """``sample.py``.  Returns the output directory.  ``metrics=True`` scores the molecules sampled in this call against
     the data set's own (``metrics.compute_metrics``: valence rule, connectivity, uniqueness, novelty, recovery) and writes
     the result to ``metrics.json`` in the output directory; with ``geometry=True`` as well, the symmetry-aware RMSD of the
@@ -110,7 +110,14 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
     diverse subset of ``K`` of them per input (MaxMin from the most typical sample) and writes ``selection.json``
     (``metrics.selection_report``: every sample's record by ``<uuid>/<i>_.<format>``, ``picked``, ``clusters``).  Both are
     ``metrics.select_records``: this project's own statement of the rules on this project's own fingerprint, NOT RDKit's
-    ``Butina.ClusterData`` or ``MaxMinPicker``.  No file is removed, renamed or rewritten."""
+    ``Butina.ClusterData`` or ``MaxMinPicker``.  No file is removed, renamed or rewritten.
+    ``relax=STEPS`` cleans the linker of every sample up before its files are written (``molecule_builder.relax_samples``:
+    ``STEPS`` steps of a restrained FIRE minimisation in fp64 under a rule of this project's own, NOT UFF, MMFF or RDKit's or
+    OpenBabel's optimiser; fragments fixed bit for bit, topology frozen, heavy atoms only, no torsion term; the pocket rows of
+    a pocket data set are the wall).  The sample files carry the relaxed linker, and bonds, ``bond_orders='geometric'`` and
+    ``hydrogens`` run on it; ``relax.json`` gets one record per written file and ``metrics.json`` the
+    ``metrics.compute_relaxation`` keys.  EVERY OTHER SCORE STAYS A SCORE OF THE RAW SAMPLE; with ``pose_checks=True`` the
+    pose keys of the samples are written a second time, on the relaxed coordinates, under ``<key>_relaxed``."""
     select = _check_selection(cluster, pick, select_view)
     if hydrogens and output_format == 'xyz':
         raise ValueError('hydrogens are written to the .sdf files: pass output_format sdf or both (--output_format); the '
@@ -122,6 +129,7 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
         raise ValueError(f'bond_orders must be one of {BOND_ORDERS}, got {bond_orders!r}')
     pred_aromatic, true_aromatic = [], []
     pred_poses, true_poses = [], []
+    relax_records, relaxed_poses, relax_names = [], [], []
     found, pred, true, input_index = [], [], [], []
     pred_x, true_x, n_linker = [], [], []
     pred_clashes, true_clashes = [], []
@@ -223,11 +231,23 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                     hs[:, :, :model.num_classes], xs, out_mask * (1 - pad(batch['fragment_mask'])),
                     out_mask * (1 - pad(batch['pocket_mask'])), pad(batch['pocket_mask']), is_geom=model.is_geom))
                 true_contacts += true_contact_batch
+            shown_xs = xs                                      # what the files are written with; every score stays on xs
+            if relax is not None:                              # the linker cleaned up, the template's pocket rows as the wall
+                pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, out_mask.shape[1] - m.shape[1]))      # noqa: E731
+                linker_rows = out_mask * (1 - pad(batch['fragment_mask']))
+                relaxed = relax_samples(hs[:, :, :model.num_classes], xs, out_mask, model.is_geom, linker_rows,
+                                        drop_mask=pad(batch['pocket_mask']) if moad else None, steps=relax)
+                shown_xs = torch.where(linker_rows.bool(), relaxed.x, xs)       # every other row as it was, bit for bit
             if moad:
                 pock = batch['pocket_mask']
                 if pock.shape[1] < out_mask.shape[1]:          # template wider than the input (sampled sizes)
                     pock = torch.nn.functional.pad(pock, (0, 0, 0, out_mask.shape[1] - pock.shape[1]))
                 out_mask = out_mask - pock
+            if relax is not None:                              # did the clean-up change the distance table's bond list?
+                types = hs[:, :, :model.num_classes]
+                relax_records += mol_metrics.relax_to_host(relaxed, perceive_bonds(types, xs, out_mask, model.is_geom),
+                                                           perceive_bonds(types, shown_xs, out_mask, model.is_geom))
+                relax_names += [[f'{u}/{i}_.{ext}' for ext in ('xyz', 'sdf') if output_format in (ext, 'both')] for u in uuids]
             if shape:                                          # the sample against the true molecule, where both lie
                 types, true_types = hs[:, :, :model.num_classes], h[:, :, :model.num_classes]
                 pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, out_mask.shape[1] - m.shape[1]))      # noqa: E731
@@ -259,6 +279,10 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                     hs[:, :, :model.num_classes], xs, out_mask, model.is_geom, out_mask * (1 - pad(batch['fragment_mask'])),
                     drop_mask=pad(batch['pocket_mask']) if moad else None))
                 true_poses += true_pose_batch
+                if relax is not None:                          # the same checks once more, on what the files hold
+                    relaxed_poses += mol_metrics.pose_checks_to_host(mol_metrics.analyze_pose_checks(
+                        hs[:, :, :model.num_classes], shown_xs, out_mask, model.is_geom,
+                        out_mask * (1 - pad(batch['fragment_mask'])), drop_mask=pad(batch['pocket_mask']) if moad else None))
             if diversity or select:                            # likewise
                 pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, out_mask.shape[1] - m.shape[1]))      # noqa: E731
                 pred_prints.append(mol_metrics.analyze_fingerprints(
@@ -271,20 +295,20 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 select_input += uuids
                 select_names += [[f'{u}/{i}_.{ext}' for ext in ('xyz', 'sdf') if output_format in (ext, 'both')] for u in uuids]
             if output_format != 'sdf':
-                save_xyz_file(output_dir, hs, xs, out_mask, [f'{u}/{i}' for u in uuids], is_geom=model.is_geom)
+                save_xyz_file(output_dir, hs, shown_xs, out_mask, [f'{u}/{i}' for u in uuids], is_geom=model.is_geom)
             if output_format != 'xyz':
-                found.append(perceive_all_bonds(hs, xs, out_mask, model.is_geom))
+                found.append(perceive_all_bonds(hs, shown_xs, out_mask, model.is_geom))
                 shown = found[-1]
                 planar = None
                 if bond_orders == 'geometric':                 # Kekule orders for the planar rings, from the same geometry
-                    shown, ring_atoms = refine_bond_orders(shown, hs[:, :, :model.num_classes], xs, out_mask, model.is_geom)
+                    shown, ring_atoms = refine_bond_orders(shown, hs[:, :, :model.num_classes], shown_xs, out_mask, model.is_geom)
                     planar = ring_atoms.atom_aromatic
                 more = {}
                 if hydrogens:                                  # on the list the file is written with
-                    more['hydrogens'] = add_hydrogens(shown, hs[:, :, :model.num_classes], xs, out_mask, model.is_geom,
+                    more['hydrogens'] = add_hydrogens(shown, hs[:, :, :model.num_classes], shown_xs, out_mask, model.is_geom,
                                                       atom_planar=planar)
                     n_hydrogens.append(more['hydrogens'].n_h)
-                save_sdf_file(output_dir, hs, xs, out_mask, shown.bonds, shown.n_bonds, [f'{u}/{i}' for u in uuids],
+                save_sdf_file(output_dir, hs, shown_xs, out_mask, shown.bonds, shown.n_bonds, [f'{u}/{i}' for u in uuids],
                               is_geom=model.is_geom, **more)
             if metrics:
                 types = hs[:, :, :model.num_classes]
@@ -305,7 +329,11 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
         if pick is not None:
             with open(os.path.join(output_dir, 'selection.json'), 'w') as f:
                 json.dump(mol_metrics.selection_report(selection, select_names), f, indent=1)
-    if metrics or clashes or shape or rings or aromatic or diversity or pharmacophore or interactions or pose_checks or select:
+    if relax is not None:                                      # one record per written file
+        with open(os.path.join(output_dir, 'relax.json'), 'w') as f:
+            json.dump({path: mol_metrics.relax_report(m) for m, paths in zip(relax_records, relax_names) for path in paths}, f, indent=1)
+    if (metrics or clashes or shape or rings or aromatic or diversity or pharmacophore or interactions or pose_checks or select
+            or relax is not None):
         with open(os.path.join(output_dir, 'metrics.json'), 'w') as f:
             scores = {}
             if metrics:
@@ -326,6 +354,10 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 scores.update(mol_metrics.compute_aromatic(pred_aromatic, true_aromatic))
             if pose_checks:
                 scores.update(mol_metrics.compute_pose_checks(pred_poses, true_poses))
+                if relax is not None:
+                    scores.update({f'{k}_relaxed': v for k, v in mol_metrics.compute_pose_checks(relaxed_poses).items()})
+            if relax is not None:
+                scores.update(mol_metrics.compute_relaxation(relax_records))
             if diversity:
                 reference = None if diversity_reference is None else reference_fingerprints(model, diversity_reference)
                 scores.update(_diversity_scores(pred_prints, true_prints, print_input, reference))
@@ -460,6 +492,7 @@ def main(argv=None):
                         'recommended: the distance table\'s arbitrary orders inside aromatic rings give arbitrary hydrogen '
                         'counts there')
     add_selection_arguments(p)
+    add_relax_argument(p)
     p.add_argument('--pose_checks', action='store_true',
                    help='check the internal geometry of every sample and of its true molecule on the GPU - bond lengths, bond '
                         'angles, clashes between atoms four or more bonds apart, always on the geometric bond orders (a rule of '
@@ -479,7 +512,8 @@ def main(argv=None):
                      **({'pharmacophore': True} if a.pharmacophore else {}),
                      **({'interactions': True} if a.interactions else {}),
                      **({'hydrogens': True} if a.hydrogens else {}),
-                     **({'pose_checks': True} if a.pose_checks else {}), **selection_arguments(a)))
+                     **({'pose_checks': True} if a.pose_checks else {}),
+                     **({'relax': a.relax} if a.relax is not None else {}), **selection_arguments(a)))
 
 
 if __name__ == '__main__':

@@ -94,6 +94,10 @@
  *                                           geometry is plausible) bond lengths against the reference's typical lengths, bond
  *                                           angles against the ideal of the centre's class, and clashes between atoms four or
  *                                           more bonds apart.  The rule stated below is this project's own, NOT PoseBusters'
+ *   dl_relax_molecules                   <- (no reference counterpart: the field cleans a sampled linker up with RDKit's or
+ *                                           OpenBabel's force fields on the host) a restrained FIRE minimisation of the linker
+ *                                           atoms in fp64 with the topology frozen.  The rule stated below is this project's
+ *                                           own, NOT UFF, MMFF or either toolkit's optimiser
  *   dl_size_train_forward / dl_size_train_backward
  *                                        <- SizeClassifier.forward in training mode + loss.backward()
  *                                           (src/linker_size_lightning.py:83-117, :163-167)
@@ -1904,6 +1908,112 @@ typedef struct dl_pose_args {
     void* stream;                   /* hipStream_t; NULL: the default stream */
 } dl_pose_args;
 int32_t dl_pose_checks(const dl_pose_args* args);
+
+/* ---- restrained clean-up of the marked atoms: a FIRE minimisation in fp64 (relax.hip) ----------------------------------
+ * Moves the MOVABLE atoms of every molecule - the linker - down a restraint energy for a fixed number of FIRE steps (Bitzek,
+ * Koskinen, Gaehler, Moseler & Gumbsch, PRL 97, 170201 (2006)) with the topology frozen at the bond list it is given.  One
+ * 256-thread workgroup per molecule, ONE launch per batch, the stream as the last field, as dl_pose_checks.  THE RULE BELOW IS
+ * THIS PROJECT'S OWN.  It is NOT UFF, NOT MMFF and NOT RDKit's or OpenBabel's optimiser, its energies are in units of its own
+ * and compare runs of this project with each other only.  tests/relax_ref.py restates it in numpy and the kernel agrees with
+ * that in every output bit.
+ *
+ * CONVENTIONS: atoms, kept atoms, bonds (first entry of a repeated pair, DL_POSE_BAD_BOND), drop_mask, mark_mask,
+ * atom_planar and status_in exactly as for dl_pose_checks; at most DL_RELAX_MAX_ATOMS kept atoms, N <= 1024.  Kept atoms are
+ * numbered among themselves in row order (the KEPT INDEX); "lower" and "ascending" below mean by kept index.
+ * `bond_aromatic` ([B,capacity], may be NULL: none) flags list entries, as dl_aromatic_rings writes it; the first entry of a
+ * pair gives the pair its flag as it gives it its order.  MOVABLE: kept and marked; with mark_mask NULL every kept atom.
+ * WALL atoms: the rows with node_mask != 0 and drop_mask != 0 in row order (their WALL RANK), when use_wall != 0; none
+ * otherwise.  The type of an atom is the first largest entry of its one_hot row.
+ *
+ * ARITHMETIC.  fp64 on (double) x, contraction off, every + - * / and sqrt rounded on its own in the order written;
+ * v . w = (v_x*w_x + v_y*w_y) + v_z*w_z; no transcendental function.  Products with a vector are by component.
+ *
+ * ENERGY.  Only items that touch a movable atom count, each once.
+ * 1. BONDS.  A kept pair (a, j), a < j, types (s, t): L0 = aromatic_length0[s][t] when flagged, else
+ *    length0[s][t][order-1]; L0 == 0: no term.  w = x_j - x_a, d = sqrt(w . w); d == 0: no term.
+ *    e = k_bond * ((d - L0) * (d - L0)).  Force on a: g * w with g = ((2 * k_bond) * (d - L0)) / d; on j the same with
+ *    w = x_a - x_j.
+ * 2. ANGLES.  Centres, classes and the pairs (j, k), j < k, of a centre a as in dl_pose_checks rule 2, three- and four-rings
+ *    exempt; exempt too when a neighbour of j other than a is bonded to a neighbour of k other than a (a five-ring).
+ *    p = x_j - x_a, q = x_k - x_a; p . p == 0 or q . q == 0: no term.  den = sqrt((p . p) * (q . q)), c = (p . q) / den,
+ *    c0 = ideal_cos[class], e = k_angle * ((c - c0) * (c - c0)).  With mg = (2 * k_angle) * (c0 - c), inv = 1 / den,
+ *    pa = c / (p . p), pb = c / (q . q): F_j = mg * (q * inv - p * pa), F_k = mg * (p * inv - q * pb), F_a = -(F_j + F_k).
+ * 3. INTERNAL REPULSION over the FAR PAIRS of dl_pose_checks rule 3.  For atom u and partner p: w = x_u - x_p, d2 = w . w,
+ *    R2 = reach2[type of the lower][type of the higher]; when d2 < R2 (strict): s = 1 - d2 / R2, e = k_rep * (s * s), force
+ *    on u: g * w with g = ((4 * k_rep) * s) / R2.
+ * 4. WALL.  The same form between every movable atom u and every wall atom, with k_wall and wall_reach2[type of u][type of
+ *    the wall atom].  A wall atom with a NaN or inf coordinate fails the comparison and contributes nothing.
+ * 5. RESTRAINT.  Every movable atom: w = x - x0, e = k_pos * (w . w), force (2 * k_pos) * (x0 - x); x0 is its input position.
+ *
+ * FORCE ON A MOVABLE ATOM u, by component.  acc = +0.0; then, each as acc = acc + term: its bond terms by neighbour ascending;
+ * the angle terms with u as centre in pair order (k ascending, then j ascending); the angle terms with u as an end, by centre
+ * ascending, then by other end ascending.  The far-pair sum and the wall sum are each split into 64 partials: partner p (kept
+ * index, or wall rank) belongs to partial p mod 64, and each partial sums its partners ascending from +0.0.  The 64 partials
+ * are combined by the balanced tree over adjacent elements, T'[i] = T[2i] + T[2i+1].  F = (acc + (far + wall)) + restraint.
+ * The sums over atoms (F . v, F . F, v . v and the energies) are the same tree over 256 slots by kept index, +0.0 in the slots
+ * of atoms that do not contribute.
+ *
+ * ITERATION.  dt = dt0, alpha = alpha0, n_pos = 0, v = 0.  For `steps` steps: (1) the forces; a non-finite component ends the
+ * run with DL_RELAX_DIVERGED.  (2) f = the largest |F| component; f < f_tol ends the run.  (3) P = sum F . v, ff = sum F . F,
+ * vv = sum v . v.  (4) P > 0: n_pos += 1, v = (1 - alpha) * v + ((alpha * sqrt(vv)) / sqrt(ff)) * F, and when n_pos > n_min:
+ * dt = min(dt * f_inc, dt_max), alpha = alpha * f_alpha.  (5) otherwise n_pos = 0, v = 0, dt = dt * f_dec, alpha = alpha0.
+ * (6) v = v + dt * F, s = dt * v.  (7) l = sqrt(s . s); when l > max_step: s = s * (max_step / l).  (8) x = x + s; one more
+ * step is done.  A non-finite x after the last step is DL_RELAX_DIVERGED too.
+ *
+ *   x_out       [B][N][3], written in full: the bits of x, except the movable atoms of a molecule that ran, whose fp64
+ *               positions are rounded to fp32 once.
+ *   energy      [B][2][5]: bonds, angles, repulsion, wall, restraint at the input and at the final positions.  Per term: every
+ *               OWNER's items summed from +0.0 in the force order (a bond is owned by its lower end, neighbours ascending; an
+ *               angle by its centre; a far pair by its lower atom, in 64 partials as above; a wall pair and a restraint by
+ *               the movable atom), then the tree over the 256 slots.
+ *   steps_done  [B]: steps done; f_max [B]: the last f (0 when no step began); moved2 [B]: the largest |x - x0|^2 (fp64).
+ *   status      [B]: the bits of status_in (may be NULL), DL_BONDS_OVERFLOW, DL_POSE_BAD_BOND, and
+ *               DL_POSE_TOO_LARGE / DL_POSE_NONFINITE (values and meaning of dl_pose_checks): x_out = x, every other output
+ *                 is 0, no coordinate (TOO_LARGE: nor the list) is looked at;
+ *               DL_RELAX_DIVERGED: x_out = x; energy[0] and steps_done stand, energy[1], f_max and moved2 are 0.
+ *               A molecule with no movable atom succeeds with steps_done 0.  None disturbs the other molecules.
+ *
+ * Global memory is written with plain stores only; the callee allocates nothing and needs no workspace.  A null `args`, B < 0,
+ * N < 1, N > 1024, nf < 1, capacity < 0, steps < 0 or steps > DL_RELAX_MAX_STEPS return DL_ERR_BAD_ARG; then B == 0 returns
+ * DL_OK without a launch; then a null pointer (other than drop_mask, mark_mask, atom_planar, bond_aromatic, status_in, stream,
+ * and `bonds` when capacity is 0) returns DL_ERR_BAD_ARG, all before any device work.
+ * Limits: heavy atoms only, no hydrogens in the energy; no torsion, planarity or electrostatic term; the wall is the dropped
+ * rows of the batch, not a whole protein; a planar ring that is not flagged aromatic keeps its Kekule lengths; the topology
+ * is frozen during the run; at most 256 kept atoms. */
+#define DL_RELAX_MAX_ATOMS 256      /* kept atoms per molecule */
+#define DL_RELAX_MAX_STEPS 1000
+#define DL_RELAX_DIVERGED 128       /* status bit: a force or a position turned non-finite */
+#define DL_RELAX_TERMS 5            /* values per row of `energy` */
+typedef struct dl_relax_args {
+    int32_t B, N, nf;
+    const float* x;                 /* device f32 [B,N,3], Angstrom */
+    const float* one_hot;           /* device f32 [B,N,nf] */
+    const float* node_mask;         /* device f32 [B,N] */
+    const float* drop_mask;         /* device f32 [B,N] or NULL */
+    const float* mark_mask;         /* device f32 [B,N] or NULL */
+    const int32_t* atom_planar;     /* device int32 [B,N] by atom number, or NULL */
+    const double* length0;          /* device f64 [nf,nf,3]: typical length per order, A; 0: no term */
+    const double* aromatic_length0; /* device f64 [nf,nf]: length of a bond flagged aromatic, A; 0: no term */
+    const double* ideal_cos;        /* device f64 [3]: ideal cosine of LINEAR, TRIGONAL, TETRAHEDRAL */
+    const double* reach2;           /* device f64 [nf,nf]: squared reach of the internal repulsion, A^2 */
+    const double* wall_reach2;      /* device f64 [nf,nf]: squared reach of the wall, [movable][wall], A^2 */
+    int32_t capacity;               /* bonds the list holds per molecule */
+    const int32_t* n_bonds_in;      /* device int32 [B] */
+    const int32_t* bonds;           /* device int32 [B,capacity,3] (may be NULL when capacity is 0) */
+    const int32_t* bond_aromatic;   /* device int32 [B,capacity] or NULL: dl_aromatic_args.bond_aromatic */
+    const int32_t* status_in;       /* device int32 [B] or NULL */
+    int32_t use_wall, steps, n_min;
+    double k_bond, k_angle, k_rep, k_wall, k_pos;
+    double dt0, dt_max, alpha0, f_inc, f_dec, f_alpha, max_step, f_tol;
+    float* x_out;                   /* device f32 [B,N,3] out */
+    double* energy;                 /* device f64 [B,2,5] out */
+    int32_t* steps_done;            /* device int32 [B] out */
+    double* f_max;                  /* device f64 [B] out */
+    double* moved2;                 /* device f64 [B] out */
+    int32_t* status;                /* device int32 [B] out */
+    void* stream;                   /* hipStream_t; NULL: the default stream */
+} dl_relax_args;
+int32_t dl_relax_molecules(const dl_relax_args* args);
 
 const char* dl_error_string(int32_t status);
 int32_t dl_last_hip_error(void);
