@@ -426,6 +426,22 @@ class DLRelaxArgs(ctypes.Structure):                  # the stream is the last F
     ]
 
 
+DL_CANON_MAX_ATOMS, DL_CANON_MAX_BONDS, DL_CANON_MAX_DEPTH, DL_CANON_MAX_LEAVES = 256, 2048, 32, 65536   # dl_canon_args limits
+DL_CANON_TOO_LARGE, DL_CANON_BAD_BOND, DL_CANON_BUDGET = 4, 8, 256     # dl_canon_args.status bits, beside the DL_BONDS_* bits
+
+
+class DLCanonArgs(ctypes.Structure):                  # the stream is the last FIELD, as for dl_relax_molecules
+    _fields_ = [
+        ('B', ctypes.c_int32), ('N', ctypes.c_int32), ('nf', ctypes.c_int32),
+        ('one_hot', ctypes.c_void_p), ('node_mask', ctypes.c_void_p), ('drop_mask', ctypes.c_void_p),
+        ('capacity', ctypes.c_int32),
+        ('n_bonds_in', ctypes.c_void_p), ('bonds', ctypes.c_void_p), ('status_in', ctypes.c_void_p),
+        ('max_leaves', ctypes.c_int32),
+        ('rank', ctypes.c_void_p), ('code', ctypes.c_void_p), ('n_leaves', ctypes.c_void_p), ('status', ctypes.c_void_p),
+        ('stream', ctypes.c_void_p),
+    ]
+
+
 class DLFeatureMatchArgs(ctypes.Structure):           # likewise
     _fields_ = [
         ('B', ctypes.c_int32), ('Fa', ctypes.c_int32), ('Fb', ctypes.c_int32),
@@ -450,7 +466,7 @@ EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_stri
            'dl_egnn_backward_pocket_workspace_bytes', 'dl_egnn_backward_pocket',
            'dl_size_train_num_params', 'dl_size_train_workspace_bytes', 'dl_size_train_forward', 'dl_size_train_backward',
            'dl_join_workspace_bytes', 'dl_sample_chain_fc_join', 'dl_tanimoto_cluster', 'dl_tanimoto_pick',
-           'dl_bonds_workspace_bytes', 'dl_perceive_bonds',
+           'dl_bonds_workspace_bytes', 'dl_canonical_ranks', 'dl_perceive_bonds',
            'dl_pose_checks',
            'dl_interaction_types', 'dl_relax_molecules', 'dl_interaction_scores', 'dl_add_hydrogens',
            'dl_molecule_keys', 'dl_clash_scores', 'dl_shape_scores', 'dl_ring_scores', 'dl_fragment_cuts',
@@ -478,11 +494,14 @@ STRUCT_ENTRY_POINTS = {
 SELECT_ENTRY_POINTS = {'dl_tanimoto_cluster': DLClusterArgs, 'dl_tanimoto_pick': DLPickArgs}
 # The relaxation (relax.hip), likewise a table of its own: tests/test_select_host.py pins the one above.
 RELAX_ENTRY_POINTS = {'dl_relax_molecules': DLRelaxArgs}
+# The canonical labelling (canon.hip), likewise: tests/test_relax_host.py pins the one above.
+CANON_ENTRY_POINTS = {'dl_canonical_ranks': DLCanonArgs}
+ALL_ENTRY_POINTS = {**STRUCT_ENTRY_POINTS, **SELECT_ENTRY_POINTS, **RELAX_ENTRY_POINTS, **CANON_ENTRY_POINTS}
 
 
 def entry_struct(name):
-    """The args struct of a struct-taking entry point, from whichever of the three tables lists it."""
-    return {**STRUCT_ENTRY_POINTS, **SELECT_ENTRY_POINTS, **RELAX_ENTRY_POINTS}[name]
+    """The args struct of a struct-taking entry point, from whichever of the four tables lists it."""
+    return ALL_ENTRY_POINTS[name]
 
 
 def _stream_is_field(struct):
@@ -578,7 +597,7 @@ def _open(path):
     lib.dl_inpaint_step.argtypes = [i32, i32, i32] + [vp] * 10 + [DLInpaintCoef, vp, vp]
     lib.dl_philox_fill.restype = i32
     lib.dl_philox_fill.argtypes = [ctypes.c_uint64, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp]
-    for name, struct in {**STRUCT_ENTRY_POINTS, **SELECT_ENTRY_POINTS, **RELAX_ENTRY_POINTS}.items():
+    for name, struct in ALL_ENTRY_POINTS.items():
         getattr(lib, name).restype = i32
         getattr(lib, name).argtypes = [ctypes.POINTER(struct)] if _stream_is_field(struct) else [ctypes.POINTER(struct), vp]
     lib.dl_edm_loss_grad.restype = i32
@@ -623,7 +642,7 @@ def ptr(t):
 
 
 def launch(name, args, device):
-    """Call the entry point ``name`` of ``STRUCT_ENTRY_POINTS``, ``SELECT_ENTRY_POINTS`` or ``RELAX_ENTRY_POINTS`` on ``args`` with ``device`` current and on torch's current
+    """Call the entry point ``name`` of ``ALL_ENTRY_POINTS`` (the four tables above) on ``args`` with ``device`` current and on torch's current
     stream of that device, handed over as the entry point takes it, and raise ``HipLibraryError`` unless it answers ``DL_OK``.
     Nothing is built, allocated or synchronised here."""
     with torch.cuda.device(device):

@@ -88,7 +88,7 @@ def _check_hydrogens(hydrogens, output_format):
 def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_dir, name, com_key, hide_pocket,
                      output_format='xyz', metrics=False, clashes=False, protein=None, rings=False, bond_orders='distance',
                      aromatic=False, diversity=False, interactions=False, typed_protein=None, hydrogens=False,
-                     pose_checks=False, cluster=None, pick=None, select_view='linker', relax=None):
+                     pose_checks=False, cluster=None, pick=None, select_view='linker', relax=None, smiles=False):
     if output_format not in OUTPUT_FORMATS:
         raise ValueError(f'output_format must be one of {OUTPUT_FORMATS}, got {output_format!r}')
     if bond_orders not in BOND_ORDERS:
@@ -99,6 +99,7 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
     written, found, scored, clash_records, ring_records, aromatic_records = [], [], [], [], [], []
     prints, contact_records, pose_records, eligible = [], [], [], []
     relax_records, relaxed_pose_records = [], []
+    smiles_rows = []
     for batch_i, data in enumerate(_batches(dataset, batch_size, collate_fn)):
         n = len(data['positions'])
         chain = None
@@ -171,6 +172,14 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
             save_sdf_file(output_dir, h, shown_x, node_mask, shown.bonds, shown.n_bonds, names=names,
                           is_geom=ddpm.is_geom, suffix='', **more)
             written += [os.path.join(output_dir, f'{nm}_.sdf') for nm in names]
+        if smiles:                                            # of the bond list the .sdf files carry (or would carry)
+            pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, x.shape[1] - m.shape[1]))     # noqa: E731
+            types = h[:, :, :ddpm.num_classes]
+            listed = perceive_all_bonds(h, shown_x, node_mask, ddpm.is_geom)
+            if bond_orders == 'geometric':
+                listed = refine_bond_orders(listed, types, shown_x, node_mask, ddpm.is_geom)[0]
+            smiles_rows += mol_metrics.smiles_records(types, node_mask, listed, node_mask * (1 - pad(data['fragment_mask'])),
+                                                      drop_mask=pad(data['pocket_mask']) if 'pocket_mask' in data else None)
         if metrics:                                           # the molecules as written: without the pocket
             types = h[:, :, :ddpm.num_classes]
             scored += mol_metrics.to_host(mol_metrics.analyze(types, x, node_mask, ddpm.is_geom), types, node_mask)
@@ -234,6 +243,8 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
             scores.update(mol_metrics.compute_diversity(records, with_true=False, with_reference=False))
         if select:
             scores.update(mol_metrics.compute_selection(selection))
+        if smiles and metrics:
+            scores.update(mol_metrics.compute_smiles(smiles_rows, scored))     # the samples uniqueness counts
         with open(os.path.join(output_dir, 'metrics.json'), 'w') as f:
             json.dump(scores, f, indent=1)
     if clashes:                                               # one record per written file, by its name
@@ -262,6 +273,10 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
         with open(os.path.join(output_dir, 'relax.json'), 'w') as f:
             json.dump({os.path.basename(path): mol_metrics.relax_report(by_name[os.path.basename(path).rsplit('_.', 1)[0]])
                        for path in written}, f, indent=1)
+    if smiles:                                                # likewise: one row per written file
+        by_name = {f'output_{i}_{name}': m for i, m in enumerate(smiles_rows)}
+        mol_metrics.write_smiles_csv(os.path.join(output_dir, 'smiles.csv'), [os.path.basename(path) for path in written],
+                                     [by_name[os.path.basename(path).rsplit('_.', 1)[0]] for path in written])
     if select:                                                # likewise, and the two answers a reader came for
         with open(os.path.join(output_dir, 'selection.json'), 'w') as f:
             json.dump(mol_metrics.selection_report(selection, _files_of_samples(written, name, len(selection))), f, indent=1)
@@ -297,7 +312,7 @@ def _files_of_samples(written, name, n):
 
 def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anchors=None, device=None, output_format='xyz',
              metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False, diversity=False,
-             hydrogens=False, pose_checks=False, cluster=None, pick=None, select_view='linker', relax=None):
+             hydrogens=False, pose_checks=False, cluster=None, pick=None, select_view='linker', relax=None, smiles=False):
     """``generate.py`` main(): fragments file -> ``n_samples`` molecules with a sampled linker, as ``.xyz`` files
     (``output_format='sdf'``: ``.sdf`` files with perceived bonds instead, ``'both'``: both; one JSON line with the number of
     molecules, the share in one piece and the mean bond count is printed then).  ``metrics=True`` also writes
@@ -335,7 +350,14 @@ def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anc
     ``relax.json`` gets one record per written file and ``metrics.json`` the ``metrics.compute_relaxation`` keys.  EVERY
     OTHER SCORE STAYS A SCORE OF THE RAW SAMPLE, because the scores measure the model; with ``pose_checks=True`` the pose
     keys are written a second time, on the relaxed coordinates, under ``<key>_relaxed``.  The pocket variants take it as
-    well: there the wall is the pocket rows of the batch, not the whole protein of ``generate_with_protein``."""
+    well: there the wall is the pocket rows of the batch, not the whole protein of ``generate_with_protein``.
+    ``smiles=True`` writes ``smiles.csv`` with one row per written file: ``file``, ``smiles`` (the whole molecule, pocket atoms
+    left out), ``linker_smiles`` (the linker atoms as a molecule of their own), ``code`` (the canonical 64-bit code, hex) and
+    ``canonical`` (0 when a search budget was hit or the bond list was flagged).  The strings describe the bond list the
+    ``.sdf`` files carry - ``bond_orders='geometric'`` and ``relax`` apply to them - canonical under this project's own rule
+    (``metrics.canonical_ranks``, ``molecule_builder.smiles``), NOT RDKit's canonical SMILES: Kekule orders as perceived, no
+    aromatic lower case, brackets only on over-valent atoms, no charges, no stereo.  With ``metrics=True`` ``metrics.json``
+    gains ``smiles_uniqueness`` and ``smiles_canonical`` (``metrics.compute_smiles``).  The pocket variants take it as well."""
     _check_hydrogens(hydrogens, output_format)
     selection = _selection_arguments(cluster, pick, select_view)
     if clashes:
@@ -362,13 +384,14 @@ def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anc
                             com_key='fragment_mask', hide_pocket=False, output_format=output_format, metrics=metrics,
                             rings=rings, bond_orders=bond_orders, aromatic=aromatic, diversity=diversity,
                             **({'hydrogens': True} if hydrogens else {}), **({'pose_checks': True} if pose_checks else {}),
-                            **({'relax': relax} if relax is not None else {}), **selection)
+                            **({'relax': relax} if relax is not None else {}), **({'smiles': True} if smiles else {}),
+                            **selection)
 
 
 def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size, device,
                             output_format, metrics=False, clashes=False, protein=None, rings=False, bond_orders='distance',
                             aromatic=False, interactions=False, typed_protein=None, hydrogens=False, pose_checks=False,
-                            selection=None, relax=None):
+                            selection=None, relax=None, smiles=False):
     frag_pos, frag_one_hot, frag_charges = frag
     pocket_pos, pocket_one_hot, pocket_charges = pocket
     positions = np.concatenate([frag_pos, pocket_pos], axis=0)
@@ -392,13 +415,14 @@ def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_s
                             rings=rings, bond_orders=bond_orders, aromatic=aromatic, interactions=interactions,
                             typed_protein=typed_protein, **({'hydrogens': True} if hydrogens else {}),
                             **({'pose_checks': True} if pose_checks else {}), **({'relax': relax} if relax is not None else {}),
-                            **(selection or {}))
+                            **({'smiles': True} if smiles else {}), **(selection or {}))
 
 
 def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, output_dir, n_samples, n_steps, linker_size,
                          anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz',
                          metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False, interactions=False,
-                         hydrogens=False, pose_checks=False, cluster=None, pick=None, select_view='linker', relax=None):
+                         hydrogens=False, pose_checks=False, cluster=None, pick=None, select_view='linker', relax=None,
+                         smiles=False):
     """``generate_with_pocket.py`` main(): the pocket is given as its own PDB file.  ``clashes=True`` scores every sample's
     generated atoms against the pocket atoms (``metrics.analyze_clashes``), adds the ``metrics.compute_clashes`` keys to
     ``metrics.json`` and writes ``clashes.json``: ``n_clashes``, ``n_clash_atoms`` and ``min_distance`` per written file.
@@ -408,7 +432,8 @@ def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, ou
     ``interactions.json``: ``score``, the five fixed-point ``terms`` (units of 2^-32), ``n_pairs``, ``n_hbonds``,
     ``n_hydrophobic`` and ``status`` per written file.  ``hydrogens=True`` as in ``generate``: the scores above keep counting
     heavy atoms alone.  ``pose_checks=True`` as in ``generate``, on the ligand without the pocket atoms; ``cluster``, ``pick``
-    and ``select_view`` likewise; ``relax=STEPS`` as in ``generate``, the pocket atoms as the wall."""
+    and ``select_view`` likewise; ``relax=STEPS`` as in ``generate``, the pocket atoms as the wall; ``smiles=True`` as in
+    ``generate``, the pocket atoms left out of the strings."""
     _check_hydrogens(hydrogens, output_format)
     selection = _selection_arguments(cluster, pick, select_view)
     device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
@@ -433,6 +458,7 @@ def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, ou
                                    aromatic=aromatic, interactions=interactions, **({'hydrogens': True} if hydrogens else {}),
                                    **({'pose_checks': True} if pose_checks else {}),
                                    **({'relax': relax} if relax is not None else {}),
+                                   **({'smiles': True} if smiles else {}),
                                    **({'selection': selection} if selection else {}))
 
 
@@ -440,14 +466,14 @@ def generate_with_protein(input_path, protein_path, backbone_atoms_only, model, 
                           linker_size, anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz',
                           metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False,
                           interactions=False, hydrogens=False, pose_checks=False, cluster=None, pick=None,
-                          select_view='linker', relax=None):
+                          select_view='linker', relax=None, smiles=False):
     """``generate_with_protein.py`` main(): the pocket = residues of the protein within 6 A of the fragments.
     ``clashes=True`` as in ``generate_with_pocket``, but against ALL protein atoms whose element is in the vocabulary
     (``io.get_protein_atoms``), residues outside the pocket the model saw included; the pocket rows of the batch are then not
     targets, so no atom counts twice.  ``interactions=True`` likewise scores against the whole protein, which is typed once
     (``metrics.protein_types``), so no residue is cut at a pocket boundary.  ``hydrogens=True``, ``pose_checks=True``,
     ``cluster``, ``pick`` and ``select_view`` as in ``generate``; ``relax=STEPS`` likewise, with the pocket rows of the batch
-    as the wall, not the whole protein."""
+    as the wall, not the whole protein; ``smiles=True`` as in ``generate_with_pocket``."""
     _check_hydrogens(hydrogens, output_format)
     selection = _selection_arguments(cluster, pick, select_view)
     device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
@@ -476,6 +502,7 @@ def generate_with_protein(input_path, protein_path, backbone_atoms_only, model, 
                                    typed_protein=typed_protein, **({'hydrogens': True} if hydrogens else {}),
                                    **({'pose_checks': True} if pose_checks else {}),
                                    **({'relax': relax} if relax is not None else {}),
+                                   **({'smiles': True} if smiles else {}),
                                    **({'selection': selection} if selection else {}))
 
 
@@ -488,6 +515,17 @@ def add_relax_argument(p):
                         'the topology frozen (a rule of this project, NOT UFF, MMFF or RDKit\'s or OpenBabel\'s optimiser; heavy '
                         'atoms only, no torsion term).  Writes relax.json and the relax_* keys of metrics.json; every other '
                         'score stays a score of the raw sample')
+
+
+def add_smiles_argument(p):
+    """``--smiles``, shared with ``sample``."""
+    p.add_argument('--smiles', action='store_true',
+                   help='write smiles.csv with one row per written file: the SMILES of the molecule (pocket atoms left out) and '
+                        'of its linker, the canonical 64-bit code and whether the search stayed within its budgets.  Atoms are '
+                        'ranked on the GPU by an individualisation-refinement search; the strings are canonical under this '
+                        'project\'s own rule, NOT RDKit\'s canonical SMILES (Kekule orders as the .sdf files carry them, no '
+                        'aromatic lower case, no charges, no stereo, at most 256 atoms).  With --metrics adds smiles_uniqueness '
+                        'and smiles_canonical to metrics.json')
 
 
 def add_selection_arguments(p):
@@ -568,6 +606,7 @@ def main(argv=None):
                         'pose_valid and its parts to metrics.json and write pose_checks.json with one record per written file')
     add_relax_argument(p)
     add_selection_arguments(p)
+    add_smiles_argument(p)
     a = p.parse_args(argv)
     if a.clashes and a.pocket is None and a.protein is None:
         raise ValueError('--clashes scores the generated atoms against a protein: pass --pocket or --protein')
@@ -588,6 +627,8 @@ def main(argv=None):
     if a.relax is not None:
         more['relax'] = a.relax
     more.update(selection_arguments(a))
+    if a.smiles:
+        more['smiles'] = True
     if a.pocket is not None:
         files = generate_with_pocket(a.fragments, a.pocket, a.backbone_atoms_only, a.model, a.output, a.n_samples,
                                      a.n_steps, a.linker_size, a.anchors, a.max_batch_size, a.random_seed,

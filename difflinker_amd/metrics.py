@@ -62,6 +62,12 @@ project's fingerprint - NOT RDKit's ``Butina.ClusterData`` or ``MaxMinPicker`` o
 ``relax_to_host`` / ``compute_relaxation`` report what ``molecule_builder.relax`` (``dl_relax_molecules``, ``csrc/relax.hip``)
 did to every sample: the restraint energy before and after, how far atoms moved, how many runs converged and how often the
 distance table's bond list changed.  This project's own restrained clean-up - NOT UFF, MMFF or any toolkit's optimiser.
+
+``canonical_ranks`` / ``smiles_to_host`` / ``compute_smiles`` say WHICH molecule a sample is: canonical atom ranks and a
+canonical 64-bit code by an individualisation-refinement search over the colours of ``molecule_keys`` (``dl_canonical_ranks``,
+``csrc/canon.hip``), and from the ranks one SMILES string per molecule (``molecule_builder.smiles``).  This project's own
+rule - NOT RDKit's canonical ranks or canonical SMILES: Kekule orders as perceived, no aromatic lower case, no hydrogens
+beyond brackets on over-valent atoms, no charges, no stereo, at most 256 atoms.
 """
 import math
 from collections import namedtuple
@@ -72,7 +78,7 @@ import numpy as np
 import torch
 
 from . import _lib, const
-from .molecule_builder import normalize_bonds, perceive_all_bonds, perceive_bonds, refine_bond_orders
+from .molecule_builder import normalize_bonds, perceive_all_bonds, perceive_bonds, refine_bond_orders, smiles
 
 Analysis = namedtuple('Analysis', 'n_atoms n_over n_components n_bonds key colour status bonds')
 Graph = namedtuple('Graph', 'types bonds colours')
@@ -114,6 +120,118 @@ def molecule_keys(one_hot, node_mask, found, is_geom, drop_mask=None):
         n_bonds=out.n_bonds.data_ptr(), key=out.key.data_ptr(), colour=out.colour.data_ptr(), status=out.status.data_ptr())
     _lib.launch('dl_molecule_keys', args, dev)
     return out
+
+
+def canonical_ranks(one_hot, node_mask, found, is_geom, drop_mask=None, max_leaves=256):
+    """``dl_canonical_ranks`` (``csrc/canon.hip``) on the result ``found`` of ``perceive_bonds`` for the same ``one_hot`` and
+    ``node_mask``, with the input handling of ``molecule_keys``; device tensors in, a dict of device tensors out, no host
+    synchronisation.  ``is_geom`` plays no part in the rule (the graph carries type indices); it is taken so that the call
+    reads like ``molecule_keys``.
+
+    ``rank``      int32 ``[B,N]`` by atom number: the canonical ranks, a permutation of ``0..n-1`` over the kept atoms, -1 for
+                  dropped atoms and from the atom count on
+    ``code``      int64 ``[B]``: the 64 bits of the canonical code.  Equal codes: the same graph (elements, bond orders) up to
+                  a 64-bit hash, where equal keys of ``molecule_keys`` are only necessary
+    ``n_leaves``  int32 ``[B]``: leaves of the search that were evaluated
+    ``status``    int32 ``[B]``: the bits of ``found.status`` plus ``_lib.DL_CANON_TOO_LARGE`` (more than 256 kept atoms or 2048
+                  kept bonds: ranks -1, code 0), ``_lib.DL_CANON_BAD_BOND`` and ``_lib.DL_CANON_BUDGET`` (more than
+                  ``max_leaves`` leaves or 32 branching levels: the ranks are a permutation, but not promised canonical)
+
+    The rule is this project's own (``include/difflinker_hip.h``, restated in ``tests/canon_ref.py``), NOT RDKit's ranks."""
+    _lib.require_device('canonical_ranks', one_hot=one_hot, node_mask=node_mask, drop_mask=drop_mask)
+    B, N, nf = one_hot.shape
+    if node_mask.numel() != B * N or (drop_mask is not None and drop_mask.numel() != B * N):
+        raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, node_mask {tuple(node_mask.shape)}')
+    if not 1 <= int(max_leaves) <= _lib.DL_CANON_MAX_LEAVES:
+        raise ValueError(f'max_leaves must be in 1..{_lib.DL_CANON_MAX_LEAVES}, got {max_leaves!r}')
+    dev = one_hot.device
+    one_hot, node_mask, drop_mask = (_lib.dense(t, dev, torch.float32) for t in (one_hot, node_mask, drop_mask))
+    out = {'rank': _lib.empty_i32(dev, B, N), 'code': torch.empty(B, dtype=torch.int64, device=dev),
+           'n_leaves': _lib.empty_i32(dev, B), 'status': _lib.empty_i32(dev, B)}
+    found = normalize_bonds(found, B, dev, 'canonical_ranks')
+    capacity = found.bonds.shape[1]
+    args = _lib.DLCanonArgs(
+        B=B, N=N, nf=nf, one_hot=one_hot.data_ptr(), node_mask=node_mask.data_ptr(), drop_mask=_lib.ptr(drop_mask),
+        capacity=capacity, n_bonds_in=found.n_bonds.data_ptr(), bonds=found.bonds.data_ptr() if capacity else None,
+        status_in=found.status.data_ptr(), max_leaves=int(max_leaves), rank=out['rank'].data_ptr(),
+        code=out['code'].data_ptr(), n_leaves=out['n_leaves'].data_ptr(), status=out['status'].data_ptr())
+    _lib.launch('dl_canonical_ranks', args, dev)
+    return out
+
+
+def smiles_to_host(result, one_hot, node_mask, found, drop_mask=None):
+    """One string per molecule of a ``canonical_ranks`` result, on the host (``molecule_builder.smiles`` on the kept atoms,
+    renumbered from 0, with the bonds of ``found`` between them and the canonical ranks): ``None`` for a molecule without
+    ranks (``DL_CANON_TOO_LARGE``) or with more than 99 ring closures open at once.  Synchronises."""
+    B, N = one_hot.shape[:2]
+    rank = result['rank'].cpu().tolist()
+    too_large = (result['status'].cpu() & _lib.DL_CANON_TOO_LARGE).tolist()
+    n_bonds, bonds = found.n_bonds.cpu().tolist(), found.bonds.cpu()
+    real = node_mask.reshape(B, N).cpu() != 0
+    types = one_hot.detach().cpu().argmax(dim=2)
+    out = []
+    for b in range(B):
+        t = types[b][real[b]].tolist()
+        new = {k: r for k, r in enumerate(rank[b][:len(t)]) if r >= 0}      # atom number -> rank, kept atoms only
+        if too_large[b]:
+            out.append(None)
+            continue
+        index = {k: at for at, k in enumerate(new)}
+        rows = bonds[b, :max(0, min(n_bonds[b], bonds.shape[1]))].tolist()
+        out.append(smiles([t[k] for k in new], [(index[i], index[j], o) for i, j, o in rows if i in index and j in index],
+                          [new[k] for k in new]))
+    return out
+
+
+SmilesRecord = namedtuple('SmilesRecord', 'smiles linker_smiles code canonical')
+SMILES_NAMES = ('smiles_uniqueness', 'smiles_canonical')
+SMILES_COLUMNS = ('file',) + SmilesRecord._fields
+
+
+def smiles_records(one_hot, node_mask, found, linker_mask, drop_mask=None, max_leaves=256):
+    """One ``SmilesRecord`` per molecule of a batch, from TWO launches of ``dl_canonical_ranks`` on the bond list ``found``
+    (the list the ``.sdf`` files carry): ``smiles`` of the molecule without the ``drop_mask`` rows (the pocket), ``linker_smiles``
+    of the ``linker_mask`` rows as a molecule of their own (as ``analyze_rings`` takes them), ``code`` the whole molecule's
+    canonical code as 16 hex digits, and ``canonical``: 1 unless a launch set ``DL_CANON_BUDGET``, a bad-bond or the
+    too-large bit (a string is ``''`` then where there is none).  Synchronises."""
+    B, N = one_hot.shape[:2]
+    linker = linker_mask.reshape(B, N).to(torch.float32)
+    not_linker = (linker == 0).to(torch.float32)
+    whole = canonical_ranks(one_hot, node_mask, found, True, drop_mask, max_leaves)
+    part = canonical_ranks(one_hot, node_mask, found, True, not_linker, max_leaves)
+    strings = smiles_to_host(whole, one_hot, node_mask, found, drop_mask)
+    linker_strings = smiles_to_host(part, one_hot, node_mask, found, not_linker)
+    flagged = ((whole['status'] | part['status']) &
+               (_lib.DL_CANON_BUDGET | _lib.DL_CANON_BAD_BOND | _lib.DL_CANON_TOO_LARGE)).cpu().tolist()
+    codes = whole['code'].cpu().tolist()
+    return [SmilesRecord(strings[b] or '', linker_strings[b] or '', format(codes[b] & 0xFFFFFFFFFFFFFFFF, '016x'),
+                         0 if flagged[b] or strings[b] is None or linker_strings[b] is None else 1) for b in range(B)]
+
+
+def write_smiles_csv(path, files, records):
+    """``smiles.csv``: one row per written file (``files``: its name as the other reports give it, with the record of its
+    molecule), columns ``SMILES_COLUMNS``."""
+    import csv
+    with open(path, 'w', newline='') as f:
+        out = csv.writer(f)
+        out.writerow(SMILES_COLUMNS)
+        for name, record in zip(files, records):
+            out.writerow((name,) + tuple(record))
+
+
+def compute_smiles(rows, pred, true=None):
+    """The two scores of the strings: ``rows`` are the ``SmilesRecord`` values of the samples (``smiles_records``), ``pred`` and
+    ``true`` the ``Molecule`` records ``compute_metrics`` takes for the same samples.
+
+    ``smiles_uniqueness``  distinct strings among the samples ``uniqueness`` counts classes of (valid, in one piece, clean
+                           status, and with ``true`` a true molecule that is so as well) / their number: all inputs at once,
+                           as ``uniqueness`` is.  The two agree unless a 64-bit code collided or a budget was hit.  0 without
+                           such a sample
+    ``smiles_canonical``   share of rows with ``canonical`` set; 0 without rows"""
+    chosen = [k for k in range(len(rows)) if _good(pred[k]) and (true is None or _good(true[k]))]
+    distinct = {rows[k].smiles for k in chosen}
+    return {'smiles_uniqueness': len(distinct) / len(chosen) if chosen else 0.0,
+            'smiles_canonical': sum(1 for r in rows if r.canonical) / len(rows) if rows else 0.0}
 
 
 def analyze(one_hot, x, node_mask, is_geom, drop_mask=None, margins=const.MARGINS_EDM):

@@ -355,3 +355,90 @@ def summary(found):
     n = int(n_bonds.numel())
     return {'molecules': n, 'connected': float(one_piece.float().mean()) if n else 0.0,
             'mean_bonds': float(n_bonds.mean()) if n else 0.0}
+
+
+_BOND_SYMBOL = {1: '', 2: '=', 3: '#'}
+
+
+def smiles(types, bonds, rank):
+    """One SMILES string for one molecule, on the host: ``types`` per atom (element indices of the vocabulary, or element
+    symbols), ``bonds`` rows ``(i, j, order)`` with orders 1..3, ``rank`` a permutation of ``0..n-1`` per atom - the
+    canonical ranks of ``metrics.canonical_ranks``, which make the string canonical under THIS project's rule.  It is NOT
+    RDKit's canonical SMILES.
+
+    Pieces are joined by ``.`` in the order of their smallest rank, and each starts at its atom of smallest rank.  The walk
+    is depth first, neighbours in ascending rank; every child subtree but the last goes in parentheses, the bond symbol
+    (none, ``=``, ``#``) in front of the child.  A bond to an atom already visited that is not the parent is a ring
+    closure: at an atom its closures are listed in ascending rank of the partner; the end written first opens with the
+    lowest free number (1..9, then ``%10``..``%99``) behind the bond symbol, the other end closes with the bare number.  A
+    number is free again from the atom AFTER the one that closed it on, so no atom closes and opens the same number.  More
+    than 99 numbers open at once: ``None``.  An atom is written bare when the sum of its bond orders is at most
+    ``const.DEFAULT_VALENCE`` of its element and as ``[El]`` otherwise, so a reader's implicit hydrogens are those
+    ``add_hydrogens`` places: none on an over-valent atom.  Orders are written as the list has them (Kekule forms, no
+    aromatic lower case); no charges, no stereo.  Nothing recurses: a chain of any length is walked with explicit stacks."""
+    n = len(types)
+    symbol = [t if isinstance(t, str) else const.GEOM_IDX2ATOM[int(t)] for t in types]
+    adj = [dict() for _ in range(n)]
+    for i, j, order in bonds:
+        adj[i][j] = order
+        adj[j][i] = order
+    near = [sorted(adj[u], key=lambda w: rank[w]) for u in range(n)]
+    atom = [s if sum(adj[u].values()) <= const.DEFAULT_VALENCE[s] else f'[{s}]' for u, s in enumerate(symbol)]
+    # first pass: the spanning forest of the walk, the order in which atoms are written, and the closures
+    when, parent, children, closures, roots = [-1] * n, [-1] * n, [[] for _ in range(n)], [[] for _ in range(n)], []
+    for root in sorted(range(n), key=lambda u: rank[u]):
+        if when[root] >= 0:
+            continue
+        roots.append(root)
+        when[root] = sum(1 for w in when if w >= 0)
+        clock = when[root]
+        stack = [(root, 0)]
+        while stack:
+            u, at = stack.pop()
+            if at == len(near[u]):
+                continue
+            stack.append((u, at + 1))
+            w = near[u][at]
+            if when[w] < 0:
+                clock += 1
+                when[w], parent[w] = clock, u
+                children[u].append(w)
+                stack.append((w, 0))
+            elif w != parent[u] and parent[w] != u and u not in closures[w]:
+                closures[u].append(w)
+                closures[w].append(u)
+    # second pass: the text
+    free, number, parts = list(range(1, 100)), {}, []
+    for root in roots:
+        out, todo = [], [('atom', root, '')]
+        while todo:
+            kind, u, bond = todo.pop()
+            if kind == 'text':
+                out.append(bond)
+                continue
+            out.append(bond + atom[u])
+            closed = []
+            for w in sorted(closures[u], key=lambda v: rank[v]):
+                pair = (min(u, w), max(u, w))
+                if pair in number:
+                    k = number.pop(pair)
+                    closed.append(k)
+                    out.append(str(k) if k < 10 else f'%{k}')
+                else:
+                    if not free:
+                        return None
+                    k = free.pop(0)
+                    number[pair] = k
+                    out.append(_BOND_SYMBOL[adj[u][w]] + (str(k) if k < 10 else f'%{k}'))
+            free = sorted(free + closed)
+            kids = children[u]
+            for at in range(len(kids) - 1, -1, -1):
+                w = kids[at]
+                if at < len(kids) - 1:
+                    todo.append(('text', -1, ')'))
+                    todo.append(('atom', w, _BOND_SYMBOL[adj[u][w]]))
+                    todo.append(('text', -1, '('))
+                else:
+                    todo.append(('atom', w, _BOND_SYMBOL[adj[u][w]]))
+        parts.append(''.join(out))
+    return '.'.join(parts)

@@ -16,7 +16,8 @@ import torch
 from . import metrics as mol_metrics
 from . import utils
 from .datasets import MOADDataset, collate, collate_with_fragment_edges, get_dataloader
-from .generate import BOND_ORDERS, OUTPUT_FORMATS, _check_selection, add_relax_argument, add_selection_arguments, selection_arguments
+from .generate import (BOND_ORDERS, OUTPUT_FORMATS, _check_selection, add_relax_argument, add_selection_arguments,
+                       add_smiles_argument, selection_arguments)
 from .io import save_sdf_file, save_xyz_file
 from .lightning import DDPM
 from .linker_size import SizeClassifier
@@ -58,7 +59,8 @@ def _prepare(checkpoint, prefix, data, n_steps, device):
 def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=None, linker_size_model=None,
            output_format='xyz', metrics=False, geometry=False, clashes=False, shape=False, rings=False,
            bond_orders='distance', aromatic=False, diversity=False, diversity_reference=None, pharmacophore=False,
-           interactions=False, hydrogens=False, pose_checks=False, cluster=None, pick=None, select_view='linker', relax=None):
+           interactions=False, hydrogens=False, pose_checks=False, cluster=None, pick=None, select_view='linker', relax=None,
+           smiles=False):
     """``sample.py``.  Returns the output directory.  ``metrics=True`` scores the molecules sampled in this call against
     the data set's own (``metrics.compute_metrics``: valence rule, connectivity, uniqueness, novelty, recovery) and writes
     the result to ``metrics.json`` in the output directory; with ``geometry=True`` as well, the symmetry-aware RMSD of the
@@ -117,7 +119,14 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
     a pocket data set are the wall).  The sample files carry the relaxed linker, and bonds, ``bond_orders='geometric'`` and
     ``hydrogens`` run on it; ``relax.json`` gets one record per written file and ``metrics.json`` the
     ``metrics.compute_relaxation`` keys.  EVERY OTHER SCORE STAYS A SCORE OF THE RAW SAMPLE; with ``pose_checks=True`` the
-    pose keys of the samples are written a second time, on the relaxed coordinates, under ``<key>_relaxed``."""
+    pose keys of the samples are written a second time, on the relaxed coordinates, under ``<key>_relaxed``.
+    ``smiles=True`` writes ``smiles.csv`` to the output directory with one row per written sample file
+    (``<uuid>/<i>_.<format>``): ``smiles`` of the sample without its pocket rows, ``linker_smiles`` of its linker as a molecule
+    of its own, ``code`` (the canonical 64-bit code, hex) and ``canonical`` (0 when a search budget was hit or the bond list
+    was flagged).  The strings describe the bond list the ``.sdf`` files carry (``bond_orders='geometric'`` and ``relax``
+    apply), canonical under this project's own rule (``metrics.canonical_ranks``, ``molecule_builder.smiles``), NOT RDKit's
+    canonical SMILES.  With ``metrics=True`` ``metrics.json`` gains ``smiles_uniqueness`` and ``smiles_canonical``
+    (``metrics.compute_smiles``)."""
     select = _check_selection(cluster, pick, select_view)
     if hydrogens and output_format == 'xyz':
         raise ValueError('hydrogens are written to the .sdf files: pass output_format sdf or both (--output_format); the '
@@ -139,6 +148,7 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
     pred_rings, true_rings = [], []
     pred_prints, true_prints, print_input = [], [], []
     eligible, select_input, select_names = [], [], []
+    smiles_rows, smiles_names = [], []
     diversity = diversity or diversity_reference is not None
     geometry = geometry and metrics
     exp = 'model' if isinstance(checkpoint, DDPM) else checkpoint.split('/')[-1].replace('.ckpt', '')
@@ -310,6 +320,14 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                     n_hydrogens.append(more['hydrogens'].n_h)
                 save_sdf_file(output_dir, hs, shown_xs, out_mask, shown.bonds, shown.n_bonds, [f'{u}/{i}' for u in uuids],
                               is_geom=model.is_geom, **more)
+            if smiles:                                         # of the bond list the .sdf files carry (or would carry)
+                pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, out_mask.shape[1] - m.shape[1]))      # noqa: E731
+                types = hs[:, :, :model.num_classes]
+                listed = perceive_all_bonds(hs, shown_xs, out_mask, model.is_geom)
+                if bond_orders == 'geometric':
+                    listed = refine_bond_orders(listed, types, shown_xs, out_mask, model.is_geom)[0]
+                smiles_rows += mol_metrics.smiles_records(types, out_mask, listed, out_mask * (1 - pad(batch['fragment_mask'])))
+                smiles_names += [[f'{u}/{i}_.{ext}' for ext in ('xyz', 'sdf') if output_format in (ext, 'both')] for u in uuids]
             if metrics:
                 types = hs[:, :, :model.num_classes]
                 pred += mol_metrics.to_host(mol_metrics.analyze(types, xs, out_mask, model.is_geom), types, out_mask)
@@ -329,6 +347,9 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
         if pick is not None:
             with open(os.path.join(output_dir, 'selection.json'), 'w') as f:
                 json.dump(mol_metrics.selection_report(selection, select_names), f, indent=1)
+    if smiles:                                                 # one row per written file
+        mol_metrics.write_smiles_csv(os.path.join(output_dir, 'smiles.csv'), [path for paths in smiles_names for path in paths],
+                                     [m for m, paths in zip(smiles_rows, smiles_names) for _ in paths])
     if relax is not None:                                      # one record per written file
         with open(os.path.join(output_dir, 'relax.json'), 'w') as f:
             json.dump({path: mol_metrics.relax_report(m) for m, paths in zip(relax_records, relax_names) for path in paths}, f, indent=1)
@@ -363,6 +384,8 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 scores.update(_diversity_scores(pred_prints, true_prints, print_input, reference))
             if select:
                 scores.update(mol_metrics.compute_selection(selection))
+            if smiles and metrics:                             # over the samples uniqueness counts
+                scores.update(mol_metrics.compute_smiles(smiles_rows, pred, true))
             json.dump(scores, f, indent=1)
     return output_dir
 
@@ -493,6 +516,7 @@ def main(argv=None):
                         'counts there')
     add_selection_arguments(p)
     add_relax_argument(p)
+    add_smiles_argument(p)
     p.add_argument('--pose_checks', action='store_true',
                    help='check the internal geometry of every sample and of its true molecule on the GPU - bond lengths, bond '
                         'angles, clashes between atoms four or more bonds apart, always on the geometric bond orders (a rule of '
@@ -513,7 +537,8 @@ def main(argv=None):
                      **({'interactions': True} if a.interactions else {}),
                      **({'hydrogens': True} if a.hydrogens else {}),
                      **({'pose_checks': True} if a.pose_checks else {}),
-                     **({'relax': a.relax} if a.relax is not None else {}), **selection_arguments(a)))
+                     **({'relax': a.relax} if a.relax is not None else {}), **({'smiles': True} if a.smiles else {}),
+                     **selection_arguments(a)))
 
 
 if __name__ == '__main__':

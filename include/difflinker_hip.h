@@ -98,6 +98,11 @@
  *                                           OpenBabel's force fields on the host) a restrained FIRE minimisation of the linker
  *                                           atoms in fp64 with the topology frozen.  The rule stated below is this project's
  *                                           own, NOT UFF, MMFF or either toolkit's optimiser
+ *   dl_canonical_ranks                   <- the identity the reference gets from Chem.MolToSmiles (src/metrics.py:12-54, the
+ *                                           strings behind its uniqueness, novelty and recovery): canonical atom ranks and
+ *                                           a canonical 64-bit code by an individualisation-refinement search over the
+ *                                           colours of dl_molecule_keys.  The rule stated below is this project's own, NOT
+ *                                           RDKit's canonical ranks or SMILES
  *   dl_size_train_forward / dl_size_train_backward
  *                                        <- SizeClassifier.forward in training mode + loss.backward()
  *                                           (src/linker_size_lightning.py:83-117, :163-167)
@@ -2014,6 +2019,92 @@ typedef struct dl_relax_args {
     void* stream;                   /* hipStream_t; NULL: the default stream */
 } dl_relax_args;
 int32_t dl_relax_molecules(const dl_relax_args* args);
+
+/* ---- canonical atom ranks and a canonical code of a perceived batch (canon.hip) -------------------------------------
+ * A canonical labelling of the bond graph dl_perceive_bonds left on the device, by an individualisation-refinement search
+ * over the colour refinement of dl_molecule_keys: one 256-thread workgroup per molecule, ONE launch per batch, everything per
+ * molecule in LDS, the stream as the last field, as dl_relax_molecules.  The key of dl_molecule_keys is 1-WL and cannot tell cubane from cuneane; the code below is the hash of a
+ * labelled form, so two molecules with equal codes are the same graph up to a 64-bit collision, and the ranks are the atom
+ * order molecule_builder.smiles writes a string from.  THE RULE BELOW IS THIS PROJECT'S OWN: NOT RDKit's canonical ranks, and
+ * the strings are NOT RDKit's canonical SMILES.  tests/canon_ref.py restates it in plain Python and numpy and the kernel agrees with
+ * that in every output bit.
+ *
+ * THE GRAPH is the one dl_molecule_keys reads: atom k is the k-th row with node_mask != 0; `drop_mask` (may be NULL) removes
+ * atoms AFTER that numbering together with every bond that touches them; the kept atoms are numbered among themselves in row
+ * order (the KEPT INDEX; "lowest" and "ascending" below mean by kept index).  The type of an atom is the first largest entry of
+ * its one_hot row.  An entry (i, j, order) of the list is a bond when 0 <= i, j < atoms, i != j and 1 <= order <= 3, in either
+ * orientation; any other entry is skipped and sets DL_CANON_BAD_BOND.  A pair that is listed more than once also sets
+ * DL_CANON_BAD_BOND, and every one of its entries counts as a bond of its own wherever the rule sums over "the kept bonds" or
+ * counts an atom's bonds (as in dl_molecule_keys).  n is the number of kept atoms.  mix64, mix2 and the two seeds are those of
+ * dl_molecule_keys above (SEED_COLOUR = 0x243F6A8885A308D3, SEED_KEY = 0x13198A2E03707344); all arithmetic is modulo 2^64.
+ *
+ *   refine(c)   exactly n rounds of c'[i] = mix2(c[i], sum over the kept bonds (i, j, o) of mix2(c[j], o)).  The count
+ *               depends on n alone; there is no settle test.
+ *   ranks       rank[i] = the number of kept atoms whose colour is strictly smaller than c[i]: tied atoms share a rank.
+ *   root        c[i] = mix2(SEED_COLOUR, type_i + 1); refine; rank.
+ *   leaf        a node whose ranks are all distinct.
+ *   branching   any other node takes the CELL of tied atoms with the smallest rank.  For each member v of the cell, in
+ *               ascending order, the child is c[i] = mix2(SEED_COLOUR, 2 * rank[i] + (i == v ? 0 : 1)); refine; rank; the
+ *               children are searched depth first.
+ *   twins       when every member of the cell has exactly one kept bond, all to the same atom with the same order (the F of
+ *               a CF3, the methyls of a tert-butyl, the O of an SO2), only the lowest member is taken: any two members are
+ *               exchanged by an automorphism, so the other branches could only reproduce the same form.  A twin step is no
+ *               branching level.
+ *   depth       a path that already has DL_CANON_MAX_DEPTH (32) branching levels above it does not branch at a cell that
+ *               is no twin cell: it takes the lowest member only, and sets DL_CANON_BUDGET.
+ *   (guard)     every step down a path splits a cell, so a path has fewer than n steps.  Should two different 64-bit colours
+ *               ever collide and merge cells again, a path ends after n steps as if it were a leaf and sets DL_CANON_BUDGET;
+ *               the ranks are then no permutation.  No such input is known.
+ *   leaf code   mix2(mix2(SEED_KEY, A), Bsum);  A = sum over the kept atoms of mix2(rank[i], type_i + 1);  Bsum = sum over
+ *               the kept bonds of mix2(mix2(min(rank_i, rank_j), max(rank_i, rank_j)), order).
+ *   best        the leaf with the smallest code, compared as unsigned integers, wins; on equal codes the earlier leaf stays.
+ *   leaves      the search stops when `max_leaves` leaves have been evaluated and another one would be: that sets
+ *               DL_CANON_BUDGET.  A search that ends by itself after exactly max_leaves leaves does not set it.
+ *
+ *   rank        [B,N] by atom number as `colour` of dl_molecule_keys: the best leaf's ranks, a permutation of 0..n-1 over
+ *               the kept atoms; -1 for a dropped atom and from the atom count on.
+ *   code        [B] the best leaf's code; n = 0 gives mix2(mix2(SEED_KEY, 0), 0), one leaf and no ranks.
+ *   n_leaves    [B] leaves evaluated (at least 1).
+ *   status      the bits of `status_in`, plus DL_BONDS_OVERFLOW when n_bonds_in > capacity (a negative n_bonds_in counts as
+ *               0), DL_CANON_BAD_BOND, DL_CANON_BUDGET (ranks are still a valid permutation, merely not promised to be
+ *               canonical), and DL_CANON_TOO_LARGE for more than DL_CANON_MAX_ATOMS kept atoms or more than
+ *               DL_CANON_MAX_BONDS kept list entries: rank is then all -1, code 0 and n_leaves 0 (with too many
+ *               atoms the list is not looked at and DL_CANON_BAD_BOND is not added; with too many entries it is added for
+ *               an entry that is no bond, and repeated pairs are not looked for).
+ *
+ * Integer work only, commutative sums: the same bits on every run and under every order and orientation of the list.  Global
+ * memory is written with plain stores only, every output element is written, the callee allocates nothing and needs no
+ * workspace.  The work is bounded by max_leaves * (n + DL_CANON_MAX_DEPTH) refinements of n rounds each; molecule-like
+ * graphs need a handful of leaves (profiles/canon/README.md).  A null `args`, B < 0, N < 1, N > 1024, nf < 1, nf > 256,
+ * capacity < 0, max_leaves < 1 or max_leaves > DL_CANON_MAX_LEAVES return DL_ERR_BAD_ARG; then B == 0 returns DL_OK without
+ * a launch; then a null pointer (other than drop_mask, stream, and `bonds` when capacity is 0) returns DL_ERR_BAD_ARG, all before any
+ * device work.
+ * Not here: stereo, charges, aromatic perception (orders are taken as the list has them, so two Kekule forms of one ring are
+ * two graphs), hydrogens. */
+#define DL_CANON_MAX_ATOMS 256      /* kept atoms per molecule */
+#define DL_CANON_MAX_BONDS 2048     /* kept list entries per molecule */
+#define DL_CANON_MAX_DEPTH 32       /* branching levels of a path */
+#define DL_CANON_MAX_LEAVES 65536   /* largest max_leaves */
+#define DL_CANON_TOO_LARGE 4        /* status bit, same value as DL_KEYS_TOO_LARGE */
+#define DL_CANON_BAD_BOND 8         /* status bit, same value as DL_KEYS_BAD_BOND */
+#define DL_CANON_BUDGET 256         /* status bit: the leaf or the depth budget ended or narrowed the search */
+typedef struct dl_canon_args {
+    int32_t B, N, nf;
+    const float* one_hot;           /* device f32 [B,N,nf] */
+    const float* node_mask;         /* device f32 [B,N] */
+    const float* drop_mask;         /* device f32 [B,N] or NULL */
+    int32_t capacity;               /* bonds the list holds per molecule */
+    const int32_t* n_bonds_in;      /* device int32 [B]: dl_bonds_args.n_bonds */
+    const int32_t* bonds;           /* device int32 [B,capacity,3]: dl_bonds_args.bonds (may be NULL when capacity is 0) */
+    const int32_t* status_in;       /* device int32 [B]: dl_bonds_args.status */
+    int32_t max_leaves;             /* 1..DL_CANON_MAX_LEAVES; the Python layer's default is 256 */
+    int32_t* rank;                  /* device int32 [B,N] out */
+    uint64_t* code;                 /* device 64-bit [B] out */
+    int32_t* n_leaves;              /* device int32 [B] out */
+    int32_t* status;                /* device int32 [B] out */
+    void* stream;                   /* hipStream_t; NULL: the default stream */
+} dl_canon_args;
+int32_t dl_canonical_ranks(const dl_canon_args* args);
 
 const char* dl_error_string(int32_t status);
 int32_t dl_last_hip_error(void);
