@@ -338,6 +338,7 @@ __global__ __launch_bounds__(WG) void relax_kernel(dl_relax_args a) {
     const double two_k_bond = 2.0 * a.k_bond, two_k_angle = 2.0 * a.k_angle, two_k_pos = 2.0 * a.k_pos;
     const double four_k_rep = 4.0 * a.k_rep, four_k_wall = 4.0 * a.k_wall;
     const double infinity = __longlong_as_double(0x7ff0000000000000ll);
+    const double overflowed = __longlong_as_double(0x7fefffffffffffffll);   // stands for an |F| of +inf in s_red: no sqrt of a finite sum reaches it
     V3 vel = {0.0, 0.0, 0.0};
     double dt = a.dt0, alpha = a.alpha0, f_last = 0.0;
     int n_pos = 0, done = 0;
@@ -429,12 +430,11 @@ __global__ __launch_bounds__(WG) void relax_kernel(dl_relax_args a) {
         if (mov_u) {
             const V3 xu = dpoint(s_x, u);
             F = add(add(acc, dpoint(s_nb, u)), times(two_k_pos, sub(x0, xu)));
-            const double fx = fabs(F.x), fy = fabs(F.y), fz = fabs(F.z);
-            top = fx > fy ? fx : fy;
-            top = fz > top ? fz : top;
+            top = sqrt(dot(F, F));                  // the atom's |F|: the same in every frame, which a largest component is not
+            if (top == infinity) top = overflowed;  // finite components whose squares overflow: f is +inf, no divergence
             if (nonfinite(F.x) || nonfinite(F.y) || nonfinite(F.z)) top = infinity;
         }
-        // F.v, F.F, v.v by the tree and the largest component, in one pass over s_red
+        // F.v, F.F, v.v by the tree and the largest |F|, in one pass over s_red
         const double w_p = wave_tree_sum(dot(F, vel)), w_ff = wave_tree_sum(dot(F, F)), w_vv = wave_tree_sum(dot(vel, vel));
         const double w_top = wave_max(top);
         if (lane == 0) {
@@ -454,7 +454,7 @@ __global__ __launch_bounds__(WG) void relax_kernel(dl_relax_args a) {
             diverged = true;
             break;
         }
-        f_last = f_now;
+        f_last = f_now == overflowed ? infinity : f_now;
         if (f_now < a.f_tol) break;
         if (P > 0.0) {
             ++n_pos;

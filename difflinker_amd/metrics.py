@@ -2054,7 +2054,7 @@ def bonds_changed(raw, relaxed):
 
 def relax_to_host(result, raw=None, relaxed=None, f_tol=const.RELAX_DEFAULTS['f_tol']):
     """One ``RelaxRecord`` of plain values per molecule of a ``Relaxed`` (``molecule_builder.relax``): the five energy terms
-    (``RELAX_TERMS``) before and after, the steps done, the last largest force component, the largest displacement of an atom
+    (``RELAX_TERMS``) before and after, the steps done, the last largest force on an atom (its length), the largest displacement of an atom
     in Angstrom, ``status``, whether the distance-table bond list changed (``raw`` and ``relaxed``: the ``perceive_bonds`` of
     the two sets of coordinates; ``None`` without them) and whether the run stopped on ``f_tol``."""
     energy, steps, status = result.energy.cpu().tolist(), result.steps_done.cpu().tolist(), result.status.cpu().tolist()

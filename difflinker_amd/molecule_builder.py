@@ -255,7 +255,7 @@ def relax(found, one_hot, x, node_mask, is_geom, mark_mask, drop_mask=None, atom
     ``mark_mask`` and ``drop_mask`` are ``[B,N]`` or ``[B,N,1]`` by row, ``atom_planar`` is ``[B,N]`` by atom number,
     ``bond_aromatic`` ``[B,capacity]`` by list entry.  Returns a ``Relaxed`` of device tensors: ``x [B,N,3]`` fp32, ``energy
     [B,2,5]`` fp64 (bonds, angles, repulsion, wall, restraint; before and after), ``steps_done [B]``, ``f_max [B]`` and
-    ``moved2 [B]`` fp64 (the last largest force component; the largest squared displacement) and ``status [B]``: the bits
+    ``moved2 [B]`` fp64 (the last largest |F| of an atom; the largest squared displacement) and ``status [B]``: the bits
     of ``found.status`` plus ``_lib.DL_POSE_*`` (more than 256 kept atoms or a non-finite coordinate: ``x`` comes back) and
     ``_lib.DL_RELAX_DIVERGED``."""
     unknown = sorted(set(constants) - set(const.RELAX_DEFAULTS))

@@ -1959,7 +1959,9 @@ int32_t dl_pose_checks(const dl_pose_args* args);
  * of atoms that do not contribute.
  *
  * ITERATION.  dt = dt0, alpha = alpha0, n_pos = 0, v = 0.  For `steps` steps: (1) the forces; a non-finite component ends the
- * run with DL_RELAX_DIVERGED.  (2) f = the largest |F| component; f < f_tol ends the run.  (3) P = sum F . v, ff = sum F . F,
+ * run with DL_RELAX_DIVERGED.  (2) f = the largest |F| = sqrt(F . F) of a movable atom (a length: the
+ * same in every frame, which a largest component is not; an F . F that overflows makes f +inf, no divergence); f < f_tol ends
+ * the run.  (3) P = sum F . v, ff = sum F . F,
  * vv = sum v . v.  (4) P > 0: n_pos += 1, v = (1 - alpha) * v + ((alpha * sqrt(vv)) / sqrt(ff)) * F, and when n_pos > n_min:
  * dt = min(dt * f_inc, dt_max), alpha = alpha * f_alpha.  (5) otherwise n_pos = 0, v = 0, dt = dt * f_dec, alpha = alpha0.
  * (6) v = v + dt * F, s = dt * v.  (7) l = sqrt(s . s); when l > max_step: s = s * (max_step / l).  (8) x = x + s; one more

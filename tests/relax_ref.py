@@ -296,7 +296,7 @@ class Molecule:
                 if not np.isfinite(F[M]).all():
                     diverged = True
                     break
-                f_max = float(np.abs(F[M]).max()) if len(M) else 0.0
+                f_max = float(np.sqrt(dot(F[M], F[M])).max()) if len(M) else 0.0
                 if f_max < c['f_tol']:
                     break
                 P, ff, vv = self.total(dot(F, v)), self.total(dot(F, F)), self.total(dot(v, v))
