@@ -442,6 +442,29 @@ class DLCanonArgs(ctypes.Structure):                  # the stream is the last F
     ]
 
 
+DL_SUB_MAX_ATOMS, DL_SUB_MAX_BONDS = 256, 2048         # dl_substructure_args: kept atoms and kept list entries per molecule
+DL_SUB_MAX_PATTERN_ATOMS, DL_SUB_MAX_SUBPATTERNS, DL_SUB_MAX_LEVELS, DL_SUB_MAX_PRED = 48, 256, 4, 32      # the limits of a catalogue
+DL_SUB_TOO_LARGE, DL_SUB_BAD_BOND, DL_SUB_BUDGET = 4, 8, 512       # dl_substructure_args.status bits, beside the DL_BONDS_* bits
+
+
+class DLSubstructureArgs(ctypes.Structure):           # the stream is the last FIELD, as for dl_canonical_ranks
+    _fields_ = [
+        ('B', ctypes.c_int32), ('N', ctypes.c_int32), ('nf', ctypes.c_int32),
+        ('one_hot', ctypes.c_void_p), ('node_mask', ctypes.c_void_p), ('drop_mask', ctypes.c_void_p),
+        ('mark_mask', ctypes.c_void_p), ('atomic_number', ctypes.c_void_p), ('default_valence', ctypes.c_void_p),
+        ('capacity', ctypes.c_int32),
+        ('n_bonds_in', ctypes.c_void_p), ('bonds', ctypes.c_void_p), ('bond_aromatic', ctypes.c_void_p),
+        ('status_in', ctypes.c_void_p),
+        ('n_sub', ctypes.c_int32), ('n_top', ctypes.c_int32), ('n_levels', ctypes.c_int32),
+        ('level_end', ctypes.c_int32 * DL_SUB_MAX_LEVELS),
+        ('pat', ctypes.c_void_p), ('atoms', ctypes.c_void_p), ('closures', ctypes.c_void_p), ('preds', ctypes.c_void_p),
+        ('n_atoms_table', ctypes.c_int32), ('n_closures', ctypes.c_int32), ('n_preds', ctypes.c_int32),
+        ('max_steps', ctypes.c_int32),
+        ('first_root', ctypes.c_void_p), ('first_root_marked', ctypes.c_void_p), ('n_hits', ctypes.c_void_p),
+        ('n_hits_marked', ctypes.c_void_p), ('status', ctypes.c_void_p), ('stream', ctypes.c_void_p),
+    ]
+
+
 class DLFeatureMatchArgs(ctypes.Structure):           # likewise
     _fields_ = [
         ('B', ctypes.c_int32), ('Fa', ctypes.c_int32), ('Fb', ctypes.c_int32),
@@ -465,6 +488,7 @@ EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_stri
            'dl_egnn_backward_fc_workspace_bytes', 'dl_egnn_backward_max_atoms', 'dl_egnn_backward_fc',
            'dl_egnn_backward_pocket_workspace_bytes', 'dl_egnn_backward_pocket',
            'dl_size_train_num_params', 'dl_size_train_workspace_bytes', 'dl_size_train_forward', 'dl_size_train_backward',
+           'dl_substructure_match',
            'dl_join_workspace_bytes', 'dl_sample_chain_fc_join', 'dl_tanimoto_cluster', 'dl_tanimoto_pick',
            'dl_bonds_workspace_bytes', 'dl_canonical_ranks', 'dl_perceive_bonds',
            'dl_pose_checks',
@@ -496,11 +520,14 @@ SELECT_ENTRY_POINTS = {'dl_tanimoto_cluster': DLClusterArgs, 'dl_tanimoto_pick':
 RELAX_ENTRY_POINTS = {'dl_relax_molecules': DLRelaxArgs}
 # The canonical labelling (canon.hip), likewise: tests/test_relax_host.py pins the one above.
 CANON_ENTRY_POINTS = {'dl_canonical_ranks': DLCanonArgs}
-ALL_ENTRY_POINTS = {**STRUCT_ENTRY_POINTS, **SELECT_ENTRY_POINTS, **RELAX_ENTRY_POINTS, **CANON_ENTRY_POINTS}
+# The substructure search (substructure.hip), likewise: tests/test_canon_host.py pins the one above.
+SUBSTRUCTURE_ENTRY_POINTS = {'dl_substructure_match': DLSubstructureArgs}
+ALL_ENTRY_POINTS = {**STRUCT_ENTRY_POINTS, **SELECT_ENTRY_POINTS, **RELAX_ENTRY_POINTS, **CANON_ENTRY_POINTS,
+                    **SUBSTRUCTURE_ENTRY_POINTS}
 
 
 def entry_struct(name):
-    """The args struct of a struct-taking entry point, from whichever of the four tables lists it."""
+    """The args struct of a struct-taking entry point, from whichever of the tables lists it."""
     return ALL_ENTRY_POINTS[name]
 
 
@@ -642,7 +669,7 @@ def ptr(t):
 
 
 def launch(name, args, device):
-    """Call the entry point ``name`` of ``ALL_ENTRY_POINTS`` (the four tables above) on ``args`` with ``device`` current and on torch's current
+    """Call the entry point ``name`` of ``ALL_ENTRY_POINTS`` (the tables above) on ``args`` with ``device`` current and on torch's current
     stream of that device, handed over as the entry point takes it, and raise ``HipLibraryError`` unless it answers ``DL_OK``.
     Nothing is built, allocated or synchronised here."""
     with torch.cuda.device(device):

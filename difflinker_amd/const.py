@@ -134,6 +134,12 @@ def default_valence_table(is_geom):
     return torch.tensor([DEFAULT_VALENCE[idx2atom[k]] for k in range(len(idx2atom))], dtype=torch.int32)
 
 
+def atomic_number_table(is_geom):
+    """int32 ``[n_types]``: the atomic number of every element of the vocabulary, in index order (``CHARGES``)."""
+    idx2atom, numbers = (GEOM_IDX2ATOM, GEOM_CHARGES) if is_geom else (IDX2ATOM, CHARGES)
+    return torch.tensor([numbers[idx2atom[k]] for k in range(len(idx2atom))], dtype=torch.int32)
+
+
 # X-H bond lengths in Angstrom at which ``molecule_builder.add_hydrogens`` places a hydrogen on an atom of every element
 # (the usual textbook single-bond lengths to hydrogen; the rule itself is stated in ``include/difflinker_hip.h``)
 XH_LENGTH = {'C': 1.09, 'N': 1.01, 'O': 0.96, 'F': 0.92, 'S': 1.34, 'Cl': 1.27, 'Br': 1.41, 'I': 1.61, 'P': 1.42}

@@ -88,7 +88,8 @@ def _check_hydrogens(hydrogens, output_format):
 def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_dir, name, com_key, hide_pocket,
                      output_format='xyz', metrics=False, clashes=False, protein=None, rings=False, bond_orders='distance',
                      aromatic=False, diversity=False, interactions=False, typed_protein=None, hydrogens=False,
-                     pose_checks=False, cluster=None, pick=None, select_view='linker', relax=None, smiles=False):
+                     pose_checks=False, cluster=None, pick=None, select_view='linker', relax=None, smiles=False,
+                     filters=None):
     if output_format not in OUTPUT_FORMATS:
         raise ValueError(f'output_format must be one of {OUTPUT_FORMATS}, got {output_format!r}')
     if bond_orders not in BOND_ORDERS:
@@ -100,6 +101,7 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
     prints, contact_records, pose_records, eligible = [], [], [], []
     relax_records, relaxed_pose_records = [], []
     smiles_rows = []
+    catalogue, filter_records = (mol_metrics.load_filters(filters) if filters is not None else None), []
     for batch_i, data in enumerate(_batches(dataset, batch_size, collate_fn)):
         n = len(data['positions'])
         chain = None
@@ -180,6 +182,11 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
                 listed = refine_bond_orders(listed, types, shown_x, node_mask, ddpm.is_geom)[0]
             smiles_rows += mol_metrics.smiles_records(types, node_mask, listed, node_mask * (1 - pad(data['fragment_mask'])),
                                                       drop_mask=pad(data['pocket_mask']) if 'pocket_mask' in data else None)
+        if filters is not None:                               # on the raw sample and the geometric orders, whatever the files hold
+            pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, x.shape[1] - m.shape[1]))     # noqa: E731
+            filter_records += mol_metrics.patterns_to_host(mol_metrics.analyze_patterns(
+                h[:, :, :ddpm.num_classes], x, node_mask, ddpm.is_geom, node_mask * (1 - pad(data['fragment_mask'])), catalogue,
+                drop_mask=pad(data['pocket_mask']) if 'pocket_mask' in data else None), catalogue.names)
         if metrics:                                           # the molecules as written: without the pocket
             types = h[:, :, :ddpm.num_classes]
             scored += mol_metrics.to_host(mol_metrics.analyze(types, x, node_mask, ddpm.is_geom), types, node_mask)
@@ -245,6 +252,8 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
             scores.update(mol_metrics.compute_selection(selection))
         if smiles and metrics:
             scores.update(mol_metrics.compute_smiles(smiles_rows, scored))     # the samples uniqueness counts
+        if filters is not None and metrics:
+            scores.update(mol_metrics.compute_filters(filter_records))
         with open(os.path.join(output_dir, 'metrics.json'), 'w') as f:
             json.dump(scores, f, indent=1)
     if clashes:                                               # one record per written file, by its name
@@ -277,6 +286,10 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
         by_name = {f'output_{i}_{name}': m for i, m in enumerate(smiles_rows)}
         mol_metrics.write_smiles_csv(os.path.join(output_dir, 'smiles.csv'), [os.path.basename(path) for path in written],
                                      [by_name[os.path.basename(path).rsplit('_.', 1)[0]] for path in written])
+    if filters is not None:                                   # likewise: one record per written file
+        by_name = {f'output_{i}_{name}': m for i, m in enumerate(filter_records)}
+        mol_metrics.write_filters_json(os.path.join(output_dir, 'filters.json'), [os.path.basename(path) for path in written],
+                                       [by_name[os.path.basename(path).rsplit('_.', 1)[0]] for path in written])
     if select:                                                # likewise, and the two answers a reader came for
         with open(os.path.join(output_dir, 'selection.json'), 'w') as f:
             json.dump(mol_metrics.selection_report(selection, _files_of_samples(written, name, len(selection))), f, indent=1)
@@ -312,7 +325,8 @@ def _files_of_samples(written, name, n):
 
 def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anchors=None, device=None, output_format='xyz',
              metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False, diversity=False,
-             hydrogens=False, pose_checks=False, cluster=None, pick=None, select_view='linker', relax=None, smiles=False):
+             hydrogens=False, pose_checks=False, cluster=None, pick=None, select_view='linker', relax=None, smiles=False,
+             filters=None):
     """``generate.py`` main(): fragments file -> ``n_samples`` molecules with a sampled linker, as ``.xyz`` files
     (``output_format='sdf'``: ``.sdf`` files with perceived bonds instead, ``'both'``: both; one JSON line with the number of
     molecules, the share in one piece and the mean bond count is printed then).  ``metrics=True`` also writes
@@ -357,7 +371,16 @@ def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anc
     ``.sdf`` files carry - ``bond_orders='geometric'`` and ``relax`` apply to them - canonical under this project's own rule
     (``metrics.canonical_ranks``, ``molecule_builder.smiles``), NOT RDKit's canonical SMILES: Kekule orders as perceived, no
     aromatic lower case, brackets only on over-valent atoms, no charges, no stereo.  With ``metrics=True`` ``metrics.json``
-    gains ``smiles_uniqueness`` and ``smiles_canonical`` (``metrics.compute_smiles``).  The pocket variants take it as well."""
+    gains ``smiles_uniqueness`` and ``smiles_canonical`` (``metrics.compute_smiles``).  The pocket variants take it as well.
+
+    ``filters='basic'`` or ``filters=FILE`` matches a catalogue of structural alerts against every sample
+    (``metrics.analyze_patterns``: ``'basic'`` is this project's own short list, ``data/filters_basic.csv``; a file is CSV
+    with a SMARTS and an optional name per row, the form of the reference's PAINS list) and writes ``filters.json`` with one
+    record per written file: ``file``, ``hits``, ``linker_hits`` (the alerts matched through a linker atom) and ``status``.
+    Always on the geometric bond orders and on the raw sample, whatever ``bond_orders`` and ``relax`` say.  With
+    ``metrics=True`` ``metrics.json`` gains ``filters_passed``, ``filters_passed_linker``, ``filter_hits_per_molecule`` and
+    ``filters_budget`` (``metrics.compute_filters``).  A SMARTS subset and a matcher of this project's own, NOT RDKit's.  The
+    pocket variants take it as well."""
     _check_hydrogens(hydrogens, output_format)
     selection = _selection_arguments(cluster, pick, select_view)
     if clashes:
@@ -385,13 +408,14 @@ def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anc
                             rings=rings, bond_orders=bond_orders, aromatic=aromatic, diversity=diversity,
                             **({'hydrogens': True} if hydrogens else {}), **({'pose_checks': True} if pose_checks else {}),
                             **({'relax': relax} if relax is not None else {}), **({'smiles': True} if smiles else {}),
+                            **({'filters': filters} if filters is not None else {}),
                             **selection)
 
 
 def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size, device,
                             output_format, metrics=False, clashes=False, protein=None, rings=False, bond_orders='distance',
                             aromatic=False, interactions=False, typed_protein=None, hydrogens=False, pose_checks=False,
-                            selection=None, relax=None, smiles=False):
+                            selection=None, relax=None, smiles=False, filters=None):
     frag_pos, frag_one_hot, frag_charges = frag
     pocket_pos, pocket_one_hot, pocket_charges = pocket
     positions = np.concatenate([frag_pos, pocket_pos], axis=0)
@@ -415,14 +439,15 @@ def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_s
                             rings=rings, bond_orders=bond_orders, aromatic=aromatic, interactions=interactions,
                             typed_protein=typed_protein, **({'hydrogens': True} if hydrogens else {}),
                             **({'pose_checks': True} if pose_checks else {}), **({'relax': relax} if relax is not None else {}),
-                            **({'smiles': True} if smiles else {}), **(selection or {}))
+                            **({'smiles': True} if smiles else {}), **({'filters': filters} if filters is not None else {}),
+                            **(selection or {}))
 
 
 def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, output_dir, n_samples, n_steps, linker_size,
                          anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz',
                          metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False, interactions=False,
                          hydrogens=False, pose_checks=False, cluster=None, pick=None, select_view='linker', relax=None,
-                         smiles=False):
+                         smiles=False, filters=None):
     """``generate_with_pocket.py`` main(): the pocket is given as its own PDB file.  ``clashes=True`` scores every sample's
     generated atoms against the pocket atoms (``metrics.analyze_clashes``), adds the ``metrics.compute_clashes`` keys to
     ``metrics.json`` and writes ``clashes.json``: ``n_clashes``, ``n_clash_atoms`` and ``min_distance`` per written file.
@@ -459,6 +484,7 @@ def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, ou
                                    **({'pose_checks': True} if pose_checks else {}),
                                    **({'relax': relax} if relax is not None else {}),
                                    **({'smiles': True} if smiles else {}),
+                                   **({'filters': filters} if filters is not None else {}),
                                    **({'selection': selection} if selection else {}))
 
 
@@ -466,7 +492,7 @@ def generate_with_protein(input_path, protein_path, backbone_atoms_only, model, 
                           linker_size, anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz',
                           metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False,
                           interactions=False, hydrogens=False, pose_checks=False, cluster=None, pick=None,
-                          select_view='linker', relax=None, smiles=False):
+                          select_view='linker', relax=None, smiles=False, filters=None):
     """``generate_with_protein.py`` main(): the pocket = residues of the protein within 6 A of the fragments.
     ``clashes=True`` as in ``generate_with_pocket``, but against ALL protein atoms whose element is in the vocabulary
     (``io.get_protein_atoms``), residues outside the pocket the model saw included; the pocket rows of the batch are then not
@@ -503,6 +529,7 @@ def generate_with_protein(input_path, protein_path, backbone_atoms_only, model, 
                                    **({'pose_checks': True} if pose_checks else {}),
                                    **({'relax': relax} if relax is not None else {}),
                                    **({'smiles': True} if smiles else {}),
+                                   **({'filters': filters} if filters is not None else {}),
                                    **({'selection': selection} if selection else {}))
 
 
@@ -515,6 +542,18 @@ def add_relax_argument(p):
                         'the topology frozen (a rule of this project, NOT UFF, MMFF or RDKit\'s or OpenBabel\'s optimiser; heavy '
                         'atoms only, no torsion term).  Writes relax.json and the relax_* keys of metrics.json; every other '
                         'score stays a score of the raw sample')
+
+
+def add_filters_argument(p):
+    """``--filters``, shared with ``sample``."""
+    p.add_argument('--filters', default=None, metavar='FILE|basic',
+                   help='match structural alerts against every sample on the GPU and write filters.json with one record per '
+                        'written file (the alerts hit, those hit through a linker atom, the status): "basic" is this '
+                        'project\'s own short catalogue, FILE a CSV with a SMARTS and an optional name per row (the form of a '
+                        'PAINS list).  A SMARTS subset and a matching rule of this project\'s own (NOT RDKit\'s matcher: no '
+                        'charges, no stereo, no explicit hydrogens, no SSSR counts), always on the geometric bond orders.  With '
+                        '--metrics adds filters_passed, filters_passed_linker, filter_hits_per_molecule and filters_budget to '
+                        'metrics.json')
 
 
 def add_smiles_argument(p):
@@ -607,6 +646,7 @@ def main(argv=None):
     add_relax_argument(p)
     add_selection_arguments(p)
     add_smiles_argument(p)
+    add_filters_argument(p)
     a = p.parse_args(argv)
     if a.clashes and a.pocket is None and a.protein is None:
         raise ValueError('--clashes scores the generated atoms against a protein: pass --pocket or --protein')
@@ -629,6 +669,8 @@ def main(argv=None):
     more.update(selection_arguments(a))
     if a.smiles:
         more['smiles'] = True
+    if a.filters is not None:
+        more['filters'] = a.filters
     if a.pocket is not None:
         files = generate_with_pocket(a.fragments, a.pocket, a.backbone_atoms_only, a.model, a.output, a.n_samples,
                                      a.n_steps, a.linker_size, a.anchors, a.max_batch_size, a.random_seed,

@@ -68,7 +68,14 @@ canonical 64-bit code by an individualisation-refinement search over the colours
 ``csrc/canon.hip``), and from the ranks one SMILES string per molecule (``molecule_builder.smiles``).  This project's own
 rule - NOT RDKit's canonical ranks or canonical SMILES: Kekule orders as perceived, no aromatic lower case, no hydrogens
 beyond brackets on over-valent atoms, no charges, no stereo, at most 256 atoms.
+
+``match_patterns`` / ``analyze_patterns`` / ``compute_filters`` ask whether a sample contains a substructure: the reference's
+PAINS filter (compute_metrics.py, RDKit's ``FilterCatalog`` over the SMARTS file given as ``pains_smarts_loc``) and any
+other list of structural alerts, as a depth-first search per pattern and root atom on the refined bond graph
+(``dl_substructure_match``, ``csrc/substructure.hip``; the patterns compiled by ``patterns.py``).  A subset of SMARTS and a
+matching rule of this project's own - NOT RDKit's matcher: no charges, no stereo, no explicit hydrogens, no SSSR counts.
 """
+import ctypes
 import math
 from collections import namedtuple
 from fractions import Fraction
@@ -78,6 +85,7 @@ import numpy as np
 import torch
 
 from . import _lib, const
+from . import patterns as pattern_compiler
 from .molecule_builder import normalize_bonds, perceive_all_bonds, perceive_bonds, refine_bond_orders, smiles
 
 Analysis = namedtuple('Analysis', 'n_atoms n_over n_components n_bonds key colour status bonds')
@@ -2097,3 +2105,164 @@ def compute_relaxation(records):
             'relax_displacement_max': max([m.displacement for m in good]) if good else None,
             'relax_converged': mean([bool(m.converged) for m in good]),
             'relax_bonds_changed': mean([bool(v) for v in judged])}
+
+
+PatternMatches = namedtuple('PatternMatches', 'first_root first_root_marked n_hits n_hits_marked status')
+FilterRecord = namedtuple('FilterRecord', 'hits linker_hits status')
+FILTER_NAMES = ('filters_passed', 'filters_passed_linker', 'filter_hits_per_molecule', 'filters_budget')
+MAX_PATTERN_STEPS = 1 << 24
+_PATTERN_TABLES = {}
+_ELEMENT_TABLES = {}
+
+
+def _pattern_tables(device, patterns):
+    """The compiled tables of ``patterns`` on ``device``, uploaded once per catalogue and device."""
+    key = (device, id(patterns))
+    if key not in _PATTERN_TABLES:
+        _PATTERN_TABLES[key] = (patterns, tuple(t.to(device=device, dtype=torch.int32).contiguous()
+                                                for t in (patterns.pat, patterns.atoms, patterns.closures, patterns.preds)))
+    return _PATTERN_TABLES[key][1]
+
+
+def _element_tables(device, is_geom):
+    key = (device, bool(is_geom))
+    if key not in _ELEMENT_TABLES:
+        _ELEMENT_TABLES[key] = (const.atomic_number_table(is_geom).to(device).contiguous(),
+                                const.default_valence_table(is_geom).to(device).contiguous())
+    return _ELEMENT_TABLES[key]
+
+
+def match_patterns(one_hot, x, node_mask, found, bond_aromatic, patterns, is_geom, drop_mask=None, mark_mask=None,
+                   max_steps=4096):
+    """``dl_substructure_match`` (``csrc/substructure.hip``) on the results ``(found, aromatic)`` of ``refine_bond_orders`` for
+    the same ``one_hot``, ``x`` and ``node_mask``: ``found`` is the refined ``Bonds`` (any ``Bonds`` does), ``bond_aromatic`` is
+    ``aromatic.bond_aromatic`` ``[B,capacity of the list]`` (``None``: no bond is aromatic) and ``patterns`` a catalogue
+    compiled by ``patterns.compile_patterns``.  Device tensors in, a ``PatternMatches`` of int32 device tensors out, on torch's
+    current stream, no host synchronisation.  ``x`` plays no part in the rule; it is taken so that the call reads like
+    ``pharmacophore_features``.
+
+    THE RULE is this project's own (``include/difflinker_hip.h`` states it in full, ``tests/substructure_ref.py`` restates
+    it): NOT RDKit's matcher.  For every pattern and every kept atom as root a depth-first search, in the order the pattern is
+    written, for an injective map of the pattern's atoms to kept atoms under which every atom predicate holds and every
+    pattern bond falls on a kept bond whose predicate holds.  Every candidate tested is one step; a root's search stops after
+    ``max_steps`` steps and sets ``_lib.DL_SUB_BUDGET``.
+
+    ``drop_mask`` (the pocket) removes atoms together with their bonds, ``mark_mask`` (the linker) marks atoms, both ``[B,N]``
+    or ``[B,N,1]`` by row.  ``first_root [B,P]``: the lowest row that roots a match of pattern ``p``, -1 for none;
+    ``first_root_marked``: the same for matches that touch a marked atom (all -1 without ``mark_mask``); ``n_hits``,
+    ``n_hits_marked`` ``[B]``; ``status [B]``: the bits of ``found.status`` plus ``_lib.DL_SUB_TOO_LARGE`` (more than 256 kept
+    atoms or 2048 kept bonds: nothing is searched), ``_lib.DL_SUB_BAD_BOND`` and ``_lib.DL_SUB_BUDGET``.  An empty catalogue
+    gives zero counts and the status of ``found`` (with ``DL_BONDS_OVERFLOW`` for a list cut short, as with any other)."""
+    masks = (node_mask,) + tuple(m for m in (drop_mask, mark_mask) if m is not None)
+    _lib.require_device('match_patterns', one_hot=one_hot, bond_aromatic=bond_aromatic, bonds=found.bonds, node_mask=node_mask,
+                        drop_mask=drop_mask, mark_mask=mark_mask)
+    B, N, nf = one_hot.shape
+    if any(m.numel() != B * N for m in masks) or found.bonds.dim() != 3 or found.bonds.shape[0] != B \
+            or (bond_aromatic is not None and bond_aromatic.shape != found.bonds.shape[:2]):
+        raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, masks {[tuple(m.shape) for m in masks]}, bonds '
+                         f'{tuple(found.bonds.shape)}, bond_aromatic '
+                         f'{None if bond_aromatic is None else tuple(bond_aromatic.shape)}')
+    if not 1 <= int(max_steps) <= MAX_PATTERN_STEPS:
+        raise ValueError(f'max_steps must be in 1..{MAX_PATTERN_STEPS}, got {max_steps!r}')
+    dev = one_hot.device
+    found = normalize_bonds(found, B, dev, 'match_patterns')
+    one_hot, node_mask, drop_mask, mark_mask = (_lib.dense(t, dev, torch.float32)
+                                                for t in (one_hot, node_mask, drop_mask, mark_mask))
+    bond_aromatic = _lib.dense(bond_aromatic, dev, torch.int32)
+    numbers, valences = _element_tables(dev, is_geom)
+    if numbers.numel() < nf:
+        raise ValueError(f'one_hot has {nf} types, the vocabulary {numbers.numel()}')
+    P = patterns.n_top
+    if P == 0:
+        zeros = partial(torch.zeros, dtype=torch.int32, device=dev)
+        cut = (found.n_bonds > found.bonds.shape[1]).to(torch.int32) * _lib.DL_BONDS_OVERFLOW      # as the kernel adds it
+        return PatternMatches(zeros((B, 0)), zeros((B, 0)), zeros(B), zeros(B), found.status.to(torch.int32) | cut)
+    pat, atoms, closures, preds = _pattern_tables(dev, patterns)
+    capacity = found.bonds.shape[1]
+    i32 = partial(_lib.empty_i32, dev)
+    out = PatternMatches(i32(B, P), i32(B, P), i32(B), i32(B), i32(B))
+    args = _lib.DLSubstructureArgs(
+        B=B, N=N, nf=nf, one_hot=one_hot.data_ptr(), node_mask=node_mask.data_ptr(), drop_mask=_lib.ptr(drop_mask),
+        mark_mask=_lib.ptr(mark_mask), atomic_number=numbers.data_ptr(), default_valence=valences.data_ptr(), capacity=capacity,
+        n_bonds_in=found.n_bonds.data_ptr(), bonds=found.bonds.data_ptr() if capacity else None,
+        bond_aromatic=bond_aromatic.data_ptr() if capacity and bond_aromatic is not None else None,
+        status_in=found.status.data_ptr(), n_sub=patterns.n_sub, n_top=P, n_levels=len(patterns.level_end),
+        level_end=(ctypes.c_int32 * _lib.DL_SUB_MAX_LEVELS)(*patterns.level_end),
+        pat=pat.data_ptr(), atoms=atoms.data_ptr(), closures=closures.data_ptr() if closures.numel() else None,
+        preds=preds.data_ptr() if preds.numel() else None, n_atoms_table=atoms.shape[0], n_closures=closures.shape[0],
+        n_preds=preds.numel(), max_steps=int(max_steps), first_root=out.first_root.data_ptr(),
+        first_root_marked=out.first_root_marked.data_ptr(), n_hits=out.n_hits.data_ptr(),
+        n_hits_marked=out.n_hits_marked.data_ptr(), status=out.status.data_ptr())
+    _lib.launch('dl_substructure_match', args, dev)
+    return out
+
+
+def analyze_patterns(one_hot, x, node_mask, is_geom, linker_mask, patterns, drop_mask=None, margins=const.MARGINS_EDM,
+                     max_steps=4096):
+    """The catalogue ``patterns`` matched against every molecule of a batch on the HIP device without a host synchronisation:
+    ``perceive_bonds``, then ``refine_bond_orders``, then ``match_patterns`` with the ``linker_mask`` rows (``[B,N]`` or
+    ``[B,N,1]``) marked and the ``drop_mask`` rows (the pocket) left out.  Returns a ``PatternMatches``.  ``perceive_bonds``
+    is used with its default capacity, as in ``analyze_pharmacophores``.  The bond orders and the aromatic flags are those
+    of this project's geometric perception of five- and six-rings, NOT RDKit's aromaticity model."""
+    _lib.require_device('analyze_patterns', one_hot=one_hot, x=x, node_mask=node_mask, linker_mask=linker_mask)
+    B, N = one_hot.shape[:2]
+    if linker_mask.numel() != B * N or node_mask.numel() != B * N:
+        raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, node_mask {tuple(node_mask.shape)}, linker_mask '
+                         f'{tuple(linker_mask.shape)}')
+    found = perceive_bonds(one_hot, x, node_mask, is_geom, margins)
+    refined, aromatic = refine_bond_orders(found, one_hot, x, node_mask, is_geom, drop_mask, linker_mask)
+    return match_patterns(one_hot, x, node_mask, refined, aromatic.bond_aromatic, patterns, is_geom, drop_mask, linker_mask,
+                          max_steps)
+
+
+def patterns_to_host(result, names):
+    """One ``FilterRecord`` per molecule of a ``PatternMatches``: ``hits``, the names of the patterns that match, in catalogue
+    order; ``linker_hits``, those that match through a marked atom; and ``status``.  Synchronises."""
+    first, marked = result.first_root.cpu().tolist(), result.first_root_marked.cpu().tolist()
+    status = result.status.cpu().tolist()
+    hit = lambda row: [names[p] for p, r in enumerate(row) if r >= 0]                   # noqa: E731
+    return [FilterRecord(hit(first[b]), hit(marked[b]), status[b]) for b in range(len(status))]
+
+
+def compute_filters(pred, true=None):
+    """Scores of the ``FilterRecord`` values ``pred`` (``patterns_to_host``), in fp64, over ALL records:
+
+    ``filters_passed``            share of molecules with no hit and no budget bit - the reference's ``pains`` column, as a
+                                  fraction, on whatever catalogue was given.  A molecule that was not searched
+                                  (``DL_SUB_TOO_LARGE``) does not pass
+    ``filters_passed_linker``     share with no hit that touches the linker, and no budget bit: the informative one, because
+                                  the fragments are input
+    ``filter_hits_per_molecule``  mean number of patterns hit
+    ``filters_budget``            share with ``DL_SUB_BUDGET`` set (a search was cut short: raise ``max_steps``)
+
+    With ``true`` - one record per prediction, the data set's own molecule - the same four over those records as ``true_...``.
+    A share over nothing is ``None``, as in ``compute_rings``."""
+    if true is not None and len(true) != len(pred):
+        raise ValueError(f'{len(pred)} predictions, {len(true)} true records')
+    mean = lambda values: float(sum(values) / len(values)) if values else None      # noqa: E731
+    unsure = _lib.DL_SUB_BUDGET | _lib.DL_SUB_TOO_LARGE
+
+    def scores(records, prefix):
+        return {f'{prefix}filters_passed': mean([not m.hits and not m.status & unsure for m in records]),
+                f'{prefix}filters_passed_linker': mean([not m.linker_hits and not m.status & unsure for m in records]),
+                f'{prefix}filter_hits_per_molecule': mean([len(m.hits) for m in records]),
+                f'{prefix}filters_budget': mean([bool(m.status & _lib.DL_SUB_BUDGET) for m in records])}
+    out = scores(pred, '')
+    if true is not None:
+        out.update(scores(true, 'true_'))
+    return out
+
+
+def write_filters_json(path, files, records):
+    """``filters.json``: one record per written file (``files``: its name as the other reports give it, with the
+    ``FilterRecord`` of its molecule): ``file``, ``hits``, ``linker_hits`` and ``status``."""
+    import json
+    with open(path, 'w') as f:
+        json.dump([{'file': name, 'hits': list(m.hits), 'linker_hits': list(m.linker_hits), 'status': m.status}
+                   for name, m in zip(files, records)], f, indent=1)
+
+
+def load_filters(spec):
+    """The catalogue behind ``--filters``: ``'basic'`` (``data/filters_basic.csv``, this project's own short list of structural
+    alerts) or the path of a pattern file (CSV: SMARTS, optional name; the reference's PAINS list has this form), compiled."""
+    return pattern_compiler.load_catalogue(spec)

@@ -17,7 +17,7 @@ from . import metrics as mol_metrics
 from . import utils
 from .datasets import MOADDataset, collate, collate_with_fragment_edges, get_dataloader
 from .generate import (BOND_ORDERS, OUTPUT_FORMATS, _check_selection, add_relax_argument, add_selection_arguments,
-                       add_smiles_argument, selection_arguments)
+                       add_filters_argument, add_smiles_argument, selection_arguments)
 from .io import save_sdf_file, save_xyz_file
 from .lightning import DDPM
 from .linker_size import SizeClassifier
@@ -60,7 +60,7 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
            output_format='xyz', metrics=False, geometry=False, clashes=False, shape=False, rings=False,
            bond_orders='distance', aromatic=False, diversity=False, diversity_reference=None, pharmacophore=False,
            interactions=False, hydrogens=False, pose_checks=False, cluster=None, pick=None, select_view='linker', relax=None,
-           smiles=False):
+           smiles=False, filters=None):
     """``sample.py``.  Returns the output directory.  ``metrics=True`` scores the molecules sampled in this call against
     the data set's own (``metrics.compute_metrics``: valence rule, connectivity, uniqueness, novelty, recovery) and writes
     the result to ``metrics.json`` in the output directory; with ``geometry=True`` as well, the symmetry-aware RMSD of the
@@ -126,7 +126,15 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
     was flagged).  The strings describe the bond list the ``.sdf`` files carry (``bond_orders='geometric'`` and ``relax``
     apply), canonical under this project's own rule (``metrics.canonical_ranks``, ``molecule_builder.smiles``), NOT RDKit's
     canonical SMILES.  With ``metrics=True`` ``metrics.json`` gains ``smiles_uniqueness`` and ``smiles_canonical``
-    (``metrics.compute_smiles``)."""
+    (``metrics.compute_smiles``).
+
+    ``filters='basic'`` or ``filters=FILE`` matches a catalogue of structural alerts against every sample and its true
+    molecule, pocket rows left out (``metrics.analyze_patterns``; ``generate`` describes the catalogue), and writes
+    ``filters.json`` to the output directory with one record per written sample file: ``file``, ``hits``, ``linker_hits`` and
+    ``status``.  Always on the geometric bond orders and on the raw sample, whatever ``bond_orders`` and ``relax`` say.  With
+    ``metrics=True`` ``metrics.json`` gains ``filters_passed`` (the reference's ``pains`` column as a fraction, on the catalogue
+    given), ``filters_passed_linker``, ``filter_hits_per_molecule``, ``filters_budget`` and their ``true_`` values
+    (``metrics.compute_filters``).  A SMARTS subset and a matcher of this project's own, NOT RDKit's."""
     select = _check_selection(cluster, pick, select_view)
     if hydrogens and output_format == 'xyz':
         raise ValueError('hydrogens are written to the .sdf files: pass output_format sdf or both (--output_format); the '
@@ -146,6 +154,8 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
     shapes, linker_shapes = [], []
     pharm, linker_pharm = [], []
     pred_rings, true_rings = [], []
+    catalogue = mol_metrics.load_filters(filters) if filters is not None else None
+    pred_filters, true_filters, filter_names = [], [], []
     pred_prints, true_prints, print_input = [], [], []
     eligible, select_input, select_names = [], [], []
     smiles_rows, smiles_names = [], []
@@ -216,6 +226,10 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
         if aromatic:
             true_aromatic_batch = mol_metrics.aromatic_to_host(mol_metrics.analyze_aromatic(
                 h[:, :, :model.num_classes], x, node_mask, model.is_geom, batch['linker_mask']))
+        if filters is not None:                                # the data set's own molecule, without the pocket
+            true_filter_batch = mol_metrics.patterns_to_host(mol_metrics.analyze_patterns(
+                h[:, :, :model.num_classes], x, node_mask, model.is_geom, batch['linker_mask'], catalogue,
+                drop_mask=batch['pocket_mask'] if moad else None), catalogue.names)
         if pose_checks:
             true_pose_batch = mol_metrics.pose_checks_to_host(mol_metrics.analyze_pose_checks(
                 h[:, :, :model.num_classes], x, node_mask, model.is_geom, batch['linker_mask'],
@@ -278,6 +292,13 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 pred_rings += mol_metrics.rings_to_host(*mol_metrics.analyze_rings(
                     hs[:, :, :model.num_classes], xs, out_mask, model.is_geom, out_mask * (1 - pad(batch['fragment_mask']))))
                 true_rings += true_ring_batch
+            if filters is not None:                            # on the raw sample and the geometric orders, always
+                pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, out_mask.shape[1] - m.shape[1]))      # noqa: E731
+                pred_filters += mol_metrics.patterns_to_host(mol_metrics.analyze_patterns(
+                    hs[:, :, :model.num_classes], xs, out_mask, model.is_geom, out_mask * (1 - pad(batch['fragment_mask'])),
+                    catalogue), catalogue.names)
+                true_filters += true_filter_batch
+                filter_names += [[f'{u}/{i}_.{ext}' for ext in ('xyz', 'sdf') if output_format in (ext, 'both')] for u in uuids]
             if aromatic:                                       # likewise
                 pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, out_mask.shape[1] - m.shape[1]))      # noqa: E731
                 pred_aromatic += mol_metrics.aromatic_to_host(mol_metrics.analyze_aromatic(
@@ -350,6 +371,10 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
     if smiles:                                                 # one row per written file
         mol_metrics.write_smiles_csv(os.path.join(output_dir, 'smiles.csv'), [path for paths in smiles_names for path in paths],
                                      [m for m, paths in zip(smiles_rows, smiles_names) for _ in paths])
+    if filters is not None:                                    # one record per written file
+        mol_metrics.write_filters_json(os.path.join(output_dir, 'filters.json'),
+                                       [path for paths in filter_names for path in paths],
+                                       [m for m, paths in zip(pred_filters, filter_names) for _ in paths])
     if relax is not None:                                      # one record per written file
         with open(os.path.join(output_dir, 'relax.json'), 'w') as f:
             json.dump({path: mol_metrics.relax_report(m) for m, paths in zip(relax_records, relax_names) for path in paths}, f, indent=1)
@@ -386,6 +411,8 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 scores.update(mol_metrics.compute_selection(selection))
             if smiles and metrics:                             # over the samples uniqueness counts
                 scores.update(mol_metrics.compute_smiles(smiles_rows, pred, true))
+            if filters is not None and metrics:
+                scores.update(mol_metrics.compute_filters(pred_filters, true_filters))
             json.dump(scores, f, indent=1)
     return output_dir
 
@@ -517,6 +544,7 @@ def main(argv=None):
     add_selection_arguments(p)
     add_relax_argument(p)
     add_smiles_argument(p)
+    add_filters_argument(p)
     p.add_argument('--pose_checks', action='store_true',
                    help='check the internal geometry of every sample and of its true molecule on the GPU - bond lengths, bond '
                         'angles, clashes between atoms four or more bonds apart, always on the geometric bond orders (a rule of '
@@ -538,6 +566,7 @@ def main(argv=None):
                      **({'hydrogens': True} if a.hydrogens else {}),
                      **({'pose_checks': True} if a.pose_checks else {}),
                      **({'relax': a.relax} if a.relax is not None else {}), **({'smiles': True} if a.smiles else {}),
+                     **({'filters': a.filters} if a.filters is not None else {}),
                      **selection_arguments(a)))
 
 

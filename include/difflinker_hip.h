@@ -103,6 +103,11 @@
  *                                           a canonical 64-bit code by an individualisation-refinement search over the
  *                                           colours of dl_molecule_keys.  The rule stated below is this project's own, NOT
  *                                           RDKit's canonical ranks or SMILES
+ *   dl_substructure_match                <- the PAINS filter of compute_metrics.py (FilterCatalog over the SMARTS of the file
+ *                                           given as pains_smarts_loc) and every other "does the sample contain X": a subset
+ *                                           of SMARTS compiled on the host, matched by a depth-first search per (pattern, root
+ *                                           atom).  The language and the rule stated below are this project's own, NOT RDKit's
+ *                                           matcher
  *   dl_size_train_forward / dl_size_train_backward
  *                                        <- SizeClassifier.forward in training mode + loss.backward()
  *                                           (src/linker_size_lightning.py:83-117, :163-167)
@@ -2107,6 +2112,115 @@ typedef struct dl_canon_args {
     void* stream;                   /* hipStream_t; NULL: the default stream */
 } dl_canon_args;
 int32_t dl_canonical_ranks(const dl_canon_args* args);
+
+/* ---- substructure search over a perceived batch: a SMARTS subset, structural alerts (substructure.hip) ----------------
+ * For every molecule of a batch and every pattern of a compiled catalogue: is there an injective map of the pattern's atoms
+ * to the molecule's kept atoms under which every atom predicate holds and every pattern bond falls on a kept bond whose
+ * predicate holds (the match is not induced), and which original row roots the first one.  One 256-thread workgroup per
+ * molecule, ONE launch per batch, the molecule in LDS, the compiled tables read-only in global memory, the stream as the last
+ * field, as dl_canonical_ranks.  THE LANGUAGE AND THE RULE BELOW ARE THIS PROJECT'S OWN: NOT RDKit's SMARTS parser or matcher,
+ * and these are NOT RDKit's numbers: no charges (every atom is neutral), no stereo, no isotopes, no explicit hydrogens in
+ * molecules, no SSSR ring counts.  difflinker_amd/patterns.py compiles the tables; tests/substructure_ref.py restates the
+ * search in plain Python and the kernel agrees with that in every output bit.
+ *
+ * THE GRAPH is the one dl_pharmacophore_features reads: atom k is the k-th row with node_mask != 0; `drop_mask` (may be NULL)
+ * removes atoms AFTER that numbering together with every bond that touches them; the kept atoms are numbered among themselves
+ * in row order (the KEPT INDEX).  `mark_mask` (may be NULL) marks atoms (the callers pass the linker).  The type of an atom is
+ * the first largest entry of its one_hot row; Z = atomic_number[type] and dv = default_valence[type], both clamped to 0..255.
+ * An entry (i, j, order) of the list is a bond when 0 <= i, j < atoms, i != j and 1 <= order <= 3, in either orientation; any
+ * other entry is skipped and sets DL_SUB_BAD_BOND.  A pair listed more than once also sets DL_SUB_BAD_BOND, and its FIRST entry
+ * gives the pair its order and its aromatic flag (bond_aromatic[entry] != 0; a NULL bond_aromatic flags nothing).  A bond is a
+ * RING BOND when its ends are joined by another path; its ring size is the length of the shortest such path plus one.
+ *
+ * ATOM PROPERTIES, each saturating at 255:  D the kept neighbours;  S the sum of the orders of the kept bonds;
+ * H = max(0, dv - S);  X = D + H;  V = S + H;  AROM: a kept bond of the atom is flagged aromatic;  XR the ring bonds of the
+ * atom;  RS the smallest ring size over them (0 without one).
+ *
+ * THE TABLES (all int32, device): with Q = n_sub + n_top patterns, the n_sub sub-patterns (the bodies of $(...)) first,
+ *   pat      [Q,8]   atom_off, n_atoms, level, screen[4], 0.  A pattern's atoms are rows atom_off .. atom_off + n_atoms - 1
+ *                    of `atoms`; 1 <= n_atoms <= DL_SUB_MAX_PATTERN_ATOMS, any other pattern matches nothing.  A screen word
+ *                    Z | count << 8 (0: unused) says the pattern needs `count` kept atoms of element Z; a pattern whose screen
+ *                    fails, or with more atoms than the molecule has kept atoms, is not searched at all (no step is taken).
+ *   atoms    [A,6]   parent (an earlier atom of the pattern; -1 for atom 0), the 12-bit mask of the bond to the parent,
+ *                    pred_off, pred_len, closure_off, closure_len.
+ *   closures [C,2]   an earlier atom of the pattern, the mask of the bond to it (the ring closures).
+ *   preds    [T]     tokens op | arg << 8 | NEG << 24 | END_AND << 25 | END_OR << 26.  An atom's predicate is its pred_len
+ *                    tokens: an AND of ORs of ANDs.  Each token's value (negated under NEG) is ANDed into the running
+ *                    conjunction; END_AND ORs the conjunction into the running alternative and restarts it; END_OR ANDs the
+ *                    alternative into the result and restarts it.  At most DL_SUB_MAX_PRED tokens.  ops: 0 TRUE, 1 Z == arg,
+ *                    2 Z == arg and not AROM, 3 Z == arg and AROM, 4 AROM, 5 D == arg, 6 H == arg, 7 H >= arg, 8 X == arg,
+ *                    9 V == arg, 10 XR > 0, 11 RS == arg, 12 XR == arg, 13 sub-pattern `arg` matches with its root here;
+ *                    any other op is false.
+ *   A bond's STATE is (order - 1) + 3 * aromatic + 6 * ring, and a bond predicate is the mask of the states it accepts.
+ *   level_end[L] (in the struct, L < n_levels <= DL_SUB_MAX_LEVELS): sub-patterns [level_end[L-1], level_end[L]) have
+ *   nesting level L and use sub-patterns of lower levels only; level_end[n_levels - 1] == n_sub <= DL_SUB_MAX_SUBPATTERNS.
+ *
+ * THE SEARCH of one pattern from one root (a kept atom), depth first, in the order the pattern's atoms are written: atom 0 is
+ * tested on the root; the candidates for atom k > 0 are the kept neighbours of the image of its parent, in ascending kept
+ * index; a candidate is taken when it is not yet an image, the bond from the parent's image is in the atom's mask, the atom's
+ * predicate holds, and for every closure the candidate is bonded to the image of the closure's atom by a bond in the
+ * closure's mask.  EVERY CANDIDATE TESTED IS ONE STEP, the root included.  A search that would take more than `max_steps`
+ * steps stops: what it found stands, and DL_SUB_BUDGET is set.  Without mark_mask a search ends at its first complete map.
+ * With mark_mask it goes on past complete maps that touch no marked atom (it backtracks as if the last candidate had failed)
+ * until a complete map touches one or the search ends.  Every root is searched, independently of the others, so the result
+ * and the status do not depend on how the work is spread over lanes.
+ * Sub-patterns run first, level by level, from every root, without marks; op 13 reads their per-atom results.  A sub-pattern
+ * root that runs out of budget counts as no match (and sets DL_SUB_BUDGET).
+ *
+ *   first_root         [B,n_top]: the lowest original ROW index (0 .. N-1) that roots a complete map of the pattern, -1: none
+ *   first_root_marked  [B,n_top]: the same for complete maps that touch a marked atom; all -1 without mark_mask
+ *   n_hits, n_hits_marked  [B]: the patterns with an entry >= 0
+ *   status             [B]: the bits of `status_in`, plus DL_BONDS_OVERFLOW when n_bonds_in > capacity (a negative n_bonds_in
+ *                      counts as 0), DL_SUB_BAD_BOND, DL_SUB_BUDGET, and DL_SUB_TOO_LARGE for more than DL_SUB_MAX_ATOMS kept
+ *                      atoms or more than DL_SUB_MAX_BONDS kept list entries: every entry is then -1 and the counts are 0 (with
+ *                      too many atoms the list is not looked at; with too many entries DL_SUB_BAD_BOND is added for an entry
+ *                      that is no bond, and repeated pairs are not looked for).
+ *
+ * Integer work only; global memory is written with plain stores only, no atomics on global memory, every output element is
+ * written, the callee allocates nothing and needs no workspace.  A null `args`, B < 0, N < 1, N > 1024, nf < 1, nf > 256,
+ * capacity < 0, max_steps < 1, n_sub < 0, n_sub > DL_SUB_MAX_SUBPATTERNS, n_top < 0, n_levels < 0, n_levels >
+ * DL_SUB_MAX_LEVELS, a level_end that decreases or does not end at n_sub, or a negative table length return DL_ERR_BAD_ARG;
+ * then B == 0 or n_top == 0 returns DL_OK without a launch (nothing is written); then a null pointer (other than drop_mask,
+ * mark_mask, bond_aromatic, stream, `bonds` when capacity is 0, and `closures` / `preds` of length 0) returns DL_ERR_BAD_ARG,
+ * all before any device work. */
+#define DL_SUB_MAX_ATOMS 256            /* kept atoms per molecule */
+#define DL_SUB_MAX_BONDS 2048           /* kept list entries per molecule */
+#define DL_SUB_MAX_PATTERN_ATOMS 48     /* atoms of a pattern, after the hydrogen merge */
+#define DL_SUB_MAX_SUBPATTERNS 256      /* distinct $(...) bodies of a catalogue */
+#define DL_SUB_MAX_LEVELS 4             /* nesting levels of $(...) */
+#define DL_SUB_MAX_PRED 32              /* tokens of one atom's predicate */
+#define DL_SUB_TOO_LARGE 4              /* status bit, same value as DL_CANON_TOO_LARGE */
+#define DL_SUB_BAD_BOND 8               /* status bit, same value as DL_CANON_BAD_BOND */
+#define DL_SUB_BUDGET 512               /* status bit: a root's search stopped at max_steps */
+typedef struct dl_substructure_args {
+    int32_t B, N, nf;
+    const float* one_hot;           /* device f32 [B,N,nf] */
+    const float* node_mask;         /* device f32 [B,N] */
+    const float* drop_mask;         /* device f32 [B,N] or NULL */
+    const float* mark_mask;         /* device f32 [B,N] or NULL */
+    const int32_t* atomic_number;   /* device int32 [nf] */
+    const int32_t* default_valence; /* device int32 [nf] */
+    int32_t capacity;               /* bonds the list holds per molecule */
+    const int32_t* n_bonds_in;      /* device int32 [B]: dl_bonds_args.n_bonds */
+    const int32_t* bonds;           /* device int32 [B,capacity,3] (may be NULL when capacity is 0) */
+    const int32_t* bond_aromatic;   /* device int32 [B,capacity] or NULL: dl_aromatic_args.bond_aromatic */
+    const int32_t* status_in;       /* device int32 [B]: dl_bonds_args.status */
+    int32_t n_sub, n_top, n_levels;
+    int32_t level_end[DL_SUB_MAX_LEVELS];
+    const int32_t* pat;             /* device int32 [n_sub + n_top, 8] */
+    const int32_t* atoms;           /* device int32 [n_atoms_table, 6] */
+    const int32_t* closures;        /* device int32 [n_closures, 2] */
+    const int32_t* preds;           /* device int32 [n_preds] */
+    int32_t n_atoms_table, n_closures, n_preds;
+    int32_t max_steps;              /* >= 1; the Python layer's default is 4096 */
+    int32_t* first_root;            /* device int32 [B,n_top] out */
+    int32_t* first_root_marked;     /* device int32 [B,n_top] out */
+    int32_t* n_hits;                /* device int32 [B] out */
+    int32_t* n_hits_marked;         /* device int32 [B] out */
+    int32_t* status;                /* device int32 [B] out */
+    void* stream;                   /* hipStream_t; NULL: the default stream */
+} dl_substructure_args;
+int32_t dl_substructure_match(const dl_substructure_args* args);
 
 const char* dl_error_string(int32_t status);
 int32_t dl_last_hip_error(void);
