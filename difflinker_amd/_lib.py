@@ -465,6 +465,25 @@ class DLSubstructureArgs(ctypes.Structure):           # the stream is the last F
     ]
 
 
+DL_STEREO_MAX_ATOMS, DL_STEREO_MAX_BONDS, DL_STEREO_COUNTS = 256, 2048, 4     # dl_stereo_args: kept atoms, kept list entries, values per row of counts
+DL_STEREO_TOO_LARGE, DL_STEREO_BAD_BOND, DL_STEREO_NONFINITE = 4, 8, 64      # dl_stereo_args.status bits, beside the DL_BONDS_* bits
+
+
+class DLStereoArgs(ctypes.Structure):                 # the stream is the last FIELD, as for dl_pose_checks
+    _fields_ = [
+        ('B', ctypes.c_int32), ('N', ctypes.c_int32), ('nf', ctypes.c_int32),
+        ('x', ctypes.c_void_p), ('one_hot', ctypes.c_void_p), ('node_mask', ctypes.c_void_p),
+        ('drop_mask', ctypes.c_void_p), ('mark_mask', ctypes.c_void_p), ('atom_planar', ctypes.c_void_p),
+        ('default_valence', ctypes.c_void_p),
+        ('capacity', ctypes.c_int32),
+        ('n_bonds_in', ctypes.c_void_p), ('bonds', ctypes.c_void_p), ('bond_aromatic', ctypes.c_void_p),
+        ('status_in', ctypes.c_void_p),
+        ('flat', ctypes.c_double), ('twist', ctypes.c_double), ('v_ideal4', ctypes.c_double), ('v_ideal3', ctypes.c_double),
+        ('atom_class', ctypes.c_void_p), ('atom_stereo', ctypes.c_void_p), ('bond_stereo', ctypes.c_void_p),
+        ('counts', ctypes.c_void_p), ('status', ctypes.c_void_p), ('stream', ctypes.c_void_p),
+    ]
+
+
 class DLFeatureMatchArgs(ctypes.Structure):           # likewise
     _fields_ = [
         ('B', ctypes.c_int32), ('Fa', ctypes.c_int32), ('Fb', ctypes.c_int32),
@@ -488,7 +507,7 @@ EXPORTS = ('dl_abi_version', 'dl_last_hip_error', 'dl_max_atoms', 'dl_error_stri
            'dl_egnn_backward_fc_workspace_bytes', 'dl_egnn_backward_max_atoms', 'dl_egnn_backward_fc',
            'dl_egnn_backward_pocket_workspace_bytes', 'dl_egnn_backward_pocket',
            'dl_size_train_num_params', 'dl_size_train_workspace_bytes', 'dl_size_train_forward', 'dl_size_train_backward',
-           'dl_substructure_match',
+           'dl_substructure_match', 'dl_stereo_perceive',
            'dl_join_workspace_bytes', 'dl_sample_chain_fc_join', 'dl_tanimoto_cluster', 'dl_tanimoto_pick',
            'dl_bonds_workspace_bytes', 'dl_canonical_ranks', 'dl_perceive_bonds',
            'dl_pose_checks',
@@ -522,8 +541,10 @@ RELAX_ENTRY_POINTS = {'dl_relax_molecules': DLRelaxArgs}
 CANON_ENTRY_POINTS = {'dl_canonical_ranks': DLCanonArgs}
 # The substructure search (substructure.hip), likewise: tests/test_canon_host.py pins the one above.
 SUBSTRUCTURE_ENTRY_POINTS = {'dl_substructure_match': DLSubstructureArgs}
+# The stereo perception (stereo.hip), likewise: tests/test_substructure_host.py pins the one above.
+STEREO_ENTRY_POINTS = {'dl_stereo_perceive': DLStereoArgs}
 ALL_ENTRY_POINTS = {**STRUCT_ENTRY_POINTS, **SELECT_ENTRY_POINTS, **RELAX_ENTRY_POINTS, **CANON_ENTRY_POINTS,
-                    **SUBSTRUCTURE_ENTRY_POINTS}
+                    **SUBSTRUCTURE_ENTRY_POINTS, **STEREO_ENTRY_POINTS}
 
 
 def entry_struct(name):

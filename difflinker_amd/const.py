@@ -280,3 +280,12 @@ def shape_radius_table(is_geom, scale=0.8, step=0.25):
     radii = torch.tensor([[float(scale) * VDW_RADII[t] + k * float(step) for k in range(3)] for t in range(n)],
                          dtype=torch.float64).to(TORCH_FLOAT)
     return radii * radii
+
+
+# ---- the parameters of ``metrics.stereo`` (``dl_stereo_perceive``).  Parameters of the rule, not measurements: a centre
+# squashed to a quarter of the ideal chiral volume cannot be called (``flat``), and neither can a double bond whose reference
+# arms are twisted more than 60 degrees out of plane (``twist`` = cos 60).  The two ideal volumes are the determinants of the
+# rule at the regular tetrahedron, 16/(3 sqrt 3) with four neighbours and 4/(3 sqrt 3) with three and a hydrogen, formed in
+# fp64 as plain Python floats with one rounding per operation
+STEREO_DEFAULTS = {'flat': 0.25, 'twist': 0.5}
+STEREO_V_IDEAL = (16.0 / (3.0 * math.sqrt(3.0)), 4.0 / (3.0 * math.sqrt(3.0)))

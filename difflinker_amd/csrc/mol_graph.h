@@ -1,5 +1,5 @@
 // mol_graph.h — what the kernels that read a perceived bond list with 256 threads per molecule share (mol_keys.hip,
-// fingerprint.hip, rings.hip, aromatic.hip, pharmacophore.hip, hydrogens.hip, pose_checks.hip, relax.hip, canon.hip), on top of workgroup.h: the
+// fingerprint.hip, rings.hip, aromatic.hip, pharmacophore.hip, hydrogens.hip, pose_checks.hip, relax.hip, canon.hip, stereo.hip), on top of workgroup.h: the
 // 64-bit mixing function of the colour refinement, the test that says whether a list entry is a bond, the list's length and
 // overflow bit, the numbering of the real and of the kept rows, the 256 x 256 bit matrix in LDS with its breadth-first search,
 // and the two-pass build of the matrices by bond order that the last three share (rings.hip and aromatic.hip build through

@@ -1,5 +1,5 @@
 // points.h — coordinates for the kernels that stage a molecule's kept atoms in LDS as fp32 and compute on them in fp64
-// (pharmacophore.hip, hydrogens.hip, pose_checks.hip; relax.hip keeps its state in fp64 and takes the arithmetic).  Every operation rounds once, in the order written: contraction is
+// (pharmacophore.hip, hydrogens.hip, pose_checks.hip, stereo.hip; relax.hip keeps its state in fp64 and takes the arithmetic).  Every operation rounds once, in the order written: contraction is
 // switched off HERE, because a kernel's own `#pragma clang fp contract(off)` stands after its includes and would come too
 // late for `dot`.  That is also why none of this is in mol_graph.h, which integer-only kernels include.
 #pragma once

@@ -89,7 +89,7 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
                      output_format='xyz', metrics=False, clashes=False, protein=None, rings=False, bond_orders='distance',
                      aromatic=False, diversity=False, interactions=False, typed_protein=None, hydrogens=False,
                      pose_checks=False, cluster=None, pick=None, select_view='linker', relax=None, smiles=False,
-                     filters=None):
+                     filters=None, stereo=False):
     if output_format not in OUTPUT_FORMATS:
         raise ValueError(f'output_format must be one of {OUTPUT_FORMATS}, got {output_format!r}')
     if bond_orders not in BOND_ORDERS:
@@ -100,7 +100,7 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
     written, found, scored, clash_records, ring_records, aromatic_records = [], [], [], [], [], []
     prints, contact_records, pose_records, eligible = [], [], [], []
     relax_records, relaxed_pose_records = [], []
-    smiles_rows = []
+    smiles_rows, stereo_rows = [], []
     catalogue, filter_records = (mol_metrics.load_filters(filters) if filters is not None else None), []
     for batch_i, data in enumerate(_batches(dataset, batch_size, collate_fn)):
         n = len(data['positions'])
@@ -182,6 +182,11 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
                 listed = refine_bond_orders(listed, types, shown_x, node_mask, ddpm.is_geom)[0]
             smiles_rows += mol_metrics.smiles_records(types, node_mask, listed, node_mask * (1 - pad(data['fragment_mask'])),
                                                       drop_mask=pad(data['pocket_mask']) if 'pocket_mask' in data else None)
+        if stereo:                                            # on the coordinates the files carry; always on the geometric orders
+            pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, x.shape[1] - m.shape[1]))     # noqa: E731
+            stereo_rows += mol_metrics.analyze_stereo(
+                h[:, :, :ddpm.num_classes], shown_x, node_mask, ddpm.is_geom, node_mask * (1 - pad(data['fragment_mask'])),
+                drop_mask=pad(data['pocket_mask']) if 'pocket_mask' in data else None)
         if filters is not None:                               # on the raw sample and the geometric orders, whatever the files hold
             pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, x.shape[1] - m.shape[1]))     # noqa: E731
             filter_records += mol_metrics.patterns_to_host(mol_metrics.analyze_patterns(
@@ -254,6 +259,8 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
             scores.update(mol_metrics.compute_smiles(smiles_rows, scored))     # the samples uniqueness counts
         if filters is not None and metrics:
             scores.update(mol_metrics.compute_filters(filter_records))
+        if stereo and metrics:                                # no true molecule here: no stereo recovery
+            scores.update(mol_metrics.compute_stereo(stereo_rows, scored))
         with open(os.path.join(output_dir, 'metrics.json'), 'w') as f:
             json.dump(scores, f, indent=1)
     if clashes:                                               # one record per written file, by its name
@@ -284,8 +291,14 @@ def _sample_and_save(ddpm, dataset, collate_fn, sample_fn, batch_size, output_di
                        for path in written}, f, indent=1)
     if smiles:                                                # likewise: one row per written file
         by_name = {f'output_{i}_{name}': m for i, m in enumerate(smiles_rows)}
+        by_stereo = {f'output_{i}_{name}': m.isomeric_smiles for i, m in enumerate(stereo_rows)}
         mol_metrics.write_smiles_csv(os.path.join(output_dir, 'smiles.csv'), [os.path.basename(path) for path in written],
-                                     [by_name[os.path.basename(path).rsplit('_.', 1)[0]] for path in written])
+                                     [by_name[os.path.basename(path).rsplit('_.', 1)[0]] for path in written],
+                                     *([[by_stereo[os.path.basename(path).rsplit('_.', 1)[0]] for path in written]] if stereo else []))
+    if stereo:                                                # likewise: one record per written file
+        by_name = {f'output_{i}_{name}': m for i, m in enumerate(stereo_rows)}
+        mol_metrics.write_stereo_json(os.path.join(output_dir, 'stereo.json'), [os.path.basename(path) for path in written],
+                                      [by_name[os.path.basename(path).rsplit('_.', 1)[0]] for path in written])
     if filters is not None:                                   # likewise: one record per written file
         by_name = {f'output_{i}_{name}': m for i, m in enumerate(filter_records)}
         mol_metrics.write_filters_json(os.path.join(output_dir, 'filters.json'), [os.path.basename(path) for path in written],
@@ -326,7 +339,7 @@ def _files_of_samples(written, name, n):
 def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anchors=None, device=None, output_format='xyz',
              metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False, diversity=False,
              hydrogens=False, pose_checks=False, cluster=None, pick=None, select_view='linker', relax=None, smiles=False,
-             filters=None):
+             filters=None, stereo=False):
     """``generate.py`` main(): fragments file -> ``n_samples`` molecules with a sampled linker, as ``.xyz`` files
     (``output_format='sdf'``: ``.sdf`` files with perceived bonds instead, ``'both'``: both; one JSON line with the number of
     molecules, the share in one piece and the mean bond count is printed then).  ``metrics=True`` also writes
@@ -408,14 +421,14 @@ def generate(input_path, model, output_dir, n_samples, n_steps, linker_size, anc
                             rings=rings, bond_orders=bond_orders, aromatic=aromatic, diversity=diversity,
                             **({'hydrogens': True} if hydrogens else {}), **({'pose_checks': True} if pose_checks else {}),
                             **({'relax': relax} if relax is not None else {}), **({'smiles': True} if smiles else {}),
-                            **({'filters': filters} if filters is not None else {}),
+                            **({'filters': filters} if filters is not None else {}), **({'stereo': True} if stereo else {}),
                             **selection)
 
 
 def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_samples, anchors, max_batch_size, device,
                             output_format, metrics=False, clashes=False, protein=None, rings=False, bond_orders='distance',
                             aromatic=False, interactions=False, typed_protein=None, hydrogens=False, pose_checks=False,
-                            selection=None, relax=None, smiles=False, filters=None):
+                            selection=None, relax=None, smiles=False, filters=None, stereo=False):
     frag_pos, frag_one_hot, frag_charges = frag
     pocket_pos, pocket_one_hot, pocket_charges = pocket
     positions = np.concatenate([frag_pos, pocket_pos], axis=0)
@@ -440,14 +453,14 @@ def _generate_pocket_common(frag, pocket, ddpm, sample_fn, output_dir, name, n_s
                             typed_protein=typed_protein, **({'hydrogens': True} if hydrogens else {}),
                             **({'pose_checks': True} if pose_checks else {}), **({'relax': relax} if relax is not None else {}),
                             **({'smiles': True} if smiles else {}), **({'filters': filters} if filters is not None else {}),
-                            **(selection or {}))
+                            **({'stereo': True} if stereo else {}), **(selection or {}))
 
 
 def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, output_dir, n_samples, n_steps, linker_size,
                          anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz',
                          metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False, interactions=False,
                          hydrogens=False, pose_checks=False, cluster=None, pick=None, select_view='linker', relax=None,
-                         smiles=False, filters=None):
+                         smiles=False, filters=None, stereo=False):
     """``generate_with_pocket.py`` main(): the pocket is given as its own PDB file.  ``clashes=True`` scores every sample's
     generated atoms against the pocket atoms (``metrics.analyze_clashes``), adds the ``metrics.compute_clashes`` keys to
     ``metrics.json`` and writes ``clashes.json``: ``n_clashes``, ``n_clash_atoms`` and ``min_distance`` per written file.
@@ -485,6 +498,7 @@ def generate_with_pocket(input_path, pocket_path, backbone_atoms_only, model, ou
                                    **({'relax': relax} if relax is not None else {}),
                                    **({'smiles': True} if smiles else {}),
                                    **({'filters': filters} if filters is not None else {}),
+                                   **({'stereo': True} if stereo else {}),
                                    **({'selection': selection} if selection else {}))
 
 
@@ -492,7 +506,7 @@ def generate_with_protein(input_path, protein_path, backbone_atoms_only, model, 
                           linker_size, anchors=None, max_batch_size=64, random_seed=None, device=None, output_format='xyz',
                           metrics=False, clashes=False, rings=False, bond_orders='distance', aromatic=False,
                           interactions=False, hydrogens=False, pose_checks=False, cluster=None, pick=None,
-                          select_view='linker', relax=None, smiles=False, filters=None):
+                          select_view='linker', relax=None, smiles=False, filters=None, stereo=False):
     """``generate_with_protein.py`` main(): the pocket = residues of the protein within 6 A of the fragments.
     ``clashes=True`` as in ``generate_with_pocket``, but against ALL protein atoms whose element is in the vocabulary
     (``io.get_protein_atoms``), residues outside the pocket the model saw included; the pocket rows of the batch are then not
@@ -530,6 +544,7 @@ def generate_with_protein(input_path, protein_path, backbone_atoms_only, model, 
                                    **({'relax': relax} if relax is not None else {}),
                                    **({'smiles': True} if smiles else {}),
                                    **({'filters': filters} if filters is not None else {}),
+                                   **({'stereo': True} if stereo else {}),
                                    **({'selection': selection} if selection else {}))
 
 
@@ -565,6 +580,20 @@ def add_smiles_argument(p):
                         'project\'s own rule, NOT RDKit\'s canonical SMILES (Kekule orders as the .sdf files carry them, no '
                         'aromatic lower case, no charges, no stereo, at most 256 atoms).  With --metrics adds smiles_uniqueness '
                         'and smiles_canonical to metrics.json')
+
+
+def add_stereo_argument(p):
+    """``--stereo``, shared with ``sample``."""
+    p.add_argument('--stereo', action='store_true',
+                   help='perceive stereo from the 3D coordinates the files carry, on the GPU, and write stereo.json with one '
+                        'record per written file: assigned tetrahedral centres and stereo double bonds (all, and those that '
+                        'touch the linker), the undetermined ones (a centre too flat, a double bond too twisted to call), a '
+                        'stereo-aware canonical code, whether the molecule is chiral, and an isomeric SMILES.  A rule of this '
+                        'project\'s own, NOT RDKit\'s stereo perception and NOT CIP: labels relative to this project\'s '
+                        'symmetry classes, no R/S or E/Z names, no trivalent N, P or sulfoxide centres, no allenes or '
+                        'atropisomers, always on the geometric bond orders.  With --metrics adds stereocentres_per_molecule, '
+                        'stereo_bonds_per_molecule, stereo_undetermined, chiral_fraction and stereo_uniqueness to metrics.json; '
+                        'with --smiles adds an isomeric_smiles column to smiles.csv')
 
 
 def add_selection_arguments(p):
@@ -647,6 +676,7 @@ def main(argv=None):
     add_selection_arguments(p)
     add_smiles_argument(p)
     add_filters_argument(p)
+    add_stereo_argument(p)
     a = p.parse_args(argv)
     if a.clashes and a.pocket is None and a.protein is None:
         raise ValueError('--clashes scores the generated atoms against a protein: pass --pocket or --protein')
@@ -671,6 +701,8 @@ def main(argv=None):
         more['smiles'] = True
     if a.filters is not None:
         more['filters'] = a.filters
+    if a.stereo:
+        more['stereo'] = True
     if a.pocket is not None:
         files = generate_with_pocket(a.fragments, a.pocket, a.backbone_atoms_only, a.model, a.output, a.n_samples,
                                      a.n_steps, a.linker_size, a.anchors, a.max_batch_size, a.random_seed,

@@ -74,6 +74,11 @@ PAINS filter (compute_metrics.py, RDKit's ``FilterCatalog`` over the SMARTS file
 other list of structural alerts, as a depth-first search per pattern and root atom on the refined bond graph
 (``dl_substructure_match``, ``csrc/substructure.hip``; the patterns compiled by ``patterns.py``).  A subset of SMARTS and a
 matching rule of this project's own - NOT RDKit's matcher: no charges, no stereo, no explicit hydrogens, no SSSR counts.
+``stereo`` / ``stereo_codes`` / ``analyze_stereo`` / ``compute_stereo`` say WHICH STEREOISOMER a sample is, from its coordinates:
+tetrahedral centres and stereo double bonds with labels relative to the colour classes of ``canonical_ranks``
+(``dl_stereo_perceive``, ``csrc/stereo.hip``), stereo-aware codes by two more launches of ``dl_canonical_ranks`` on types widened
+by the labels, and isomeric strings (``molecule_builder.smiles``).  This project's own rule - NOT RDKit's stereo perception
+and NOT CIP: no R/S or E/Z names, no trivalent N, P or sulfoxide centres, no allenes or atropisomers.
 """
 import ctypes
 import math
@@ -216,15 +221,16 @@ def smiles_records(one_hot, node_mask, found, linker_mask, drop_mask=None, max_l
                          0 if flagged[b] or strings[b] is None or linker_strings[b] is None else 1) for b in range(B)]
 
 
-def write_smiles_csv(path, files, records):
+def write_smiles_csv(path, files, records, isomeric=None):
     """``smiles.csv``: one row per written file (``files``: its name as the other reports give it, with the record of its
-    molecule), columns ``SMILES_COLUMNS``."""
+    molecule), columns ``SMILES_COLUMNS``; with ``isomeric`` (one string per file, ``StereoRecord.isomeric_smiles``) a last
+    column ``isomeric_smiles``."""
     import csv
     with open(path, 'w', newline='') as f:
         out = csv.writer(f)
-        out.writerow(SMILES_COLUMNS)
-        for name, record in zip(files, records):
-            out.writerow((name,) + tuple(record))
+        out.writerow(SMILES_COLUMNS + (() if isomeric is None else ('isomeric_smiles',)))
+        for at, (name, record) in enumerate(zip(files, records)):
+            out.writerow((name,) + tuple(record) + (() if isomeric is None else (isomeric[at],)))
 
 
 def compute_smiles(rows, pred, true=None):
@@ -2266,3 +2272,251 @@ def load_filters(spec):
     """The catalogue behind ``--filters``: ``'basic'`` (``data/filters_basic.csv``, this project's own short list of structural
     alerts) or the path of a pattern file (CSV: SMARTS, optional name; the reference's PAINS list has this form), compiled."""
     return pattern_compiler.load_catalogue(spec)
+
+
+# ---- stereo perception from 3D (``dl_stereo_perceive``, ``csrc/stereo.hip``) ---------------------------------------------------
+STEREO_COUNTS = ('centres', 'centres_undetermined', 'double_bonds', 'double_bonds_undetermined')
+_STEREO_TABLES = {}
+
+
+def _stereo_valence(device, is_geom):
+    key = (device, bool(is_geom))
+    if key not in _STEREO_TABLES:
+        _STEREO_TABLES[key] = const.default_valence_table(is_geom).to(device).contiguous()
+    return _STEREO_TABLES[key]
+
+
+def stereo(one_hot, x, node_mask, found, is_geom, drop_mask=None, mark_mask=None, atom_planar=None, bond_aromatic=None,
+           flat=const.STEREO_DEFAULTS['flat'], twist=const.STEREO_DEFAULTS['twist']):
+    """ONE launch of ``dl_stereo_perceive`` (``csrc/stereo.hip``) on the bond list ``found`` of ``perceive_bonds`` or
+    ``refine_bond_orders`` for the same ``one_hot``, ``x`` and ``node_mask``, with the input handling of ``pose_checks``;
+    device tensors in, a dict of device tensors out, no host synchronisation.  ``drop_mask`` and ``mark_mask`` are ``[B,N]`` or
+    ``[B,N,1]`` by row, ``atom_planar`` is ``[B,N]`` by atom number and ``bond_aromatic`` ``[B,capacity of the list]`` (the
+    ``atom_aromatic`` and ``bond_aromatic`` of ``refine_bond_orders``); each may be ``None``.
+
+    THE RULE is this project's own (``include/difflinker_hip.h`` states it in full, ``tests/stereo_ref.py`` restates it): NOT
+    RDKit's stereo perception and NOT CIP.  A kept atom with single bonds only, four different neighbours (or three and one
+    implicit hydrogen) by the colour classes of ``canonical_ranks``' root refinement is a centre; the sign of the determinant
+    of the unit vectors to its neighbours in class order is its label 1 or 2, and 3 (undetermined) when the volume is below
+    ``flat`` times the ideal one.  A double bond outside aromatic rings and rings of fewer than 8 atoms whose ends each have
+    one or two single-bonded other neighbours of different classes is a stereo double bond: label 1 when the two highest-class
+    neighbours are on one side (cosine of the torsion above ``twist``), 2 when on opposite sides, 3 in between.  The labels
+    are relative to the classes: no R/S, no E/Z.
+
+    ``atom_class``   int32 ``[B,N]`` by atom number: the classes (tied ranks); -1 for dropped atoms and from the atom count on
+    ``atom_stereo``  int32 ``[B,N]`` by atom number: 0 no centre, 1, 2, 3; -1 where ``atom_class`` is
+    ``bond_stereo``  int32 ``[B,capacity]`` by list entry: the label on the first entry of a stereo double bond's pair, else 0
+    ``counts``       int32 ``[B,2,4]``: ``STEREO_COUNTS`` over the kept molecule, and over the items with a marked atom
+    ``status``       int32 ``[B]``: the bits of ``found.status`` plus ``_lib.DL_STEREO_*`` (more than 256 kept atoms or 2048
+                     kept list entries: classes -1 and nothing perceived; a non-finite coordinate: classes only)"""
+    others = tuple(m for m in (node_mask, drop_mask, mark_mask, atom_planar) if m is not None)
+    _lib.require_device('stereo', one_hot=one_hot, x=x, node_mask=node_mask, drop_mask=drop_mask, mark_mask=mark_mask,
+                        atom_planar=atom_planar, bond_aromatic=bond_aromatic)
+    B, N, nf = one_hot.shape
+    if x.shape != (B, N, 3) or any(m.numel() != B * N for m in others):
+        raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, x {tuple(x.shape)}, masks '
+                         f'{[tuple(m.shape) for m in others]}')
+    flat, twist = float(flat), float(twist)
+    if not (flat >= 0.0 and twist >= 0.0):
+        raise ValueError(f'flat and twist must not be negative or NaN, got {flat!r} and {twist!r}')
+    dev = one_hot.device
+    given = normalize_bonds(found, B, dev, 'stereo')
+    capacity = given.bonds.shape[1]
+    if bond_aromatic is not None and tuple(bond_aromatic.shape) != (B, capacity):
+        raise ValueError(f'bond_aromatic {tuple(bond_aromatic.shape)} does not go with bonds {tuple(given.bonds.shape)}')
+    one_hot, x, node_mask, drop_mask, mark_mask = (_lib.dense(t, dev, torch.float32)
+                                                   for t in (one_hot, x, node_mask, drop_mask, mark_mask))
+    if atom_planar is not None:
+        atom_planar = _lib.dense(atom_planar.reshape(B, N) != 0, dev, torch.int32)
+    bond_aromatic = _lib.dense(bond_aromatic, dev, torch.int32)
+    valences = _stereo_valence(dev, is_geom)
+    if valences.numel() < nf:
+        raise ValueError(f'one_hot has {nf} types, the vocabulary {valences.numel()}')
+    out = {'atom_class': _lib.empty_i32(dev, B, N), 'atom_stereo': _lib.empty_i32(dev, B, N),
+           'bond_stereo': _lib.empty_i32(dev, B, capacity), 'counts': _lib.empty_i32(dev, B, 2, _lib.DL_STEREO_COUNTS),
+           'status': _lib.empty_i32(dev, B)}
+    args = _lib.DLStereoArgs(
+        B=B, N=N, nf=nf, x=x.data_ptr(), one_hot=one_hot.data_ptr(), node_mask=node_mask.data_ptr(), drop_mask=_lib.ptr(drop_mask),
+        mark_mask=_lib.ptr(mark_mask), atom_planar=_lib.ptr(atom_planar), default_valence=valences.data_ptr(), capacity=capacity,
+        n_bonds_in=given.n_bonds.data_ptr(), bonds=given.bonds.data_ptr() if capacity else None,
+        bond_aromatic=bond_aromatic.data_ptr() if capacity and bond_aromatic is not None else None,
+        status_in=_lib.ptr(given.status), flat=flat, twist=twist, v_ideal4=const.STEREO_V_IDEAL[0],
+        v_ideal3=const.STEREO_V_IDEAL[1], atom_class=out['atom_class'].data_ptr(), atom_stereo=out['atom_stereo'].data_ptr(),
+        bond_stereo=out['bond_stereo'].data_ptr() if capacity else None, counts=out['counts'].data_ptr(),
+        status=out['status'].data_ptr())
+    _lib.launch('dl_stereo_perceive', args, dev)
+    return out
+
+
+def stereo_types(one_hot, node_mask, found, atom_stereo, bond_stereo, mirror=False):
+    """The widened one-hot ``[B,N,16 nf]`` that folds the labels of a ``stereo`` result into the atom types, on the device of
+    its inputs (they may be host tensors: the tests build the host codes from it): the type index of a row is
+    ``type * 16 + atom_label * 4 + bond_label``, with ``atom_label`` the atom's ``atom_stereo`` (3 and -1 count as 0; 1 and 2
+    exchanged with ``mirror``) and ``bond_label`` the label of the atom's stereo double bond (3 counts as 0; an atom has at most
+    one, because its other bonds are single)."""
+    B, N, nf = one_hot.shape
+    if nf * 16 > 256:
+        raise ValueError(f'{nf} atom types times 16 labels do not fit the 256 types of dl_canonical_ranks')
+    dev = one_hot.device
+    real = node_mask.reshape(B, N) != 0
+    number = (real.to(torch.int64).cumsum(dim=1) - 1).clamp(min=0)              # the atom number of a real row
+    label = atom_stereo.to(torch.int64)
+    label = torch.where((label == 1) | (label == 2), 3 - label if mirror else label, torch.zeros_like(label))
+    on_bond = bond_stereo.to(torch.int64)
+    on_bond = torch.where(on_bond == 3, torch.zeros_like(on_bond), on_bond)
+    by_atom = torch.zeros((B, N), dtype=torch.int64, device=dev)
+    if on_bond.shape[1]:
+        ends = found.bonds.to(torch.int64).clamp(min=0, max=N - 1)              # an entry that is no bond carries label 0
+        by_atom.scatter_add_(1, ends[:, :, 0], on_bond)
+        by_atom.scatter_add_(1, ends[:, :, 1], on_bond)
+    index = one_hot.argmax(dim=2) * 16 + label.gather(1, number) * 4 + by_atom.gather(1, number)
+    index = torch.where(real, index, torch.zeros_like(index))
+    return torch.nn.functional.one_hot(index, nf * 16).to(torch.float32)
+
+
+def stereo_codes(result, one_hot, node_mask, found, drop_mask=None, max_leaves=256):
+    """Stereo-aware canonical codes from a ``stereo`` result, by TWO launches of the existing ``dl_canonical_ranks`` on the
+    widened types of ``stereo_types`` (``csrc/canon.hip`` is unchanged: its atom types come from a one-hot row up to 256 wide).
+    Device tensors in and out, no host synchronisation.
+
+    ``stereo_code``  int64 ``[B]``: the canonical code of the graph with its labels; ``stereo_rank`` int32 ``[B,N]``: its ranks
+    ``mirror_code``  int64 ``[B]``: the same with the atom labels 1 and 2 exchanged - the mirror image's ``stereo_code``
+    ``chiral``       bool ``[B]``: ``stereo_code != mirror_code``; a meso compound is not chiral
+    ``complete``     bool ``[B]``: no label was 3 (undetermined labels are left out of the code) and neither launch set
+                     ``DL_CANON_BUDGET``, ``DL_CANON_BAD_BOND`` or ``DL_CANON_TOO_LARGE``
+    ``status``       int32 ``[B]``: the status bits of the two launches"""
+    _lib.require_device('stereo_codes', one_hot=one_hot, node_mask=node_mask, drop_mask=drop_mask,
+                        atom_stereo=result['atom_stereo'], bond_stereo=result['bond_stereo'])
+    B = one_hot.shape[0]
+    given = normalize_bonds(found, B, one_hot.device, 'stereo_codes')
+    # (is_geom plays no part in canonical_ranks: the graph carries type indices, here the widened ones of any vocabulary)
+    runs = [canonical_ranks(stereo_types(one_hot, node_mask, given, result['atom_stereo'], result['bond_stereo'], mirror),
+                            node_mask, given, True, drop_mask, max_leaves) for mirror in (False, True)]
+    status = runs[0]['status'] | runs[1]['status']
+    undetermined = result['counts'][:, 0, 1] + result['counts'][:, 0, 3]
+    flagged = status & (_lib.DL_CANON_BUDGET | _lib.DL_CANON_BAD_BOND | _lib.DL_CANON_TOO_LARGE)
+    return {'stereo_code': runs[0]['code'], 'stereo_rank': runs[0]['rank'], 'mirror_code': runs[1]['code'],
+            'chiral': runs[0]['code'] != runs[1]['code'], 'complete': (undetermined == 0) & (flagged == 0), 'status': status}
+
+
+StereoRecord = namedtuple('StereoRecord', 'centres centres_linker double_bonds double_bonds_linker undetermined candidates '
+                                          'code stereo_code mirror_code chiral complete isomeric_smiles')
+STEREO_NAMES = ('stereocentres_per_molecule', 'stereocentres_per_molecule_linker', 'stereo_bonds_per_molecule',
+                'stereo_bonds_per_molecule_linker', 'stereo_undetermined', 'chiral_fraction', 'stereo_uniqueness')
+STEREO_TRUE_NAMES = ('stereo_recovery', 'stereo_mirror', 'stereo_recovered_inputs')
+STEREO_JSON = ('centres', 'centres_linker', 'double_bonds', 'double_bonds_linker', 'undetermined', 'stereo_code', 'chiral',
+               'complete', 'isomeric_smiles')
+
+
+def isomeric_smiles_to_host(result, codes, one_hot, node_mask, found, drop_mask=None):
+    """One isomeric string per molecule from a ``stereo`` result and its ``stereo_codes``, on the host:
+    ``molecule_builder.smiles`` on the kept atoms with the ranks of the stereo-aware labelling, the classes and the labels.
+    ``None`` as ``smiles_to_host`` answers it.  Synchronises."""
+    B, N = one_hot.shape[:2]
+    rank, classes, labels = (t.cpu().tolist() for t in (codes['stereo_rank'], result['atom_class'], result['atom_stereo']))
+    on_bond = result['bond_stereo'].cpu().tolist()
+    too_large = (codes['status'].cpu() & _lib.DL_CANON_TOO_LARGE).tolist()
+    n_bonds, bonds = found.n_bonds.cpu().tolist(), found.bonds.cpu()
+    real = node_mask.reshape(B, N).cpu() != 0
+    types = one_hot.detach().cpu().argmax(dim=2)
+    out = []
+    for b in range(B):
+        t = types[b][real[b]].tolist()
+        new = {k: r for k, r in enumerate(rank[b][:len(t)]) if r >= 0}      # atom number -> rank, kept atoms only
+        if too_large[b]:
+            out.append(None)
+            continue
+        index = {k: at for at, k in enumerate(new)}
+        rows = [(e, row) for e, row in enumerate(bonds[b, :max(0, min(n_bonds[b], bonds.shape[1]))].tolist())
+                if row[0] in index and row[1] in index and row[0] != row[1] and 1 <= row[2] <= 3]
+        out.append(smiles([t[k] for k in new], [(index[i], index[j], o) for _, (i, j, o) in rows], [new[k] for k in new],
+                          [classes[b][k] for k in new], [labels[b][k] for k in new], [on_bond[b][e] for e, _ in rows]))
+    return out
+
+
+def stereo_records(one_hot, x, node_mask, found, is_geom, linker_mask, drop_mask=None, atom_planar=None, bond_aromatic=None,
+                   flat=const.STEREO_DEFAULTS['flat'], twist=const.STEREO_DEFAULTS['twist'], max_leaves=256):
+    """One ``StereoRecord`` per molecule of a batch on the bond list ``found`` (the geometric orders of
+    ``refine_bond_orders``, with its ``atom_aromatic`` and ``bond_aromatic``): one launch of ``dl_stereo_perceive`` and three of
+    ``dl_canonical_ranks`` (the plain code, ``stereo_codes``' two).  ``centres`` and ``double_bonds`` count the assigned
+    items (label 1 or 2), ``*_linker`` those that touch a ``linker_mask`` atom, ``undetermined`` the label-3 items of both
+    kinds and ``candidates`` all items; ``code``, ``stereo_code`` and ``mirror_code`` are 16 hex digits; ``isomeric_smiles`` is
+    ``''`` where there is none.  Synchronises."""
+    B, N = one_hot.shape[:2]
+    linker = linker_mask.reshape(B, N).to(torch.float32)
+    result = stereo(one_hot, x, node_mask, found, is_geom, drop_mask, linker, atom_planar, bond_aromatic, flat, twist)
+    codes = stereo_codes(result, one_hot, node_mask, found, drop_mask, max_leaves)
+    plain = canonical_ranks(one_hot, node_mask, found, is_geom, drop_mask, max_leaves)
+    strings = isomeric_smiles_to_host(result, codes, one_hot, node_mask, found, drop_mask)
+    counts = result['counts'].cpu().tolist()
+    hexed = lambda t: [format(v & 0xFFFFFFFFFFFFFFFF, '016x') for v in t.cpu().tolist()]      # noqa: E731
+    code, stereo_code, mirror_code = hexed(plain['code']), hexed(codes['stereo_code']), hexed(codes['mirror_code'])
+    chiral, complete = codes['chiral'].cpu().tolist(), codes['complete'].cpu().tolist()
+    return [StereoRecord(counts[b][0][0], counts[b][1][0], counts[b][0][2], counts[b][1][2], counts[b][0][1] + counts[b][0][3],
+                         sum(counts[b][0]), code[b], stereo_code[b], mirror_code[b], int(chiral[b]),
+                         int(complete[b] and strings[b] is not None), strings[b] or '') for b in range(B)]
+
+
+def analyze_stereo(one_hot, x, node_mask, is_geom, linker_mask, drop_mask=None, margins=const.MARGINS_EDM,
+                   flat=const.STEREO_DEFAULTS['flat'], twist=const.STEREO_DEFAULTS['twist'], max_leaves=256):
+    """The ``StereoRecord`` of every molecule of a batch from its coordinates alone: ``perceive_all_bonds``,
+    ``refine_bond_orders`` and ``stereo_records``.  The perception ALWAYS runs on the geometric (Kekule) orders with the
+    aromatic atoms as planar and the aromatic bonds flagged, whatever orders the files are written with: the distance table's
+    orders inside aromatic rings are arbitrary.  Synchronises."""
+    _lib.require_device('analyze_stereo', one_hot=one_hot, x=x, node_mask=node_mask, linker_mask=linker_mask)
+    B, N = one_hot.shape[:2]
+    if linker_mask.numel() != B * N:
+        raise ValueError(f'shapes disagree: one_hot {tuple(one_hot.shape)}, linker_mask {tuple(linker_mask.shape)}')
+    found = perceive_all_bonds(one_hot, x, node_mask, is_geom, margins)
+    linker = linker_mask.reshape(B, N).to(torch.float32)
+    refined, aromatic = refine_bond_orders(found, one_hot, x, node_mask, is_geom, drop_mask, linker)
+    return stereo_records(one_hot, x, node_mask, refined._replace(status=aromatic.status), is_geom, linker, drop_mask,
+                          aromatic.atom_aromatic, aromatic.bond_aromatic, flat, twist, max_leaves)
+
+
+def compute_stereo(rows, pred, true=None, true_rows=None, input_index=None):
+    """The stereo scores: ``rows`` are the ``StereoRecord`` values of the samples (``stereo_records``), ``pred`` and ``true`` the
+    ``Molecule`` records ``compute_metrics`` takes for the same samples, ``true_rows`` the ``StereoRecord`` of every sample's
+    true molecule and ``input_index`` the input every sample came from (each its own without it).
+
+    ``stereocentres_per_molecule(_linker)``  assigned centres per sample (those that touch the linker)
+    ``stereo_bonds_per_molecule(_linker)``   assigned stereo double bonds per sample
+    ``stereo_undetermined``                  share of all candidates (centres and double bonds) with label 3
+    ``chiral_fraction``                      share of samples whose code differs from their mirror image's
+    ``stereo_uniqueness``                    distinct ``stereo_code`` among the samples ``uniqueness`` counts / their number
+    With ``true_rows``, among the samples whose PLAIN canonical ``code`` equals their true molecule's:
+    ``stereo_recovery``                      share with the true molecule's ``stereo_code``
+    ``stereo_mirror``                        share with its ``mirror_code`` and not its ``stereo_code``: the wrong enantiomer
+    ``stereo_recovered_inputs``              share of ALL inputs with at least one stereo-recovered sample
+    Every score is 0 where it has nothing to count.  ``recovery``, ``uniqueness`` and the clusters are unchanged by this."""
+    n = len(rows)
+    share = lambda total: total / n if n else 0.0            # noqa: E731
+    candidates = sum(r.candidates for r in rows)
+    chosen = [k for k in range(n) if _good(pred[k]) and (true is None or _good(true[k]))]
+    out = {'stereocentres_per_molecule': share(sum(r.centres for r in rows)),
+           'stereocentres_per_molecule_linker': share(sum(r.centres_linker for r in rows)),
+           'stereo_bonds_per_molecule': share(sum(r.double_bonds for r in rows)),
+           'stereo_bonds_per_molecule_linker': share(sum(r.double_bonds_linker for r in rows)),
+           'stereo_undetermined': sum(r.undetermined for r in rows) / candidates if candidates else 0.0,
+           'chiral_fraction': share(sum(1 for r in rows if r.chiral)),
+           'stereo_uniqueness': len({rows[k].stereo_code for k in chosen}) / len(chosen) if chosen else 0.0}
+    if true_rows is None:
+        return out
+    if len(true_rows) != n or (input_index is not None and len(input_index) != n):
+        raise ValueError(f'{n} samples, {len(true_rows)} true records')
+    input_index = list(range(n)) if input_index is None else list(input_index)
+    same = [k for k in range(n) if rows[k].code == true_rows[k].code]
+    hit = [k for k in same if rows[k].stereo_code == true_rows[k].stereo_code]
+    mirror = [k for k in same if rows[k].stereo_code == true_rows[k].mirror_code and rows[k].stereo_code != true_rows[k].stereo_code]
+    out['stereo_recovery'] = len(hit) / len(same) if same else 0.0
+    out['stereo_mirror'] = len(mirror) / len(same) if same else 0.0
+    out['stereo_recovered_inputs'] = len({input_index[k] for k in hit}) / len(set(input_index)) if n else 0.0
+    return out
+
+
+def write_stereo_json(path, files, records):
+    """``stereo.json``: one object per written file (``files``: its name as the other reports give it), keys ``STEREO_JSON``."""
+    import json
+    with open(path, 'w') as f:
+        json.dump([dict(file=name, **{key: getattr(record, key) for key in STEREO_JSON}) for name, record in zip(files, records)],
+                  f, indent=1)

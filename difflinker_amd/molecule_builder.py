@@ -360,7 +360,86 @@ def summary(found):
 _BOND_SYMBOL = {1: '', 2: '=', 3: '#'}
 
 
-def smiles(types, bonds, rank):
+def _parity(keys):
+    """+1 when sorting ``keys`` takes an even permutation, -1 when an odd one."""
+    return -1 if sum(1 for q in range(len(keys)) for p in range(q) if keys[p] > keys[q]) % 2 else 1
+
+
+def _direction_symbols(adj, when, classes, labelled):
+    """The ``/`` and ``\\`` of a string: ``{(first written, second written): +1 for '/', -1 for '\\'}`` for the single bonds
+    to the reference neighbours of the double bonds ``labelled`` (``{(a, b): 1 cis or 2 trans}``).  Read from a double-bond atom
+    outward (the symbol as written when that atom is written first, reversed otherwise), equal symbols on the two ends of a
+    double bond mean cis, and two symbols at one end differ.  A single bond that serves two double bonds (a diene) carries
+    one symbol, so the symbols are the solution of a system of parities: every connected part of it starts with ``/`` on its
+    bond written first.  A part whose parities contradict each other (possible in a conjugated ring only), and any part
+    that would make the string state a configuration for a double bond that has none, is left without symbols."""
+    def node(u, w):
+        return (u, w) if when[u] < when[w] else (w, u)
+
+    def outward(u, w):                               # the factor between the symbol of node(u, w) and its reading from u
+        return 1 if when[u] < when[w] else -1
+
+    reference, rules = {}, []
+    for (a, b), label in labelled.items():
+        ends = []
+        for u, v in ((a, b), (b, a)):
+            others = [w for w in adj[u] if w != v]
+            if not 1 <= len(others) <= 2 or any(adj[u][w] != 1 for w in others):
+                break
+            ends.append(max(others, key=lambda w: classes[w]))
+        else:
+            reference[(a, b)] = ends
+            rules.append((node(a, ends[0]), node(b, ends[1]), (1 if label == 1 else -1) * outward(a, ends[0]) * outward(b, ends[1])))
+    nodes = sorted({n for rule in rules for n in rule[:2]}, key=lambda n: (when[n[0]], when[n[1]]))
+    doubled = [u for u in range(len(adj)) if 2 in adj[u].values()]
+    for u in doubled:                                # two arms at one end of a double bond are on opposite sides
+        arms = [w for w in adj[u] if adj[u][w] == 1 and node(u, w) in nodes]
+        if len(arms) == 2:
+            rules.append((node(u, arms[0]), node(u, arms[1]), -outward(u, arms[0]) * outward(u, arms[1])))
+    near = {n: [] for n in nodes}
+    for n1, n2, product in rules:
+        near[n1].append((n2, product))
+        near[n2].append((n1, product))
+    value, part_of, parts = {}, {}, []
+    for start in nodes:
+        if start in value:
+            continue
+        value[start], members, todo, sound = 1, [start], [start], True
+        while todo:
+            n1 = todo.pop()
+            for n2, product in near[n1]:
+                if n2 not in value:
+                    value[n2] = value[n1] * product
+                    members.append(n2)
+                    todo.append(n2)
+                elif value[n2] != value[n1] * product:
+                    sound = False
+        for n in members:
+            part_of[n] = len(parts)
+        parts.append(members if sound else [])
+        if not sound:
+            for n in members:
+                del value[n]
+    def arms(u, v):                                  # the single bonds at end u of the double bond (u, v) that carry a symbol
+        return [node(u, w) for w in adj[u] if w != v and adj[u][w] == 1 and node(u, w) in value]
+
+    pairs = [(u, v) for u in doubled for v in adj[u] if adj[u][v] == 2 and u < v]
+    while True:                                      # no configuration for a double bond that has none
+        stray = []
+        for u, v in pairs:
+            ends = reference.get((u, v)) and (u, v) or reference.get((v, u)) and (v, u)
+            whole = ends and all(node(t, r) in value for t, r in zip(ends, reference[ends]))
+            if arms(u, v) and arms(v, u) and not whole:
+                stray = arms(u, v) + arms(v, u)
+                break
+        if not stray:
+            return value
+        for bond in stray:
+            for n in parts[part_of[bond]]:
+                value.pop(n, None)
+
+
+def smiles(types, bonds, rank, classes=None, atom_stereo=None, bond_stereo=None):
     """One SMILES string for one molecule, on the host: ``types`` per atom (element indices of the vocabulary, or element
     symbols), ``bonds`` rows ``(i, j, order)`` with orders 1..3, ``rank`` a permutation of ``0..n-1`` per atom - the
     canonical ranks of ``metrics.canonical_ranks``, which make the string canonical under THIS project's rule.  It is NOT
@@ -375,7 +454,25 @@ def smiles(types, bonds, rank):
     than 99 numbers open at once: ``None``.  An atom is written bare when the sum of its bond orders is at most
     ``const.DEFAULT_VALENCE`` of its element and as ``[El]`` otherwise, so a reader's implicit hydrogens are those
     ``add_hydrogens`` places: none on an over-valent atom.  Orders are written as the list has them (Kekule forms, no
-    aromatic lower case); no charges, no stereo.  Nothing recurses: a chain of any length is walked with explicit stacks."""
+    aromatic lower case); no charges.  Nothing recurses: a chain of any length is walked with explicit stacks.
+
+    STEREO.  With ``classes``, ``atom_stereo`` and ``bond_stereo`` all ``None`` there is none and the string is what it always
+    was.  With them - ``classes`` and ``atom_stereo`` per atom and ``bond_stereo`` per row of ``bonds``, as ``metrics.stereo``
+    perceives them - the string is an isomeric SMILES under THIS project's rule (NOT RDKit's, NOT CIP):
+
+    - A centre (label 1 or 2) is written ``[C@H]``, ``[C@@H]``, ``[C@]`` or ``[C@@]``: the element, ``@`` or ``@@``, and ``H``
+      when it has three neighbours.  Its neighbours in STRING ORDER are the preceding atom, then the implicit H, then the
+      ring-closure digits in written order, then the children in written order.  ``@`` means: seen from the first of these,
+      the others run anticlockwise - a NEGATIVE determinant ``det[n1 - n0, n2 - n0, n3 - n0]`` in that order in a right-handed
+      frame - and ``@@`` clockwise.  Label 1 is a positive determinant in CLASS order (ascending ``classes``, the H lowest),
+      so the symbol follows from the label and the parity of the permutation between the two orders.
+    - A stereo double bond (label 1 cis, 2 trans, with respect to the neighbour of highest class at each end) puts ``/`` or
+      ``\\`` on the single bonds to those two neighbours.  A symbol is read from the atom written first to the atom written
+      second.  Re-expressed as read from the double-bond atom outward (reversing ``/`` and ``\\`` when the neighbour was written
+      first), EQUAL symbols on the two ends mean cis: ``F/C=C\\F`` is cis, ``F/C=C/F`` trans.  A single bond that is the arm of two
+      double bonds (a diene) carries one symbol that both agree with; a ring-closure bond carries its symbol at the opening
+      digit and the complementary one at the closing digit (``_direction_symbols`` states the rare cases that get none).
+    - Label 3 (undetermined) writes nothing."""
     n = len(types)
     symbol = [t if isinstance(t, str) else const.GEOM_IDX2ATOM[int(t)] for t in types]
     adj = [dict() for _ in range(n)]
@@ -407,6 +504,17 @@ def smiles(types, bonds, rank):
             elif w != parent[u] and parent[w] != u and u not in closures[w]:
                 closures[u].append(w)
                 closures[w].append(u)
+    slash = {}
+    if classes is not None and atom_stereo is not None and bond_stereo is not None:
+        for u in range(n):
+            if atom_stereo[u] in (1, 2) and len(adj[u]) in (3, 4) and all(o == 1 for o in adj[u].values()):
+                around = ([parent[u]] if parent[u] >= 0 else []) + ([-1] if len(adj[u]) == 3 else []) \
+                    + sorted(closures[u], key=lambda v: rank[v]) + children[u]
+                sign = (1 if atom_stereo[u] == 1 else -1) * _parity([-1 if w < 0 else classes[w] for w in around])
+                atom[u] = f'[{symbol[u]}{"@@" if sign > 0 else "@"}{"H" if len(adj[u]) == 3 else ""}]'
+        labelled = {(i, j): label for (i, j, order), label in zip(bonds, bond_stereo) if label in (1, 2) and adj[i][j] == 2}
+        slash = {pair: '/' if v > 0 else '\\' for pair, v in _direction_symbols(adj, when, classes, labelled).items()}
+    turned = {'/': '\\', '\\': '/', '': ''}
     # second pass: the text
     free, number, parts = list(range(1, 100)), {}, []
     for root in roots:
@@ -423,22 +531,22 @@ def smiles(types, bonds, rank):
                 if pair in number:
                     k = number.pop(pair)
                     closed.append(k)
-                    out.append(str(k) if k < 10 else f'%{k}')
+                    out.append(turned[slash.get((w, u), '')] + (str(k) if k < 10 else f'%{k}'))
                 else:
                     if not free:
                         return None
                     k = free.pop(0)
                     number[pair] = k
-                    out.append(_BOND_SYMBOL[adj[u][w]] + (str(k) if k < 10 else f'%{k}'))
+                    out.append(_BOND_SYMBOL[adj[u][w]] + slash.get((u, w), '') + (str(k) if k < 10 else f'%{k}'))
             free = sorted(free + closed)
             kids = children[u]
             for at in range(len(kids) - 1, -1, -1):
                 w = kids[at]
                 if at < len(kids) - 1:
                     todo.append(('text', -1, ')'))
-                    todo.append(('atom', w, _BOND_SYMBOL[adj[u][w]]))
+                    todo.append(('atom', w, _BOND_SYMBOL[adj[u][w]] + slash.get((u, w), '')))
                     todo.append(('text', -1, '('))
                 else:
-                    todo.append(('atom', w, _BOND_SYMBOL[adj[u][w]]))
+                    todo.append(('atom', w, _BOND_SYMBOL[adj[u][w]] + slash.get((u, w), '')))
         parts.append(''.join(out))
     return '.'.join(parts)

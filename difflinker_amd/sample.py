@@ -17,7 +17,7 @@ from . import metrics as mol_metrics
 from . import utils
 from .datasets import MOADDataset, collate, collate_with_fragment_edges, get_dataloader
 from .generate import (BOND_ORDERS, OUTPUT_FORMATS, _check_selection, add_relax_argument, add_selection_arguments,
-                       add_filters_argument, add_smiles_argument, selection_arguments)
+                       add_filters_argument, add_smiles_argument, add_stereo_argument, selection_arguments)
 from .io import save_sdf_file, save_xyz_file
 from .lightning import DDPM
 from .linker_size import SizeClassifier
@@ -60,7 +60,7 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
            output_format='xyz', metrics=False, geometry=False, clashes=False, shape=False, rings=False,
            bond_orders='distance', aromatic=False, diversity=False, diversity_reference=None, pharmacophore=False,
            interactions=False, hydrogens=False, pose_checks=False, cluster=None, pick=None, select_view='linker', relax=None,
-           smiles=False, filters=None):
+           smiles=False, filters=None, stereo=False):
     """``sample.py``.  Returns the output directory.  ``metrics=True`` scores the molecules sampled in this call against
     the data set's own (``metrics.compute_metrics``: valence rule, connectivity, uniqueness, novelty, recovery) and writes
     the result to ``metrics.json`` in the output directory; with ``geometry=True`` as well, the symmetry-aware RMSD of the
@@ -159,6 +159,7 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
     pred_prints, true_prints, print_input = [], [], []
     eligible, select_input, select_names = [], [], []
     smiles_rows, smiles_names = [], []
+    stereo_rows, true_stereo_rows, stereo_names, stereo_input = [], [], [], []
     diversity = diversity or diversity_reference is not None
     geometry = geometry and metrics
     exp = 'model' if isinstance(checkpoint, DDPM) else checkpoint.split('/')[-1].replace('.ckpt', '')
@@ -230,6 +231,9 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
             true_filter_batch = mol_metrics.patterns_to_host(mol_metrics.analyze_patterns(
                 h[:, :, :model.num_classes], x, node_mask, model.is_geom, batch['linker_mask'], catalogue,
                 drop_mask=batch['pocket_mask'] if moad else None), catalogue.names)
+        if stereo:                                             # the data set's own molecule, without the pocket
+            true_stereo_batch = mol_metrics.analyze_stereo(h[:, :, :model.num_classes], x, node_mask, model.is_geom,
+                                                           batch['linker_mask'], drop_mask=batch['pocket_mask'] if moad else None)
         if pose_checks:
             true_pose_batch = mol_metrics.pose_checks_to_host(mol_metrics.analyze_pose_checks(
                 h[:, :, :model.num_classes], x, node_mask, model.is_geom, batch['linker_mask'],
@@ -349,6 +353,14 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                     listed = refine_bond_orders(listed, types, shown_xs, out_mask, model.is_geom)[0]
                 smiles_rows += mol_metrics.smiles_records(types, out_mask, listed, out_mask * (1 - pad(batch['fragment_mask'])))
                 smiles_names += [[f'{u}/{i}_.{ext}' for ext in ('xyz', 'sdf') if output_format in (ext, 'both')] for u in uuids]
+            if stereo:                                         # on the coordinates the files carry; always the geometric orders
+                pad = lambda m: torch.nn.functional.pad(m, (0, 0, 0, out_mask.shape[1] - m.shape[1]))      # noqa: E731
+                stereo_rows += mol_metrics.analyze_stereo(
+                    hs[:, :, :model.num_classes], shown_xs, out_mask, model.is_geom, out_mask * (1 - pad(batch['fragment_mask'])),
+                    drop_mask=pad(batch['pocket_mask']) if moad else None)
+                true_stereo_rows += true_stereo_batch
+                stereo_input += [(batch_idx, k) for k in range(len(uuids))]
+                stereo_names += [[f'{u}/{i}_.{ext}' for ext in ('xyz', 'sdf') if output_format in (ext, 'both')] for u in uuids]
             if metrics:
                 types = hs[:, :, :model.num_classes]
                 pred += mol_metrics.to_host(mol_metrics.analyze(types, xs, out_mask, model.is_geom), types, out_mask)
@@ -370,7 +382,12 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 json.dump(mol_metrics.selection_report(selection, select_names), f, indent=1)
     if smiles:                                                 # one row per written file
         mol_metrics.write_smiles_csv(os.path.join(output_dir, 'smiles.csv'), [path for paths in smiles_names for path in paths],
-                                     [m for m, paths in zip(smiles_rows, smiles_names) for _ in paths])
+                                     [m for m, paths in zip(smiles_rows, smiles_names) for _ in paths],
+                                     *([[m.isomeric_smiles for m, paths in zip(stereo_rows, stereo_names) for _ in paths]]
+                                       if stereo else []))
+    if stereo:                                                 # one record per written file
+        mol_metrics.write_stereo_json(os.path.join(output_dir, 'stereo.json'), [path for paths in stereo_names for path in paths],
+                                      [m for m, paths in zip(stereo_rows, stereo_names) for _ in paths])
     if filters is not None:                                    # one record per written file
         mol_metrics.write_filters_json(os.path.join(output_dir, 'filters.json'),
                                        [path for paths in filter_names for path in paths],
@@ -413,6 +430,8 @@ def sample(checkpoint, samples, prefix, n_samples, device, data=None, n_steps=No
                 scores.update(mol_metrics.compute_smiles(smiles_rows, pred, true))
             if filters is not None and metrics:
                 scores.update(mol_metrics.compute_filters(pred_filters, true_filters))
+            if stereo and metrics:
+                scores.update(mol_metrics.compute_stereo(stereo_rows, pred, true, true_stereo_rows, stereo_input))
             json.dump(scores, f, indent=1)
     return output_dir
 
@@ -544,6 +563,7 @@ def main(argv=None):
     add_selection_arguments(p)
     add_relax_argument(p)
     add_smiles_argument(p)
+    add_stereo_argument(p)
     add_filters_argument(p)
     p.add_argument('--pose_checks', action='store_true',
                    help='check the internal geometry of every sample and of its true molecule on the GPU - bond lengths, bond '
@@ -565,7 +585,7 @@ def main(argv=None):
                      **({'interactions': True} if a.interactions else {}),
                      **({'hydrogens': True} if a.hydrogens else {}),
                      **({'pose_checks': True} if a.pose_checks else {}),
-                     **({'relax': a.relax} if a.relax is not None else {}), **({'smiles': True} if a.smiles else {}),
+                     **({'relax': a.relax} if a.relax is not None else {}), **({'smiles': True} if a.smiles else {}), **({'stereo': True} if a.stereo else {}),
                      **({'filters': a.filters} if a.filters is not None else {}),
                      **selection_arguments(a)))
 

@@ -108,6 +108,11 @@
  *                                           of SMARTS compiled on the host, matched by a depth-first search per (pattern, root
  *                                           atom).  The language and the rule stated below are this project's own, NOT RDKit's
  *                                           matcher
+ *   dl_stereo_perceive                   <- (no reference counterpart: the reference calls Chem.RemoveStereochemistry before
+ *                                           it compares strings, src/metrics.py) tetrahedral centres and stereo double bonds
+ *                                           read off the 3D sample, with labels relative to the colour classes of
+ *                                           dl_canonical_ranks.  The rule stated below is this project's own, NOT RDKit's
+ *                                           stereo perception and NOT CIP
  *   dl_size_train_forward / dl_size_train_backward
  *                                        <- SizeClassifier.forward in training mode + loss.backward()
  *                                           (src/linker_size_lightning.py:83-117, :163-167)
@@ -2221,6 +2226,106 @@ typedef struct dl_substructure_args {
     void* stream;                   /* hipStream_t; NULL: the default stream */
 } dl_substructure_args;
 int32_t dl_substructure_match(const dl_substructure_args* args);
+
+/* ---- stereo perception from 3D: tetrahedral centres and double bonds (stereo.hip) -----------------------------------
+ * Which kept atoms are tetrahedral stereocentres and which double bonds are stereo double bonds, and which of their two
+ * configurations the coordinates show: one 256-thread workgroup per molecule, ONE launch per batch, the molecule in LDS, the
+ * stream as the last field, as dl_pose_checks and dl_canonical_ranks.  The reference removes stereo before it compares
+ * strings (Chem.RemoveStereochemistry, src/metrics.py); this reads it off the sample.  THE RULE BELOW IS THIS PROJECT'S OWN:
+ * NOT RDKit's stereo perception and NOT CIP.  The labels 1 and 2 are relative to this project's symmetry classes; they are
+ * no R/S and no E/Z.  tests/stereo_ref.py restates the rule in plain Python and numpy and the kernel agrees with that in
+ * every output bit.
+ *
+ * CONVENTIONS, those of dl_pose_checks.  Atom k is the k-th row with node_mask != 0; its type t is the FIRST largest entry
+ * of its one_hot row.  `drop_mask` (may be NULL) removes atoms AFTER that numbering, together with their bonds; the kept atoms
+ * are numbered among themselves in row order (the KEPT INDEX).  An entry (i, j, order) is a bond when 0 <= i, j < atoms,
+ * i != j and 1 <= order <= 3, in either orientation; any other entry is skipped and sets DL_STEREO_BAD_BOND.  A repeated pair
+ * sets DL_STEREO_BAD_BOND too and is ONE pair with its FIRST entry's order and bond_aromatic flag (in the classes below
+ * every one of its entries counts, as in dl_canonical_ranks).  "Kept" means: not dropped, both ends for a bond; a
+ * "neighbour" is the other end of a kept pair; d is the number of neighbours.  `mark_mask` (may be NULL) marks atoms by row.
+ *
+ * CLASSES.  The symmetry class of a kept atom is its tied rank after the ROOT refinement of dl_canonical_ranks:
+ * c[i] = mix2(SEED_COLOUR, type_i + 1); n rounds of c'[i] = mix2(c[i], sum over the kept list entries (i, j, o) of
+ * mix2(c[j], o)); class[i] = the number of kept atoms with a strictly smaller colour.  This is 1-WL: it does not see stereo,
+ * and it can call two substituents equal that an orbit computation would separate (and the reverse never).  Centres and
+ * double bonds whose substituents it ties are not perceived.
+ *
+ * ARITHMETIC.  fp64 on (double) x, contraction off, every + - * / and sqrt rounded on its own in the order written;
+ * v . w = (v_x*w_x + v_y*w_y) + v_z*w_z; v x w = (v_y*w_z - v_z*w_y, v_z*w_x - v_x*w_z, v_x*w_y - v_y*w_x);
+ * det[a, b, c] = a . (b x c); unit(v) = (v_x/n, v_y/n, v_z/n) with n = sqrt(v . v).
+ *
+ * 1. TETRAHEDRAL CENTRES.  A kept atom a with atom_planar[a] == 0 (by atom number; NULL: none is planar) is a CENTRE when
+ *    every one of its pairs has order 1, and, with vs the sum of its pairs' orders and h = max(0, default_valence[t] - vs),
+ *    d == 4 and h == 0, or d == 3 and h == 1, and the classes of its neighbours are pairwise distinct (the implicit H is a
+ *    class below all others).  So a trivalent N or P is no centre, a four-coordinate N is one.  Its neighbours sorted by
+ *    ascending class are n0 < n1 < n2 < n3 (d == 3: n1 < n2 < n3, the H is n0).  u_k = unit(x_nk - x_a).
+ *    d == 4: V = det[u1 - u0, u2 - u0, u3 - u0], T = flat * v_ideal4.  d == 3: V = det[u1, u2, u3], T = flat * v_ideal3.
+ *    Label 1 when V > T, label 2 when V < -T, label 3 (UNDETERMINED) otherwise; a neighbour at zero distance gives label 3
+ *    without the arithmetic.  The host passes v_ideal4 = 16/(3 sqrt 3) and v_ideal3 = 4/(3 sqrt 3), the values of V at
+ *    the ideal tetrahedron.  A mirror image exchanges labels 1 and 2 exactly: negating one coordinate negates V bit for bit.
+ * 2. STEREO DOUBLE BONDS.  A kept pair (a, b) of order 2, a < b by kept index, is a STEREO DOUBLE BOND when its first entry
+ *    is not flagged in bond_aromatic (NULL: none is), it is in no ring of fewer than 8 atoms (the shortest path from a to b
+ *    that does not use the pair has 7 or more bonds, or there is none), and each end has one or two OTHER neighbours, all
+ *    through pairs of order 1, whose classes differ when there are two.  The REFERENCE neighbour of an end is the other
+ *    neighbour with the highest class.  e = unit(x_b - x_a); w = x_ra - x_a for the reference ra of a, s = w . e,
+ *    p = w - s * e by component; likewise q from x_rb - x_b.  lp = sqrt(p . p), lq = sqrt(q . q).  Label 3 when
+ *    x_b - x_a has zero length, or lp < 0.1 or lq < 0.1 (A).  Otherwise c = (p . q) / (lp * lq): label 1 (cis: the two
+ *    reference neighbours on one side) when c > twist, label 2 (trans) when c < -twist, label 3 otherwise.
+ *
+ *   atom_class   [B,N] by atom number, written in full: the class; -1 for a dropped atom and from the atom count on
+ *   atom_stereo  [B,N] by atom number, written in full: 0 no centre, 1, 2 or 3; -1 where atom_class is -1
+ *   bond_stereo  [B,capacity] by list entry, written in full: 0, 1, 2 or 3 on the first entry of a stereo double bond's pair,
+ *                0 on every other entry
+ *   counts       [B][2][4], written in full: centres with label 1 or 2, centres with label 3, double bonds with label 1 or 2,
+ *                double bonds with label 3.  Row 0: all; row 1: the items with a marked atom among the centre and its
+ *                neighbours, or among the bond's two ends and two reference neighbours.
+ *   status       [B]: the bits of `status_in` (may be NULL: none), plus DL_BONDS_OVERFLOW when n_bonds_in > capacity (a
+ *                negative n_bonds_in counts as 0), DL_STEREO_BAD_BOND, and the limits.  None disturbs the other molecules.
+ *                DL_STEREO_TOO_LARGE: more than DL_STEREO_MAX_ATOMS KEPT atoms (N itself may be 1024; neither the list nor
+ *                  the coordinates are looked at) or more than DL_STEREO_MAX_BONDS kept list entries (DL_STEREO_BAD_BOND is
+ *                  then added for an entry that is no bond only): atom_class and atom_stereo are -1 everywhere, bond_stereo
+ *                  and counts 0.
+ *                DL_STEREO_NONFINITE: a kept atom has a NaN or inf coordinate: atom_class stands, every label and count is 0.
+ *
+ * Integer sums only, and every fp64 decision is made by one thread from LDS-resident data in the order written above (ends
+ * ordered by kept index, neighbours by class): the same bits on every run and under every order and orientation of the list.
+ * Global memory is written with plain stores only; the callee allocates nothing and needs no workspace.  A null `args`, B < 0,
+ * N < 1, N > 1024, nf < 1, nf > 256, capacity < 0, a flat or twist that is negative or NaN, or a v_ideal4 or v_ideal3 that is
+ * not positive (NaN included) return DL_ERR_BAD_ARG; then
+ * B == 0 returns DL_OK without a launch; then a null pointer (other than drop_mask, mark_mask, atom_planar, bond_aromatic,
+ * status_in, stream, and `bonds` / `bond_stereo` when capacity is 0) returns DL_ERR_BAD_ARG, all before any device work.
+ * Not here: R/S and E/Z names; pseudo-asymmetric and stereo-dependent centres (the classes do not see stereo); trivalent N, P
+ * and sulfoxide centres; allenes, cumulenes and atropisomers; amide bonds (order 1). */
+#define DL_STEREO_MAX_ATOMS 256     /* kept atoms per molecule */
+#define DL_STEREO_MAX_BONDS 2048    /* kept list entries per molecule */
+#define DL_STEREO_TOO_LARGE 4       /* status bit, same value as DL_POSE_TOO_LARGE and DL_CANON_TOO_LARGE */
+#define DL_STEREO_BAD_BOND 8        /* status bit, same value as DL_POSE_BAD_BOND and DL_CANON_BAD_BOND */
+#define DL_STEREO_NONFINITE 64      /* status bit, same value as DL_POSE_NONFINITE */
+#define DL_STEREO_COUNTS 4          /* values per row of `counts` */
+typedef struct dl_stereo_args {
+    int32_t B, N, nf;
+    const float* x;                 /* device f32 [B,N,3], Angstrom */
+    const float* one_hot;           /* device f32 [B,N,nf] */
+    const float* node_mask;         /* device f32 [B,N] */
+    const float* drop_mask;         /* device f32 [B,N] or NULL */
+    const float* mark_mask;         /* device f32 [B,N] or NULL */
+    const int32_t* atom_planar;     /* device int32 [B,N] by atom number, or NULL: dl_aromatic_args.atom_aromatic */
+    const int32_t* default_valence; /* device int32 [nf]: the table of dl_add_hydrogens */
+    int32_t capacity;               /* bonds the list holds per molecule */
+    const int32_t* n_bonds_in;      /* device int32 [B]: dl_bonds_args.n_bonds */
+    const int32_t* bonds;           /* device int32 [B,capacity,3] (may be NULL when capacity is 0) */
+    const int32_t* bond_aromatic;   /* device int32 [B,capacity] or NULL: dl_aromatic_args.bond_aromatic */
+    const int32_t* status_in;       /* device int32 [B] or NULL: dl_bonds_args.status or dl_aromatic_args.status */
+    double flat, twist;             /* the rule's two parameters; the Python layer's defaults are 0.25 and 0.5 */
+    double v_ideal4, v_ideal3;      /* 16/(3 sqrt 3) and 4/(3 sqrt 3), formed by the host */
+    int32_t* atom_class;            /* device int32 [B,N] out */
+    int32_t* atom_stereo;           /* device int32 [B,N] out */
+    int32_t* bond_stereo;           /* device int32 [B,capacity] out (may be NULL when capacity is 0) */
+    int32_t* counts;                /* device int32 [B,2,4] out */
+    int32_t* status;                /* device int32 [B] out */
+    void* stream;                   /* hipStream_t; NULL: the default stream */
+} dl_stereo_args;
+int32_t dl_stereo_perceive(const dl_stereo_args* args);
 
 const char* dl_error_string(int32_t status);
 int32_t dl_last_hip_error(void);
