@@ -2039,7 +2039,9 @@ int32_t dl_relax_molecules(const dl_relax_args* args);
  * labelled form, so two molecules with equal codes are the same graph up to a 64-bit collision, and the ranks are the atom
  * order molecule_builder.smiles writes a string from.  THE RULE BELOW IS THIS PROJECT'S OWN: NOT RDKit's canonical ranks, and
  * the strings are NOT RDKit's canonical SMILES.  tests/canon_ref.py restates it in plain Python and numpy and the kernel agrees with
- * that in every output bit.
+ * that in every output bit.  "Equal codes exactly for the same graph" is checked by the atlas sweep (tests/test_atlas_host.py,
+ * tests/test_gpu_atlas.py) against networkx's isomorphism test: every graph of up to 7 atoms and seeded colourings of those of
+ * up to 6, under renumbering, and vertex-transitive cage graphs, the 4x4 rook's graph and the Shrikhande graph among them.
  *
  * THE GRAPH is the one dl_molecule_keys reads: atom k is the k-th row with node_mask != 0; `drop_mask` (may be NULL) removes
  * atoms AFTER that numbering together with every bond that touches them; the kept atoms are numbered among themselves in row
@@ -2248,7 +2250,9 @@ int32_t dl_substructure_match(const dl_substructure_args* args);
  * c[i] = mix2(SEED_COLOUR, type_i + 1); n rounds of c'[i] = mix2(c[i], sum over the kept list entries (i, j, o) of
  * mix2(c[j], o)); class[i] = the number of kept atoms with a strictly smaller colour.  This is 1-WL: it does not see stereo,
  * and it can call two substituents equal that an orbit computation would separate (and the reverse never).  Centres and
- * double bonds whose substituents it ties are not perceived.
+ * double bonds whose substituents it ties are not perceived.  "The reverse never" is checked by the atlas sweep
+ * (tests/test_atlas_host.py, tests/test_gpu_atlas.py): on every graph of up to 7 atoms and on vertex-transitive cage graphs,
+ * two atoms that an automorphism found by networkx exchanges share their class.
  *
  * ARITHMETIC.  fp64 on (double) x, contraction off, every + - * / and sqrt rounded on its own in the order written;
  * v . w = (v_x*w_x + v_y*w_y) + v_z*w_z; v x w = (v_y*w_z - v_z*w_y, v_z*w_x - v_x*w_z, v_x*w_y - v_y*w_x);
